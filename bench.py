@@ -19,6 +19,9 @@ Workloads (BASELINE.json `configs`, synthetic data):
             to the other ranks over RCCL / xGMI (replicated per GPU, no data-path collective)
   --config 2|3|4|5 forces one of them at any N (4 = config3 + junction colours; 5 = k=31, 500 M entries, 100 k reads
   of 500 b - 20 kb); --reads / --kmers / --k override single figures (the label then says "custom").
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the side measurements of N = 1 (CPU
+oracle baseline with its parity spot-check, host-to-host pass, branching-graph workload, end-to-end CLI run; each can be
+left out with its --no-* switch).  --dump-outputs DIR writes the last timed step's records (dump_outputs below).
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -57,6 +60,11 @@ def parse(argv=None):
     ap.add_argument("--kmers", type=int, default=None, help="distinct k-mers in the synthetic dump (override)")
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the CPU oracle baseline (flat + std::map), the host-to-host pass, the "
+                         "branching-graph workload and the end-to-end CLI run (N = 1); the --no-* switches below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="reads of the same workload timed on the CPU oracle (0 = sized for ~15 s from a pilot run)")
     ap.add_argument("--cpu-backend", choices=["flat", "map"], default="flat",
@@ -270,7 +278,7 @@ def main():
     a.gpus = world
     out_fd = claim_stdout()
     e2e = None
-    if world == 1 and not a.no_e2e and not under_profiler():
+    if world == 1 and a.full and not a.no_e2e and not under_profiler():
         # before anything in this process touches the GPU: the CLI is a child process of a GPU-free parent (under
         # rocprofv3 the preloaded tool has initialised the GPU already and would trace the child into the same files)
         e2e = end_to_end_cli(a, resolve_workload(a, 1))
@@ -294,6 +302,8 @@ def main():
 
     log = (lambda m: print("[bench r%d] %s" % (rank, m), file=sys.stderr, flush=True))
     w = resolve_workload(a, world)
+    if a.dump_outputs and 20 * w["reads"] + 8 > DUMP_BUDGET_BYTES:
+        raise SystemExit("--dump-outputs: the per-read arrays of %d reads exceed %d bytes" % (w["reads"], DUMP_BUDGET_BYTES))
     t_setup = time.time()
     synth = Synth(target_kmers=w["kmers"], k=w["k"], seed=a.seed, mixed_lengths=int(w["mixed"]))
     params = T.default_params(k=w["k"], use_junctions=int(w["junctions"]))
@@ -320,7 +330,7 @@ def main():
     # the std::map oracle table (the reference's own backend) takes about a minute to build for 54 M k-mers:
     # one host thread builds it while the GPU legs run (the box has far more cores than those legs use)
     map_job = None
-    if world == 1 and rank == 0 and not a.no_cpu and not a.no_map and a.cpu_backend != "map":
+    if world == 1 and rank == 0 and a.full and not a.no_cpu and not a.no_map and a.cpu_backend != "map":
         map_job = MapTableJob(w, synth, keys, counts)
 
     comm_dev = "cpu" if (world > 1 and rehearsal()) else "cuda"
@@ -494,13 +504,19 @@ def main():
             "kernels_ms": tm,
             "retried_reads": n_retried,
         }
-    if world == 1 and not a.no_h2h:
+    if rank == 0 and a.dump_outputs:
+        if world == 1:
+            dump_outputs(a.dump_outputs, out, oo, st, synth.read_lengths(0, w["reads"]), log)
+        elif merged_reads is not None:
+            dump_outputs(a.dump_outputs, np.frombuffer(seq_all, dtype=np.uint8), off_all, st_all,
+                         synth.read_lengths(0, w["reads"]), log)
+    if world == 1 and a.full and not a.no_h2h:
         h2h = host_to_host(T, table, params, dev, bases, offs, max(2, a.steps), log)
         if rank == 0:
             result["host_to_host"] = h2h
             result["config"]["host_to_host_bases_per_s"] = h2h["value"]
             result["config"]["host_to_host_ms_per_step"] = h2h["ms_per_step"]
-    if world == 1 and not a.no_paralog and rank == 0:
+    if world == 1 and a.full and not a.no_paralog and rank == 0:
         pw = paralog_workload(T, dev, log, with_cpu=not a.no_cpu)
         result["paralog_workload"] = pw
         result["config"]["paralog_bases_per_s"] = pw["value"]
@@ -516,9 +532,9 @@ def main():
                 result["config"]["end_to_end_split_s"] = e2e["split_s"]
             else:
                 result["config"]["end_to_end_error"] = e2e.get("error")
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             result["cpu_baseline"] = cpu_baseline(a, w, synth, keys, counts, bases, offs, out, oo, st, map_job, log)
-        elif not a.no_cpu:
+        elif a.full and not a.no_cpu:
             result["cpu_baseline"] = None   # (N > 1: the CPU baseline is rank 0's N = 1 leg, see BENCH at N = 1)
         if gatherers:
             result["config"]["gather_host_reads_per_step_rank0"] = sum(g.host_syncs for g in gatherers) / max(a.steps + a.warmup, 1)
@@ -526,6 +542,47 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs writes at most this much in all (under 64 MB)
+DUMP_SEED = 20261016             # the seeded sample of reads whose records are written out whole
+
+
+def dump_outputs(path, records, offsets, status, read_lengths, log):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step — the corrected records (uint8
+    ASCII, back to back), their offsets and every read's status — as .npy files two builds can be compared by:
+      status.npy          float32[n]    read status (lib.READ_*), every read
+      offsets.npy         float64[n+1]  record offsets into the corrected bytes, every read
+      record_crc32.npy    float64[n]    CRC-32 of each read's record, every read
+      sample_reads.npy    float64[m]    indices of a fixed, seeded sample of reads (ascending)
+      sample_records.npy  float32[...]  those reads' records back to back (ASCII codes)
+    The sample is drawn from the read indices and the input read lengths alone, so it names the same reads for every
+    build; it takes what the budget leaves after the per-read arrays (records hold at most about twice their read)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    n = len(status)
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    crc = np.fromiter((zlib.crc32(records[int(offsets[i]):int(offsets[i + 1])]) for i in range(n)), dtype=np.float64, count=n)
+    per_read_bytes = 4 * n + 8 * (n + 1) + 8 * n
+    room = max(DUMP_BUDGET_BYTES - per_read_bytes, 0) // 4 - 2 * n   # float32 record elements (index array included)
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    take = int(np.searchsorted(np.cumsum(np.asarray(read_lengths, dtype=np.int64)[order]), room // 2, side="right"))
+    sample = np.sort(order[:take])
+    lens = (offsets[sample + 1] - offsets[sample]).astype(np.int64)
+    keep = int(np.searchsorted(np.cumsum(lens), room, side="right"))   # (a record longer than twice its read: drop the tail)
+    sample = sample[:keep]
+    parts = [records[int(offsets[i]):int(offsets[i + 1])] for i in sample]
+    arrays = {
+        "status": np.asarray(status).astype(np.float32),
+        "offsets": offsets.astype(np.float64),
+        "record_crc32": crc,
+        "sample_reads": sample.astype(np.float64),
+        "sample_records": (np.concatenate(parts) if parts else np.zeros(0, np.uint8)).astype(np.float32),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log("outputs of the last step -> %s: %d reads, %d of them whole (%.1f MB)"
+        % (path, n, len(sample), sum(x.nbytes for x in arrays.values()) / 1e6))
 
 
 def under_profiler():

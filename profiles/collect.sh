@@ -13,7 +13,7 @@ DST=$ROOT/gpurun_out/profiles/$ROUND
 mkdir -p "$OUT" "$DST"
 export TMPDIR=/tmp
 
-python3 bench.py --steps 10 --warmup 3 > "$DST/${TAG}_bench.json"
+python3 bench.py --full --steps 10 --warmup 3 > "$DST/${TAG}_bench.json"
 echo "[collect] bench done"
 
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu --no-h2h --no-paralog --no-e2e > "$DST/${TAG}_bench_under_rocprof.json"

@@ -9,7 +9,7 @@ O=gpurun_out
 bash profiles/collect.sh r03 $TAG || exit 1
 bash profiles/r03/scripts/r03_lanes.sh ${TAG}_lanes > $O/${TAG}_lanes.log 2>&1 && cp $O/${TAG}_lanes_sq.json $O/profiles/r03/${TAG}_sq_counters.json
 for c in 3 4 5; do
-  python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu --no-paralog --no-e2e > $O/profiles/r03/${TAG}_bench_c$c.json 2> $O/${TAG}_bench_c$c.err || { tail -5 $O/${TAG}_bench_c$c.err; exit 1; }
+  python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu --no-paralog --no-e2e > $O/profiles/r03/${TAG}_bench_c$c.json 2> $O/${TAG}_bench_c$c.err || { tail -5 $O/${TAG}_bench_c$c.err; exit 1; }
   echo "[collect] config $c done"
 done
 for c in 2 5; do

@@ -39,12 +39,12 @@ if has pmc || has sq; then
   python3 profiles/aggregate_counters.py "$COLL" "$DST" "$TAG" || exit 1
   mkdir -p profiles && cp $O/pmc_traffic.json $O/sq_search.json profiles/ 2>/dev/null   # (on the GPU box: so that the bench below sees them)
 fi
-timeout -k 10 400 python3 bench.py --steps 10 --warmup 3 > "$DST/${TAG}_bench.json" 2> $COLL/bench.err || { tail -20 $COLL/bench.err; exit 1; }
-timeout -k 10 400 python3 bench.py > "$DST/${TAG}_bench_default.json" 2> $COLL/bench_default.err || { tail -20 $COLL/bench_default.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 3 > "$DST/${TAG}_bench.json" 2> $COLL/bench.err || { tail -20 $COLL/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > "$DST/${TAG}_bench_default.json" 2> $COLL/bench_default.err || { tail -20 $COLL/bench_default.err; exit 1; }
 echo "[collect] bench lines done"
 if has configs; then
   for c in 3 4 5; do
-    timeout -k 10 500 python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu --no-paralog --no-e2e > $DST/${TAG}_bench_c$c.json 2> $COLL/bench_c$c.err || { tail -5 $COLL/bench_c$c.err; exit 1; }
+    timeout -k 10 500 python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu --no-paralog --no-e2e > $DST/${TAG}_bench_c$c.json 2> $COLL/bench_c$c.err || { tail -5 $COLL/bench_c$c.err; exit 1; }
     echo "[collect] config $c done"
   done
 fi
