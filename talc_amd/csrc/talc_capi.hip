@@ -10,7 +10,6 @@
 #include <cstring>
 #include <fstream>
 #include <map>
-#include <numeric>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -20,6 +19,7 @@
 #include "talc_kernels_build.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
+#include "talc_switches.h"
 #include "talc_table_host.h"
 
 using namespace talc;
@@ -94,6 +94,7 @@ struct talc_ctx {
   hipEvent_t ev[8];
   TableView view;
   talc_timing timing;
+  Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   Stage stage;          // default scratch
   uint32_t* d_queue = nullptr;   // work-queue counters
   uint32_t* d_hist = nullptr;    // 1024 buckets of the work-queue ordering
@@ -172,13 +173,13 @@ struct talc_batch {
   uint64_t n_bases = 0, n_kmers = 0;
   uint32_t max_len = 0;
   std::vector<uint64_t> h_offsets, h_koff;
-  std::vector<uint32_t> h_tile_read, h_tile_start, h_chunk_read, h_chunk_start, h_order;
+  std::vector<uint32_t> h_tile_read, h_tile_start, h_chunk_read, h_chunk_start;
   uint8_t* d_raw = nullptr;
   uint8_t* d_codes = nullptr;
   uint64_t* d_offsets = nullptr;
   uint64_t* d_koff = nullptr;
   uint32_t *d_tile_read = nullptr, *d_tile_start = nullptr, *d_chunk_read = nullptr, *d_chunk_start = nullptr;
-  uint32_t* d_order = nullptr;
+  uint32_t* d_order = nullptr;       // the work queue: read numbers, heaviest first (k_order_scatter)
   uint2* d_cov = nullptr;            // hit pairs, packed per tile inside each read's dense slot (talc_common.h: CovWord)
   CovWord* d_covw = nullptr;         // one word per 64 k-mer positions
   int32_t* d_nin = nullptr;
@@ -263,7 +264,7 @@ int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64
   for (long i = 0; i < (long)n; ++i) kept += counts[i] >= p->min_count ? 1 : 0;
   talc_table* t = new talc_table();
   t->h.p = *p;
-  if (!t->h.allocate(kept)) { delete t; return fail(TALC_ERR_NOMEM, "cannot allocate host table for %llu k-mers", (unsigned long long)kept); }
+  if (!t->h.allocate(kept, read_switches().tableSlotsX10)) { delete t; return fail(TALC_ERR_NOMEM, "cannot allocate host table for %llu k-mers", (unsigned long long)kept); }
   t->h.insertAll(kmers, counts, n);
   *out = t;
   return TALC_OK;
@@ -273,14 +274,14 @@ int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64
 // the device builder's core: n dump lines as device arrays dK / dC (line i of the dump at index i; the kernels drop the
 // lines below MIN_COUNT themselves), `kept` = how many reach MIN_COUNT (sizes the tables).  Takes ownership of dK / dC.
 static int build_table_from_device_arrays(uint64_t* dK, uint32_t* dC, uint64_t n, uint64_t kept, const talc_params* p, int device,
-                                          talc_table** out, double h2d_seconds, double h2d_megabytes) {
+                                          talc_table** out, double h2d_seconds, double h2d_megabytes, const Switches& sw) {
   talc_table* t = new talc_table();
   t->h.p = *p;
   {   // (sparser than load 0.5 when the device has the room: HostTable::capacity_for)
     hipDeviceProp_t prop;
     uint64_t devBytes = 0;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) devBytes = (uint64_t)prop.totalGlobalMem;
-    t->h.capacity = HostTable::capacity_for(kept, devBytes);
+    t->h.capacity = HostTable::capacity_for(kept, devBytes, sw.tableSlotsX10);
   }
   uint32_t *dSR = nullptr, *dSL = nullptr;
   unsigned long long* dStats = nullptr;
@@ -290,7 +291,6 @@ static int build_table_from_device_arrays(uint64_t* dK, uint32_t* dC, uint64_t n
   t->hostValid = false;
   const uint64_t cap = t->h.capacity, bytes = cap * sizeof(Bucket);
 #define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); hipFree(dR); hipFree(dL); delete t; return fail(TALC_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-  const bool timing = getenv("TALC_TIMING") != nullptr;
   auto tnow = []() { return std::chrono::steady_clock::now(); };
   auto tsec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   const auto td1 = tnow();
@@ -315,7 +315,7 @@ static int build_table_from_device_arrays(uint64_t* dK, uint32_t* dC, uint64_t n
 #undef BCHK
   const auto td3 = tnow();
   cleanup();
-  if (timing) fprintf(stderr, "[talc-lib] device build: %.0f MB to the device %.3f s, table allocations + clears %.3f s, kernels %.3f s, frees %.3f s\n",
+  if (sw.timing) fprintf(stderr, "[talc-lib] device build: %.0f MB to the device %.3f s, table allocations + clears %.3f s, kernels %.3f s, frees %.3f s\n",
                       h2d_megabytes, h2d_seconds, tsec(td1, td2), tsec(td2, td3), tsec(td3, tnow()));
   t->stagedDev = device; t->stR = dR; t->stL = dL;
   t->h.nkmers = st[0]; t->h.nbuckets_right = st[1]; t->h.nbuckets_left = st[2];
@@ -342,18 +342,18 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
   if (e == hipSuccess && n) e = hipMemcpy(dC, counts, n * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) { hipFree(dK); hipFree(dC); return fail(TALC_ERR_DEVICE, "copying the dump's arrays to the device: %s", hipGetErrorString(e)); }
   const double h2d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return build_table_from_device_arrays(dK, dC, n, kept, p, device, out, h2d, (double)n * 12 / 1e6);
+  return build_table_from_device_arrays(dK, dC, n, kept, p, device, out, h2d, (double)n * 12 / 1e6, read_switches());
 }
 
 // The text dump parsed ON the device (talc_kernels_build.h): the file's bytes are read by a few host threads into
 // page-locked buffers and copied as they are; two kernels make the builder's arrays.  Returns TALC_OK with *out set, or
 // a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory):
 // the caller then parses on the host, as before.
-static int table_from_text_on_device(const char* path, const talc_params* p, int device, talc_table** out, DumpStats& ds) {
+static int table_from_text_on_device(const char* path, const talc_params* p, int device, talc_table** out, DumpStats& ds, const Switches& sw) {
   struct stat sb;
   if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
   const uint64_t size = (uint64_t)sb.st_size;
-  if (size < (8u << 20) || getenv("TALC_HOST_PARSE")) return 1;
+  if (size < (8u << 20) || sw.hostParse) return 1;
   {   // a Jellyfish 2 count file goes the host's way (talc_jf.h)
     char head[64] = {0};
     FILE* f = fopen(path, "rb");
@@ -362,7 +362,6 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
     fclose(f);
     if (jfLooksLike(head, got)) return 1;
   }
-  const bool timing = getenv("TALC_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   auto secs = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
   if (hipSetDevice(device) != hipSuccess || hipFree(nullptr) != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
@@ -420,13 +419,13 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
   dText = nullptr; dCount = nullptr; dFirst = nullptr; dPS = nullptr;
   if (ps.flags != 0) {   // a line the device parser does not take: the host's tokeniser decides what every line means
     hipFree(dK); hipFree(dC);
-    if (timing) fprintf(stderr, "[talc-lib] the dump has lines that are not 'KMER count': parsing on the host\n");
+    if (sw.timing) fprintf(stderr, "[talc-lib] the dump has lines that are not 'KMER count': parsing on the host\n");
     return 1;
   }
-  if (timing) fprintf(stderr, "[talc-lib] dump parsed on the device: %.0f MB of text to the device in %.3f s (%d reader threads), %llu lines parsed in %.3f s\n",
+  if (sw.timing) fprintf(stderr, "[talc-lib] dump parsed on the device: %.0f MB of text to the device in %.3f s (%d reader threads), %llu lines parsed in %.3f s\n",
                       (double)size / 1e6, tUp, T, (unsigned long long)nlines, secs(t1));
   ds.nread += (int64_t)nlines; ds.nkept += (int64_t)ps.kept;
-  return build_table_from_device_arrays(dK, dC, nlines, ps.kept, p, device, out, 0.0, 0.0);
+  return build_table_from_device_arrays(dK, dC, nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
 }
 
 // Junction colouring (Jellyfish.cpp:273-290) on the staged device image: last line wins, both strands.
@@ -474,14 +473,14 @@ static int table_build_impl(const char* dump_path, const char* junction_path, co
   std::vector<uint32_t> counts;
   DumpStats ds;
   std::string why;
-  const bool timing = getenv("TALC_TIMING") != nullptr;   // (diagnostic: where a table build's wall time goes, on stderr)
+  const Switches sw = read_switches();   // (TALC_TIMING: where a table build's wall time goes, on stderr)
   const auto tb0 = std::chrono::steady_clock::now();
   talc_table* t = nullptr;
   int viaDevice = 1;   // > 0: not taken
   if (device >= 0) {
-    viaDevice = table_from_text_on_device(dump_path, p, device, &t, ds);
+    viaDevice = table_from_text_on_device(dump_path, p, device, &t, ds, sw);
     if (viaDevice < 0) return viaDevice;
-    if (viaDevice == 0 && timing)
+    if (viaDevice == 0 && sw.timing)
       fprintf(stderr, "[talc-lib] dump to table on the device %.3f s (%llu lines)\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count(), (unsigned long long)ds.nread);
   }
   if (viaDevice > 0) {
@@ -490,7 +489,7 @@ static int table_build_impl(const char* dump_path, const char* junction_path, co
     const auto tb1 = std::chrono::steady_clock::now();
     rc = (device >= 0) ? talc_table_from_arrays_device(kmers.data(), counts.data(), kmers.size(), p, device, &t)
                        : talc_table_from_arrays(kmers.data(), counts.data(), kmers.size(), p, &t);
-    if (timing) {
+    if (sw.timing) {
       const auto tb2 = std::chrono::steady_clock::now();
       fprintf(stderr, "[talc-lib] dump parse %.3f s (%llu lines), table build on %s %.3f s\n", std::chrono::duration<double>(tb1 - tb0).count(),
               (unsigned long long)ds.nread, device >= 0 ? "the device (incl. its first HIP call)" : "the host", std::chrono::duration<double>(tb2 - tb1).count());
@@ -541,10 +540,8 @@ int talc_table_decolour_repeats(talc_table* t) {
   return TALC_OK;
 }
 uint64_t talc_table_size(const talc_table* t) { return t ? t->h.nkmers : 0; }
-// bits per k-mer of the presence filter (config 2: 10 bits 2.64 ms, 14 2.49, 20 2.39, 28 2.34 for k_coverage; TALC_FILTER_BITS: experiments)
-static uint64_t filter_words_for(uint64_t nkmers) {
-  uint64_t bitsPerKmer = 20;
-  if (const char* e = getenv("TALC_FILTER_BITS")) bitsPerKmer = std::min<uint64_t>(64, std::max<uint64_t>(4, strtoull(e, nullptr, 10)));
+// presence-filter words for `bitsPerKmer` bits per k-mer (default 20; config 2's k_coverage: 10 bits 2.64 ms, 14 2.49, 20 2.39, 28 2.34)
+static uint64_t filter_words_for(uint64_t nkmers, uint64_t bitsPerKmer) {
   return (std::max<uint64_t>(64, (nkmers * bitsPerKmer + 63) / 64) + 7) & ~7ull;   // whole 64-byte blocks
 }
 // device bytes of one uploaded copy (what talc_table_upload allocated), or — before any upload — of the copy an upload
@@ -555,12 +552,13 @@ uint64_t talc_table_device_bytes(const talc_table* t) {
     const DeviceCopy& dc = t->h.dev.begin()->second;
     return 2 * t->h.capacity * sizeof(Bucket) + dc.filterWords * 8 + (dc.walkRight ? 2 * t->h.capacity * sizeof(WalkEntry) : 0);
   }
-  return 2 * t->h.capacity * sizeof(Bucket) + filter_words_for(t->h.nkmers) * 8;
+  return 2 * t->h.capacity * sizeof(Bucket) + filter_words_for(t->h.nkmers, read_switches().filterBits) * 8;
 }
 
 int talc_table_upload(talc_table* t, int device) {
   if (!t) return fail(TALC_ERR_INVALID, "null table");
   if (t->h.dev.count(device)) return TALC_OK;
+  const Switches sw = read_switches();
   const uint64_t bytes = t->h.capacity * sizeof(Bucket);
   const bool adopt = (t->stagedDev == device);
   // everything this call allocates is freed again when a later step fails; an adopted image stays the table's staged one
@@ -588,7 +586,7 @@ int talc_table_upload(talc_table* t, int device) {
     HIPCHK(hipMemcpy(dc.left, t->h.left, bytes, hipMemcpyHostToDevice));
   }
   {   // presence filter, from the RIGHT table
-    dc.filterWords = filter_words_for(t->h.nkmers);
+    dc.filterWords = filter_words_for(t->h.nkmers, sw.filterBits);
     HIPCHK(hipMalloc((void**)&dc.filter, dc.filterWords * 8));
     HIPCHK(hipMemset(dc.filter, 0, dc.filterWords * 8));
     if (t->h.capacity)
@@ -605,17 +603,16 @@ int talc_table_upload(talc_table* t, int device) {
   // walk tables (WalkEntry, talc_common.h).  Built when they leave the correction batches and their scratch a reserve
   // (64 GB, or a quarter of the device if that is less).  TALC_WALK=0 turns them off, TALC_WALK=1 insists.
   {
-    const char* env = getenv("TALC_WALK");
     const uint64_t wbytes = t->h.capacity * sizeof(WalkEntry);
     size_t freeB = 0, totalB = 0;
     HIPCHK(hipMemGetInfo(&freeB, &totalB));
     const uint64_t reserve = std::min<uint64_t>(64ull << 30, (uint64_t)totalB / 4);
-    const bool want = env ? atoi(env) != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
+    const bool want = sw.walk >= 0 ? sw.walk != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
     if (want && t->h.capacity) {
       if (hipMalloc((void**)&dc.walkRight, wbytes) != hipSuccess || hipMalloc((void**)&dc.walkLeft, wbytes) != hipSuccess) {
         (void)hipGetLastError();
         hipFree(dc.walkRight); dc.walkRight = dc.walkLeft = nullptr;
-        if (env) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
+        if (sw.walk == 1) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
       } else {
         const uint64_t nthr = 2 * t->h.capacity;
         hipLaunchKernelGGL(k_build_walk, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, dc.right, dc.left, t->h.capacity,
@@ -773,6 +770,7 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   HIPCHK(hipSetDevice(device));
   talc_ctx* c = new talc_ctx();
   c->table = t; c->p = *p; c->device = device; c->view = v;
+  c->sw = read_switches();
   memset(&c->timing, 0, sizeof c->timing);
   DevParams& d = c->dp;
   d.K = p->k; d.MIN_COUNT = p->min_count; d.ALPHA = p->alpha; d.WINDOW = p->window_size; d.ERR = p->sr_error_rate;
@@ -782,12 +780,7 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   d.CHECK_INTERVAL = p->check_interval; d.FAILURE_RATE = p->allowed_failure_rate;
   d.MAX_BORDER_FAILURES = p->max_nb_border_failures; d.MAX_BORDER_LEN = p->max_border_length;
   d.costEdgeLin = 2800; d.costEdgeQuad = 135;
-  if (const char* e = getenv("TALC_COST_LIN")) d.costEdgeLin = (uint32_t)strtoul(e, nullptr, 10);     // (tuning runs)
-  if (const char* e = getenv("TALC_COST_QUAD")) d.costEdgeQuad = (uint32_t)strtoul(e, nullptr, 10);
   d.costGapQuad = 10; d.costGapFork = 200; d.costGapCap = 900; d.pad_ = 0;   // (profiles/r03/cost_sweep.txt)
-  if (const char* e = getenv("TALC_COST_GAPQ")) d.costGapQuad = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("TALC_COST_GAPFORK")) d.costGapFork = (uint32_t)strtoul(e, nullptr, 10);
-  if (const char* e = getenv("TALC_COST_GAPCAP")) d.costGapCap = (uint32_t)strtoul(e, nullptr, 10);
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
   HIPCHK(hipMalloc((void**)&c->d_queue, kQueueWords * sizeof(uint32_t)));
@@ -864,12 +857,6 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   }
   b->h_koff[n_reads] = ko; b->h_regoff[n_reads] = ro; b->h_outoff[n_reads] = oo;
   b->n_kmers = ko; b->out_capacity = oo;
-  // longest reads first: the path-search queue is consumed in this order
-  b->h_order.resize(n_reads);
-  std::iota(b->h_order.begin(), b->h_order.end(), 0u);
-  std::stable_sort(b->h_order.begin(), b->h_order.end(), [&](uint32_t x, uint32_t y) {
-    return (offsets[x + 1] - offsets[x]) > (offsets[y + 1] - offsets[y]);
-  });
   hipStream_t s = c->stream;
   int rc;
   if ((rc = ctx_alloc(c, (void**)&b->d_raw, std::max<uint64_t>(b->n_bases, 1)))) return rc;
@@ -884,7 +871,7 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   if ((rc = up(c, &b->d_tile_start, b->h_tile_start, s))) return rc;
   if ((rc = up(c, &b->d_chunk_read, b->h_chunk_read, s))) return rc;
   if ((rc = up(c, &b->d_chunk_start, b->h_chunk_start, s))) return rc;
-  if ((rc = up(c, &b->d_order, b->h_order, s))) return rc;
+  if ((rc = ctx_alloc(c, (void**)&b->d_order, std::max<uint32_t>(n_reads, 1) * sizeof(uint32_t)))) return rc;   // (run_pipeline orders the queue)
   if ((rc = ctx_alloc(c, (void**)&b->d_cov, std::max<uint64_t>(b->n_kmers, 1) * sizeof(uint2)))) return rc;
   if ((rc = ctx_alloc(c, (void**)&b->d_covw, cov_words_total(b->n_kmers, n_reads) * sizeof(CovWord)))) return rc;
   if ((rc = ctx_alloc(c, (void**)&b->d_nin, std::max<uint32_t>(n_reads, 1) * sizeof(int32_t)))) return rc;

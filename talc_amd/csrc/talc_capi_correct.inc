@@ -1,15 +1,6 @@
 // talc_capi_correct.inc — included by talc_capi.hip inside extern "C": the correction pipeline
 // (coverage -> structure -> search -> pack) and the fetch / trace entry points.
 
-static uint32_t g_slots_override = 0;   // test hook: TALC_SEARCH_SLOTS env
-
-// First pass: bytes of the arena the Trail buffers of a search are cut from (TALC_SEQ_ARENA: a test hook — a small
-// value sends the long gaps through the retry pass); 0 = the default of make_caps.
-static uint32_t first_pass_arena_limit() {
-  const char* e = getenv("TALC_SEQ_ARENA");
-  return (e && atoi(e) > 0) ? (uint32_t)atoi(e) : 0u;
-}
-
 // every k_search launch of the process gets a number of its own: the alignment rows a wave keeps in its scratch carry
 // it, so that a row left by an earlier launch (or by another wave's slot, when the layout has changed) is never taken
 // for one of this launch's (24 bits + a high byte no matrix value can have; it wraps after 16 M launches)
@@ -17,30 +8,15 @@ static uint32_t next_launch_stamp() {
   static std::atomic<uint32_t> launches{0};
   return 0x01000000u + (launches.fetch_add(1) & 0xFFFFFFu);
 }
-// (diagnostic switches: bit 0, scoreBridges aligns every Trail from scratch; bit 1, forks go through the generic step; bit 2, the
-//  generic bridge step makes its children one at a time; bit 3, a test hook of the edge tasks)
-static uint32_t search_flags() {
-  return (getenv("TALC_NO_ROWS") ? 1u : 0u) | (getenv("TALC_NO_FORKSTEP") ? 2u : 0u) | (getenv("TALC_CHILDREN_SEQ") ? 4u : 0u) |
-         0u;
-}
-// Edge tasks (talc_kernels_search.h): the thresholds, with their tuning switches
-static uint32_t env_u32(const char* name, long dflt, long lo, long hi) {
-  const char* e = getenv(name);
-  return (uint32_t)std::min<long>(std::max<long>(e ? atol(e) : dflt, lo), hi);
-}
 // the boxes of the first pass: a candidate of an edge search is at most its Trail (K + 1.2 gap + 2 K bases) followed by the
 // rest of its reference (gap + K), gap <= MAX_BORDER_LEN + what the start anchors lie inside their region (a longer one
 // sends the edge back to the in-order search)
 static void ensure_edge_boxes(talc_ctx* c, Stage& st) {
-  const char* sw0 = getenv("TALC_EDGE_TASKS");
-  if (getenv("TALC_NO_EDGE_TASKS") || (sw0 && atoi(sw0) == 0) || c->p.max_start_anchors < 2 || c->p.max_start_anchors > EDGE_BOX_ANCHORS) {
-    if (st.boxes) { hipFree(st.boxes); st.boxes = nullptr; st.boxes_bytes = 0; }
-    return;
-  }
   const uint64_t gap = (uint64_t)c->p.max_border_length + 256;
   const uint32_t seqCap = (uint32_t)align_up((uint64_t)(2.2 * (double)gap) + 4ull * c->p.k + 64, 16);
   const uint64_t need = (uint64_t)st.n_slots * edge_box_bytes(seqCap) + (uint64_t)st.n_slots * 4;
-  if (seqCap > (1u << 16) || need > (1ull << 30)) {   // (a border length in the tens of kilobases: not worth a gigabyte)
+  if (c->sw.edgeTasks == 0 || c->p.max_start_anchors < 2 || c->p.max_start_anchors > EDGE_BOX_ANCHORS ||
+      seqCap > (1u << 16) || need > (1ull << 30)) {   // (a border length in the tens of kilobases: not worth a gigabyte)
     if (st.boxes) { hipFree(st.boxes); st.boxes = nullptr; st.boxes_bytes = 0; }
     return;
   }
@@ -53,19 +29,15 @@ static void ensure_edge_boxes(talc_ctx* c, Stage& st) {
 }
 
 static int ensure_stage(talc_ctx* c, Stage& st, uint32_t maxLen, uint32_t scale, uint32_t n_work) {
-  const char* tiny = getenv("TALC_TEST_TINY_CAPS");
-  SearchCaps caps = make_caps(maxLen, c->p.k, scale, scale == 1 ? first_pass_arena_limit() : 0, scale == 1 && tiny && atoi(tiny) > 0);
-  if (const char* pad = getenv("TALC_SLOT_PAD")) caps.slotBytes += (uint64_t)(atoll(pad) > 0 ? atoll(pad) : 0) / 256 * 256;   // (experiments: the stride between the waves' scratch slots)
+  const SearchCaps caps = make_caps(maxLen, c->p.k, scale, scale == 1 ? c->sw.seqArena : 0, scale == 1 && c->sw.tinyCaps);
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, c->device));
   // (a retry stage's slots are 8 / 64 times a first-pass slot: one wave per SIMD at x 8 — 28 GB for 2 kb reads, halved below
   //  until it fits —, one per CU at x 64; a batch of nearly clean reads over a branching graph retries by the thousand)
   uint32_t want = (uint32_t)prop.multiProcessorCount * (scale == 1 ? 4u * TALC_SEARCH_WAVES_PER_SIMD : scale <= 8 ? 4u : 1u);
-  const char* env = getenv("TALC_SEARCH_SLOTS");
-  if (env && atoi(env) > 0) want = (uint32_t)atoi(env);
-  if (g_slots_override) want = g_slots_override;
+  if (c->sw.searchSlots) want = c->sw.searchSlots;
   const uint32_t wantSlots = std::max<uint32_t>(1, std::min<uint32_t>(want, n_work));
-  if (scale > 1 && getenv("TALC_TEST_FAIL_RETRY_ALLOC"))   // test hook: the retry stage does not fit
+  if (scale > 1 && c->sw.failRetryAlloc)   // test hook: the retry stage does not fit
     return fail(TALC_ERR_NOMEM, "TALC_TEST_FAIL_RETRY_ALLOC: the retry stage is refused");
   // keep the scratch below ~60 % of what is free; the context's cached batch buffers are given back first when that
   // would cost slots (or the allocation itself fails)
@@ -103,13 +75,60 @@ struct TraceHost {
   uint32_t cap = 0, poolCap = 0;
 };
 
-static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead, int traceSteps) {
+#ifdef TALC_PROF
+// the profile build's report of a corrected batch (TALC_PROF_READS / _PRINT / _SLOW); `counters`: c->d_counters[0 .. 127]
+static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
+  if (!c->sw.profReads.empty()) {   // one row per read (its last pass): the cost estimate, its inputs, the search's duration
+    if (FILE* f = fopen(c->sw.profReads.c_str(), "w")) {
+      fprintf(f, "read\tlen\tstatus\tregions\tcost_est\thead\ttail\tgap_sum\tfork\tsolid\tticks_100MHz\tgap_sq\tgap_max\tsq640\tsteps\tedge_ticks\tanchors\tanchor_max\tstart\tbridges\tbridge_max\n");
+      for (uint32_t r = 0; r < b->n_reads; ++r) {
+        const ReadState& st = b->h_state[r];
+        fprintf(f, "%u\t%llu\t%d\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", r, (unsigned long long)(b->h_offsets[r + 1] - b->h_offsets[r]), st.status,
+                st.nRegions, st.costEst, st.pfHead, st.pfTail, st.pfGapSum, st.pfFork, st.pfSolid, st.pfTicks, st.pfGapSq, st.pfGapMax, st.pfShortReg, st.pfSteps, st.pfEdgeTicks, st.pfAnchors, st.pfAnchorMax, st.pfStart, st.pfBridges, st.pfBridgeMax);
+      }
+      fclose(f);
+    }
+  }
+  if (!c->sw.profPrint) return TALC_OK;
+  static const char* nm[] = TALC_PF_NAMES;   // starred entries are totals that contain other entries
+  const uint64_t tot = counters[2 + PF_TOTAL];
+  for (int i = 0; i < PF_N; ++i) fprintf(stderr, "[prof] %-10s %14llu cycles  %5.1f%%\n", nm[i], (unsigned long long)counters[2 + i], tot ? 100.0 * counters[2 + i] / tot : 0.0);
+  if (counters[127] > counters[126] && c->stage.n_slots)
+    fprintf(stderr, "[prof] wave utilisation: %.1f%% of %u waves x %.3f ms (first start to last end, 100 MHz counter)\n",
+            100.0 * (double)counters[125] / ((double)(counters[127] - counters[126]) * c->stage.n_slots), c->stage.n_slots,
+            (double)(counters[127] - counters[126]) / 1e5);
+  if (counters[124] != ~0ull && counters[124] > counters[126])
+    fprintf(stderr, "[prof] the work queue ran dry %.3f ms after the first wave's start\n", (double)(counters[124] - counters[126]) / 1e5);
+  if (c->sw.profSlow && c->stage.n_slots) {   // the record of every wave's last read: the waves that end last
+    const uint32_t nw = std::min<uint32_t>(c->stage.n_slots, 8192);
+    std::vector<uint64_t> lg(2 * (size_t)nw);
+    HIPCHK(hipMemcpy(lg.data(), c->d_counters + 128, lg.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> idx(nw);
+    for (uint32_t i = 0; i < nw; ++i) idx[i] = i;
+    const uint32_t t0 = (uint32_t)counters[126];
+    auto endOf = [&](uint32_t w) { return (uint32_t)((uint32_t)lg[2 * w + 1] - t0); };
+    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b2) { return endOf(a) > endOf(b2); });
+    fprintf(stderr, "[slow] wave end times (ms), deciles from the last:");
+    for (int d = 0; d <= 10; ++d) fprintf(stderr, " %.1f", endOf(idx[std::min<uint32_t>(nw - 1, (uint32_t)((uint64_t)d * nw / 10))]) / 1e5);
+    fprintf(stderr, "\n");
+    for (uint32_t i = 0; i < std::min<uint32_t>(nw, 24); ++i) {
+      const uint32_t w = idx[i];
+      const uint32_t qi = (uint32_t)(lg[2 * w] >> 32), r = (uint32_t)lg[2 * w], st = (uint32_t)(lg[2 * w + 1] >> 32) - t0;
+      const uint64_t L = (b->h_offsets.empty() || r >= b->n_reads) ? 0 : b->h_offsets[r + 1] - b->h_offsets[r];
+      fprintf(stderr, "[slow] wave %5u ends %8.3f ms: last read %7u (queue %7u, len %6llu) started %8.3f ms\n", w, endOf(w) / 1e5, r, qi,
+              (unsigned long long)L, st / 1e5);
+    }
+  }
+  return TALC_OK;
+}
+#endif
+
+static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int rc;
-  TraceBuf tb;
-  memset(&tb, 0, sizeof tb);
-  if (th) { tb.recs = th->d_recs; tb.nrec = th->d_nrec; tb.cap = th->cap; tb.pool = th->d_pool; tb.npool = th->d_npool; tb.poolCap = th->poolCap; tb.steps = traceSteps; }
+  TraceBuf tb = {};
+  if (th) { tb.recs = th->d_recs; tb.nrec = th->d_nrec; tb.cap = th->cap; tb.pool = th->d_pool; tb.npool = th->d_npool; tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   HIPCHK(hipEventRecord(c->ev[0], s));
@@ -123,20 +142,15 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
                        b->d_cov, b->d_covw, b->d_nin, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->n_reads, tb, traceRead, c->d_hist + 1024);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[3], s));
-  // ---- the work queue: heaviest reads first, by k_structure's estimate (TALC_ORDER=length keeps the batch's own order,
-  // longest read first)
-  {
-    const char* oe = getenv("TALC_ORDER");
-    if (b->n_reads && !(oe && !strcmp(oe, "length"))) {
-      HIPCHK(hipMemsetAsync(c->d_hist, 0, 1024 * sizeof(uint32_t), s));
-      const unsigned nb = (b->n_reads + 255) / 256;
-      const char* gs = getenv("TALC_ORDER_GAP_SCALE");   // (tuning runs: the gap scale in 1/256, instead of the one from the batch's fork share)
-      hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, c->d_hist + 1024, (uint32_t)(gs && atoi(gs) > 0 ? atoi(gs) : 0));
-      hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, c->d_hist + 1024);
-      hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, s, c->d_hist);
-      hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, b->d_order, c->d_hist + 1024);
-      HIPCHK(hipGetLastError());
-    }
+  // ---- the work queue: heaviest reads first, by k_structure's estimate
+  if (b->n_reads) {
+    HIPCHK(hipMemsetAsync(c->d_hist, 0, 1024 * sizeof(uint32_t), s));
+    const unsigned nb = (b->n_reads + 255) / 256;
+    hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, c->d_hist + 1024);
+    hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, c->d_hist + 1024);
+    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, s, c->d_hist);
+    hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, b->d_order, c->d_hist + 1024);
+    HIPCHK(hipGetLastError());
   }
   // ---- search, first pass
   HIPCHK(hipMemsetAsync(c->d_queue, 0, kQueueWords * sizeof(uint32_t), s));
@@ -146,24 +160,19 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   if (b->n_reads) {
     if ((rc = ensure_stage(c, c->stage, b->max_len, 1, b->n_reads))) return rc;
     ensure_edge_boxes(c, c->stage);
-    EdgeTaskArgs ea;
-    memset(&ea, 0, sizeof ea);
+    EdgeTaskArgs ea = {};
     if (c->stage.boxes) {   // the claim counters sit behind the boxes
       ea.boxes = c->stage.boxes;
       ea.avail = (uint32_t*)(c->stage.boxes + (uint64_t)c->stage.n_slots * edge_box_bytes(c->stage.box_seq_cap));
       ea.seqCap = c->stage.box_seq_cap;
-      ea.minWeak = env_u32("TALC_EDGE_TASK_MIN", 150, 0, 1 << 30);
-      ea.heavy = env_u32("TALC_EDGE_TASK_HEAVY", 200, 0, 1 << 30);
-      ea.heavyRounds = env_u32("TALC_EDGE_TASK_ROUNDS", 0xFFFF, 0, 0xFFFF);
-      ea.lingerMod = env_u32("TALC_EDGE_LINGER_MOD", 16, 1, 1 << 20);
-      ea.test = getenv("TALC_TEST_EDGE_REDO") ? 1u : 0u;
-      const char* sw = getenv("TALC_EDGE_TASKS");   // 1: whatever the batch looks like (tests); unset: when its graph branches
-      ea.autoSwitch = (sw && atoi(sw) > 0) ? nullptr : c->d_hist + 1024 + 129;
+      ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
+      ea.lingerMod = c->sw.edgeLingerMod; ea.test = c->sw.edgeRedo ? 1u : 0u;
+      ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : c->d_hist + 1024 + 129;   // (switched on: whatever the batch looks like)
       HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)c->stage.n_slots * 4, s));
     }
     hipLaunchKernelGGL(k_search, dim3(c->stage.n_slots), dim3(64), 0, s, c->dp, c->view, c->stage.caps, b->d_codes, b->d_offsets,
                        b->d_koff, b->d_cov, b->d_covw, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->d_out, b->d_outoff, b->d_order,
-                       b->n_reads, c->d_queue, c->stage.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), search_flags(), ea);
+                       b->n_reads, c->d_queue, c->stage.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), ea);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(c->ev[4], s));
@@ -173,19 +182,6 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   // ---- retry passes for the reads whose scratch overflowed: buffers sized from the batch's longest read (a path
   // can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
   std::vector<uint32_t> retry;
-#ifdef TALC_PROF
-  if (const char* pr = getenv("TALC_PROF_READS")) {   // one row per read: the cost estimate, its inputs, the search's duration
-    if (FILE* f = fopen(pr, "w")) {
-      fprintf(f, "read\tlen\tstatus\tregions\tcost_est\thead\ttail\tgap_sum\tfork\tsolid\tticks_100MHz\tgap_sq\tgap_max\tsq640\tsteps\tedge_ticks\tanchors\tanchor_max\tstart\tbridges\tbridge_max\n");
-      for (uint32_t r = 0; r < b->n_reads; ++r) {
-        const ReadState& st = b->h_state[r];
-        fprintf(f, "%u\t%llu\t%d\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", r, (unsigned long long)(b->h_offsets[r + 1] - b->h_offsets[r]), st.status,
-                st.nRegions, st.costEst, st.pfHead, st.pfTail, st.pfGapSum, st.pfFork, st.pfSolid, st.pfTicks, st.pfGapSq, st.pfGapMax, st.pfShortReg, st.pfSteps, st.pfEdgeTicks, st.pfAnchors, st.pfAnchorMax, st.pfStart, st.pfBridges, st.pfBridgeMax);
-      }
-      fclose(f);
-    }
-  }
-#endif
   for (uint32_t r = 0; r < b->n_reads; ++r) if (b->h_state[r].overflow) retry.push_back(r);
   c->timing.n_retried = (uint32_t)retry.size();
   HIPCHK(hipEventRecord(c->ev[5], s));
@@ -208,7 +204,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
     HIPCHK(hipMemsetAsync(c->d_queue, 0, kQueueWords * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_search, dim3(big.n_slots), dim3(64), 0, s, c->dp, c->view, big.caps, b->d_codes, b->d_offsets, b->d_koff,
                        b->d_cov, b->d_covw, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->d_out, b->d_outoff, d_retry, (uint32_t)retry.size(),
-                       c->d_queue, big.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), search_flags(), EdgeTaskArgs());
+                       c->d_queue, big.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), EdgeTaskArgs());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state, b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -252,37 +248,9 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   c->timing.n_trail_steps = counters[0];
   c->timing.n_dp_cells = counters[1];
   c->timing.n_failed = nfail;
-  if (getenv("TALC_PROF_PRINT")) {
-    static const char* nm[] = TALC_PF_NAMES;   // starred entries are totals that contain other entries
-    const uint64_t tot = counters[2 + PF_TOTAL];
-    for (int i = 0; i < PF_N; ++i) fprintf(stderr, "[prof] %-10s %14llu cycles  %5.1f%%\n", nm[i], (unsigned long long)counters[2 + i], tot ? 100.0 * counters[2 + i] / tot : 0.0);
-    if (counters[127] > counters[126] && c->stage.n_slots)
-      fprintf(stderr, "[prof] wave utilisation: %.1f%% of %u waves x %.3f ms (first start to last end, 100 MHz counter)\n",
-              100.0 * (double)counters[125] / ((double)(counters[127] - counters[126]) * c->stage.n_slots), c->stage.n_slots,
-              (double)(counters[127] - counters[126]) / 1e5);
-    if (counters[124] != ~0ull && counters[124] > counters[126])
-      fprintf(stderr, "[prof] the work queue ran dry %.3f ms after the first wave's start\n", (double)(counters[124] - counters[126]) / 1e5);
-    if (getenv("TALC_PROF_SLOW") && c->stage.n_slots) {   // the profile build's record of every wave's last read: the waves that end last
-      const uint32_t nw = std::min<uint32_t>(c->stage.n_slots, 8192);
-      std::vector<uint64_t> lg(2 * (size_t)nw);
-      HIPCHK(hipMemcpy(lg.data(), c->d_counters + 128, lg.size() * 8, hipMemcpyDeviceToHost));
-      std::vector<uint32_t> idx(nw);
-      for (uint32_t i = 0; i < nw; ++i) idx[i] = i;
-      const uint32_t t0 = (uint32_t)counters[126];
-      auto endOf = [&](uint32_t w) { return (uint32_t)((uint32_t)lg[2 * w + 1] - t0); };
-      std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b2) { return endOf(a) > endOf(b2); });
-      fprintf(stderr, "[slow] wave end times (ms), deciles from the last:");
-      for (int d = 0; d <= 10; ++d) fprintf(stderr, " %.1f", endOf(idx[std::min<uint32_t>(nw - 1, (uint32_t)((uint64_t)d * nw / 10))]) / 1e5);
-      fprintf(stderr, "\n");
-      for (uint32_t i = 0; i < std::min<uint32_t>(nw, 24); ++i) {
-        const uint32_t w = idx[i];
-        const uint32_t qi = (uint32_t)(lg[2 * w] >> 32), r = (uint32_t)lg[2 * w], st = (uint32_t)(lg[2 * w + 1] >> 32) - t0;
-        const uint64_t L = (b->h_offsets.empty() || r >= b->n_reads) ? 0 : b->h_offsets[r + 1] - b->h_offsets[r];
-        fprintf(stderr, "[slow] wave %5u ends %8.3f ms: last read %7u (queue %7u, len %6llu) started %8.3f ms\n", w, endOf(w) / 1e5, r, qi,
-                (unsigned long long)L, st / 1e5);
-      }
-    }
-  }
+#ifdef TALC_PROF
+  if ((rc = prof_report(c, b, counters))) return rc;
+#endif
   b->corrected = true;
   if (nfail) {   // the batch is valid: those reads are passed through unchanged with status TALC_READ_ERROR
     fail(TALC_WARN_READ_ERRORS, "%u read(s) exhausted the device scratch even in the retry pass (status TALC_READ_ERROR)", nfail);
@@ -293,7 +261,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
 
 int talc_batch_correct(talc_ctx* c, talc_batch* b) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  return run_pipeline(c, b, nullptr, 0xFFFFFFFFu, 0);
+  return run_pipeline(c, b, nullptr, 0xFFFFFFFFu);
 }
 
 uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->corrected) ? b->h_dense_off[b->n_reads] : 0; }
@@ -382,8 +350,7 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
   HIPCHK(hipMalloc((void**)&th.d_nrec, 4)); HIPCHK(hipMalloc((void**)&th.d_npool, 4));
   HIPCHK(hipMalloc((void**)&th.d_pool, th.poolCap));
   HIPCHK(hipMemsetAsync(th.d_nrec, 0, 4, c->stream)); HIPCHK(hipMemsetAsync(th.d_npool, 0, 4, c->stream));   // (the null stream is not ordered with c->stream)
-  const char* st_env = getenv("TALC_TRACE_STEPS");
-  rc = run_pipeline(c, tbch, &th, 0, (st_env && atoi(st_env)) ? 1 : 0);
+  rc = run_pipeline(c, tbch, &th, 0);
   std::ostringstream os;
   uint32_t nrec = 0, npool = 0;
   HIPCHK(hipMemcpy(&nrec, th.d_nrec, 4, hipMemcpyDeviceToHost));

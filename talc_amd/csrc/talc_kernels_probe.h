@@ -113,9 +113,6 @@ __global__ void k_encode(const uint8_t* __restrict__ raw, uint8_t* __restrict__ 
 //     (LDS), the words' ranks are a 32-element scan, and every hit's pair goes to its rank at the start of the tile's
 //     stretch (talc_common.h: CovWord): only hits are written, contiguously.
 //  #{count > MIN_COUNT} (Read.cpp:190) is reduced per block and added to the read's counter.
-#ifndef TALC_COV_EXP
-#define TALC_COV_EXP 0   /* timing experiments (results wrong on purpose): bit 0 = no table traffic, bit 1 = no filter traffic */
-#endif
 #define COV_TILE TALC_COV_TILE
 #ifndef COV_THREADS
 #define COV_THREADS 64   /* one wave per tile of 512 positions: 32 independent tiles per CU, no wave waits at another's barrier (1.66 ms with 256 threads on 2048 positions, 1.37 ms so; config 2) */
@@ -271,11 +268,7 @@ k_coverage(TableView T, const uint8_t* __restrict__ codes, const uint64_t* __res
 #else
         const uint64_t idx = filter_block(h.x, nBlocks) * 8 + (h.y >> 29);
 #endif
-#if (TALC_COV_EXP & 2)   /* timing experiment: no filter traffic, the same share of survivors */
-        fword[it] = ((h.x & 15u) == 0u) ? ~0ULL : 0ULL; (void)idx;
-#else
         fword[it] = filter[idx];
-#endif
       }
     }
   }
@@ -308,13 +301,9 @@ k_coverage(TableView T, const uint8_t* __restrict__ codes, const uint64_t* __res
       const uint32_t p = s_queue[qi];
       const uint64_t kmer = window(p) >> kshift;
       uint32_t c = 0, j = 0, dL = 0;
-#if (TALC_COV_EXP & 1)   /* timing experiment: no table traffic */
-      (void)dL; (void)kmer;
-#else
       uint32_t degPrev;
       cov_count(T, kmer, min_count, c, j, dL, degPrev);
       if (p > 0) s_degR[p - 1] = (uint8_t)degPrev;
-#endif
       if (c != 0) {
         atomicOr(&s_bits[p >> 6], 1ull << (p & 63u));
         j |= kCovDegKnown | (dL << kCovDegLShift);

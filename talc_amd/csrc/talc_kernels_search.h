@@ -722,7 +722,7 @@ struct Wv {
   bool tracing, traceSteps;        // this read is the traced one / ... and its steps are wanted
   // (later additions go here, at the end: the offsets of the fields above are what the hot code's LDS addressing sees)
   unsigned long long* wideBloom;   // WIDE_BLOOM_WORDS words in HBM
-  int* rowPool;                    // ROW_ARENA_INTS ints in HBM (nullptr: every scoring aligns from scratch)
+  int* rowPool;                    // ROW_ARENA_INTS ints in HBM
   uint32_t searchNo;               // number of the current search of this wave (stamps the kept rows)
   uint32_t rowStride, rowAvail;    // the current search's records: ints per record, records (0: none)
   uint32_t wideMask;               // words - 1 of the current search's wide filter; 0: the LDS filter is in use
@@ -732,8 +732,6 @@ struct Wv {
   uint32_t LH, RH;                 // ... of the current LEFT / RIGHT region
   const uint32_t* headCov;         // the current read's kHeadCov dense counts
   uint8_t* refBuf;                 // the scratch buffer a search's reference is assembled in (ref points there, or into the read)
-  uint32_t noForkStep;             // TALC_NO_FORKSTEP=1 (k_search flags bit 1): forks go through the generic step (A/B switch)
-  uint32_t childrenByLane;         // 0 with TALC_CHILDREN_SEQ=1 (flags bit 2): the generic step makes its children one at a time
   // edge tasks (the start anchors of a head / tail search handed to waves that have run out of reads; nullptr: none)
   uint8_t* boxes; uint32_t* avail; uint32_t* qwords;
   uint32_t boxBytes, boxSeqCap, nSlots, mySlot, nWork, taskMinWeak;
@@ -743,7 +741,7 @@ struct Wv {
   uint32_t stealSeq;               // calls of edge_task_steal (which window of avail[] the next one looks at)
   unsigned long long moreCells, moreSteps;   // of the anchors run for other waves between this wave's reads
   uint32_t nanSeen;                // record_edge has seen a distance that is not a number (the fold is then order-dependent)
-  uint32_t taskTest;               // test hook (flags bit 3, TALC_TEST_EDGE_REDO): every anchor another wave has run is flagged for the in-order redo
+  uint32_t taskTest;               // test hook (TALC_TEST_EDGE_REDO): every anchor another wave has run is flagged for the in-order redo
 };
 
 enum { LOC_HEAD = 0, LOC_INNER = 1, LOC_TAIL = 2 };
@@ -1008,7 +1006,7 @@ TALC_D void rows_shape() {
   const uint32_t n = (uint32_t)uni((int)X.refLen);
   uint32_t stride = 0, avail = 0;
   const uint32_t sn = (uint32_t)uni((int)X.searchNo) + 1u;
-  if (X.rowPool != nullptr && n <= (uint32_t)ROW_MAX_REF && sn < 0x7FFF0u) {   // (a wave's half-millionth search of a launch goes without)
+  if (n <= (uint32_t)ROW_MAX_REF && sn < 0x7FFF0u) {   // (a wave's half-millionth search of a launch goes without)
     stride = (n + 2u + 3u) & ~3u;
     avail = min((uint32_t)NBUF, (uint32_t)ROW_ARENA_INTS / stride);
   }
@@ -2194,7 +2192,6 @@ TALC_D int step_bridge(int nCur, int len, uint32_t& stepCounter) {
   int nNew = 0;
   uint32_t pend = 0; int nPend = 0;   // this step's children, to be entered into the filter (bloom_flush)
   const bool complexIn = ((uint32_t)nCur > P.MAXB);
-  const bool byLane = uni((int)X.childrenByLane) != 0;
   for (int base = 0; base < nCur; base += 64) {
     const int tl = base + l;
     PROF_BEGIN();
@@ -2202,7 +2199,7 @@ TALC_D int step_bridge(int nCur, int len, uint32_t& stepCounter) {
     PROF_END(PF_PROBE);
     const int cnt = min(64, nCur - base);
     X.steps += (unsigned long long)cnt;
-    if (byLane && nCur > 1) {   // (one Trail: the sequential form is as quick, and a call saves and restores 17 registers)
+    if (nCur > 1) {   // (one Trail: the sequential form is as quick, and a call saves and restores 17 registers)
       PROF_BEGIN();
       const int nn = uni(bridge_children_by_lane(mine.tags, mine.nc[0], mine.nc[1], mine.nc[2], mine.nc[3], base, cnt, len, nNew));
       PROF_END(PF_CHILD);
@@ -2853,7 +2850,7 @@ TALC_DN int fork_step(int len_, uint32_t sc_, uint32_t PMAX_) {
   const int l = lane_id();
   const int len = uni(len_);
   const uint32_t sc = (uint32_t)uni((int)sc_), PMAX = (uint32_t)uni((int)PMAX_);
-  if (uni((int)X.traceSteps) != 0 || uni((int)X.noForkStep) != 0) return 0;
+  if (uni((int)X.traceSteps) != 0) return 0;
   if ((uint32_t)uni((int)P.MAXB) < 2u || (uint32_t)uni((int)P.MAX_INNER_PATHS) < 2u) return 0;
   const TrailRec r0 = tr_get(X.ia, 0);
   if (uni64(r0.nmask) != 0ull) return 0;
@@ -3693,7 +3690,7 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
          uint8_t* __restrict__ outAll,
          const uint64_t* __restrict__ outoff, const uint32_t* __restrict__ order, uint32_t n_work,
          uint32_t* __restrict__ queue, uint8_t* __restrict__ scratchAll, uint64_t* __restrict__ counters, TraceBuf trace,
-         uint32_t traceRead, uint32_t launchStamp, uint32_t flags, EdgeTaskArgs E) {
+         uint32_t traceRead, uint32_t launchStamp, EdgeTaskArgs E) {
   __shared__ uint32_t s_next;
   const int l = lane_id();
   uint8_t* slot = scratchAll + (uint64_t)blockIdx.x * C.slotBytes;
@@ -3708,10 +3705,8 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
   X.edgeLong = slot + C.o_edgeLong; X.edgeShort = slot + C.o_edgeShort; X.edgeTmp = slot + C.o_edgeTmp;
   X.dpG = (int*)(slot + C.o_dp);
   X.wideBloom = (unsigned long long*)(slot + C.o_wideBloom); X.wideMask = 0;
-  X.rowPool = (flags & 1u) ? nullptr : (int*)(slot + C.o_rowPool); X.rowStride = 0; X.rowAvail = 0;   // (flags bit 0: TALC_NO_ROWS)
+  X.rowPool = (int*)(slot + C.o_rowPool); X.rowStride = 0; X.rowAvail = 0;
   X.launchStamp = launchStamp;
-  X.noForkStep = (flags >> 1) & 1u;
-  X.childrenByLane = ((flags >> 2) & 1u) ^ 1u;
   // (over a graph that does not branch the queue's order alone keeps the waves busy 95 % of the launch, and the tasks'
   //  bookkeeping and the waves that stay cost config 2 0.7 %: the batch's fork share decides, k_order_scale)
   if (E.boxes != nullptr && E.autoSwitch != nullptr && *E.autoSwitch == 0u) E.boxes = nullptr;
@@ -3988,7 +3983,7 @@ TALC_D uint32_t order_bucket(const ReadState& st, uint32_t gapScale) {
   const uint32_t m = (e >= 5) ? ((c >> (e - 5)) & 31u) : ((c << (5 - e)) & 31u);
   return 1022u - min(1022u, (uint32_t)e * 32u + m);                  // heavy first
 }
-__global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batchStats, uint32_t fixedScale) {   // batchStats[128] := the gap scale, [129] := the graph branches
+__global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batchStats) {   // batchStats[128] := the gap scale, [129] := the graph branches
   const int l = lane_id();
   const unsigned long long fork = wave_sum_u64(batchStats[2 * l]), solid = wave_sum_u64(batchStats[2 * l + 1]);
   uint32_t scale = 256u;
@@ -3996,9 +3991,7 @@ __global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batch
     const unsigned long long perMille10 = fork * 10000ull / solid;   // fork share in 1/10000
     if (perMille10 > 120ull) scale = 256u + (uint32_t)min((perMille10 - 120ull) * 256ull / 100ull, 512ull);
   }
-  if (l == 0) batchStats[129] = scale > 256u ? 1u : 0u;   // (the edge tasks' switch)
-  if (fixedScale) scale = fixedScale;
-  if (l == 0) batchStats[128] = scale;
+  if (l == 0) { batchStats[128] = scale; batchStats[129] = scale > 256u ? 1u : 0u; }   // [129]: the edge tasks' switch
 }
 __global__ void k_order_hist(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ hist, const uint32_t* __restrict__ batchStats) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;

@@ -45,6 +45,7 @@
 #include <unistd.h>
 
 #include "talc_hip.h"
+#include "talc_switches.h"
 
 namespace {
 
@@ -386,6 +387,7 @@ int main(int argc, const char** argv) {
             << "******************************************************" << std::endl;
   std::cout << "[TALC]: Parsing arguments" << std::endl;
   Options o = parse(argc, argv);
+  const talc::Switches sw = talc::read_switches();   // (TALC_TIMING, TALC_FAKE_GPUS)
   const std::string outFile = o.outPrefix + ".fa", statFile = o.outPrefix + ".stats_basics.txt", logFile = o.outPrefix + ".log";
   outputConfig(o, statFile);          // Settings.cpp:122
   setBasicReadStatsHeader(statFile);  // main.cpp:204
@@ -478,7 +480,7 @@ int main(int argc, const char** argv) {
     ndev = nphys;
     // TALC_FAKE_GPUS=n (a rehearsal hook for one-GPU boxes): the sharder runs as if n GPUs were present, logical GPU d on
     // physical device d mod the real count — the same worker threads, contexts, dealing and ordered merge
-    if (const char* fk = getenv("TALC_FAKE_GPUS")) if (atoi(fk) > 0) ndev = atoi(fk);
+    if (sw.fakeGpus) ndev = (int)sw.fakeGpus;
     if (o.gpus > 0) ndev = std::min(ndev, o.gpus);
     for (int d = 0; d < std::min(ndev, nphys); ++d)
       if (talc_table_upload(table, d) != TALC_OK) { std::cerr << "talc: device error: " << talc_last_error() << "\n"; talc_table_destroy(table); return 2; }
@@ -664,7 +666,7 @@ int main(int argc, const char** argv) {
         const auto tu0 = std::chrono::steady_clock::now();
         formatChunk(*c, outb.p, oo.data());
         unpackUs += usSince(tu0);
-        if (const char* tv = getenv("TALC_TIMING")) if (tv[0] == '2') {   // per batch: where this worker's time went
+        if (sw.timing == 2) {   // per batch: where this worker's time went
           talc_timing tm; talc_ctx_get_timing(ctx, &tm);
           fprintf(stderr, "[talc-batch] reads %u: create+H2D %.3f s, correct %.3f s (kernels: coverage %.1f structure %.1f search %.1f retry %.1f ms), fetch %.3f s, text %.3f s\n",
                   n, std::chrono::duration<double>(tk0 - td0).count(), std::chrono::duration<double>(tf0 - tk0).count(), tm.coverage_ms, tm.structure_ms, tm.search_ms, tm.retry_ms,

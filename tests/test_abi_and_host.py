@@ -28,6 +28,19 @@ def test_library_exports_every_declared_symbol():
     assert L.talc_abi_version() == 1
 
 
+def test_environment_is_read_in_one_place_and_documented():
+    """talc_switches.h is the one file of the native sources that reads the environment, and the switches it reads are
+    exactly the ones INTEGRATION.md "Library switches" lists (one list item per switch, its name first)."""
+    csrc = os.path.join(ROOT, "talc_amd", "csrc")
+    readers = sorted(f for f in os.listdir(csrc) if "getenv" in open(os.path.join(csrc, f), errors="replace").read())
+    assert readers == ["talc_switches.h"]
+    read = set(re.findall(r'"(TALC_[A-Z0-9_]+)"', open(os.path.join(csrc, "talc_switches.h")).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("## Library switches", 1)[1].split("\n## ", 1)[0]
+    listed = set(re.findall(r"^- `(TALC_[A-Z0-9_]+)`", section, flags=re.M))
+    assert read and read == listed, (sorted(read - listed), sorted(listed - read))
+
+
 def test_params_default_match_reference_defaults():
     p = T.default_params()
     q = O.params()

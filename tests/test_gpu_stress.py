@@ -9,6 +9,7 @@ import pytest
 import parity_util as PU
 from stress_cases import CASES, half_corrected
 from talc_amd import build as B
+from talc_amd import lib as T
 from talc_amd.synth import Synth
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +56,9 @@ def test_edge_anchors_run_by_other_waves_match_oracle(monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        g_out, g_off, g_st = pair.ctx.correct(bases, offs)
+        ctx = T.Context(pair.ttab, pair.p, 0)   # (a context reads the switches when it is created)
+        g_out, g_off, g_st = ctx.correct(bases, offs)
+        ctx.close()
         sg = PU.seqs_of(g_out, g_off)
         bad = [i for i in range(len(so)) if so[i] != sg[i] or int(o_st[i]) != int(g_st[i])]
         assert not bad, (env, bad[:5])
