@@ -178,6 +178,33 @@ int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uin
                                  uint32_t* jcounts);
 void talc_table_destroy(talc_table* t);
 
+/* ---------------------------------------------------------------- (1b) k-mer counter ------
+ * Replaces the first two steps of the reference README's pipeline (README.md:37-49), `jellyfish count -m K` and
+ * `jellyfish dump -c`: the short reads are counted on GPU `device` and the table is built from the counts there, with no
+ * count file in between.  The contract (docs/kmer_counting.md): in every record, every window of K consecutive bytes
+ * that are all one of ACGTacgt counts once; any other byte ends the window; windows never span two records.  k-mers are
+ * directional and packed as above.  Counts are 32-bit: a count that would pass 2^32 - 1 fails the counter with
+ * TALC_ERR_INVALID, it never wraps.  One host thread uses a counter at a time (as a talc_ctx).  There is no host counter:
+ * without a GPU talc_counter_create fails with TALC_ERR_DEVICE. */
+typedef struct talc_counter talc_counter;   /* replaces `jellyfish count` + `dump -c` (README.md:37-49) */
+/* expected_distinct: a hint that sizes the first hash (0: small); the hash grows on the device as needed. */
+int talc_counter_create(const talc_params* p, int device, uint64_t expected_distinct, talc_counter** out);
+/* bases / offsets[n_reads+1] as for talc_batch_create.  Returns once the caller's buffers can be reused, without waiting
+ * for the kernel; the calls are ordered on the counter's stream.  TALC_ERR_NOMEM names the distinct count reached. */
+int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets, uint32_t n_reads);
+/* {windows counted, distinct k-mers, distinct k-mers with count >= p->min_count} (waits for the queued batches) */
+int talc_counter_stats(talc_counter* c, uint64_t stats[3]);
+/* the k-mers with count >= min_count, in no particular order; kmers == NULL: only *n_out.  TALC_ERR_CAPACITY (with
+ * *n_out set) when capacity < *n_out. */
+int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uint32_t* counts,
+                       uint64_t capacity, uint64_t* n_out);
+/* The k-mers with count >= p->min_count as a staged device table, as talc_table_build_device makes from a dump that
+ * lists the same counts (then junction colouring from junction_path if not NULL, and the homopolymer de-colouring);
+ * stats (may be NULL) = {distinct k-mers ("lines read"), kept, malformed junction lines}.  The counter is spent
+ * afterwards: only talc_counter_destroy may follow. */
+int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]);
+void talc_counter_destroy(talc_counter* c);
+
 /* ---------------------------------------------------------------- (2) per-read surface ---
  * Replaces, for a whole batch, the loop body of main.cpp:247-308:
  *   Read(id, seq); getLength()>K; reCoverage(); defineStructure2(); correct2(); getCorrSeq()

@@ -339,6 +339,28 @@ void makeRead(const Synth& S, uint64_t index, std::string& out) {
   }
 }
 
+// one short read of `len` bases from (seed, index): a transcript drawn with probability ~ length * lambda (the same
+// expression model as the dump's counts), a uniform start, substitutions at sub_rate and 'N' at n_rate; shorter when the
+// transcript is.  Its own generator stream: the long reads and the dump are unchanged.
+void makeShortRead(const Synth& S, uint64_t index, uint32_t len, double subRate, double nRate, std::string& out) {
+  out.clear();
+  Rng rng((S.sp.seed ^ 0x7A1C0005ULL) + 0x9E3779B97F4A7C15ULL * (index + 1));
+  const double w = rng.uniform() * S.tcum.back();
+  size_t t = (size_t)(std::lower_bound(S.tcum.begin(), S.tcum.end(), w) - S.tcum.begin());
+  if (t >= S.tlambda.size()) t = S.tlambda.size() - 1;
+  const uint64_t b = S.tstart[t], e = S.tstart[t + 1];
+  uint64_t L = len;
+  if (L > e - b) L = e - b;
+  const uint64_t start = b + rng.below(e - b - L + 1);
+  for (uint64_t i = start; i < start + L; ++i) {
+    const double r = rng.uniform();
+    uint8_t c = S.tx[i];
+    if (r < nRate) { out.push_back('N'); continue; }
+    if (r < nRate + subRate) c = (uint8_t)((c + 1 + rng.below(3)) & 3);
+    out.push_back(D[c]);
+  }
+}
+
 std::string unpack(uint64_t km, uint32_t K) {
   std::string s(K, 'A');
   for (uint32_t i = 0; i < K; ++i) s[K - 1 - i] = D[(km >> (2 * i)) & 3];
@@ -438,6 +460,45 @@ void synth_reads(void* h, uint64_t first, uint32_t n, char* bases, uint64_t* off
   uint64_t pos = 0;
   for (uint32_t i = 0; i < n; ++i) { offsets[i] = pos; pos += len[i]; }
   offsets[n] = pos;
+}
+
+// short reads [first, first+n) of `len` bases (makeShortRead), as synth_reads: bases=NULL gives the total in offsets[n]
+void synth_short_reads(void* h, uint64_t first, uint32_t n, uint32_t len, double sub_rate, double n_rate, char* bases,
+                       uint64_t* offsets) {
+  const Synth& S = *(Synth*)h;
+  if (bases) {   // offsets[] hold the result of the sizing call
+#pragma omp parallel
+    {
+      std::string r;
+#pragma omp for schedule(dynamic, 1024)
+      for (long i = 0; i < (long)n; ++i) { makeShortRead(S, first + (uint64_t)i, len, sub_rate, n_rate, r); memcpy(bases + offsets[i], r.data(), r.size()); }
+    }
+    return;
+  }
+  std::vector<uint64_t> ln(n);
+#pragma omp parallel
+  {
+    std::string r;
+#pragma omp for schedule(dynamic, 1024)
+    for (long i = 0; i < (long)n; ++i) { makeShortRead(S, first + (uint64_t)i, len, sub_rate, n_rate, r); ln[i] = r.size(); }
+  }
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < n; ++i) { offsets[i] = pos; pos += ln[i]; }
+  offsets[n] = pos;
+}
+
+// the same reads as FASTQ: "@sr_<index>", the sequence, "+", one 'I' per base
+int synth_write_short_fastq(void* h, const char* path, uint64_t first, uint32_t n, uint32_t len, double sub_rate, double n_rate) {
+  const Synth& S = *(Synth*)h;
+  FILE* f = fopen(path, "w");
+  if (!f) return -1;
+  std::string r, q;
+  for (uint32_t i = 0; i < n; ++i) {
+    makeShortRead(S, first + i, len, sub_rate, n_rate, r);
+    q.assign(r.size(), 'I');
+    fprintf(f, "@sr_%09llu\n%s\n+\n%s\n", (unsigned long long)(first + i), r.c_str(), q.c_str());
+  }
+  return fclose(f) == 0 ? 0 : -1;
 }
 
 int synth_write_dump(void* h, const char* path) {

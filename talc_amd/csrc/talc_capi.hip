@@ -17,6 +17,7 @@
 #include "talc_common.h"
 #include "talc_hip.h"
 #include "talc_kernels_build.h"
+#include "talc_kernels_count.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
 #include "talc_switches.h"
@@ -463,6 +464,29 @@ static int decolour_on_device(talc_table* t) {
   return TALC_OK;
 }
 
+// The tail every table build shares: junction colouring (Jellyfish.cpp:273-290), then the homopolymer de-colouring
+// (main.cpp:232); stats = {lines read, lines kept, malformed lines}.  Destroys t on failure, sets *out on success.
+static int table_finish(talc_table* t, const char* junction_path, const talc_params* p, DumpStats& ds, talc_table** out,
+                        int64_t stats[3]) {
+  int rc;
+  if (junction_path && junction_path[0]) {  // Jellyfish.cpp:273-290
+    std::vector<uint64_t> jk;
+    std::vector<int64_t> jc;
+    DumpStats js;
+    std::string why;
+    if (!parseDumpFile(junction_path, p->k, 0, false, jk, nullptr, &jc, js, &why)) {
+      talc_table_destroy(t);
+      return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", junction_path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
+    }
+    ds.nbad += js.nbad;
+    if ((rc = talc_table_colour(t, jk.data(), jc.data(), jk.size()))) { talc_table_destroy(t); return rc; }
+  }
+  if ((rc = talc_table_decolour_repeats(t))) { talc_table_destroy(t); return rc; }  // main.cpp:232
+  if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
+  *out = t;
+  return TALC_OK;
+}
+
 static int table_build_impl(const char* dump_path, const char* junction_path, const talc_params* p, int device, talc_table** out,
                             int64_t stats[3]) {
   int rc = check_params(p);
@@ -498,21 +522,7 @@ static int table_build_impl(const char* dump_path, const char* junction_path, co
   }
   std::vector<uint64_t>().swap(kmers);
   std::vector<uint32_t>().swap(counts);
-  if (junction_path && junction_path[0]) {  // Jellyfish.cpp:273-290
-    std::vector<uint64_t> jk;
-    std::vector<int64_t> jc;
-    DumpStats js;
-    if (!parseDumpFile(junction_path, p->k, 0, false, jk, nullptr, &jc, js, &why)) {
-      talc_table_destroy(t);
-      return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", junction_path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
-    }
-    ds.nbad += js.nbad;
-    if ((rc = talc_table_colour(t, jk.data(), jc.data(), jk.size()))) { talc_table_destroy(t); return rc; }
-  }
-  if ((rc = talc_table_decolour_repeats(t))) { talc_table_destroy(t); return rc; }  // main.cpp:232
-  if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
-  *out = t;
-  return TALC_OK;
+  return table_finish(t, junction_path, p, ds, out, stats);
 }
 
 int talc_table_build(const char* dump_path, const char* junction_path, const talc_params* p, talc_table** out,
@@ -954,6 +964,301 @@ int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint
   if (kmer_offsets) memcpy(kmer_offsets, b->h_koff.data(), (b->n_reads + 1) * 8);
   if (n_in_kmers && b->n_reads) HIPCHK(hipMemcpy(n_in_kmers, b->d_nin, b->n_reads * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
+}
+
+// ------------------------------------------------------------------ k-mer counter (talc_kernels_count.h)
+// Replaces `jellyfish count -m K` + `jellyfish dump -c` (README.md:37-49).  One stream; talc_counter_add copies the
+// caller's records into one of two page-locked staging buffers (one separator byte after each record), queues the copy
+// to the device and the count kernel, and returns.  The hash grows before a batch whose windows could push it past load
+// 0.7: the host keeps an upper bound of the distinct k-mers (the exact number at the last synchronisation plus every
+// window queued since) and reads the exact number back only when that bound says the batch might not fit.
+struct talc_counter {
+  talc_params p;
+  int device = 0;
+  Switches sw;
+  hipStream_t stream = nullptr;
+  CountSlot* tab = nullptr;
+  uint64_t cap = 0;
+  unsigned long long* dStats = nullptr;   // [0] windows counted, [1] distinct, [2] compaction output counter
+  uint32_t* dOverflow = nullptr;
+  uint8_t* dText = nullptr;
+  uint64_t dTextCap = 0;
+  char* stage[2] = {nullptr, nullptr};
+  uint64_t stageCap[2] = {0, 0};
+  hipEvent_t stageEv[2] = {nullptr, nullptr};
+  bool stageBusy[2] = {false, false};
+  int next = 0;
+  uint64_t distinctKnown = 0;   // exact distinct k-mers at the last synchronisation
+  uint64_t winsSince = 0;       // windows (upper bound) queued since then
+  uint64_t winsTotal = 0;       // windows (upper bound) over every batch: counts cannot pass it
+  bool spent = false;
+  // TALC_TIMING
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+  uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
+  double packS = 0, growS = 0;
+};
+
+static void counter_free_hash(talc_counter* c) {
+  hipFree(c->tab); c->tab = nullptr; c->cap = 0;
+  hipFree(c->dText); c->dText = nullptr; c->dTextCap = 0;
+}
+
+// the exact counters from the device (synchronises the stream); fails when a count has passed 2^32 - 1
+static int counter_sync(talc_counter* c, unsigned long long st[2]) {
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  uint32_t ovf = 0;
+  HIPCHK(hipMemcpy(st, c->dStats, 2 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&ovf, c->dOverflow, 4, hipMemcpyDeviceToHost));
+  if (ovf) return fail(TALC_ERR_INVALID, "a k-mer count passed 2^32 - 1 (counts are 32-bit); the counter is unusable");
+  c->distinctKnown = st[1];
+  c->winsSince = 0;
+  return TALC_OK;
+}
+
+// slots with count >= thr: how many (outK == nullptr) or the arrays themselves (device pointers of outCap entries)
+static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32_t* outC, uint64_t outCap, uint64_t* n) {
+  HIPCHK(hipMemsetAsync(c->dStats + 2, 0, 8, c->stream));
+  if (c->cap)
+    hipLaunchKernelGGL(k_count_compact, dim3((unsigned)((c->cap + 4 * 64 * kCompactRows - 1) / (4 * 64 * kCompactRows))), dim3(256), 0,
+                       c->stream, c->tab, c->cap, thr, outK, outC, outCap, c->dStats + 2);
+  HIPCHK(hipGetLastError());
+  unsigned long long v = 0;
+  HIPCHK(hipMemcpyAsync(&v, c->dStats + 2, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *n = v;
+  return TALC_OK;
+}
+
+// a larger power of two that holds `need` distinct k-mers at load <= 0.7; the old slots are rehashed on the device
+static int counter_grow(talc_counter* c, uint64_t need) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t nc = c->cap;
+  while ((double)need > 0.7 * (double)nc) nc *= 2;
+  CountSlot* nt = nullptr;
+  if (hipMalloc((void**)&nt, nc * sizeof(CountSlot)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TALC_ERR_NOMEM, "the k-mer counter cannot grow to %llu slots (%llu bytes) after %llu distinct k-mers",
+                (unsigned long long)nc, (unsigned long long)(nc * sizeof(CountSlot)), (unsigned long long)c->distinctKnown);
+  }
+  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, nt, nc);
+  hipLaunchKernelGGL(k_count_rehash, dim3((unsigned)((c->cap + 255) / 256)), dim3(256), 0, c->stream, c->tab, c->cap, nt, nc - 1);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess) {
+    hipFree(c->tab);
+    c->tab = nt; c->cap = nc;
+    ++c->nGrows;
+    c->growS += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return TALC_OK;
+  }
+  hipFree(nt);
+  return fail(TALC_ERR_DEVICE, "rehashing the k-mer counter: %s", hipGetErrorString(e));
+}
+
+int talc_counter_create(const talc_params* p, int device, uint64_t expected_distinct, talc_counter** out) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  const int ndev = talc_device_count();
+  if (device < 0 || device >= ndev)
+    return fail(TALC_ERR_DEVICE, "no GPU %d for the k-mer counter (%d visible); there is no host counter", device, ndev);
+  talc_counter* c = new talc_counter();
+  c->p = *p;
+  c->device = device;
+  c->sw = read_switches();
+  uint64_t cap = 1u << 16;   // 1 MiB without a hint
+  while (expected_distinct && (double)expected_distinct > 0.7 * (double)cap) cap *= 2;
+  auto bad = [&](hipError_t e, const char* what) {
+    talc_counter_destroy(c);
+    return fail(e == hipErrorOutOfMemory ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "k-mer counter: %s: %s", what, hipGetErrorString(e));
+  };
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess) return bad(e, "hipSetDevice");
+  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
+  for (int i = 0; i < 2; ++i)
+    if ((e = hipEventCreateWithFlags(&c->stageEv[i], hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+  if ((e = hipMalloc((void**)&c->tab, cap * sizeof(CountSlot))) != hipSuccess) return bad(e, "hash allocation");
+  c->cap = cap;
+  if ((e = hipMalloc((void**)&c->dStats, 4 * 8)) != hipSuccess) return bad(e, "counter allocation");
+  if ((e = hipMalloc((void**)&c->dOverflow, 4)) != hipSuccess) return bad(e, "counter allocation");
+  if ((e = hipMemsetAsync(c->dStats, 0, 4 * 8, c->stream)) != hipSuccess) return bad(e, "hipMemset");
+  if ((e = hipMemsetAsync(c->dOverflow, 0, 4, c->stream)) != hipSuccess) return bad(e, "hipMemset");
+  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->stream, c->tab, cap);
+  if ((e = hipGetLastError()) != hipSuccess) return bad(e, "k_count_init");
+  *out = c;
+  return TALC_OK;
+}
+
+int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets, uint32_t n_reads) {
+  if (!c || (n_reads && (!bases || !offsets))) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (!n_reads) return TALC_OK;
+  const uint32_t K = c->p.k;
+  const uint64_t o0 = offsets[0];
+  uint64_t wins = 0;
+  for (uint32_t r = 0; r < n_reads; ++r) {
+    if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must not decrease (read %u)", r);
+    const uint64_t L = offsets[r + 1] - offsets[r];
+    wins += L >= K ? L - K + 1 : 0;
+  }
+  const uint64_t nbytes = offsets[n_reads] - o0 + n_reads;   // one separator after each record
+  HIPCHK(hipSetDevice(c->device));
+  // growth: the bound first, the exact number only when the bound says the batch might not fit
+  if ((double)(c->distinctKnown + c->winsSince + wins) > 0.7 * (double)c->cap) {
+    unsigned long long st[2];
+    int rc = counter_sync(c, st);
+    if (rc) return rc;
+    if ((double)(c->distinctKnown + wins) > 0.7 * (double)c->cap && (rc = counter_grow(c, c->distinctKnown + wins))) return rc;
+  }
+  // staging buffer: free once the copy that last read it is done
+  const auto tp0 = std::chrono::steady_clock::now();
+  const int b = c->next;
+  c->next ^= 1;
+  if (c->stageBusy[b]) { HIPCHK(hipEventSynchronize(c->stageEv[b])); c->stageBusy[b] = false; }
+  if (c->stageCap[b] < nbytes) {
+    if (c->stage[b]) { hipHostFree(c->stage[b]); c->stage[b] = nullptr; c->stageCap[b] = 0; }
+    const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
+    if (hipHostMalloc((void**)&c->stage[b], want, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      c->stage[b] = nullptr;
+      return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want);
+    }
+    c->stageCap[b] = want;
+  }
+  char* dst = c->stage[b];
+#pragma omp parallel for schedule(static) if (n_reads > 100000)
+  for (long r = 0; r < (long)n_reads; ++r) {
+    const uint64_t at = offsets[r] - o0 + (uint64_t)r;
+    memcpy(dst + at, bases + offsets[r], offsets[r + 1] - offsets[r]);
+    dst[at + offsets[r + 1] - offsets[r]] = '\n';
+  }
+  c->packS += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
+  if (c->dTextCap < nbytes) {   // (the previous kernel may still read the old buffer)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    hipFree(c->dText); c->dText = nullptr; c->dTextCap = 0;
+    const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
+    if (hipMalloc((void**)&c->dText, want) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes for a batch of the k-mer counter (%llu distinct k-mers so far)",
+                  (unsigned long long)want, (unsigned long long)c->distinctKnown);
+    }
+    c->dTextCap = want;
+  }
+  HIPCHK(hipMemcpyAsync(c->dText, dst, nbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(c->stageEv[b], c->stream));
+  c->stageBusy[b] = true;
+  c->winsTotal += wins;
+  const bool checked = c->winsTotal >= 0xFFFFFFFFull;   // below that no count can reach 2^32
+  const uint64_t nblk = (nbytes + kCountTile - 1) / kCountTile;
+  if (nblk >= (1ull << 31)) return fail(TALC_ERR_INVALID, "batch of %llu bytes is too large", (unsigned long long)nbytes);
+  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  if (c->sw.timing && hipEventCreate(&ev.first) == hipSuccess && hipEventCreate(&ev.second) == hipSuccess)
+    HIPCHK(hipEventRecord(ev.first, c->stream));
+  if (checked)
+    hipLaunchKernelGGL(k_count_batch<true>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText, nbytes, K, c->tab,
+                       c->cap - 1, c->dStats, c->dOverflow);
+  else
+    hipLaunchKernelGGL(k_count_batch<false>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText, nbytes, K, c->tab,
+                       c->cap - 1, c->dStats, c->dOverflow);
+  HIPCHK(hipGetLastError());
+  if (ev.second) { HIPCHK(hipEventRecord(ev.second, c->stream)); c->kev.push_back(ev); }
+  c->winsSince += wins;
+  ++c->nBatches;
+  c->nBytes += nbytes;
+  return TALC_OK;
+}
+
+int talc_counter_stats(talc_counter* c, uint64_t stats[3]) {
+  if (!c || !stats) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  unsigned long long st[2];
+  int rc = counter_sync(c, st);
+  if (rc) return rc;
+  uint64_t kept = 0;
+  if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept))) return rc;
+  stats[0] = st[0]; stats[1] = st[1]; stats[2] = kept;
+  return TALC_OK;
+}
+
+int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uint32_t* counts, uint64_t capacity, uint64_t* n_out) {
+  if (!c || (kmers && !counts)) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  unsigned long long st[2];
+  int rc = counter_sync(c, st);
+  if (rc) return rc;
+  uint64_t n = 0;
+  if ((rc = counter_compact(c, min_count, nullptr, nullptr, 0, &n))) return rc;
+  if (n_out) *n_out = n;
+  if (!kmers) return TALC_OK;
+  if (capacity < n) return fail(TALC_ERR_CAPACITY, "%llu k-mers need the output arrays' room, %llu given", (unsigned long long)n,
+                                (unsigned long long)capacity);
+  uint64_t* dK = nullptr;
+  uint32_t* dC = nullptr;
+  auto drop = [&]() { hipFree(dK); hipFree(dC); };
+  hipError_t e = hipMalloc((void**)&dK, std::max<uint64_t>(n, 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&dC, std::max<uint64_t>(n, 1) * 4);
+  if (e != hipSuccess) { (void)hipGetLastError(); drop(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu k-mers for the fetch", (unsigned long long)n); }
+  uint64_t got = 0;
+  if ((rc = counter_compact(c, min_count, dK, dC, n, &got))) { drop(); return rc; }
+  if (got != n) { drop(); return fail(TALC_ERR_STATE, "the counter changed between two compactions (%llu, %llu)", (unsigned long long)n, (unsigned long long)got); }
+  e = hipMemcpy(kmers, dK, n * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(counts, dC, n * 4, hipMemcpyDeviceToHost);
+  drop();
+  if (e != hipSuccess) return fail(TALC_ERR_DEVICE, "copying the counts to the host: %s", hipGetErrorString(e));
+  return TALC_OK;
+}
+
+int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]) {
+  if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned long long st[2];
+  int rc = counter_sync(c, st);
+  if (rc) return rc;
+  const auto t1 = std::chrono::steady_clock::now();
+  uint64_t kept = 0;
+  if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept))) return rc;
+  if (kept >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
+  uint64_t* dK = nullptr;
+  uint32_t* dC = nullptr;
+  hipError_t e = hipMalloc((void**)&dK, std::max<uint64_t>(kept, 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&dC, std::max<uint64_t>(kept, 1) * 4);
+  if (e != hipSuccess) { (void)hipGetLastError(); hipFree(dK); hipFree(dC); return fail(TALC_ERR_NOMEM, "cannot allocate the %llu kept k-mers", (unsigned long long)kept); }
+  uint64_t got = 0;
+  if ((rc = counter_compact(c, c->p.min_count, dK, dC, kept, &got))) { hipFree(dK); hipFree(dC); return rc; }
+  // the hash goes before the builder allocates its buckets; the counter is spent from here on
+  counter_free_hash(c);
+  c->spent = true;
+  const auto t2 = std::chrono::steady_clock::now();
+  if (c->sw.timing) {
+    double kms = 0;
+    for (auto& ev : c->kev) { float ms = 0; if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) kms += ms; }
+    fprintf(stderr, "[talc-lib] k-mer counter: %llu batches, %.0f MB, %llu windows, %llu distinct, %llu kept; pack %.3f s, count kernels %.3f ms "
+                    "(%.3f ms per batch), %llu grows %.3f s, last batch wait %.3f s, compaction %.3f s\n",
+            (unsigned long long)c->nBatches, (double)c->nBytes / 1e6, st[0], st[1], (unsigned long long)kept, c->packS, kms,
+            c->nBatches ? kms / (double)c->nBatches : 0.0, (unsigned long long)c->nGrows, c->growS,
+            std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t2 - t1).count());
+  }
+  talc_table* t = nullptr;
+  if ((rc = build_table_from_device_arrays(dK, dC, kept, kept, &c->p, c->device, &t, 0.0, 0.0, c->sw))) return rc;
+  DumpStats ds;
+  ds.nread = (int64_t)st[1];
+  ds.nkept = (int64_t)kept;
+  return table_finish(t, junction_path, &c->p, ds, out, stats);
+}
+
+void talc_counter_destroy(talc_counter* c) {
+  if (!c) return;
+  if (hipSetDevice(c->device) == hipSuccess) {
+    if (c->stream) hipStreamSynchronize(c->stream);
+    counter_free_hash(c);
+    hipFree(c->dStats); hipFree(c->dOverflow);
+    for (int i = 0; i < 2; ++i) { if (c->stage[i]) hipHostFree(c->stage[i]); if (c->stageEv[i]) hipEventDestroy(c->stageEv[i]); }
+    for (auto& ev : c->kev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    if (c->stream) hipStreamDestroy(c->stream);
+  }
+  (void)hipGetLastError();
+  delete c;
 }
 
 #include "talc_capi_correct.inc"

@@ -16,6 +16,9 @@
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
 //                    dump` (the tool the reference would have queried k-mer by k-mer, Jellyfish.cpp:323-379), without it
 //                    from the native reader of the .jf; with neither a -jf2 nor a .jf the reference's behaviour is kept
+//   --SRReads FILE   (repeatable, instead of -SR) short reads, FASTA or FASTQ: their k-mers are counted on the GPU
+//                    (talc_counter_*, docs/kmer_counting.md) in place of `jellyfish count` + `dump -c` (README.md:37-49)
+//   --SRCountsOut F  with --SRReads: the kept k-mers as `jellyfish dump -c` text, for a later -SR F
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -51,6 +54,8 @@ namespace {
 
 struct Options {
   std::string seqFile, outPrefix = "out", queryMode = "memory", dump, jdump, jf2;
+  std::vector<std::string> srReads;   // --SRReads, in order
+  std::string srCountsOut;            // --SRCountsOut
   talc_params p;
   bool haveK = false, haveSR = false, useJ = false;
   int gpus = -1;
@@ -67,7 +72,10 @@ void usage(FILE* f) {
           "  -o, --output TEXT           prefix of the output files (default: out)\n"
           "  -k, --kmerSize INT          k-mer length, 18..31 (required)\n"
           "  -qm, --query-mode TEXT      memory | jellyfish2 (default: memory)\n"
-          "  -SR, --SRCounts TEXT        short-read k-mer counts: `jellyfish dump -c` text or the .jf itself (required)\n"
+          "  -SR, --SRCounts TEXT        short-read k-mer counts: `jellyfish dump -c` text or the .jf itself (this or --SRReads)\n"
+          "  --SRReads TEXT              short reads (FASTA or FASTQ; repeat for several files): their k-mers are counted on\n"
+          "                              the GPU instead of read from -SR (every window of K ACGT bases of a record, directional)\n"
+          "  --SRCountsOut TEXT          with --SRReads: write the kept k-mers as `jellyfish dump -c` text (usable as -SR)\n"
           "  -j, --junctions TEXT        k-mers flanking junctions and their counts\n"
           "  -jf2, --pathToJF2 TEXT      directory of the jellyfish program: -qm jellyfish2 then reads the .jf through\n"
           "                              `jellyfish dump` (without it: the native .jf reader)\n"
@@ -116,6 +124,8 @@ Options parse(int argc, const char** argv) {
     else if (is(a, "k", "kmerSize")) { double v = num(need(i), "k"); range(v, 18, 31, "k"); o.p.k = (uint32_t)v; o.haveK = true; }
     else if (is(a, "qm", "query-mode")) { o.queryMode = need(i); if (o.queryMode != "memory" && o.queryMode != "jellyfish2") parse_error("the given value '" + o.queryMode + "' is not in the list of allowed values [memory, jellyfish2]"); }
     else if (is(a, "SR", "SRCounts")) { o.dump = need(i); o.haveSR = true; }
+    else if (a == "--SRReads") o.srReads.push_back(need(i));
+    else if (a == "--SRCountsOut") o.srCountsOut = need(i);
     else if (is(a, "j", "junctions")) { o.jdump = need(i); o.useJ = true; }
     else if (is(a, "jf2", "pathToJF2")) o.jf2 = need(i);
     else if (is(a, "MIN_INNER_SCORE", "MIN_INNER_SCORE")) { o.p.min_inner_score = num(need(i), "MIN_INNER_SCORE"); range(o.p.min_inner_score, 0.3, 0.9, "MIN_INNER_SCORE"); }
@@ -141,7 +151,10 @@ Options parse(int argc, const char** argv) {
   }
   if (o.seqFile.empty()) parse_error("not enough arguments were provided");
   if (!o.haveK) parse_error("option requires a value: -k, --kmerSize");
-  if (!o.haveSR) parse_error("option requires a value: -SR, --SRCounts");
+  if (!o.haveSR && o.srReads.empty()) parse_error("option requires a value: -SR, --SRCounts");
+  if (o.haveSR && !o.srReads.empty()) parse_error("-SR and --SRReads exclude each other: give the counts or the short reads");
+  if (!o.srReads.empty() && o.queryMode == "jellyfish2") parse_error("--SRReads counts the k-mers itself: it does not go with -qm jellyfish2");
+  if (!o.srCountsOut.empty() && o.srReads.empty()) parse_error("--SRCountsOut needs --SRReads");
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
 }
@@ -233,6 +246,8 @@ class SeqReader {
   }
   bool ok() const { return ok_; }
   bool fastq() const { return fastq_; }
+  // a FASTQ record whose qualities ran out before its sequence's length (the long-read path reads on regardless)
+  bool truncated() const { return truncated_; }
   // next record; false at the end of the file (or on a malformed FASTQ header: bad() then says so).  sink(p, n) is called
   // with every piece of the record's sequence and returns false to stop (no memory).
   template <class Sink>
@@ -252,6 +267,7 @@ class SeqReader {
       while (in_.getline(lp_, ll_)) { if (ll_ != 0 && lp_[0] == '+') break; if (ll_ && !sink(lp_, ll_)) { ok_ = false; return false; } n += ll_; }
       size_t got = 0;
       while (got < n && in_.getline(lp_, ll_)) got += ll_;
+      if (got < n) truncated_ = true;
       return true;
     }
     id.assign(lp_ + 1, ll_ - 1);
@@ -270,7 +286,7 @@ class SeqReader {
   LineReader in_;
   const char* lp_ = nullptr;
   size_t ll_ = 0;
-  bool ok_ = true, fastq_ = false, pending_ = false;
+  bool ok_ = true, fastq_ = false, pending_ = false, truncated_ = false;
 };
 
 // One batch of reads on its way through the pipeline: read -> corrected on a device -> written, in input order.
@@ -376,6 +392,85 @@ double secs(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::
   return std::chrono::duration<double>(b - a).count();
 }
 
+// --SRReads: every short-read file read once, front to back (a pipe works), in batches of about 64 MB of bases handed to
+// the GPU counter, which copies them and returns while its kernel runs, so reading the next batch overlaps counting this
+// one.  Then --SRCountsOut, then the table (junction colouring with -j).  Returns 0, or the exit code after a message.
+int countShortReads(const Options& o, const talc::Switches& sw, talc_table** table, int64_t st[3]) {
+  if (talc_device_count() <= 0) { std::cerr << "talc: no MI355X / HIP device visible; the correction path has no CPU fallback\n"; return 2; }
+  talc_counter* ctr = nullptr;
+  if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+  struct Guard { talc_counter*& c; ~Guard() { talc_counter_destroy(c); } } guard{ctr};
+  const size_t kBatchBytes = 64u << 20;
+  std::string buf;
+  std::vector<uint64_t> offs{0};
+  buf.reserve(kBatchBytes + (1u << 20));
+  double readS = 0, addS = 0;
+  uint64_t nRecords = 0, nBytes = 0, nBatches = 0;
+  auto flush = [&]() -> bool {
+    if (offs.size() < 2) return true;
+    const auto ta = std::chrono::steady_clock::now();
+    const bool ok = talc_counter_add(ctr, buf.data(), offs.data(), (uint32_t)(offs.size() - 1)) == TALC_OK;
+    const double dt = secs(ta, std::chrono::steady_clock::now());
+    addS += dt;
+    if (sw.timing == 2) fprintf(stderr, "[talc-count] batch %llu: %zu records, %zu bytes, counter add (pack + queue) %.4f s\n", (unsigned long long)nBatches, offs.size() - 1, buf.size(), dt);
+    ++nBatches;
+    buf.clear();
+    offs.assign(1, 0);
+    return ok;
+  };
+  const auto t0 = std::chrono::steady_clock::now();
+  for (const std::string& file : o.srReads) {
+    SeqReader r(file);
+    if (!r.ok()) { std::cerr << "talc: " << file << " is not a FASTA or FASTQ file that can be read\n"; return 2; }
+    std::string id;
+    uint64_t rec = 0;
+    auto tr = std::chrono::steady_clock::now();
+    while (r.next(id, [&](const char* p, size_t n) { buf.append(p, n); return true; })) {
+      ++rec;
+      if (r.truncated()) { std::cerr << "talc: " << file << ": FASTQ record " << rec << " (" << id << ") is malformed: its qualities are shorter than its sequence\n"; return 2; }
+      offs.push_back(buf.size());
+      if (buf.size() >= kBatchBytes) {
+        readS += secs(tr, std::chrono::steady_clock::now());
+        nBytes += buf.size();
+        if (!flush()) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+        tr = std::chrono::steady_clock::now();
+      }
+    }
+    readS += secs(tr, std::chrono::steady_clock::now());
+    if (!r.ok()) { std::cerr << "talc: " << file << ": FASTQ record " << rec + 1 << " (after '" << id << "') is malformed: it does not start with '@'\n"; return 2; }
+    nRecords += rec;
+  }
+  nBytes += buf.size();
+  if (!flush()) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+  const auto t1 = std::chrono::steady_clock::now();
+  if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers
+    uint64_t n = 0;
+    if (talc_counter_fetch(ctr, o.p.min_count, nullptr, nullptr, 0, &n) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+    std::vector<uint64_t> km(std::max<uint64_t>(n, 1));
+    std::vector<uint32_t> ct(std::max<uint64_t>(n, 1));
+    if (talc_counter_fetch(ctr, o.p.min_count, km.data(), ct.data(), n, &n) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+    FILE* f = fopen(o.srCountsOut.c_str(), "w");
+    if (!f) { std::cerr << "talc: cannot write " << o.srCountsOut << "\n"; return 2; }
+    const uint32_t K = o.p.k;
+    std::vector<char> line(K + 16);
+    for (uint64_t i = 0; i < n; ++i) {
+      for (uint32_t j = 0; j < K; ++j) line[j] = "ACGT"[(km[i] >> (2 * (K - 1 - j))) & 3];
+      const int m = snprintf(line.data() + K, 16, " %u\n", ct[i]);
+      fwrite(line.data(), 1, K + (size_t)m, f);
+    }
+    if (fclose(f) != 0) { std::cerr << "talc: cannot write " << o.srCountsOut << "\n"; return 2; }
+  }
+  const auto t2 = std::chrono::steady_clock::now();
+  if (talc_counter_build_table(ctr, o.useJ ? o.jdump.c_str() : nullptr, table, st) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+  if (sw.timing)
+    fprintf(stderr, "[talc] short reads: %zu file(s), %llu records, %llu bytes in %llu batches; read %.3f s (%.4f s per batch), counter add (pack + queue) %.3f s "
+                    "(%.4f s per batch), counts out %.3f s, last batches + table build %.3f s, counting stage %.3f s\n",
+            o.srReads.size(), (unsigned long long)nRecords, (unsigned long long)nBytes, (unsigned long long)nBatches, readS,
+            nBatches ? readS / (double)nBatches : 0.0, addS, nBatches ? addS / (double)nBatches : 0.0, secs(t1, t2),
+            secs(t2, std::chrono::steady_clock::now()), secs(t0, std::chrono::steady_clock::now()));
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, const char** argv) {
@@ -442,14 +537,23 @@ int main(int argc, const char** argv) {
   talc_table* table = nullptr;
   uint64_t tableSize = 0;
   if (buildTable) {  // main.cpp:224-238
-    if (o.useJ) std::cout << "[TALC]: Building the SR-cdBG from count files: " << o.dump << " and " << o.jdump << std::endl;
-    else std::cout << "[TALC]: Building the SR-dBG from count file: " << o.dump << std::endl;
     int64_t st[3] = {0, 0, 0};
-    // the insert loop of buildCDBG runs on the first GPU when there is one (same table, ~10x faster on a 50 M dump)
-    int rc = (talc_device_count() > 0)
-                 ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &table, st)
-                 : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &table, st);
-    for (const auto& f : tmpFiles) std::remove(f.c_str());
+    int rc = TALC_OK;
+    if (!o.srReads.empty()) {   // --SRReads: counted on the GPU, no count file in between
+      std::cout << "[TALC]: Building the SR-" << (o.useJ ? "cdBG" : "dBG") << " from the k-mers of " << o.srReads.size() << " short-read file(s)";
+      if (o.useJ) std::cout << " and count file: " << o.jdump;
+      std::cout << std::endl;
+      const int ec = countShortReads(o, sw, &table, st);
+      if (ec) return ec;
+    } else {
+      if (o.useJ) std::cout << "[TALC]: Building the SR-cdBG from count files: " << o.dump << " and " << o.jdump << std::endl;
+      else std::cout << "[TALC]: Building the SR-dBG from count file: " << o.dump << std::endl;
+      // the insert loop of buildCDBG runs on the first GPU when there is one (same table, ~10x faster on a 50 M dump)
+      rc = (talc_device_count() > 0)
+               ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &table, st)
+               : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &table, st);
+      for (const auto& f : tmpFiles) std::remove(f.c_str());
+    }
     if (rc != TALC_OK) {
       // an unreadable dump leaves the reference with an empty map (Jellyfish.cpp:249-251); anything else is fatal
       std::cerr << "talc: " << talc_last_error() << "\n";

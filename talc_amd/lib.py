@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
     "talc_batch_correct", "talc_batch_corrected_bytes", "talc_batch_fetch_corrected", "talc_batch_fetch_read_stats",
     "talc_batch_copy_corrected_device", "talc_correct_batch",
     "talc_ctx_get_timing", "talc_batch_trace_read", "talc_test_dp",
+    "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
+    "talc_counter_destroy",
 ]
 
 
@@ -145,6 +147,12 @@ def lib():
         L.talc_batch_trace_read.restype = C.c_int64
         L.talc_batch_trace_read.argtypes = [vp, vp, u32, vp, u64]
         L.talc_test_dp.argtypes = [vp, i32, C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, i32, vp]
+        L.talc_counter_create.argtypes = [C.POINTER(Params), i32, u64, C.POINTER(vp)]
+        L.talc_counter_add.argtypes = [vp, vp, vp, u32]
+        L.talc_counter_stats.argtypes = [vp, vp]
+        L.talc_counter_fetch.argtypes = [vp, u32, vp, vp, u64, vp]
+        L.talc_counter_build_table.argtypes = [vp, C.c_char_p, C.POINTER(vp), vp]
+        L.talc_counter_destroy.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -292,6 +300,61 @@ class Table:
     def close(self):
         if self._h:
             lib().talc_table_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KmerCounter:
+    """Short-read k-mer counter on GPU `device` (replaces `jellyfish count -m K` + `dump -c`; docs/kmer_counting.md):
+    every window of K bases of ACGTacgt inside one record counts once, directional, 2 bits per base."""
+
+    def __init__(self, params, device=0, expected_distinct=0):
+        self.params = params
+        self.device = int(device)
+        h = C.c_void_p()
+        _chk(lib().talc_counter_create(C.byref(params), self.device, int(expected_distinct), C.byref(h)))
+        self._h = h
+
+    def add(self, bases, offsets):
+        """Queue a batch of records (bases: uint8 / bytes concatenated, offsets: u64[n+1]); the arrays may be reused at once."""
+        if isinstance(bases, (bytes, bytearray)):
+            bases = np.frombuffer(bases, dtype=np.uint8)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        _chk(lib().talc_counter_add(self._h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1))
+
+    def stats(self):
+        """(windows counted, distinct k-mers, distinct k-mers with count >= params.min_count)."""
+        st = np.zeros(3, dtype=np.uint64)
+        _chk(lib().talc_counter_stats(self._h, st.ctypes.data))
+        return tuple(int(x) for x in st)
+
+    def fetch(self, min_count=1):
+        """(kmers u64, counts u32) of the k-mers with count >= min_count, in no particular order."""
+        n = C.c_uint64()
+        _chk(lib().talc_counter_fetch(self._h, int(min_count), None, None, 0, C.byref(n)))
+        kmers = np.empty(max(n.value, 1), dtype=np.uint64)
+        counts = np.empty(max(n.value, 1), dtype=np.uint32)
+        _chk(lib().talc_counter_fetch(self._h, int(min_count), kmers.ctypes.data, counts.ctypes.data, n.value, C.byref(n)))
+        return kmers[: n.value], counts[: n.value]
+
+    def build_table(self, junctions=None):
+        """The table of the k-mers with count >= params.min_count (staged on the counter's GPU); the counter is spent."""
+        h = C.c_void_p()
+        st = np.zeros(3, dtype=np.int64)
+        _chk(lib().talc_counter_build_table(self._h, junctions.encode() if junctions else None, C.byref(h), st.ctypes.data))
+        t = Table(h, self.params)
+        t.build_stats = st
+        return t
+
+    def close(self):
+        if self._h:
+            lib().talc_counter_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -52,6 +52,8 @@ def lib():
         L.synth_write_junctions.argtypes = [C.c_void_p, C.c_char_p]
         L.synth_write_fasta.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32]
         L.synth_spec_default.argtypes = [C.POINTER(SynthSpec)]
+        L.synth_short_reads.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.synth_write_short_fastq.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_double]
         _LIB = L
     return _LIB
 
@@ -118,6 +120,20 @@ class Synth:
         offsets = np.empty(n + 1, dtype=np.uint64)
         lib().synth_reads(self._h, first, n, None, offsets.ctypes.data)
         return np.diff(offsets.astype(np.int64))
+
+    def short_reads(self, first, n, length=150, sub_rate=0.005, n_rate=0.0):
+        """(bases uint8 ASCII concatenated, offsets u64[n+1]) of short reads [first, first+n): transcripts drawn by
+        length x lambda, uniform starts, substitutions at sub_rate, 'N' at n_rate; each read depends on (seed, index) only."""
+        L = lib()
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        L.synth_short_reads(self._h, first, n, length, sub_rate, n_rate, None, offsets.ctypes.data)
+        bases = np.empty(int(offsets[n]), dtype=np.uint8)
+        L.synth_short_reads(self._h, first, n, length, sub_rate, n_rate, bases.ctypes.data, offsets.ctypes.data)
+        return bases, offsets
+
+    def write_short_fastq(self, path, first, n, length=150, sub_rate=0.005, n_rate=0.0):
+        if lib().synth_write_short_fastq(self._h, path.encode(), first, n, length, sub_rate, n_rate) != 0:
+            raise IOError(path)
 
     def write_dump(self, path):
         if lib().synth_write_dump(self._h, path.encode()) != 0:
