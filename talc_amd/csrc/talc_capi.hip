@@ -10,11 +10,13 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
 
 #include "talc_common.h"
+#include "talc_devmem.h"
 #include "talc_hip.h"
 #include "talc_kernels_build.h"
 #include "talc_kernels_count.h"
@@ -46,12 +48,21 @@ static int fail(int code, const char* fmt, ...) {
 // table built (or imported) on a GPU has a *staged* device image there — colouring and de-colouring run on it as
 // kernels, talc_table_upload to that same GPU adopts it without any copy, and the host image is only materialised
 // when something asks for it (host lookups, an upload to another GPU).
+struct DeviceImage {   // what one upload allocated; h.dev[device] (DeviceCopy) is the view of it that the host-only code knows
+  DevBuf<Bucket> right, left;
+  DevBuf<uint64_t> filter;
+  DevBuf<WalkEntry> walkRight, walkLeft;
+};
 struct talc_table {
   HostTable h;
   bool hostValid = true;       // h.right / h.left hold the current table
   int stagedDev = -1;          // GPU holding the built, not yet uploaded image (-1: none)
-  Bucket* stR = nullptr;
-  Bucket* stL = nullptr;
+  DevBuf<Bucket> stR, stL;
+  std::map<int, DeviceImage> images;   // device -> the uploaded copy
+  ~talc_table() {
+    for (auto& kv : images) { (void)hipSetDevice(kv.first); kv.second = DeviceImage(); }
+    if (stagedDev >= 0) (void)hipSetDevice(stagedDev);
+  }
 };
 
 // make the host image current (device-built tables: copy it back from the GPU that holds it)
@@ -59,29 +70,28 @@ static int ensure_host(talc_table* t) {
   if (t->hostValid) return TALC_OK;
   const Bucket *srcR = nullptr, *srcL = nullptr;
   int dev = -1;
-  if (t->stagedDev >= 0) { srcR = t->stR; srcL = t->stL; dev = t->stagedDev; }
+  if (t->stagedDev >= 0) { srcR = t->stR.get(); srcL = t->stL.get(); dev = t->stagedDev; }
   else if (!t->h.dev.empty()) { srcR = t->h.dev.begin()->second.right; srcL = t->h.dev.begin()->second.left; dev = t->h.dev.begin()->first; }
   if (!srcR) return fail(TALC_ERR_STATE, "the table has neither a host image nor a device image");
   const uint64_t bytes = t->h.capacity * sizeof(Bucket);
   if (!t->h.right) t->h.right = (Bucket*)malloc(bytes);
   if (!t->h.left) t->h.left = (Bucket*)malloc(bytes);
   if (!t->h.right || !t->h.left) return fail(TALC_ERR_NOMEM, "cannot allocate the host image (%llu bytes)", (unsigned long long)(2 * bytes));
-  hipError_t e = hipSetDevice(dev);
-  if (e == hipSuccess) e = hipMemcpy(t->h.right, srcR, bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(t->h.left, srcL, bytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(TALC_ERR_DEVICE, "copying the table image to the host: %s", hipGetErrorString(e));
+  HIPCHK(hipSetDevice(dev));
+  HIPCHK(hipMemcpy(t->h.right, srcR, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(t->h.left, srcL, bytes, hipMemcpyDeviceToHost));
   t->hostValid = true;
   return TALC_OK;
 }
 
 struct Stage {
   // per-wave scratch for the search kernel
-  uint8_t* scratch = nullptr;
+  DevBuf<uint8_t> scratch;
   uint64_t scratch_bytes = 0;
   uint32_t n_slots = 0;
   SearchCaps caps;
   // edge tasks (first pass only): one box per slot + the slots' claim counters (talc_kernels_search.h, "edge tasks")
-  uint8_t* boxes = nullptr;
+  DevBuf<uint8_t> boxes;
   uint64_t boxes_bytes = 0;
   uint32_t box_seq_cap = 0;
 };
@@ -92,81 +102,22 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8];
+  hipEvent_t ev[8] = {};
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   Stage stage;          // default scratch
-  uint32_t* d_queue = nullptr;   // work-queue counters
-  uint32_t* d_hist = nullptr;    // 1024 buckets of the work-queue ordering
-  uint64_t* d_counters = nullptr;  // [0]=trail steps [1]=dp cells
-  uint32_t* d_thr = nullptr;       // the count model's thresholds by count (DevParams.thr)
-  // device buffers of finished batches, kept for the next batch of this context (a streaming run creates and destroys
-  // a batch per chunk of reads: ~20 hipMalloc / hipFree pairs each time otherwise)
-  std::vector<std::pair<uint64_t, void*>> pool;   // (bytes, pointer), free
-  std::map<void*, uint64_t> live;                 // pointer -> bytes, handed out
-  uint64_t pool_bytes = 0;        // bytes cached (free)
-  uint64_t live_bytes = 0;        // bytes handed out
-  uint64_t peak_live_bytes = 0;   // the largest footprint the batches of this context have had together
+  DevBuf<uint32_t> d_queue;      // work-queue counters
+  DevBuf<uint32_t> d_hist;       // 1024 buckets of the work-queue ordering
+  DevBuf<uint64_t> d_counters;   // [0]=trail steps [1]=dp cells
+  DevBuf<uint32_t> d_thr;        // the count model's thresholds by count (DevParams.thr)
+  DevCache cache;       // the device buffers of this context's batches
+  ~talc_ctx() {
+    (void)hipSetDevice(device);
+    for (auto& e : ev) if (e) hipEventDestroy(e);
+    if (stream) hipStreamDestroy(stream);
+  }
 };
-
-// drop cached buffers, oldest first, until the cache holds at most `keep_bytes`
-static void ctx_pool_trim(talc_ctx* c, uint64_t keep_bytes) {
-  while (!c->pool.empty() && c->pool_bytes > keep_bytes) {
-    c->pool_bytes -= c->pool.front().first;
-    hipFree(c->pool.front().second);
-    c->pool.erase(c->pool.begin());
-  }
-}
-
-// a device buffer of at least `bytes` from the context's cache (smallest cached one that fits and is not more than
-// twice as large), or a fresh one
-static int ctx_alloc(talc_ctx* c, void** out, uint64_t bytes) {
-  bytes = std::max<uint64_t>(bytes, 256);
-  int best = -1;
-  for (int i = 0; i < (int)c->pool.size(); ++i)
-    if (c->pool[i].first >= bytes && c->pool[i].first <= 2 * bytes + 4096 && (best < 0 || c->pool[i].first < c->pool[best].first)) best = i;
-  if (best >= 0) {
-    *out = c->pool[best].second;
-    c->live[*out] = c->pool[best].first;
-    c->live_bytes += c->pool[best].first;
-    c->peak_live_bytes = std::max(c->peak_live_bytes, c->live_bytes);
-    c->pool_bytes -= c->pool[best].first;
-    c->pool.erase(c->pool.begin() + best);
-    return TALC_OK;
-  }
-  if (hipMalloc(out, bytes) != hipSuccess) {
-    // out of memory: drop the cache and try once more
-    (void)hipGetLastError();
-    ctx_pool_trim(c, 0);
-    HIPCHK(hipMalloc(out, bytes));
-  }
-  c->live[*out] = bytes;
-  c->live_bytes += bytes;
-  c->peak_live_bytes = std::max(c->peak_live_bytes, c->live_bytes);
-  return TALC_OK;
-}
-static void ctx_release(talc_ctx* c, void* p) {
-  if (!p) return;
-  auto it = c->live.find(p);
-  if (it == c->live.end()) { hipFree(p); return; }
-  const uint64_t bytes = it->second;
-  c->live.erase(it);
-  c->live_bytes -= bytes;
-  c->pool.push_back({bytes, p});
-  c->pool_bytes += bytes;
-  // a bounded cache, by count and by bytes: what one batch hands back is what the next one of the same shape asks for, so
-  // cache + live buffers never need to exceed the largest footprint the batches of this context have had (everybody
-  // else who sizes something from hipMemGetInfo — the search scratch, the retry stage, another context on the same GPU,
-  // the walk-table decision of an upload — sees cached bytes as used)
-  while (c->pool.size() > 64) {
-    c->pool_bytes -= c->pool.front().first;
-    hipFree(c->pool.front().second);
-    c->pool.erase(c->pool.begin());
-  }
-  if (c->pool_bytes + c->live_bytes > c->peak_live_bytes)
-    ctx_pool_trim(c, c->peak_live_bytes > c->live_bytes ? c->peak_live_bytes - c->live_bytes : 0);
-}
 
 struct talc_batch {
   talc_ctx* ctx = nullptr;
@@ -175,40 +126,39 @@ struct talc_batch {
   uint32_t max_len = 0;
   std::vector<uint64_t> h_offsets, h_koff;
   std::vector<uint32_t> h_tile_read, h_tile_start, h_chunk_read, h_chunk_start;
-  uint8_t* d_raw = nullptr;
-  uint8_t* d_codes = nullptr;
-  uint64_t* d_offsets = nullptr;
-  uint64_t* d_koff = nullptr;
-  uint32_t *d_tile_read = nullptr, *d_tile_start = nullptr, *d_chunk_read = nullptr, *d_chunk_start = nullptr;
-  uint32_t* d_order = nullptr;       // the work queue: read numbers, heaviest first (k_order_scatter)
-  uint2* d_cov = nullptr;            // hit pairs, packed per tile inside each read's dense slot (talc_common.h: CovWord)
-  CovWord* d_covw = nullptr;         // one word per 64 k-mer positions
-  int32_t* d_nin = nullptr;
-  // structure + results
-  ReadState* d_state = nullptr;
-  uint32_t* d_headcov = nullptr;     // 16 x u32 per read: dense counts of its first positions (k_structure -> k_search)
-  uint32_t* d_regions = nullptr;     // 3 x u32 per region slot (start, end, hit index of the start)
-  uint64_t* d_regoff = nullptr;      // per-read offset (in regions) into d_regions
   std::vector<uint64_t> h_regoff;
-  uint8_t* d_out = nullptr;          // corrected codes, per-read capacity slots
-  uint64_t* d_outoff = nullptr;      // per-read offset into d_out
   std::vector<uint64_t> h_outoff;
   uint64_t out_capacity = 0;
   bool encoded = false, covered = false, corrected = false;
   std::vector<ReadState> h_state;
   std::vector<uint64_t> h_dense_off;
-  uint8_t* d_dense = nullptr;
   uint64_t dense_cap = 0;
-  uint64_t* d_dense_off = nullptr;
+  // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
+  // first) gets them back from d_raw to d_headcov
+  CachedBuf<uint32_t> d_headcov;     // 16 x u32 per read: dense counts of its first positions (k_structure -> k_search)
+  CachedBuf<uint64_t> d_dense_off;
+  CachedBuf<uint8_t> d_dense;
+  CachedBuf<uint64_t> d_outoff;      // per-read offset into d_out
+  CachedBuf<uint8_t> d_out;          // corrected codes, per-read capacity slots
+  CachedBuf<uint64_t> d_regoff;      // per-read offset (in regions) into d_regions
+  CachedBuf<uint32_t> d_regions;     // 3 x u32 per region slot (start, end, hit index of the start)
+  CachedBuf<ReadState> d_state;      // structure + results
+  CachedBuf<int32_t> d_nin;
+  CachedBuf<CovWord> d_covw;         // one word per 64 k-mer positions
+  CachedBuf<uint2> d_cov;            // hit pairs, packed per tile inside each read's dense slot (talc_common.h: CovWord)
+  CachedBuf<uint32_t> d_order;       // the work queue: read numbers, heaviest first (k_order_scatter)
+  CachedBuf<uint32_t> d_chunk_start, d_chunk_read, d_tile_start, d_tile_read;
+  CachedBuf<uint64_t> d_koff;
+  CachedBuf<uint64_t> d_offsets;
+  CachedBuf<uint8_t> d_codes;
+  CachedBuf<uint8_t> d_raw;
+  ~talc_batch() { if (ctx) (void)hipSetDevice(ctx->device); }
 };
 
-static int ctx_alloc(talc_ctx* c, void** out, uint64_t bytes);
 template <typename T>
-static int up(talc_ctx* c, T** d, const std::vector<T>& h, hipStream_t s) {
-  size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-  int rc_ = ctx_alloc(c, (void**)d, bytes);
-  if (rc_) return rc_;
-  if (!h.empty()) HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
+  HIPCHK(d.alloc(c->cache, std::max<size_t>(h.size(), 1)));
+  if (!h.empty()) HIPCHK(hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
   return TALC_OK;
 }
 
@@ -235,11 +185,11 @@ int talc_device_count(void) {
 
 // page-locked host memory for read / record buffers: copies to and from it are DMA transfers that run beside kernels
 void* talc_pinned_alloc(uint64_t bytes) {
-  void* p = nullptr;
-  if (hipHostMalloc(&p, std::max<uint64_t>(bytes, 1), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned host memory", (unsigned long long)bytes); return nullptr; }
-  return p;
+  PinnedBuf p;
+  if (p.alloc(std::max<uint64_t>(bytes, 1)) != hipSuccess) { (void)hipGetLastError(); fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned host memory", (unsigned long long)bytes); return nullptr; }
+  return p.release();
 }
-void talc_pinned_free(void* p) { if (p) (void)hipHostFree(p); }
+void talc_pinned_free(void* p) { PinnedBuf gone(p); }
 
 static int check_params(const talc_params* p) {
   if (!p) return fail(TALC_ERR_INVALID, "null params");
@@ -263,20 +213,20 @@ int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64
   uint64_t kept = 0;
 #pragma omp parallel for reduction(+ : kept)
   for (long i = 0; i < (long)n; ++i) kept += counts[i] >= p->min_count ? 1 : 0;
-  talc_table* t = new talc_table();
+  auto t = std::make_unique<talc_table>();
   t->h.p = *p;
-  if (!t->h.allocate(kept, read_switches().tableSlotsX10)) { delete t; return fail(TALC_ERR_NOMEM, "cannot allocate host table for %llu k-mers", (unsigned long long)kept); }
+  if (!t->h.allocate(kept, read_switches().tableSlotsX10)) return fail(TALC_ERR_NOMEM, "cannot allocate host table for %llu k-mers", (unsigned long long)kept);
   t->h.insertAll(kmers, counts, n);
-  *out = t;
+  *out = t.release();
   return TALC_OK;
 }
 
 // the table built on `device` (talc_kernels_build.h); the image stays there (staged) until talc_table_upload adopts it
 // the device builder's core: n dump lines as device arrays dK / dC (line i of the dump at index i; the kernels drop the
 // lines below MIN_COUNT themselves), `kept` = how many reach MIN_COUNT (sizes the tables).  Takes ownership of dK / dC.
-static int build_table_from_device_arrays(uint64_t* dK, uint32_t* dC, uint64_t n, uint64_t kept, const talc_params* p, int device,
+static int build_table_from_device_arrays(DevBuf<uint64_t> dK, DevBuf<uint32_t> dC, uint64_t n, uint64_t kept, const talc_params* p, int device,
                                           talc_table** out, double h2d_seconds, double h2d_megabytes, const Switches& sw) {
-  talc_table* t = new talc_table();
+  auto t = std::make_unique<talc_table>();
   t->h.p = *p;
   {   // (sparser than load 0.5 when the device has the room: HostTable::capacity_for)
     hipDeviceProp_t prop;
@@ -284,43 +234,40 @@ static int build_table_from_device_arrays(uint64_t* dK, uint32_t* dC, uint64_t n
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) devBytes = (uint64_t)prop.totalGlobalMem;
     t->h.capacity = HostTable::capacity_for(kept, devBytes, sw.tableSlotsX10);
   }
-  uint32_t *dSR = nullptr, *dSL = nullptr;
-  unsigned long long* dStats = nullptr;
-  Bucket *dR = nullptr, *dL = nullptr;
-  auto cleanup = [&]() { hipFree(dK); hipFree(dC); hipFree(dSR); hipFree(dSL); hipFree(dStats); };
-  if (t->h.capacity >= (1ULL << 32)) { cleanup(); delete t; return fail(TALC_ERR_NOMEM, "table of %llu k-mers exceeds 2^32 buckets", (unsigned long long)kept); }
+  if (t->h.capacity >= (1ULL << 32)) return fail(TALC_ERR_NOMEM, "table of %llu k-mers exceeds 2^32 buckets", (unsigned long long)kept);
   t->hostValid = false;
   const uint64_t cap = t->h.capacity, bytes = cap * sizeof(Bucket);
-#define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); hipFree(dR); hipFree(dL); delete t; return fail(TALC_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
+  DevBuf<uint32_t> dSR, dSL;
+  DevBuf<unsigned long long> dStats;
+  DevBuf<Bucket> dR, dL;
   auto tnow = []() { return std::chrono::steady_clock::now(); };
   auto tsec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   const auto td1 = tnow();
-  BCHK(hipSetDevice(device));
-  BCHK(hipMalloc((void**)&dR, bytes)); BCHK(hipMalloc((void**)&dL, bytes));
-  BCHK(hipMalloc((void**)&dSR, std::max<uint64_t>(n, 1) * 4)); BCHK(hipMalloc((void**)&dSL, std::max<uint64_t>(n, 1) * 4));
-  BCHK(hipMalloc((void**)&dStats, 3 * 8));
-  BCHK(hipMemset(dR, 0xFF, bytes)); BCHK(hipMemset(dL, 0xFF, bytes)); BCHK(hipMemset(dStats, 0, 3 * 8));
-  BCHK(hipDeviceSynchronize());
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(dR.alloc(cap)); HIPCHK(dL.alloc(cap));
+  HIPCHK(dSR.alloc(std::max<uint64_t>(n, 1))); HIPCHK(dSL.alloc(std::max<uint64_t>(n, 1)));
+  HIPCHK(dStats.alloc(3));
+  HIPCHK(hipMemset(dR.get(), 0xFF, bytes)); HIPCHK(hipMemset(dL.get(), 0xFF, bytes)); HIPCHK(hipMemset(dStats.get(), 0, 3 * 8));
+  HIPCHK(hipDeviceSynchronize());
   const auto td2 = tnow();
   if (n) {
     const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_build_claim, dim3(nb), dim3(256), 0, 0, dR, dL, cap, p->k, dK, dC, n, p->min_count, dSR, dSL);
-    hipLaunchKernelGGL(k_build_resolve, dim3(nb), dim3(256), 0, 0, dR, dL, p->k, dK, n, dSR, dSL);
-    hipLaunchKernelGGL(k_build_write, dim3(nb), dim3(256), 0, 0, dR, dL, p->k, dK, dC, n, dSR, dSL);
+    hipLaunchKernelGGL(k_build_claim, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), cap, p->k, dK.get(), dC.get(), n, p->min_count, dSR.get(), dSL.get());
+    hipLaunchKernelGGL(k_build_resolve, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), p->k, dK.get(), n, dSR.get(), dSL.get());
+    hipLaunchKernelGGL(k_build_write, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), p->k, dK.get(), dC.get(), n, dSR.get(), dSL.get());
   }
-  hipLaunchKernelGGL(k_build_finalize, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, dR, dL, cap, dStats);
-  BCHK(hipGetLastError());
-  BCHK(hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_build_finalize, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, dR.get(), dL.get(), cap, dStats.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
   unsigned long long st[3];
-  BCHK(hipMemcpy(st, dStats, 3 * 8, hipMemcpyDeviceToHost));
-#undef BCHK
+  HIPCHK(hipMemcpy(st, dStats.get(), 3 * 8, hipMemcpyDeviceToHost));
   const auto td3 = tnow();
-  cleanup();
+  dK.reset(); dC.reset(); dSR.reset(); dSL.reset(); dStats.reset();   // (before the caller colours: only the image stays)
   if (sw.timing) fprintf(stderr, "[talc-lib] device build: %.0f MB to the device %.3f s, table allocations + clears %.3f s, kernels %.3f s, frees %.3f s\n",
                       h2d_megabytes, h2d_seconds, tsec(td1, td2), tsec(td2, td3), tsec(td3, tnow()));
-  t->stagedDev = device; t->stR = dR; t->stL = dL;
+  t->stagedDev = device; t->stR = std::move(dR); t->stL = std::move(dL);
   t->h.nkmers = st[0]; t->h.nbuckets_right = st[1]; t->h.nbuckets_left = st[2];
-  *out = t;
+  *out = t.release();
   return TALC_OK;
 }
 
@@ -333,23 +280,21 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
   uint64_t kept = 0;
 #pragma omp parallel for reduction(+ : kept)
   for (long i = 0; i < (long)n; ++i) kept += counts[i] >= p->min_count ? 1 : 0;
-  uint64_t* dK = nullptr; uint32_t* dC = nullptr;
+  DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
   const auto t0 = std::chrono::steady_clock::now();
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipFree(nullptr);   // (the runtime's own start-up)
-  if (e == hipSuccess) e = hipMalloc((void**)&dK, std::max<uint64_t>(n, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&dC, std::max<uint64_t>(n, 1) * 4);
-  if (e == hipSuccess && n) e = hipMemcpy(dK, kmers, n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && n) e = hipMemcpy(dC, counts, n * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(dK); hipFree(dC); return fail(TALC_ERR_DEVICE, "copying the dump's arrays to the device: %s", hipGetErrorString(e)); }
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hip_runtime_start());
+  HIPCHK(dK.alloc(std::max<uint64_t>(n, 1))); HIPCHK(dC.alloc(std::max<uint64_t>(n, 1)));
+  if (n) { HIPCHK(hipMemcpy(dK.get(), kmers, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dC.get(), counts, n * 4, hipMemcpyHostToDevice)); }
   const double h2d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return build_table_from_device_arrays(dK, dC, n, kept, p, device, out, h2d, (double)n * 12 / 1e6, read_switches());
+  return build_table_from_device_arrays(std::move(dK), std::move(dC), n, kept, p, device, out, h2d, (double)n * 12 / 1e6, read_switches());
 }
 
 // The text dump parsed ON the device (talc_kernels_build.h): the file's bytes are read by a few host threads into
 // page-locked buffers and copied as they are; two kernels make the builder's arrays.  Returns TALC_OK with *out set, or
 // a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory):
 // the caller then parses on the host, as before.
+static int parse_on_host_instead() { (void)hipGetLastError(); return 1; }   // (an allocation or a copy failed: no error is left behind)
 static int table_from_text_on_device(const char* path, const talc_params* p, int device, talc_table** out, DumpStats& ds, const Switches& sw) {
   struct stat sb;
   if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
@@ -365,9 +310,9 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
   }
   const auto t0 = std::chrono::steady_clock::now();
   auto secs = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  if (hipSetDevice(device) != hipSuccess || hipFree(nullptr) != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
-  uint8_t* dText = nullptr;
-  if (hipMalloc((void**)&dText, size + 64) != hipSuccess) { (void)hipGetLastError(); return 1; }
+  if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
+  DevBuf<uint8_t> dText;
+  if (dText.alloc(size + 64) != hipSuccess) return parse_on_host_instead();
   // ---- the file's bytes to the device: reader threads, each with its own descriptor, page-locked buffer and stream
   const uint64_t CH = 32ull << 20;
   const uint64_t nch = (size + CH - 1) / CH;
@@ -377,56 +322,52 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
 #pragma omp parallel num_threads(T)
   {
     int fd = open(path, O_RDONLY);
-    void* pin = nullptr;
+    PinnedBuf pin;
     hipStream_t st = nullptr;
-    bool ok = fd >= 0 && hipSetDevice(device) == hipSuccess && hipHostMalloc(&pin, CH) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+    bool ok = fd >= 0 && hipSetDevice(device) == hipSuccess && pin.alloc(CH) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     while (ok && !err.load()) {
       const uint64_t i = next.fetch_add(1);
       if (i >= nch) break;
       const uint64_t off = i * CH, len = std::min<uint64_t>(CH, size - off);
       uint64_t got = 0;
-      while (got < len) { const ssize_t r = pread(fd, (char*)pin + got, len - got, (off_t)(off + got)); if (r <= 0) { ok = false; break; } got += (uint64_t)r; }
+      while (got < len) { const ssize_t r = pread(fd, pin.get() + got, len - got, (off_t)(off + got)); if (r <= 0) { ok = false; break; } got += (uint64_t)r; }
       if (!ok) break;
-      if (hipMemcpyAsync(dText + off, pin, len, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) ok = false;
+      if (hipMemcpyAsync(dText.get() + off, pin.get(), len, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) ok = false;
     }
     if (!ok) err.store(1);
     if (st) hipStreamDestroy(st);
-    if (pin) hipHostFree(pin);
     if (fd >= 0) close(fd);
   }
-  if (err.load()) { hipFree(dText); (void)hipGetLastError(); return 1; }
+  if (err.load()) return parse_on_host_instead();
   const double tUp = secs(t0);
   // ---- lines per tile, the tiles' first line numbers, the lines themselves
   const auto t1 = std::chrono::steady_clock::now();
   const uint64_t ntiles = (size + kParseTile - 1) / kParseTile;
-  uint32_t* dCount = nullptr; uint64_t* dFirst = nullptr; ParseStats* dPS = nullptr;
-  uint64_t* dK = nullptr; uint32_t* dC = nullptr;
-  auto drop = [&]() { hipFree(dText); hipFree(dCount); hipFree(dFirst); hipFree(dPS); hipFree(dK); hipFree(dC); (void)hipGetLastError(); };
-  if (ntiles >= (1ull << 31) || hipMalloc((void**)&dCount, ntiles * 4) != hipSuccess || hipMalloc((void**)&dFirst, ntiles * 8) != hipSuccess ||
-      hipMalloc((void**)&dPS, sizeof(ParseStats)) != hipSuccess || hipMemset(dPS, 0, sizeof(ParseStats)) != hipSuccess) { drop(); return 1; }
-  hipLaunchKernelGGL(k_parse_count, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dCount);
+  DevBuf<uint32_t> dCount; DevBuf<uint64_t> dFirst; DevBuf<ParseStats> dPS;
+  DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
+  if (ntiles >= (1ull << 31) || dCount.alloc(ntiles) != hipSuccess || dFirst.alloc(ntiles) != hipSuccess ||
+      dPS.alloc(1) != hipSuccess || hipMemset(dPS.get(), 0, sizeof(ParseStats)) != hipSuccess) return parse_on_host_instead();
+  hipLaunchKernelGGL(k_parse_count, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText.get(), size, dCount.get());
   std::vector<uint32_t> hCount(ntiles);
-  if (hipMemcpy(hCount.data(), dCount, ntiles * 4, hipMemcpyDeviceToHost) != hipSuccess) { drop(); return 1; }
+  if (hipMemcpy(hCount.data(), dCount.get(), ntiles * 4, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
   std::vector<uint64_t> hFirst(ntiles);
   uint64_t nlines = 0;
   for (uint64_t i = 0; i < ntiles; ++i) { hFirst[i] = nlines; nlines += hCount[i]; }
-  if (nlines == 0 || nlines >= 0xFFFFFFFEull) { drop(); return 1; }
-  if (hipMemcpy(dFirst, hFirst.data(), ntiles * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void**)&dK, nlines * 8) != hipSuccess || hipMalloc((void**)&dC, nlines * 4) != hipSuccess) { drop(); return 1; }
-  hipLaunchKernelGGL(k_parse_lines, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dFirst, p->k, p->min_count, dK, dC, dPS);
+  if (nlines == 0 || nlines >= 0xFFFFFFFEull) return parse_on_host_instead();
+  if (hipMemcpy(dFirst.get(), hFirst.data(), ntiles * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      dK.alloc(nlines) != hipSuccess || dC.alloc(nlines) != hipSuccess) return parse_on_host_instead();
+  hipLaunchKernelGGL(k_parse_lines, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText.get(), size, dFirst.get(), p->k, p->min_count, dK.get(), dC.get(), dPS.get());
   ParseStats ps;
-  if (hipGetLastError() != hipSuccess || hipMemcpy(&ps, dPS, sizeof ps, hipMemcpyDeviceToHost) != hipSuccess) { drop(); return 1; }
-  hipFree(dText); hipFree(dCount); hipFree(dFirst); hipFree(dPS);
-  dText = nullptr; dCount = nullptr; dFirst = nullptr; dPS = nullptr;
+  if (hipGetLastError() != hipSuccess || hipMemcpy(&ps, dPS.get(), sizeof ps, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
+  dText.reset(); dCount.reset(); dFirst.reset(); dPS.reset();   // (the text goes before the builder allocates its buckets)
   if (ps.flags != 0) {   // a line the device parser does not take: the host's tokeniser decides what every line means
-    hipFree(dK); hipFree(dC);
     if (sw.timing) fprintf(stderr, "[talc-lib] the dump has lines that are not 'KMER count': parsing on the host\n");
     return 1;
   }
   if (sw.timing) fprintf(stderr, "[talc-lib] dump parsed on the device: %.0f MB of text to the device in %.3f s (%d reader threads), %llu lines parsed in %.3f s\n",
                       (double)size / 1e6, tUp, T, (unsigned long long)nlines, secs(t1));
   ds.nread += (int64_t)nlines; ds.nkept += (int64_t)ps.kept;
-  return build_table_from_device_arrays(dK, dC, nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
+  return build_table_from_device_arrays(std::move(dK), std::move(dC), nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
 }
 
 // Junction colouring (Jellyfish.cpp:273-290) on the staged device image: last line wins, both strands.
@@ -436,28 +377,24 @@ static int colour_on_device(talc_table* t, const uint64_t* jkmers, const int64_t
   HIPCHK(hipSetDevice(t->stagedDev));
   uint64_t hsize = 1024;
   while (hsize < 4 * n) hsize *= 2;   // two bids per line at most: load <= 0.5
-  uint64_t *dJ = nullptr, *dIds = nullptr; int64_t* dC = nullptr; unsigned long long* dHK = nullptr; uint32_t* dHS = nullptr;
-  auto cleanup = [&]() { hipFree(dJ); hipFree(dC); hipFree(dIds); hipFree(dHK); hipFree(dHS); };
-#define CCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(TALC_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-  CCHK(hipMalloc((void**)&dJ, n * 8)); CCHK(hipMalloc((void**)&dC, n * 8)); CCHK(hipMalloc((void**)&dIds, 2 * n * 8));
-  CCHK(hipMalloc((void**)&dHK, hsize * 8)); CCHK(hipMalloc((void**)&dHS, hsize * 4));
-  CCHK(hipMemcpy(dJ, jkmers, n * 8, hipMemcpyHostToDevice)); CCHK(hipMemcpy(dC, jcounts, n * 8, hipMemcpyHostToDevice));
-  CCHK(hipMemset(dHK, 0xFF, hsize * 8)); CCHK(hipMemset(dHS, 0, hsize * 4));
+  DevBuf<uint64_t> dJ, dIds; DevBuf<int64_t> dC; DevBuf<unsigned long long> dHK; DevBuf<uint32_t> dHS;
+  HIPCHK(dJ.alloc(n)); HIPCHK(dC.alloc(n)); HIPCHK(dIds.alloc(2 * n));
+  HIPCHK(dHK.alloc(hsize)); HIPCHK(dHS.alloc(hsize));
+  HIPCHK(hipMemcpy(dJ.get(), jkmers, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dC.get(), jcounts, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dHK.get(), 0xFF, hsize * 8)); HIPCHK(hipMemset(dHS.get(), 0, hsize * 4));
   const unsigned nb = (unsigned)((2 * n + 255) / 256);
-  hipLaunchKernelGGL(k_colour_claim, dim3(nb), dim3(256), 0, 0, t->stR, t->h.capacity, t->h.p.k, dJ, dC, n, t->h.p.coloured_count_thr,
-                     dIds, dHK, dHS, hsize - 1);
-  hipLaunchKernelGGL(k_colour_write, dim3(nb), dim3(256), 0, 0, t->stR, t->stL, t->h.capacity, t->h.p.k, dJ, dC, n, dIds, dHK, dHS,
+  hipLaunchKernelGGL(k_colour_claim, dim3(nb), dim3(256), 0, 0, t->stR.get(), t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, t->h.p.coloured_count_thr,
+                     dIds.get(), dHK.get(), dHS.get(), hsize - 1);
+  hipLaunchKernelGGL(k_colour_write, dim3(nb), dim3(256), 0, 0, t->stR.get(), t->stL.get(), t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, dIds.get(), dHK.get(), dHS.get(),
                      hsize - 1);
-  CCHK(hipGetLastError());
-  CCHK(hipDeviceSynchronize());
-#undef CCHK
-  cleanup();
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
   t->hostValid = false;
   return TALC_OK;
 }
 static int decolour_on_device(talc_table* t) {
   HIPCHK(hipSetDevice(t->stagedDev));
-  hipLaunchKernelGGL(k_decolour_repeats, dim3(1), dim3(64), 0, 0, t->stR, t->stL, t->h.capacity, t->h.p.k);
+  hipLaunchKernelGGL(k_decolour_repeats, dim3(1), dim3(64), 0, 0, t->stR.get(), t->stL.get(), t->h.capacity, t->h.p.k);
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   t->hostValid = false;
@@ -465,8 +402,8 @@ static int decolour_on_device(talc_table* t) {
 }
 
 // The tail every table build shares: junction colouring (Jellyfish.cpp:273-290), then the homopolymer de-colouring
-// (main.cpp:232); stats = {lines read, lines kept, malformed lines}.  Destroys t on failure, sets *out on success.
-static int table_finish(talc_table* t, const char* junction_path, const talc_params* p, DumpStats& ds, talc_table** out,
+// (main.cpp:232); stats = {lines read, lines kept, malformed lines}.  Sets *out on success.
+static int table_finish(std::unique_ptr<talc_table> t, const char* junction_path, const talc_params* p, DumpStats& ds, talc_table** out,
                         int64_t stats[3]) {
   int rc;
   if (junction_path && junction_path[0]) {  // Jellyfish.cpp:273-290
@@ -474,16 +411,14 @@ static int table_finish(talc_table* t, const char* junction_path, const talc_par
     std::vector<int64_t> jc;
     DumpStats js;
     std::string why;
-    if (!parseDumpFile(junction_path, p->k, 0, false, jk, nullptr, &jc, js, &why)) {
-      talc_table_destroy(t);
+    if (!parseDumpFile(junction_path, p->k, 0, false, jk, nullptr, &jc, js, &why))
       return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", junction_path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
-    }
     ds.nbad += js.nbad;
-    if ((rc = talc_table_colour(t, jk.data(), jc.data(), jk.size()))) { talc_table_destroy(t); return rc; }
+    if ((rc = talc_table_colour(t.get(), jk.data(), jc.data(), jk.size()))) return rc;
   }
-  if ((rc = talc_table_decolour_repeats(t))) { talc_table_destroy(t); return rc; }  // main.cpp:232
+  if ((rc = talc_table_decolour_repeats(t.get()))) return rc;  // main.cpp:232
   if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
-  *out = t;
+  *out = t.release();
   return TALC_OK;
 }
 
@@ -522,7 +457,7 @@ static int table_build_impl(const char* dump_path, const char* junction_path, co
   }
   std::vector<uint64_t>().swap(kmers);
   std::vector<uint32_t>().swap(counts);
-  return table_finish(t, junction_path, p, ds, out, stats);
+  return table_finish(std::unique_ptr<talc_table>(t), junction_path, p, ds, out, stats);
 }
 
 int talc_table_build(const char* dump_path, const char* junction_path, const talc_params* p, talc_table** out,
@@ -573,31 +508,25 @@ int talc_table_upload(talc_table* t, int device) {
   const bool adopt = (t->stagedDev == device);
   // everything this call allocates is freed again when a later step fails; an adopted image stays the table's staged one
   // until the copy is complete (a failed upload leaves the table as it was)
-  struct Guard {
-    DeviceCopy dc; bool adopted = false, done = false;
-    ~Guard() {
-      if (done) return;
-      if (!adopted) { hipFree(dc.right); hipFree(dc.left); }
-      hipFree(dc.filter); hipFree(dc.walkRight); hipFree(dc.walkLeft);
-    }
-  } g;
-  DeviceCopy& dc = g.dc;
-  g.adopted = adopt;
+  DeviceImage img;
+  DeviceCopy dc;
   if (adopt) {   // built (or imported) on this GPU: the image is adopted as it stands
     HIPCHK(hipSetDevice(device));
-    dc.right = t->stR; dc.left = t->stL;
+    dc.right = t->stR.get(); dc.left = t->stL.get();
   } else {
     int rc = ensure_host(t);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc((void**)&dc.right, bytes));
-    HIPCHK(hipMalloc((void**)&dc.left, bytes));
+    HIPCHK(img.right.alloc(t->h.capacity));
+    HIPCHK(img.left.alloc(t->h.capacity));
+    dc.right = img.right.get(); dc.left = img.left.get();
     HIPCHK(hipMemcpy(dc.right, t->h.right, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dc.left, t->h.left, bytes, hipMemcpyHostToDevice));
   }
   {   // presence filter, from the RIGHT table
     dc.filterWords = filter_words_for(t->h.nkmers, sw.filterBits);
-    HIPCHK(hipMalloc((void**)&dc.filter, dc.filterWords * 8));
+    HIPCHK(img.filter.alloc(dc.filterWords));
+    dc.filter = img.filter.get();
     HIPCHK(hipMemset(dc.filter, 0, dc.filterWords * 8));
     if (t->h.capacity)
       hipLaunchKernelGGL(k_build_filter, dim3((unsigned)((t->h.capacity + 255) / 256)), dim3(256), 0, 0, dc.right, t->h.capacity,
@@ -619,11 +548,12 @@ int talc_table_upload(talc_table* t, int device) {
     const uint64_t reserve = std::min<uint64_t>(64ull << 30, (uint64_t)totalB / 4);
     const bool want = sw.walk >= 0 ? sw.walk != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
     if (want && t->h.capacity) {
-      if (hipMalloc((void**)&dc.walkRight, wbytes) != hipSuccess || hipMalloc((void**)&dc.walkLeft, wbytes) != hipSuccess) {
+      if (img.walkRight.alloc(t->h.capacity) != hipSuccess || img.walkLeft.alloc(t->h.capacity) != hipSuccess) {
         (void)hipGetLastError();
-        hipFree(dc.walkRight); dc.walkRight = dc.walkLeft = nullptr;
+        img.walkRight.reset(); img.walkLeft.reset();
         if (sw.walk == 1) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
       } else {
+        dc.walkRight = img.walkRight.get(); dc.walkLeft = img.walkLeft.get();
         const uint64_t nthr = 2 * t->h.capacity;
         hipLaunchKernelGGL(k_build_walk, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, dc.right, dc.left, t->h.capacity,
                            t->h.p.k, (uint32_t)t->h.p.min_count, dc.walkRight, dc.walkLeft);
@@ -632,9 +562,9 @@ int talc_table_upload(talc_table* t, int device) {
       }
     }
   }
+  if (adopt) { img.right = std::move(t->stR); img.left = std::move(t->stL); t->stagedDev = -1; }
   t->h.dev[device] = dc;
-  g.done = true;
-  if (adopt) { t->stR = t->stL = nullptr; t->stagedDev = -1; }
+  t->images[device] = std::move(img);
   t->h.frozen = true;
   return TALC_OK;
 }
@@ -649,7 +579,7 @@ int talc_table_export_device(talc_table* t, int device, void* dst_right, void* d
   const Bucket *srcR = nullptr, *srcL = nullptr;
   auto it = t->h.dev.find(device);
   if (it != t->h.dev.end()) { srcR = it->second.right; srcL = it->second.left; }
-  else if (t->stagedDev == device) { srcR = t->stR; srcL = t->stL; }
+  else if (t->stagedDev == device) { srcR = t->stR.get(); srcL = t->stL.get(); }
   else return fail(TALC_ERR_STATE, "the table has no image on device %d", device);
   HIPCHK(hipSetDevice(device));
   const uint64_t bytes = t->h.capacity * sizeof(Bucket);
@@ -664,36 +594,29 @@ int talc_table_import_device(const talc_params* p, uint64_t capacity, uint64_t n
   int rc = check_params(p);
   if (rc) return rc;
   if (!out || !src_right || !src_left || capacity == 0 || capacity >= (1ULL << 32)) return fail(TALC_ERR_INVALID, "bad argument");
-  talc_table* t = new talc_table();
+  auto t = std::make_unique<talc_table>();
   t->h.p = *p; t->h.capacity = capacity; t->h.nkmers = n_kmers; t->hostValid = false;
   const uint64_t bytes = capacity * sizeof(Bucket);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->stR, bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->stL, bytes);
-  if (e == hipSuccess) e = hipMemcpy(t->stR, src_right, bytes, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemcpy(t->stL, src_left, bytes, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
+  HIPCHK(hipSetDevice(device));
+  t->stagedDev = device;
+  HIPCHK(t->stR.alloc(capacity)); HIPCHK(t->stL.alloc(capacity));
+  HIPCHK(hipMemcpy(t->stR.get(), src_right, bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipMemcpy(t->stL.get(), src_left, bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipDeviceSynchronize());
   // an image carries no parameters of its own: what the kernels rely on — every stored count >= MIN_COUNT, keys of K - 1
   // bases — is checked against the parameters given (an image filtered with a lower MIN_COUNT would give wrong regions)
   unsigned long long chk[2] = {~0ull, 0ull};
-  unsigned long long* dChk = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&dChk, sizeof chk);
-  if (e == hipSuccess) e = hipMemcpy(dChk, chk, sizeof chk, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_image_check, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, 0, t->stR, capacity, dChk);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(chk, dChk, sizeof chk, hipMemcpyDeviceToHost);
-  hipFree(dChk);
-  if (e != hipSuccess) { hipFree(t->stR); hipFree(t->stL); delete t; return fail(TALC_ERR_DEVICE, "importing the table image: %s", hipGetErrorString(e)); }
+  DevBuf<unsigned long long> dChk;
+  HIPCHK(dChk.alloc(2));
+  HIPCHK(hipMemcpy(dChk.get(), chk, sizeof chk, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_image_check, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, 0, t->stR.get(), capacity, dChk.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(chk, dChk.get(), sizeof chk, hipMemcpyDeviceToHost));
   const unsigned long long keyBits = 2ull * (p->k - 1);
-  if ((chk[0] != ~0ull && chk[0] < p->min_count) || (keyBits < 64 && (chk[1] >> keyBits) != 0ull)) {
-    hipFree(t->stR); hipFree(t->stL); delete t;
+  if ((chk[0] != ~0ull && chk[0] < p->min_count) || (keyBits < 64 && (chk[1] >> keyBits) != 0ull))
     return fail(TALC_ERR_INVALID, "the image does not belong to these parameters: smallest stored count %llu (MIN_COUNT %u), keys wider than %llu bits: %s",
                 chk[0] == ~0ull ? 0ull : chk[0], p->min_count, keyBits, (keyBits < 64 && (chk[1] >> keyBits) != 0ull) ? "yes" : "no");
-  }
-  t->stagedDev = device;
-  *out = t;
+  *out = t.release();
   return TALC_OK;
 }
 
@@ -714,14 +637,13 @@ int talc_table_lookup_batch(talc_table* t, int device, const uint64_t* kmers, ui
   if (rc) return rc;
   if (n == 0) return TALC_OK;
   HIPCHK(hipSetDevice(device));
-  uint64_t* dk; uint32_t *dc, *dj;
-  HIPCHK(hipMalloc((void**)&dk, n * 8)); HIPCHK(hipMalloc((void**)&dc, n * 4)); HIPCHK(hipMalloc((void**)&dj, n * 4));
-  HIPCHK(hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk, n, dc, dj);
+  DevBuf<uint64_t> dk; DevBuf<uint32_t> dc, dj;
+  HIPCHK(dk.alloc(n)); HIPCHK(dc.alloc(n)); HIPCHK(dj.alloc(n));
+  HIPCHK(hipMemcpy(dk.get(), kmers, n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk.get(), n, dc.get(), dj.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(counts, dc, n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(jcounts, dj, n * 4, hipMemcpyDeviceToHost));
-  hipFree(dk); hipFree(dc); hipFree(dj);
+  HIPCHK(hipMemcpy(counts, dc.get(), n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(jcounts, dj.get(), n * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }
 
@@ -733,14 +655,13 @@ int talc_table_next_counts_batch(talc_table* t, int device, const uint64_t* kmer
   if (rc) return rc;
   if (n == 0) return TALC_OK;
   HIPCHK(hipSetDevice(device));
-  uint64_t* dk; uint32_t *dc, *dj;
-  HIPCHK(hipMalloc((void**)&dk, n * 8)); HIPCHK(hipMalloc((void**)&dc, n * 16)); HIPCHK(hipMalloc((void**)&dj, n * 16));
-  HIPCHK(hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_next_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk, n, direction ? 1 : 0, dc, dj);
+  DevBuf<uint64_t> dk; DevBuf<uint32_t> dc, dj;
+  HIPCHK(dk.alloc(n)); HIPCHK(dc.alloc(4 * n)); HIPCHK(dj.alloc(4 * n));
+  HIPCHK(hipMemcpy(dk.get(), kmers, n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_next_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk.get(), n, direction ? 1 : 0, dc.get(), dj.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(counts4, dc, n * 16, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(jcounts4, dj, n * 16, hipMemcpyDeviceToHost));
-  hipFree(dk); hipFree(dc); hipFree(dj);
+  HIPCHK(hipMemcpy(counts4, dc.get(), n * 16, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(jcounts4, dj.get(), n * 16, hipMemcpyDeviceToHost));
   return TALC_OK;
 }
 
@@ -754,19 +675,9 @@ int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uin
   return TALC_OK;
 }
 
-void talc_table_destroy(talc_table* t) {
-  if (!t) return;
-  for (auto& kv : t->h.dev) {
-    if (hipSetDevice(kv.first) == hipSuccess) { hipFree(kv.second.right); hipFree(kv.second.left); hipFree(kv.second.filter);
-      hipFree(kv.second.walkRight); hipFree(kv.second.walkLeft); }
-  }
-  if (t->stagedDev >= 0 && hipSetDevice(t->stagedDev) == hipSuccess) { hipFree(t->stR); hipFree(t->stL); }
-  delete t;
-}
+void talc_table_destroy(talc_table* t) { delete t; }
 
 // ------------------------------------------------------------------ context
-static void free_stage(Stage& s) { if (s.scratch) hipFree(s.scratch); if (s.boxes) hipFree(s.boxes); s = Stage(); }
-
 int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** out) {
   int rc = check_params(p);
   if (rc) return rc;
@@ -778,7 +689,7 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   rc = table_view(t, device, v);
   if (rc) return rc;
   HIPCHK(hipSetDevice(device));
-  talc_ctx* c = new talc_ctx();
+  auto c = std::make_unique<talc_ctx>();
   c->table = t; c->p = *p; c->device = device; c->view = v;
   c->sw = read_switches();
   memset(&c->timing, 0, sizeof c->timing);
@@ -793,35 +704,22 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   d.costGapQuad = 10; d.costGapFork = 200; d.costGapCap = 900; d.pad_ = 0;   // (profiles/r03/cost_sweep.txt)
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipMalloc((void**)&c->d_queue, kQueueWords * sizeof(uint32_t)));
-  HIPCHK(hipMalloc((void**)&c->d_hist, (1024 + 256) * sizeof(uint32_t)));   // (+ the batch's fork statistics, k_order_scale)
-  HIPCHK(hipMalloc((void**)&c->d_counters, (128 + 2 * 8192) * sizeof(uint64_t)));   // 128 counters + the profile build's record of every wave's last read
+  HIPCHK(c->d_queue.alloc(kQueueWords));
+  HIPCHK(c->d_hist.alloc(1024 + 256));   // (+ the batch's fork statistics, k_order_scale)
+  HIPCHK(c->d_counters.alloc(128 + 2 * 8192));   // 128 counters + the profile build's record of every wave's last read
   {   // isExpectedbyMyModel as two thresholds per count (Explorer.cpp:1185-1201), from the formula itself, for this ALPHA
     const uint32_t n = 4096;
-    HIPCHK(hipMalloc((void**)&c->d_thr, 2ull * n * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_build_thresholds, dim3((n + 255) / 256), dim3(256), 0, c->stream, d.ALPHA, n, c->d_thr);
+    HIPCHK(c->d_thr.alloc(2ull * n));
+    hipLaunchKernelGGL(k_build_thresholds, dim3((n + 255) / 256), dim3(256), 0, c->stream, d.ALPHA, n, c->d_thr.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    d.thr = c->d_thr; d.thrN = n; d.pad2_ = 0;
+    d.thr = c->d_thr.get(); d.thrN = n; d.pad2_ = 0;
   }
-  *out = c;
+  *out = c.release();
   return TALC_OK;
 }
 
-void talc_ctx_destroy(talc_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  free_stage(c->stage);
-  for (auto& e : c->pool) hipFree(e.second);
-  for (auto& e : c->live) hipFree(e.first);   // (batches that outlived their context: their memory goes with it)
-  if (c->d_queue) hipFree(c->d_queue);
-  if (c->d_hist) hipFree(c->d_hist);
-  if (c->d_counters) hipFree(c->d_counters);
-  if (c->d_thr) hipFree(c->d_thr);
-  for (auto& e : c->ev) if (e) hipEventDestroy(e);
-  if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
-}
+void talc_ctx_destroy(talc_ctx* c) { delete c; }
 
 int talc_ctx_get_timing(const talc_ctx* c, talc_timing* out) {
   if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
@@ -830,23 +728,15 @@ int talc_ctx_get_timing(const talc_ctx* c, talc_timing* out) {
 }
 
 // ------------------------------------------------------------------ batch
-void talc_batch_destroy(talc_batch* b) {
-  if (!b) return;
-  (void)hipSetDevice(b->ctx->device);
-  void* ptrs[] = {b->d_raw, b->d_codes, b->d_offsets, b->d_koff, b->d_tile_read, b->d_tile_start, b->d_chunk_read,
-                  b->d_chunk_start, b->d_order, b->d_cov, b->d_covw, b->d_nin, b->d_state, b->d_regions, b->d_regoff, b->d_out, b->d_outoff,
-                  b->d_dense, b->d_dense_off, b->d_headcov};
-  for (void* p : ptrs) if (p) ctx_release(b->ctx, p);
-  delete b;
-}
+void talc_batch_destroy(talc_batch* b) { delete b; }
 
 int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
   if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(c->device));
-  talc_batch* b = new talc_batch();
+  auto b = std::make_unique<talc_batch>();
   b->ctx = c; b->n_reads = n_reads;
   b->h_offsets.assign(offsets, offsets + n_reads + 1);
-  if (b->h_offsets[0] != 0) { delete b; return fail(TALC_ERR_INVALID, "offsets[0] must be 0"); }
+  if (b->h_offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
   b->n_bases = b->h_offsets[n_reads];
   const uint32_t K = c->p.k;
   b->h_koff.resize(n_reads + 1);
@@ -854,9 +744,9 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   b->h_outoff.resize(n_reads + 1);
   uint64_t ko = 0, ro = 0, oo = 0;
   for (uint32_t r = 0; r < n_reads; ++r) {
-    if (offsets[r + 1] < offsets[r]) { delete b; return fail(TALC_ERR_INVALID, "offsets must be non-decreasing"); }
+    if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must be non-decreasing");
     const uint64_t L = offsets[r + 1] - offsets[r];
-    if (L > 0x7fffff00ull) { delete b; return fail(TALC_ERR_INVALID, "read %u too long", r); }
+    if (L > 0x7fffff00ull) return fail(TALC_ERR_INVALID, "read %u too long", r);
     b->max_len = std::max<uint32_t>(b->max_len, (uint32_t)L);
     const uint64_t nk = L >= K ? L - K + 1 : 0;
     b->h_koff[r] = ko; ko += nk;
@@ -869,28 +759,28 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   b->n_kmers = ko; b->out_capacity = oo;
   hipStream_t s = c->stream;
   int rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_raw, std::max<uint64_t>(b->n_bases, 1)))) return rc;
+  HIPCHK(b->d_raw.alloc(c->cache, std::max<uint64_t>(b->n_bases, 1)));
   // (+ 64: a search may read a stretch of a read in place, and the wave routines fetch whole 8- and 16-byte words)
-  if ((rc = ctx_alloc(c, (void**)&b->d_codes, std::max<uint64_t>(b->n_bases, 1) + 64))) return rc;
-  if (b->n_bases) HIPCHK(hipMemcpyAsync(b->d_raw, bases, b->n_bases, hipMemcpyHostToDevice, s));
-  if ((rc = up(c, &b->d_offsets, b->h_offsets, s))) return rc;
-  if ((rc = up(c, &b->d_koff, b->h_koff, s))) return rc;
-  if ((rc = up(c, &b->d_regoff, b->h_regoff, s))) return rc;
-  if ((rc = up(c, &b->d_outoff, b->h_outoff, s))) return rc;
-  if ((rc = up(c, &b->d_tile_read, b->h_tile_read, s))) return rc;
-  if ((rc = up(c, &b->d_tile_start, b->h_tile_start, s))) return rc;
-  if ((rc = up(c, &b->d_chunk_read, b->h_chunk_read, s))) return rc;
-  if ((rc = up(c, &b->d_chunk_start, b->h_chunk_start, s))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_order, std::max<uint32_t>(n_reads, 1) * sizeof(uint32_t)))) return rc;   // (run_pipeline orders the queue)
-  if ((rc = ctx_alloc(c, (void**)&b->d_cov, std::max<uint64_t>(b->n_kmers, 1) * sizeof(uint2)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_covw, cov_words_total(b->n_kmers, n_reads) * sizeof(CovWord)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_nin, std::max<uint32_t>(n_reads, 1) * sizeof(int32_t)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_state, std::max<uint32_t>(n_reads, 1) * sizeof(ReadState)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_headcov, std::max<uint32_t>(n_reads, 1) * (uint64_t)kHeadCov * sizeof(uint32_t)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_regions, std::max<uint64_t>(ro, 1) * 3 * sizeof(uint32_t)))) return rc;
-  if ((rc = ctx_alloc(c, (void**)&b->d_out, std::max<uint64_t>(oo, 1)))) return rc;
+  HIPCHK(b->d_codes.alloc(c->cache, std::max<uint64_t>(b->n_bases, 1) + 64));
+  if (b->n_bases) HIPCHK(hipMemcpyAsync(b->d_raw.get(), bases, b->n_bases, hipMemcpyHostToDevice, s));
+  if ((rc = up(c, b->d_offsets, b->h_offsets, s))) return rc;
+  if ((rc = up(c, b->d_koff, b->h_koff, s))) return rc;
+  if ((rc = up(c, b->d_regoff, b->h_regoff, s))) return rc;
+  if ((rc = up(c, b->d_outoff, b->h_outoff, s))) return rc;
+  if ((rc = up(c, b->d_tile_read, b->h_tile_read, s))) return rc;
+  if ((rc = up(c, b->d_tile_start, b->h_tile_start, s))) return rc;
+  if ((rc = up(c, b->d_chunk_read, b->h_chunk_read, s))) return rc;
+  if ((rc = up(c, b->d_chunk_start, b->h_chunk_start, s))) return rc;
+  HIPCHK(b->d_order.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));   // (run_pipeline orders the queue)
+  HIPCHK(b->d_cov.alloc(c->cache, std::max<uint64_t>(b->n_kmers, 1)));
+  HIPCHK(b->d_covw.alloc(c->cache, cov_words_total(b->n_kmers, n_reads)));
+  HIPCHK(b->d_nin.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
+  HIPCHK(b->d_state.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
+  HIPCHK(b->d_headcov.alloc(c->cache, std::max<uint32_t>(n_reads, 1) * (uint64_t)kHeadCov));
+  HIPCHK(b->d_regions.alloc(c->cache, std::max<uint64_t>(ro, 1) * 3));
+  HIPCHK(b->d_out.alloc(c->cache, std::max<uint64_t>(oo, 1)));
   HIPCHK(hipStreamSynchronize(s));
-  *out = b;
+  *out = b.release();
   return TALC_OK;
 }
 
@@ -899,17 +789,17 @@ uint64_t talc_batch_num_bases(const talc_batch* b) { return b ? b->n_bases : 0; 
 
 static int launch_encode(talc_ctx* c, talc_batch* b) {
   if (!b->h_chunk_read.empty())
-    hipLaunchKernelGGL(k_encode, dim3((unsigned)b->h_chunk_read.size()), dim3(256), 0, c->stream, b->d_raw, b->d_codes,
-                       b->d_offsets, b->d_chunk_read, b->d_chunk_start, c->p.reverse ? 1 : 0);
+    hipLaunchKernelGGL(k_encode, dim3((unsigned)b->h_chunk_read.size()), dim3(256), 0, c->stream, b->d_raw.get(), b->d_codes.get(),
+                       b->d_offsets.get(), b->d_chunk_read.get(), b->d_chunk_start.get(), c->p.reverse ? 1 : 0);
   HIPCHK(hipGetLastError());
   b->encoded = true;
   return TALC_OK;
 }
 static int launch_coverage(talc_ctx* c, talc_batch* b) {
-  HIPCHK(hipMemsetAsync(b->d_nin, 0, std::max<uint32_t>(b->n_reads, 1) * sizeof(int32_t), c->stream));
+  HIPCHK(hipMemsetAsync(b->d_nin.get(), 0, std::max<uint32_t>(b->n_reads, 1) * sizeof(int32_t), c->stream));
   if (!b->h_tile_read.empty())
     hipLaunchKernelGGL(k_coverage, dim3((unsigned)b->h_tile_read.size()), dim3(COV_THREADS), 0, c->stream, c->view,
-                       b->d_codes, b->d_offsets, b->d_koff, b->d_tile_read, b->d_tile_start, b->d_cov, b->d_covw, b->d_nin,
+                       b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(), b->d_tile_read.get(), b->d_tile_start.get(), b->d_cov.get(), b->d_covw.get(), b->d_nin.get(),
                        c->p.min_count);
   HIPCHK(hipGetLastError());
   b->covered = true;
@@ -944,8 +834,8 @@ int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint
     const uint64_t nw = cov_words_total(b->n_kmers, b->n_reads);
     std::vector<uint2> h(b->n_kmers);
     std::vector<CovWord> w(nw);
-    HIPCHK(hipMemcpy(h.data(), b->d_cov, b->n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(w.data(), b->d_covw, nw * sizeof(CovWord), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.data(), b->d_cov.get(), b->n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(w.data(), b->d_covw.get(), nw * sizeof(CovWord), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < b->n_reads; ++r) {
       const uint64_t k0 = b->h_koff[r], nk = b->h_koff[r + 1] - k0;
       const CovWord* rw = w.data() + cov_word_base(k0, r);
@@ -962,7 +852,7 @@ int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint
     }
   }
   if (kmer_offsets) memcpy(kmer_offsets, b->h_koff.data(), (b->n_reads + 1) * 8);
-  if (n_in_kmers && b->n_reads) HIPCHK(hipMemcpy(n_in_kmers, b->d_nin, b->n_reads * 4, hipMemcpyDeviceToHost));
+  if (n_in_kmers && b->n_reads) HIPCHK(hipMemcpy(n_in_kmers, b->d_nin.get(), b->n_reads * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }
 
@@ -977,13 +867,13 @@ struct talc_counter {
   int device = 0;
   Switches sw;
   hipStream_t stream = nullptr;
-  CountSlot* tab = nullptr;
+  DevBuf<CountSlot> tab;
   uint64_t cap = 0;
-  unsigned long long* dStats = nullptr;   // [0] windows counted, [1] distinct, [2] compaction output counter
-  uint32_t* dOverflow = nullptr;
-  uint8_t* dText = nullptr;
+  DevBuf<unsigned long long> dStats;   // [0] windows counted, [1] distinct, [2] compaction output counter
+  DevBuf<uint32_t> dOverflow;
+  DevBuf<uint8_t> dText;
   uint64_t dTextCap = 0;
-  char* stage[2] = {nullptr, nullptr};
+  PinnedBuf stage[2];
   uint64_t stageCap[2] = {0, 0};
   hipEvent_t stageEv[2] = {nullptr, nullptr};
   bool stageBusy[2] = {false, false};
@@ -996,20 +886,21 @@ struct talc_counter {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
   uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
   double packS = 0, growS = 0;
+  ~talc_counter() {
+    (void)hipSetDevice(device);
+    for (auto& e : stageEv) if (e) hipEventDestroy(e);
+    for (auto& ev : kev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    if (stream) hipStreamDestroy(stream);
+  }
 };
-
-static void counter_free_hash(talc_counter* c) {
-  hipFree(c->tab); c->tab = nullptr; c->cap = 0;
-  hipFree(c->dText); c->dText = nullptr; c->dTextCap = 0;
-}
 
 // the exact counters from the device (synchronises the stream); fails when a count has passed 2^32 - 1
 static int counter_sync(talc_counter* c, unsigned long long st[2]) {
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   uint32_t ovf = 0;
-  HIPCHK(hipMemcpy(st, c->dStats, 2 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&ovf, c->dOverflow, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(st, c->dStats.get(), 2 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&ovf, c->dOverflow.get(), 4, hipMemcpyDeviceToHost));
   if (ovf) return fail(TALC_ERR_INVALID, "a k-mer count passed 2^32 - 1 (counts are 32-bit); the counter is unusable");
   c->distinctKnown = st[1];
   c->winsSince = 0;
@@ -1018,13 +909,13 @@ static int counter_sync(talc_counter* c, unsigned long long st[2]) {
 
 // slots with count >= thr: how many (outK == nullptr) or the arrays themselves (device pointers of outCap entries)
 static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32_t* outC, uint64_t outCap, uint64_t* n) {
-  HIPCHK(hipMemsetAsync(c->dStats + 2, 0, 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->dStats.get() + 2, 0, 8, c->stream));
   if (c->cap)
     hipLaunchKernelGGL(k_count_compact, dim3((unsigned)((c->cap + 4 * 64 * kCompactRows - 1) / (4 * 64 * kCompactRows))), dim3(256), 0,
-                       c->stream, c->tab, c->cap, thr, outK, outC, outCap, c->dStats + 2);
+                       c->stream, c->tab.get(), c->cap, thr, outK, outC, outCap, c->dStats.get() + 2);
   HIPCHK(hipGetLastError());
   unsigned long long v = 0;
-  HIPCHK(hipMemcpyAsync(&v, c->dStats + 2, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&v, c->dStats.get() + 2, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *n = v;
   return TALC_OK;
@@ -1035,24 +926,27 @@ static int counter_grow(talc_counter* c, uint64_t need) {
   const auto t0 = std::chrono::steady_clock::now();
   uint64_t nc = c->cap;
   while ((double)need > 0.7 * (double)nc) nc *= 2;
-  CountSlot* nt = nullptr;
-  if (hipMalloc((void**)&nt, nc * sizeof(CountSlot)) != hipSuccess) {
+  DevBuf<CountSlot> nt;
+  if (nt.alloc(nc) != hipSuccess) {
     (void)hipGetLastError();
     return fail(TALC_ERR_NOMEM, "the k-mer counter cannot grow to %llu slots (%llu bytes) after %llu distinct k-mers",
                 (unsigned long long)nc, (unsigned long long)(nc * sizeof(CountSlot)), (unsigned long long)c->distinctKnown);
   }
-  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, nt, nc);
-  hipLaunchKernelGGL(k_count_rehash, dim3((unsigned)((c->cap + 255) / 256)), dim3(256), 0, c->stream, c->tab, c->cap, nt, nc - 1);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess) {
-    hipFree(c->tab);
-    c->tab = nt; c->cap = nc;
-    ++c->nGrows;
-    c->growS += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return TALC_OK;
-  }
-  hipFree(nt);
-  return fail(TALC_ERR_DEVICE, "rehashing the k-mer counter: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, nt.get(), nc);
+  hipLaunchKernelGGL(k_count_rehash, dim3((unsigned)((c->cap + 255) / 256)), dim3(256), 0, c->stream, c->tab.get(), c->cap, nt.get(), nc - 1);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->tab = std::move(nt);   // (frees the old slots)
+  c->cap = nc;
+  ++c->nGrows;
+  c->growS += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return TALC_OK;
+}
+
+// a step of talc_counter_create: what does not fit is TALC_ERR_NOMEM, every other failure a device error
+static int counter_rc(hipError_t e, const char* what) {
+  if (e == hipSuccess) return TALC_OK;
+  return fail(e == hipErrorOutOfMemory ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "k-mer counter: %s: %s", what, hipGetErrorString(e));
 }
 
 int talc_counter_create(const talc_params* p, int device, uint64_t expected_distinct, talc_counter** out) {
@@ -1062,30 +956,25 @@ int talc_counter_create(const talc_params* p, int device, uint64_t expected_dist
   const int ndev = talc_device_count();
   if (device < 0 || device >= ndev)
     return fail(TALC_ERR_DEVICE, "no GPU %d for the k-mer counter (%d visible); there is no host counter", device, ndev);
-  talc_counter* c = new talc_counter();
+  auto c = std::make_unique<talc_counter>();
   c->p = *p;
   c->device = device;
   c->sw = read_switches();
   uint64_t cap = 1u << 16;   // 1 MiB without a hint
   while (expected_distinct && (double)expected_distinct > 0.7 * (double)cap) cap *= 2;
-  auto bad = [&](hipError_t e, const char* what) {
-    talc_counter_destroy(c);
-    return fail(e == hipErrorOutOfMemory ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "k-mer counter: %s: %s", what, hipGetErrorString(e));
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bad(e, "hipSetDevice");
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
-  for (int i = 0; i < 2; ++i)
-    if ((e = hipEventCreateWithFlags(&c->stageEv[i], hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
-  if ((e = hipMalloc((void**)&c->tab, cap * sizeof(CountSlot))) != hipSuccess) return bad(e, "hash allocation");
+  if ((rc = counter_rc(hipSetDevice(device), "hipSetDevice"))) return rc;
+  if ((rc = counter_rc(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+  for (auto& e : c->stageEv)
+    if ((rc = counter_rc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"))) return rc;
+  if ((rc = counter_rc(c->tab.alloc(cap), "hash allocation"))) return rc;
   c->cap = cap;
-  if ((e = hipMalloc((void**)&c->dStats, 4 * 8)) != hipSuccess) return bad(e, "counter allocation");
-  if ((e = hipMalloc((void**)&c->dOverflow, 4)) != hipSuccess) return bad(e, "counter allocation");
-  if ((e = hipMemsetAsync(c->dStats, 0, 4 * 8, c->stream)) != hipSuccess) return bad(e, "hipMemset");
-  if ((e = hipMemsetAsync(c->dOverflow, 0, 4, c->stream)) != hipSuccess) return bad(e, "hipMemset");
-  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->stream, c->tab, cap);
-  if ((e = hipGetLastError()) != hipSuccess) return bad(e, "k_count_init");
-  *out = c;
+  if ((rc = counter_rc(c->dStats.alloc(4), "counter allocation"))) return rc;
+  if ((rc = counter_rc(c->dOverflow.alloc(1), "counter allocation"))) return rc;
+  if ((rc = counter_rc(hipMemsetAsync(c->dStats.get(), 0, 4 * 8, c->stream), "hipMemset"))) return rc;
+  if ((rc = counter_rc(hipMemsetAsync(c->dOverflow.get(), 0, 4, c->stream), "hipMemset"))) return rc;
+  hipLaunchKernelGGL(k_count_init, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->stream, c->tab.get(), cap);
+  if ((rc = counter_rc(hipGetLastError(), "k_count_init"))) return rc;
+  *out = c.release();
   return TALC_OK;
 }
 
@@ -1116,16 +1005,15 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   c->next ^= 1;
   if (c->stageBusy[b]) { HIPCHK(hipEventSynchronize(c->stageEv[b])); c->stageBusy[b] = false; }
   if (c->stageCap[b] < nbytes) {
-    if (c->stage[b]) { hipHostFree(c->stage[b]); c->stage[b] = nullptr; c->stageCap[b] = 0; }
+    c->stage[b].reset(); c->stageCap[b] = 0;
     const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
-    if (hipHostMalloc((void**)&c->stage[b], want, hipHostMallocDefault) != hipSuccess) {
+    if (c->stage[b].alloc(want) != hipSuccess) {
       (void)hipGetLastError();
-      c->stage[b] = nullptr;
       return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want);
     }
     c->stageCap[b] = want;
   }
-  char* dst = c->stage[b];
+  char* dst = c->stage[b].get();
 #pragma omp parallel for schedule(static) if (n_reads > 100000)
   for (long r = 0; r < (long)n_reads; ++r) {
     const uint64_t at = offsets[r] - o0 + (uint64_t)r;
@@ -1135,16 +1023,16 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   c->packS += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
   if (c->dTextCap < nbytes) {   // (the previous kernel may still read the old buffer)
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(c->dText); c->dText = nullptr; c->dTextCap = 0;
+    c->dText.reset(); c->dTextCap = 0;
     const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
-    if (hipMalloc((void**)&c->dText, want) != hipSuccess) {
+    if (c->dText.alloc(want) != hipSuccess) {
       (void)hipGetLastError();
       return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes for a batch of the k-mer counter (%llu distinct k-mers so far)",
                   (unsigned long long)want, (unsigned long long)c->distinctKnown);
     }
     c->dTextCap = want;
   }
-  HIPCHK(hipMemcpyAsync(c->dText, dst, nbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->dText.get(), dst, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipEventRecord(c->stageEv[b], c->stream));
   c->stageBusy[b] = true;
   c->winsTotal += wins;
@@ -1152,16 +1040,19 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   const uint64_t nblk = (nbytes + kCountTile - 1) / kCountTile;
   if (nblk >= (1ull << 31)) return fail(TALC_ERR_INVALID, "batch of %llu bytes is too large", (unsigned long long)nbytes);
   std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-  if (c->sw.timing && hipEventCreate(&ev.first) == hipSuccess && hipEventCreate(&ev.second) == hipSuccess)
-    HIPCHK(hipEventRecord(ev.first, c->stream));
+  if (c->sw.timing) {   // (a complete pair belongs to the counter at once; half a pair is not kept)
+    if (hipEventCreate(&ev.first) == hipSuccess && hipEventCreate(&ev.second) == hipSuccess) c->kev.push_back(ev);
+    else { if (ev.first) hipEventDestroy(ev.first); ev = {nullptr, nullptr}; }
+  }
+  if (ev.second) HIPCHK(hipEventRecord(ev.first, c->stream));
   if (checked)
-    hipLaunchKernelGGL(k_count_batch<true>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText, nbytes, K, c->tab,
-                       c->cap - 1, c->dStats, c->dOverflow);
+    hipLaunchKernelGGL(k_count_batch<true>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText.get(), nbytes, K, c->tab.get(),
+                       c->cap - 1, c->dStats.get(), c->dOverflow.get());
   else
-    hipLaunchKernelGGL(k_count_batch<false>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText, nbytes, K, c->tab,
-                       c->cap - 1, c->dStats, c->dOverflow);
+    hipLaunchKernelGGL(k_count_batch<false>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText.get(), nbytes, K, c->tab.get(),
+                       c->cap - 1, c->dStats.get(), c->dOverflow.get());
   HIPCHK(hipGetLastError());
-  if (ev.second) { HIPCHK(hipEventRecord(ev.second, c->stream)); c->kev.push_back(ev); }
+  if (ev.second) HIPCHK(hipEventRecord(ev.second, c->stream));
   c->winsSince += wins;
   ++c->nBatches;
   c->nBytes += nbytes;
@@ -1192,19 +1083,14 @@ int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uin
   if (!kmers) return TALC_OK;
   if (capacity < n) return fail(TALC_ERR_CAPACITY, "%llu k-mers need the output arrays' room, %llu given", (unsigned long long)n,
                                 (unsigned long long)capacity);
-  uint64_t* dK = nullptr;
-  uint32_t* dC = nullptr;
-  auto drop = [&]() { hipFree(dK); hipFree(dC); };
-  hipError_t e = hipMalloc((void**)&dK, std::max<uint64_t>(n, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&dC, std::max<uint64_t>(n, 1) * 4);
-  if (e != hipSuccess) { (void)hipGetLastError(); drop(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu k-mers for the fetch", (unsigned long long)n); }
+  DevBuf<uint64_t> dK;
+  DevBuf<uint32_t> dC;
+  if (dK.alloc(std::max<uint64_t>(n, 1)) != hipSuccess || dC.alloc(std::max<uint64_t>(n, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu k-mers for the fetch", (unsigned long long)n); }
   uint64_t got = 0;
-  if ((rc = counter_compact(c, min_count, dK, dC, n, &got))) { drop(); return rc; }
-  if (got != n) { drop(); return fail(TALC_ERR_STATE, "the counter changed between two compactions (%llu, %llu)", (unsigned long long)n, (unsigned long long)got); }
-  e = hipMemcpy(kmers, dK, n * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(counts, dC, n * 4, hipMemcpyDeviceToHost);
-  drop();
-  if (e != hipSuccess) return fail(TALC_ERR_DEVICE, "copying the counts to the host: %s", hipGetErrorString(e));
+  if ((rc = counter_compact(c, min_count, dK.get(), dC.get(), n, &got))) return rc;
+  if (got != n) return fail(TALC_ERR_STATE, "the counter changed between two compactions (%llu, %llu)", (unsigned long long)n, (unsigned long long)got);
+  HIPCHK(hipMemcpy(kmers, dK.get(), n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(counts, dC.get(), n * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }
 
@@ -1219,15 +1105,14 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
   uint64_t kept = 0;
   if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept))) return rc;
   if (kept >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
-  uint64_t* dK = nullptr;
-  uint32_t* dC = nullptr;
-  hipError_t e = hipMalloc((void**)&dK, std::max<uint64_t>(kept, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&dC, std::max<uint64_t>(kept, 1) * 4);
-  if (e != hipSuccess) { (void)hipGetLastError(); hipFree(dK); hipFree(dC); return fail(TALC_ERR_NOMEM, "cannot allocate the %llu kept k-mers", (unsigned long long)kept); }
+  DevBuf<uint64_t> dK;
+  DevBuf<uint32_t> dC;
+  if (dK.alloc(std::max<uint64_t>(kept, 1)) != hipSuccess || dC.alloc(std::max<uint64_t>(kept, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the %llu kept k-mers", (unsigned long long)kept); }
   uint64_t got = 0;
-  if ((rc = counter_compact(c, c->p.min_count, dK, dC, kept, &got))) { hipFree(dK); hipFree(dC); return rc; }
+  if ((rc = counter_compact(c, c->p.min_count, dK.get(), dC.get(), kept, &got))) return rc;
   // the hash goes before the builder allocates its buckets; the counter is spent from here on
-  counter_free_hash(c);
+  c->tab.reset(); c->cap = 0;
+  c->dText.reset(); c->dTextCap = 0;
   c->spent = true;
   const auto t2 = std::chrono::steady_clock::now();
   if (c->sw.timing) {
@@ -1240,25 +1125,18 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
             std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t2 - t1).count());
   }
   talc_table* t = nullptr;
-  if ((rc = build_table_from_device_arrays(dK, dC, kept, kept, &c->p, c->device, &t, 0.0, 0.0, c->sw))) return rc;
+  if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, &t, 0.0, 0.0, c->sw))) return rc;
   DumpStats ds;
   ds.nread = (int64_t)st[1];
   ds.nkept = (int64_t)kept;
-  return table_finish(t, junction_path, &c->p, ds, out, stats);
+  return table_finish(std::unique_ptr<talc_table>(t), junction_path, &c->p, ds, out, stats);
 }
 
 void talc_counter_destroy(talc_counter* c) {
   if (!c) return;
-  if (hipSetDevice(c->device) == hipSuccess) {
-    if (c->stream) hipStreamSynchronize(c->stream);
-    counter_free_hash(c);
-    hipFree(c->dStats); hipFree(c->dOverflow);
-    for (int i = 0; i < 2; ++i) { if (c->stage[i]) hipHostFree(c->stage[i]); if (c->stageEv[i]) hipEventDestroy(c->stageEv[i]); }
-    for (auto& ev : c->kev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    if (c->stream) hipStreamDestroy(c->stream);
-  }
-  (void)hipGetLastError();
+  if (hipSetDevice(c->device) == hipSuccess && c->stream) hipStreamSynchronize(c->stream);   // (its kernels may still run)
   delete c;
+  (void)hipGetLastError();
 }
 
 #include "talc_capi_correct.inc"

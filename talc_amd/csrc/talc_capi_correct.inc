@@ -17,13 +17,12 @@ static void ensure_edge_boxes(talc_ctx* c, Stage& st) {
   const uint64_t need = (uint64_t)st.n_slots * edge_box_bytes(seqCap) + (uint64_t)st.n_slots * 4;
   if (c->sw.edgeTasks == 0 || c->p.max_start_anchors < 2 || c->p.max_start_anchors > EDGE_BOX_ANCHORS ||
       seqCap > (1u << 16) || need > (1ull << 30)) {   // (a border length in the tens of kilobases: not worth a gigabyte)
-    if (st.boxes) { hipFree(st.boxes); st.boxes = nullptr; st.boxes_bytes = 0; }
+    st.boxes.reset(); st.boxes_bytes = 0;
     return;
   }
   if (need > st.boxes_bytes || seqCap != st.box_seq_cap) {
-    if (st.boxes) hipFree(st.boxes);
-    st.boxes = nullptr; st.boxes_bytes = 0;
-    if (hipMalloc((void**)&st.boxes, need) != hipSuccess) { (void)hipGetLastError(); st.boxes = nullptr; return; }   // (the search runs without)
+    st.boxes.reset(); st.boxes_bytes = 0;   // (the old boxes go before the larger ones are asked for)
+    if (st.boxes.alloc(need) != hipSuccess) { (void)hipGetLastError(); return; }   // (the search runs without)
     st.boxes_bytes = need; st.box_seq_cap = seqCap;
   }
 }
@@ -49,16 +48,14 @@ static int ensure_stage(talc_ctx* c, Stage& st, uint32_t maxLen, uint32_t scale,
     while (slots > 1 && (uint64_t)slots * caps.slotBytes > avail) slots /= 2;
     const uint64_t need = (uint64_t)slots * caps.slotBytes;
     const bool cramped = slots < wantSlots || (uint64_t)caps.slotBytes > avail;
-    if (cramped && attempt == 0 && c->pool_bytes) { ctx_pool_trim(c, 0); continue; }
+    if (cramped && attempt == 0 && c->cache.pool_bytes) { c->cache.trim(0); continue; }
     if ((uint64_t)caps.slotBytes > avail && need > st.scratch_bytes)
       return fail(TALC_ERR_NOMEM, "per-wave scratch of %llu bytes does not fit the device", (unsigned long long)caps.slotBytes);
     if (need > st.scratch_bytes) {
-      if (st.scratch) hipFree(st.scratch);
-      st.scratch = nullptr; st.scratch_bytes = 0;
-      if (hipMalloc((void**)&st.scratch, need) != hipSuccess) {
+      st.scratch.reset(); st.scratch_bytes = 0;   // (the old scratch goes before the larger one is asked for)
+      if (st.scratch.alloc(need) != hipSuccess) {
         (void)hipGetLastError();
-        st.scratch = nullptr;
-        if (attempt == 0) { ctx_pool_trim(c, 0); continue; }
+        if (attempt == 0) { c->cache.trim(0); continue; }
         return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of search scratch", (unsigned long long)need);
       }
       st.scratch_bytes = need;
@@ -71,7 +68,7 @@ static int ensure_stage(talc_ctx* c, Stage& st, uint32_t maxLen, uint32_t scale,
 }
 
 struct TraceHost {
-  TraceRec* d_recs = nullptr; uint32_t* d_nrec = nullptr; uint8_t* d_pool = nullptr; uint32_t* d_npool = nullptr;
+  DevBuf<TraceRec> d_recs; DevBuf<uint32_t> d_nrec; DevBuf<uint8_t> d_pool; DevBuf<uint32_t> d_npool;
   uint32_t cap = 0, poolCap = 0;
 };
 
@@ -102,7 +99,7 @@ static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
   if (c->sw.profSlow && c->stage.n_slots) {   // the record of every wave's last read: the waves that end last
     const uint32_t nw = std::min<uint32_t>(c->stage.n_slots, 8192);
     std::vector<uint64_t> lg(2 * (size_t)nw);
-    HIPCHK(hipMemcpy(lg.data(), c->d_counters + 128, lg.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lg.data(), c->d_counters.get() + 128, lg.size() * 8, hipMemcpyDeviceToHost));
     std::vector<uint32_t> idx(nw);
     for (uint32_t i = 0; i < nw; ++i) idx[i] = i;
     const uint32_t t0 = (uint32_t)counters[126];
@@ -128,7 +125,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   hipStream_t s = c->stream;
   int rc;
   TraceBuf tb = {};
-  if (th) { tb.recs = th->d_recs; tb.nrec = th->d_nrec; tb.cap = th->cap; tb.pool = th->d_pool; tb.npool = th->d_npool; tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
+  if (th) { tb.recs = th->d_recs.get(); tb.nrec = th->d_nrec.get(); tb.cap = th->cap; tb.pool = th->d_pool.get(); tb.npool = th->d_npool.get(); tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   HIPCHK(hipEventRecord(c->ev[0], s));
@@ -136,48 +133,48 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   HIPCHK(hipEventRecord(c->ev[1], s));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[2], s));
-  HIPCHK(hipMemsetAsync(c->d_hist + 1024, 0, 256 * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(c->d_hist.get() + 1024, 0, 256 * sizeof(uint32_t), s));
   if (b->n_reads)
-    hipLaunchKernelGGL(k_structure, dim3(b->n_reads), dim3(64), 0, s, c->dp, c->view, b->d_codes, b->d_offsets, b->d_koff,
-                       b->d_cov, b->d_covw, b->d_nin, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->n_reads, tb, traceRead, c->d_hist + 1024);
+    hipLaunchKernelGGL(k_structure, dim3(b->n_reads), dim3(64), 0, s, c->dp, c->view, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
+                       b->d_cov.get(), b->d_covw.get(), b->d_nin.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->n_reads, tb, traceRead, c->d_hist.get() + 1024);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[3], s));
   // ---- the work queue: heaviest reads first, by k_structure's estimate
   if (b->n_reads) {
-    HIPCHK(hipMemsetAsync(c->d_hist, 0, 1024 * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(c->d_hist.get(), 0, 1024 * sizeof(uint32_t), s));
     const unsigned nb = (b->n_reads + 255) / 256;
-    hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, c->d_hist + 1024);
-    hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, c->d_hist + 1024);
-    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, s, c->d_hist);
-    hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state, b->n_reads, c->d_hist, b->d_order, c->d_hist + 1024);
+    hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, c->d_hist.get() + 1024);
+    hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, c->d_hist.get(), c->d_hist.get() + 1024);
+    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, s, c->d_hist.get());
+    hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, c->d_hist.get(), b->d_order.get(), c->d_hist.get() + 1024);
     HIPCHK(hipGetLastError());
   }
   // ---- search, first pass
-  HIPCHK(hipMemsetAsync(c->d_queue, 0, kQueueWords * sizeof(uint32_t), s));
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, (128 + 2 * 8192) * sizeof(uint64_t), s));
-  HIPCHK(hipMemsetAsync(c->d_counters + 126, 0xFF, sizeof(uint64_t), s));   // (profile build: running minimum)
-  HIPCHK(hipMemsetAsync(c->d_counters + 124, 0xFF, sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(c->d_counters.get(), 0, (128 + 2 * 8192) * sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(c->d_counters.get() + 126, 0xFF, sizeof(uint64_t), s));   // (profile build: running minimum)
+  HIPCHK(hipMemsetAsync(c->d_counters.get() + 124, 0xFF, sizeof(uint64_t), s));
   if (b->n_reads) {
     if ((rc = ensure_stage(c, c->stage, b->max_len, 1, b->n_reads))) return rc;
     ensure_edge_boxes(c, c->stage);
     EdgeTaskArgs ea = {};
     if (c->stage.boxes) {   // the claim counters sit behind the boxes
-      ea.boxes = c->stage.boxes;
-      ea.avail = (uint32_t*)(c->stage.boxes + (uint64_t)c->stage.n_slots * edge_box_bytes(c->stage.box_seq_cap));
+      ea.boxes = c->stage.boxes.get();
+      ea.avail = (uint32_t*)(c->stage.boxes.get() + (uint64_t)c->stage.n_slots * edge_box_bytes(c->stage.box_seq_cap));
       ea.seqCap = c->stage.box_seq_cap;
       ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
       ea.lingerMod = c->sw.edgeLingerMod; ea.test = c->sw.edgeRedo ? 1u : 0u;
-      ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : c->d_hist + 1024 + 129;   // (switched on: whatever the batch looks like)
+      ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : c->d_hist.get() + 1024 + 129;   // (switched on: whatever the batch looks like)
       HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)c->stage.n_slots * 4, s));
     }
-    hipLaunchKernelGGL(k_search, dim3(c->stage.n_slots), dim3(64), 0, s, c->dp, c->view, c->stage.caps, b->d_codes, b->d_offsets,
-                       b->d_koff, b->d_cov, b->d_covw, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->d_out, b->d_outoff, b->d_order,
-                       b->n_reads, c->d_queue, c->stage.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), ea);
+    hipLaunchKernelGGL(k_search, dim3(c->stage.n_slots), dim3(64), 0, s, c->dp, c->view, c->stage.caps, b->d_codes.get(), b->d_offsets.get(),
+                       b->d_koff.get(), b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), b->d_order.get(),
+                       b->n_reads, c->d_queue.get(), c->stage.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), ea);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(c->ev[4], s));
   b->h_state.resize(b->n_reads);
-  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state, b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
+  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   // ---- retry passes for the reads whose scratch overflowed: buffers sized from the batch's longest read (a path
   // can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
@@ -194,22 +191,21 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
       if (rc == TALC_ERR_NOMEM) break;
       return rc;
     }
-    uint32_t* d_retry = nullptr;
-    if (hipMalloc((void**)&d_retry, retry.size() * 4) != hipSuccess) { (void)hipGetLastError(); free_stage(big); break; }
-    HIPCHK(hipMemcpyAsync(d_retry, retry.data(), retry.size() * 4, hipMemcpyHostToDevice, s));
+    DevBuf<uint32_t> d_retry;
+    if (d_retry.alloc(retry.size()) != hipSuccess) { (void)hipGetLastError(); break; }
+    HIPCHK(hipMemcpyAsync(d_retry.get(), retry.data(), retry.size() * 4, hipMemcpyHostToDevice, s));
     for (uint32_t r : retry) {
       b->h_state[r].overflow = 0;
-      HIPCHK(hipMemcpyAsync(b->d_state + r, &b->h_state[r], sizeof(ReadState), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(b->d_state.get() + r, &b->h_state[r], sizeof(ReadState), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemsetAsync(c->d_queue, 0, kQueueWords * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(k_search, dim3(big.n_slots), dim3(64), 0, s, c->dp, c->view, big.caps, b->d_codes, b->d_offsets, b->d_koff,
-                       b->d_cov, b->d_covw, b->d_state, b->d_regions, b->d_regoff, b->d_headcov, b->d_out, b->d_outoff, d_retry, (uint32_t)retry.size(),
-                       c->d_queue, big.scratch, c->d_counters, tb, traceRead, next_launch_stamp(), EdgeTaskArgs());
+    HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_search, dim3(big.n_slots), dim3(64), 0, s, c->dp, c->view, big.caps, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
+                       b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), d_retry.get(), (uint32_t)retry.size(),
+                       c->d_queue.get(), big.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), EdgeTaskArgs());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state, b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    hipFree(d_retry);
-    free_stage(big);
+    d_retry.reset(); big = Stage();   // (both go before the next, larger stage is sized)
     std::vector<uint32_t> again;
     for (uint32_t r : retry) if (b->h_state[r].overflow) again.push_back(r);
     retry.swap(again);
@@ -227,17 +223,17 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   dense_off[b->n_reads] = pos;
   b->h_dense_off = dense_off;
   // the record buffer of an earlier pass over this batch is kept when it is large enough
-  if (b->d_dense && b->dense_cap < pos) { ctx_release(c, b->d_dense); b->d_dense = nullptr; }
-  if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(pos, 1); if ((rc = ctx_alloc(c, (void**)&b->d_dense, b->dense_cap))) return rc; }
-  if (!b->d_dense_off && (rc = ctx_alloc(c, (void**)&b->d_dense_off, (b->n_reads + 1) * 8))) return rc;
-  HIPCHK(hipMemcpyAsync(b->d_dense_off, dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  if (b->d_dense && b->dense_cap < pos) b->d_dense.reset();
+  if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(pos, 1); HIPCHK(b->d_dense.alloc(c->cache, b->dense_cap)); }
+  if (!b->d_dense_off) HIPCHK(b->d_dense_off.alloc(c->cache, b->n_reads + 1));
+  HIPCHK(hipMemcpyAsync(b->d_dense_off.get(), dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
   if (b->n_reads)
-    hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out, b->d_outoff, b->d_state, b->d_dense_off, b->d_dense,
+    hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
                        b->n_reads, c->p.reverse ? 1 : 0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[7], s));
   uint64_t counters[128] = {0};
-  HIPCHK(hipMemcpyAsync(counters, c->d_counters, 128 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(counters, c->d_counters.get(), 128 * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]));
   HIPCHK(hipEventElapsedTime(&c->timing.coverage_ms, c->ev[1], c->ev[2]));
@@ -278,7 +274,7 @@ int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t o
   if (out) {
     if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "output buffer too small: need %llu bytes", (unsigned long long)total);
     if (total) {   // on the context's stream: a DMA transfer when `out` is pinned (talc_pinned_alloc)
-      HIPCHK(hipMemcpyAsync(out, b->d_dense, total, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(out, b->d_dense.get(), total, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
     }
   }
@@ -316,7 +312,7 @@ int talc_batch_copy_corrected_device(talc_ctx* c, talc_batch* b, void* device_ou
     for (uint32_t r = 0; r < b->n_reads; ++r) status[r] = b->h_state[r].overflow ? TALC_READ_ERROR : b->h_state[r].status;
   if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "device buffer too small: need %llu bytes", (unsigned long long)total);
   if (total) {
-    HIPCHK(hipMemcpyAsync(device_out, b->d_dense, total, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(device_out, b->d_dense.get(), total, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return TALC_OK;
@@ -339,27 +335,28 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
   // a one-read batch from the resident raw bases
   const uint64_t off = b->h_offsets[read_index], len = b->h_offsets[read_index + 1] - off;
   std::vector<char> raw(std::max<uint64_t>(len, 1));
-  if (len) HIPCHK(hipMemcpy(raw.data(), b->d_raw + off, len, hipMemcpyDeviceToHost));
+  if (len) HIPCHK(hipMemcpy(raw.data(), b->d_raw.get() + off, len, hipMemcpyDeviceToHost));
   uint64_t offs[2] = {0, len};
-  talc_batch* tbch = nullptr;
-  int rc = talc_batch_create(c, raw.data(), offs, 1, &tbch);
+  talc_batch* one = nullptr;
+  int rc = talc_batch_create(c, raw.data(), offs, 1, &one);
   if (rc) return rc;
+  const std::unique_ptr<talc_batch> tbch(one);
   TraceHost th;
   th.cap = 1u << 18; th.poolCap = 1u << 24;
-  HIPCHK(hipMalloc((void**)&th.d_recs, (size_t)th.cap * sizeof(TraceRec)));
-  HIPCHK(hipMalloc((void**)&th.d_nrec, 4)); HIPCHK(hipMalloc((void**)&th.d_npool, 4));
-  HIPCHK(hipMalloc((void**)&th.d_pool, th.poolCap));
-  HIPCHK(hipMemsetAsync(th.d_nrec, 0, 4, c->stream)); HIPCHK(hipMemsetAsync(th.d_npool, 0, 4, c->stream));   // (the null stream is not ordered with c->stream)
-  rc = run_pipeline(c, tbch, &th, 0);
+  HIPCHK(th.d_recs.alloc(th.cap));
+  HIPCHK(th.d_nrec.alloc(1)); HIPCHK(th.d_npool.alloc(1));
+  HIPCHK(th.d_pool.alloc(th.poolCap));
+  HIPCHK(hipMemsetAsync(th.d_nrec.get(), 0, 4, c->stream)); HIPCHK(hipMemsetAsync(th.d_npool.get(), 0, 4, c->stream));   // (the null stream is not ordered with c->stream)
+  rc = run_pipeline(c, tbch.get(), &th, 0);
   std::ostringstream os;
   uint32_t nrec = 0, npool = 0;
-  HIPCHK(hipMemcpy(&nrec, th.d_nrec, 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&npool, th.d_npool, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&nrec, th.d_nrec.get(), 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&npool, th.d_npool.get(), 4, hipMemcpyDeviceToHost));
   nrec = std::min(nrec, th.cap); npool = std::min(npool, th.poolCap);
   std::vector<TraceRec> recs(nrec);
   std::vector<uint8_t> pool(std::max<uint32_t>(npool, 1));
-  if (nrec) HIPCHK(hipMemcpy(recs.data(), th.d_recs, (size_t)nrec * sizeof(TraceRec), hipMemcpyDeviceToHost));
-  if (npool) HIPCHK(hipMemcpy(pool.data(), th.d_pool, npool, hipMemcpyDeviceToHost));
+  if (nrec) HIPCHK(hipMemcpy(recs.data(), th.d_recs.get(), (size_t)nrec * sizeof(TraceRec), hipMemcpyDeviceToHost));
+  if (npool) HIPCHK(hipMemcpy(pool.data(), th.d_pool.get(), npool, hipMemcpyDeviceToHost));
   const int stv = tbch->h_state.empty() ? -1 : (tbch->h_state[0].overflow ? TALC_READ_ERROR : tbch->h_state[0].status);
   os << "STATUS " << stv << "\n";
   for (auto& e : recs) {
@@ -372,11 +369,9 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
   if (tbch->corrected) {
     const uint64_t total = tbch->h_dense_off[1];
     std::vector<char> o(std::max<uint64_t>(total, 1));
-    if (total) HIPCHK(hipMemcpy(o.data(), tbch->d_dense, total, hipMemcpyDeviceToHost));
+    if (total) HIPCHK(hipMemcpy(o.data(), tbch->d_dense.get(), total, hipMemcpyDeviceToHost));
     os << "OUT " << std::string(o.data(), total) << "\n";
   }
-  hipFree(th.d_recs); hipFree(th.d_nrec); hipFree(th.d_npool); hipFree(th.d_pool);
-  talc_batch_destroy(tbch);
   const std::string str = os.str();
   if (buf && str.size() + 1 <= cap) memcpy(buf, str.c_str(), str.size() + 1);
   return (int64_t)str.size() + 1;
@@ -391,18 +386,17 @@ int talc_test_dp(talc_ctx* c, int mode, const char* a, int la, const char* b, in
   std::vector<uint8_t> ha(std::max(la, 1)), hb(std::max(lb, 1));
   for (int i = 0; i < la; ++i) ha[i] = (mode == 3) ? (uint8_t)a[i] : ascii_to_code((uint8_t)a[i]);
   for (int i = 0; i < lb; ++i) hb[i] = ascii_to_code((uint8_t)b[i]);
-  uint8_t *da, *db; int *ddp, *dout;
+  DevBuf<uint8_t> da, db; DevBuf<int> ddp, dout;
   const uint32_t dpCap = (uint32_t)std::max(std::max(la, lb), 2048) + 16;   // (>= 2048: the phased x-drop keeps its hand-over state there)
-  HIPCHK(hipMalloc((void**)&da, ha.size())); HIPCHK(hipMalloc((void**)&db, hb.size()));
-  HIPCHK(hipMalloc((void**)&ddp, (3ull * dpCap + ROW_MAX_REF + 16) * 4)); HIPCHK(hipMalloc((void**)&dout, 16 * 4));   // (+ mode 7's kept row)
-  HIPCHK(hipMemcpy(da, ha.data(), ha.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db, hb.data(), hb.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(dout, 0, 64, c->stream));   // same stream as the kernel: the null stream is not ordered with it
-  hipLaunchKernelGGL(k_test_dp, dim3(1), dim3(64), 0, c->stream, mode, da, la, db, lb, p0, p1, p2, p3, (int)c->p.k, ddp, dpCap, dout,
+  HIPCHK(da.alloc(ha.size())); HIPCHK(db.alloc(hb.size()));
+  HIPCHK(ddp.alloc(3ull * dpCap + ROW_MAX_REF + 16)); HIPCHK(dout.alloc(16));   // (+ mode 7's kept row)
+  HIPCHK(hipMemcpy(da.get(), ha.data(), ha.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(db.get(), hb.data(), hb.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(dout.get(), 0, 64, c->stream));   // same stream as the kernel: the null stream is not ordered with it
+  hipLaunchKernelGGL(k_test_dp, dim3(1), dim3(64), 0, c->stream, mode, da.get(), la, db.get(), lb, p0, p1, p2, p3, (int)c->p.k, ddp.get(), dpCap, dout.get(),
                      c->p.alpha, c->p.sr_error_rate, (int)c->p.min_count);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out, dout, 12 * 4, hipMemcpyDeviceToHost));
-  hipFree(da); hipFree(db); hipFree(ddp); hipFree(dout);
+  HIPCHK(hipMemcpy(out, dout.get(), 12 * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }

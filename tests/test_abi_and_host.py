@@ -41,6 +41,20 @@ def test_environment_is_read_in_one_place_and_documented():
     assert read and read == listed, (sorted(read - listed), sorted(listed - read))
 
 
+def test_device_memory_has_one_owner_and_one_way_to_fail():
+    """talc_devmem.h is the one file of the native sources that allocates or frees device and page-locked memory (its
+    owners' destructors give it back, so a failing call returns where it stands), and the C ABI layer has no other
+    error idiom left beside HIPCHK: no local checking macros, no cleanup lambdas, no chains of `e == hipSuccess`."""
+    csrc = os.path.join(ROOT, "talc_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f), errors="replace").read() for f in os.listdir(csrc)}
+    calls = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(")
+    users = sorted(f for f, t in text.items() if any(c in t for c in calls))
+    assert users == ["talc_devmem.h"]
+    for f in ("talc_capi.hip", "talc_capi_correct.inc"):
+        for idiom in ("BCHK", "CCHK", "auto cleanup", "auto drop", "== hipSuccess) e ="):
+            assert idiom not in text[f], (f, idiom)
+
+
 def test_params_default_match_reference_defaults():
     p = T.default_params()
     q = O.params()
