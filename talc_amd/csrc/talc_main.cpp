@@ -1,10 +1,11 @@
 // talc_main.cpp — the drop-in `talc` command line over libtalc_hip.so.
 //
-// Keeps the reference's CLI / Settings / output-file surface (main.cpp:83-325, Settings.cpp:74-185,
-// io.cpp:26-111, Read.cpp:394-415) and replaces its per-read OpenMP loop (main.cpp:247-308) by a
-// multi-GPU read sharder: one host thread + one talc_ctx per GPU, reads dealt in contiguous
-// blocks balanced by bases, the k-mer table replicated on every GPU; records are merged in
-// input order by the single writer.  Pure host code (g++): it only talks to the C ABI.
+// Keeps the reference's CLI / Settings / output-file surface (main.cpp:83-325, Settings.cpp:74-185, io.cpp:26-111,
+// Read.cpp:394-415) and replaces its load-everything / per-read OpenMP loop / write-everything (main.cpp:209-310) by a
+// pipeline (class Pipeline below): one reader thread parses batches of --batch-reads reads into a small pool of
+// page-locked buffers, two workers per GPU (a talc_ctx each, the k-mer table replicated on every GPU) take the batches as
+// they come, correct them and format the records, one writer thread appends the batches' text in input order.
+// main() is the list of the reference's phases.  Pure host code (g++): it only talks to the C ABI.
 //
 // Options = the reference's table (same names, defaults, ranges), plus:
 //   --gpus N         number of GPUs to use (default: all visible)
@@ -41,16 +42,41 @@
 #include <thread>
 #include <vector>
 
-#include <fcntl.h>
 #include <spawn.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
-#include <unistd.h>
 
+#include "talc_cli_io.h"
 #include "talc_hip.h"
+#include "talc_jf.h"
 #include "talc_switches.h"
 
 namespace {
+
+using talc::HostBuf;
+using talc::SeqReader;
+using Clock = std::chrono::steady_clock;
+
+double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+double since(Clock::time_point a) { return secs(a, Clock::now()); }
+
+// every exit releases what these hold; a batch is destroyed before its context, a context before its table
+struct TableDel { void operator()(talc_table* t) const { talc_table_destroy(t); } };
+struct CtxDel { void operator()(talc_ctx* c) const { talc_ctx_destroy(c); } };
+struct BatchDel { void operator()(talc_batch* b) const { talc_batch_destroy(b); } };
+using TablePtr = std::unique_ptr<talc_table, TableDel>;
+using CtxPtr = std::unique_ptr<talc_ctx, CtxDel>;
+using BatchPtr = std::unique_ptr<talc_batch, BatchDel>;
+
+// a library call has failed on this thread: its message, and the exit code of a device error
+int libError() {
+  std::cerr << "talc: " << talc_last_error() << "\n";
+  return 2;
+}
+int noGpuError() {
+  std::cerr << "talc: no MI355X / HIP device visible; the correction path has no CPU fallback\n";
+  return 2;
+}
 
 struct Options {
   std::string seqFile, outPrefix = "out", queryMode = "memory", dump, jdump, jf2;
@@ -188,156 +214,24 @@ void setBasicReadStatsHeader(const std::string& statFile) {
        "CorrHead?\tCorrHeadLen\tCorrTail?\tCorrTailLen\tCorrlength\tnbInKmers2\n";
 }
 
-// Streaming FASTA / FASTQ reader (replaces loadSeqData, io.cpp:26-48, which holds the whole file, main.cpp:209-211):
-// the format is decided by the first non-empty line ('>' or '@'); id = the whole header line after the marker;
-// multi-line sequences are concatenated; FASTQ qualities are skipped by length.  Sequences are kept as raw text:
-// the device applies the Dna5 conversion.
-// lines of a file through one large buffer (read(2) in 8 MB pieces, memchr for the line ends): the streaming reader's
-// std::getline loop was what bounded the whole correction phase once the GPU side had become quick (1 GB/s of FASTA)
-class LineReader {
- public:
-  explicit LineReader(const std::string& file) : buf_(8u << 20) { fd_ = open(file.c_str(), O_RDONLY); }
-  ~LineReader() { if (fd_ >= 0) close(fd_); }
-  bool ok() const { return fd_ >= 0; }
-  // the next line without its "\n" / "\r\n"; the pointer is valid until the next call
-  bool getline(const char*& p, size_t& len) {
-    while (true) {
-      const char* nl = (pos_ < end_) ? (const char*)memchr(buf_.data() + pos_, '\n', end_ - pos_) : nullptr;
-      if (nl) {
-        p = buf_.data() + pos_;
-        len = (size_t)(nl - p);
-        pos_ = (size_t)(nl - buf_.data()) + 1;
-        while (len && (p[len - 1] == '\r' || p[len - 1] == '\n')) --len;
-        return true;
-      }
-      if (eof_) {
-        if (pos_ >= end_) return false;
-        p = buf_.data() + pos_; len = end_ - pos_; pos_ = end_;   // a last line without a newline
-        while (len && (p[len - 1] == '\r' || p[len - 1] == '\n')) --len;
-        return true;
-      }
-      // no line end in what is left: move the tail to the front (grow the buffer for a line longer than it) and read on
-      if (pos_ > 0) { memmove(&buf_[0], buf_.data() + pos_, end_ - pos_); end_ -= pos_; pos_ = 0; }
-      if (end_ == buf_.size()) buf_.resize(buf_.size() * 2);
-      const ssize_t r = read(fd_, &buf_[end_], buf_.size() - end_);
-      if (r <= 0) eof_ = true; else end_ += (size_t)r;
-    }
-  }
-
- private:
-  int fd_ = -1;
-  std::vector<char> buf_;
-  size_t pos_ = 0, end_ = 0;
-  bool eof_ = false;
+// the three files next to <o>.config.txt
+struct Files {
+  const std::string fa, stats, log;
+  explicit Files(const std::string& prefix) : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log") {}
 };
 
-// FASTA / FASTQ records one by one (multi-line sequences, blank lines, CRLF), the sequence appended to any sink
-class SeqReader {
- public:
-  explicit SeqReader(const std::string& file) : in_(file) {
-    if (!in_.ok()) { std::cerr << "ERROR: Could not open file " << file << "\n"; ok_ = false; return; }
-    while (in_.getline(lp_, ll_)) {   // first non-empty line decides the format
-      if (ll_ == 0) continue;
-      fastq_ = lp_[0] == '@';
-      if (!fastq_ && lp_[0] != '>') ok_ = false;
-      pending_ = true;
-      break;
-    }
-  }
-  bool ok() const { return ok_; }
-  bool fastq() const { return fastq_; }
-  // a FASTQ record whose qualities ran out before its sequence's length (the long-read path reads on regardless)
-  bool truncated() const { return truncated_; }
-  // next record; false at the end of the file (or on a malformed FASTQ header: bad() then says so).  sink(p, n) is called
-  // with every piece of the record's sequence and returns false to stop (no memory).
-  template <class Sink>
-  bool next(std::string& id, Sink&& sink) {
-    if (!ok_) return false;
-    if (!pending_) {
-      while (true) {
-        if (!in_.getline(lp_, ll_)) return false;
-        if (fastq_ ? ll_ != 0 : (ll_ != 0 && lp_[0] == '>')) break;
-      }
-    }
-    pending_ = false;
-    if (fastq_) {
-      if (lp_[0] != '@') { ok_ = false; return false; }
-      id.assign(lp_ + 1, ll_ - 1);
-      size_t n = 0;
-      while (in_.getline(lp_, ll_)) { if (ll_ != 0 && lp_[0] == '+') break; if (ll_ && !sink(lp_, ll_)) { ok_ = false; return false; } n += ll_; }
-      size_t got = 0;
-      while (got < n && in_.getline(lp_, ll_)) got += ll_;
-      if (got < n) truncated_ = true;
-      return true;
-    }
-    id.assign(lp_ + 1, ll_ - 1);
-    while (in_.getline(lp_, ll_)) {
-      if (ll_ != 0 && lp_[0] == '>') { pending_ = true; break; }
-      if (ll_ && !sink(lp_, ll_)) { ok_ = false; return false; }
-    }
-    return true;
-  }
-  bool next(std::string& id, std::string& seq) {
-    seq.clear();
-    return next(id, [&](const char* p, size_t n) { seq.append(p, n); return true; });
-  }
-
- private:
-  LineReader in_;
-  const char* lp_ = nullptr;
-  size_t ll_ = 0;
-  bool ok_ = true, fastq_ = false, pending_ = false, truncated_ = false;
+// the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
+struct TmpDumps {
+  std::vector<std::string> files;
+  ~TmpDumps() { for (const auto& f : files) std::remove(f.c_str()); }
 };
 
-// One batch of reads on its way through the pipeline: read -> corrected on a device -> written, in input order.
-// a growable page-locked host buffer (talc_pinned_alloc): the reads of a batch are parsed straight into it and the
-// corrected records come back into another one, so both directions are DMA transfers that run beside the kernels of
-// the GPU's other worker; each worker keeps its two buffers for the whole run
-struct PinnedBuf {
-  char* p = nullptr;
-  size_t cap = 0, len = 0;
-  bool pinned = false;
-  void release() { if (pinned) talc_pinned_free(p); else free(p); p = nullptr; }
-  ~PinnedBuf() { release(); }
-  bool reserve(size_t n) {
-    if (n <= cap) return true;
-    size_t nc = std::max<size_t>(n, std::max<size_t>(cap * 2, 1u << 20));
-    bool pin = true;
-    char* q = (char*)talc_pinned_alloc(nc);
-    if (!q) { q = (char*)malloc(nc); pin = false; }   // (no GPU / no page-locked memory left: pageable works too, only slower)
-    if (!q) return false;
-    if (len) memcpy(q, p, len);
-    release();
-    p = q; cap = nc; pinned = pin;
-    return true;
-  }
-  bool append(const char* s, size_t n) {
-    if (!reserve(len + n)) return false;
-    memcpy(p + len, s, n);
-    len += n;
-    return true;
-  }
-  bool append(const std::string& s) { return append(s.data(), s.size()); }
-};
-
-struct Chunk {
-  uint64_t index = 0;
-  std::vector<std::string> ids;
-  std::vector<uint64_t> offsets{0};     // into the chunk's input buffer
-  int inBuf = -1;                       // which page-locked input buffer of the pool holds the reads
-  std::vector<int32_t> status;
-  std::vector<int64_t> stats;           // 5 per read (--read-stats)
-  std::string text, logText, statsText; // what the writer appends to <o>.fa / <o>.log / <o>.stats_basics.txt
-};
-
-// a Jellyfish 2 count file starts with nine digits (the header's length) and the header's opening brace (talc_jf.h)
+// a Jellyfish 2 count file by its first bytes (talc_jf.h)
 bool isJfFile(const std::string& path) {
   std::ifstream f(path, std::ios::binary);
-  char h[10];
-  if (!f.read(h, 10)) return false;
-  for (int i = 0; i < 9; ++i)
-    if (h[i] < '0' || h[i] > '9') return false;
-  return h[9] == '{';
+  char h[16];
+  f.read(h, sizeof h);
+  return talc::jfLooksLike(h, (size_t)f.gcount());
 }
 
 // `DIR/jellyfish dump -c [-L minCount] -o out file.jf` as a child process (no shell): the program the reference's
@@ -364,41 +258,13 @@ bool jellyfishDump(const std::string& dir, const std::string& jf, uint32_t minCo
   return true;
 }
 
-// number of records of a FASTA file = lines that start with '>' (what SeqReader::next would return one by one), counted
-// over 4 MB blocks without building a string per line; -1: cannot open
-long long countFastaRecords(const std::string& file) {
-  FILE* f = fopen(file.c_str(), "rb");
-  if (!f) return -1;
-  std::vector<char> buf(4u << 20);
-  long long n = 0;
-  bool atLineStart = true;
-  size_t got;
-  while ((got = fread(buf.data(), 1, buf.size(), f)) > 0) {
-    const char* p = buf.data();
-    const char* end = p + got;
-    while (p < end) {
-      if (atLineStart) { if (*p == '>') ++n; atLineStart = false; }
-      const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-      if (!nl) break;
-      p = nl + 1;
-      atLineStart = true;
-    }
-  }
-  fclose(f);
-  return n;
-}
-
-double secs(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-  return std::chrono::duration<double>(b - a).count();
-}
-
 // --SRReads: every short-read file read once, front to back (a pipe works), in batches of about 64 MB of bases handed to
 // the GPU counter, which copies them and returns while its kernel runs, so reading the next batch overlaps counting this
 // one.  Then --SRCountsOut, then the table (junction colouring with -j).  Returns 0, or the exit code after a message.
-int countShortReads(const Options& o, const talc::Switches& sw, talc_table** table, int64_t st[3]) {
-  if (talc_device_count() <= 0) { std::cerr << "talc: no MI355X / HIP device visible; the correction path has no CPU fallback\n"; return 2; }
+int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table, int64_t st[3]) {
+  if (talc_device_count() <= 0) return noGpuError();
   talc_counter* ctr = nullptr;
-  if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+  if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) return libError();
   struct Guard { talc_counter*& c; ~Guard() { talc_counter_destroy(c); } } guard{ctr};
   const size_t kBatchBytes = 64u << 20;
   std::string buf;
@@ -408,9 +274,9 @@ int countShortReads(const Options& o, const talc::Switches& sw, talc_table** tab
   uint64_t nRecords = 0, nBytes = 0, nBatches = 0;
   auto flush = [&]() -> bool {
     if (offs.size() < 2) return true;
-    const auto ta = std::chrono::steady_clock::now();
+    const auto ta = Clock::now();
     const bool ok = talc_counter_add(ctr, buf.data(), offs.data(), (uint32_t)(offs.size() - 1)) == TALC_OK;
-    const double dt = secs(ta, std::chrono::steady_clock::now());
+    const double dt = since(ta);
     addS += dt;
     if (sw.timing == 2) fprintf(stderr, "[talc-count] batch %llu: %zu records, %zu bytes, counter add (pack + queue) %.4f s\n", (unsigned long long)nBatches, offs.size() - 1, buf.size(), dt);
     ++nBatches;
@@ -418,37 +284,37 @@ int countShortReads(const Options& o, const talc::Switches& sw, talc_table** tab
     offs.assign(1, 0);
     return ok;
   };
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = Clock::now();
   for (const std::string& file : o.srReads) {
     SeqReader r(file);
     if (!r.ok()) { std::cerr << "talc: " << file << " is not a FASTA or FASTQ file that can be read\n"; return 2; }
     std::string id;
     uint64_t rec = 0;
-    auto tr = std::chrono::steady_clock::now();
+    auto tr = Clock::now();
     while (r.next(id, [&](const char* p, size_t n) { buf.append(p, n); return true; })) {
       ++rec;
       if (r.truncated()) { std::cerr << "talc: " << file << ": FASTQ record " << rec << " (" << id << ") is malformed: its qualities are shorter than its sequence\n"; return 2; }
       offs.push_back(buf.size());
       if (buf.size() >= kBatchBytes) {
-        readS += secs(tr, std::chrono::steady_clock::now());
+        readS += since(tr);
         nBytes += buf.size();
-        if (!flush()) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
-        tr = std::chrono::steady_clock::now();
+        if (!flush()) return libError();
+        tr = Clock::now();
       }
     }
-    readS += secs(tr, std::chrono::steady_clock::now());
+    readS += since(tr);
     if (!r.ok()) { std::cerr << "talc: " << file << ": FASTQ record " << rec + 1 << " (after '" << id << "') is malformed: it does not start with '@'\n"; return 2; }
     nRecords += rec;
   }
   nBytes += buf.size();
-  if (!flush()) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
-  const auto t1 = std::chrono::steady_clock::now();
+  if (!flush()) return libError();
+  const auto t1 = Clock::now();
   if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers
     uint64_t n = 0;
-    if (talc_counter_fetch(ctr, o.p.min_count, nullptr, nullptr, 0, &n) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+    if (talc_counter_fetch(ctr, o.p.min_count, nullptr, nullptr, 0, &n) != TALC_OK) return libError();
     std::vector<uint64_t> km(std::max<uint64_t>(n, 1));
     std::vector<uint32_t> ct(std::max<uint64_t>(n, 1));
-    if (talc_counter_fetch(ctr, o.p.min_count, km.data(), ct.data(), n, &n) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+    if (talc_counter_fetch(ctr, o.p.min_count, km.data(), ct.data(), n, &n) != TALC_OK) return libError();
     FILE* f = fopen(o.srCountsOut.c_str(), "w");
     if (!f) { std::cerr << "talc: cannot write " << o.srCountsOut << "\n"; return 2; }
     const uint32_t K = o.p.k;
@@ -460,15 +326,457 @@ int countShortReads(const Options& o, const talc::Switches& sw, talc_table** tab
     }
     if (fclose(f) != 0) { std::cerr << "talc: cannot write " << o.srCountsOut << "\n"; return 2; }
   }
-  const auto t2 = std::chrono::steady_clock::now();
-  if (talc_counter_build_table(ctr, o.useJ ? o.jdump.c_str() : nullptr, table, st) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
+  const auto t2 = Clock::now();
+  talc_table* built = nullptr;
+  if (talc_counter_build_table(ctr, o.useJ ? o.jdump.c_str() : nullptr, &built, st) != TALC_OK) return libError();
+  table.reset(built);
   if (sw.timing)
     fprintf(stderr, "[talc] short reads: %zu file(s), %llu records, %llu bytes in %llu batches; read %.3f s (%.4f s per batch), counter add (pack + queue) %.3f s "
                     "(%.4f s per batch), counts out %.3f s, last batches + table build %.3f s, counting stage %.3f s\n",
             o.srReads.size(), (unsigned long long)nRecords, (unsigned long long)nBytes, (unsigned long long)nBatches, readS,
-            nBatches ? readS / (double)nBatches : 0.0, addS, nBatches ? addS / (double)nBatches : 0.0, secs(t1, t2),
-            secs(t2, std::chrono::steady_clock::now()), secs(t0, std::chrono::steady_clock::now()));
+            nBatches ? readS / (double)nBatches : 0.0, addS, nBatches ? addS / (double)nBatches : 0.0, secs(t1, t2), since(t2), since(t0));
   return 0;
+}
+
+// One batch of reads on its way through the pipeline: read -> corrected on a device -> written, in input order.
+struct Chunk {
+  uint64_t index = 0;
+  std::vector<std::string> ids;
+  std::vector<uint64_t> offsets{0};     // into the chunk's input buffer
+  int inBuf = -1;                       // which page-locked input buffer of the pool holds the reads
+  std::vector<int32_t> status;
+  std::vector<int64_t> stats;           // 5 per read (--read-stats)
+  std::string text, logText, statsText; // what the writer appends to <o>.fa / <o>.log / <o>.stats_basics.txt
+};
+
+// the text of one batch: '>' id, the sequence wrapped at 70 columns (io.cpp:50-75); the log and stats lines of its reads
+void formatChunk(const Options& o, Chunk& k, const char* recs, const uint64_t* oo) {
+  const size_t n = k.ids.size();
+  size_t need = 0;
+  for (size_t r = 0; r < n; ++r) { const size_t L = (size_t)(oo[r + 1] - oo[r]); need += k.ids[r].size() + 2 + L + (L + 69) / 70; }
+  k.text.resize(need);
+  char* w = &k.text[0];
+  for (size_t r = 0; r < n; ++r) {
+    // (a read that exhausted the device scratch is written through unchanged, like any read the reference fails on:
+    //  it logs and goes on, main.cpp:298-303)
+    const char* msg = k.status[r] == TALC_READ_NO_STRUCTURE ? "Unable to define convenient structure."       // main.cpp:290
+                      : k.status[r] == TALC_READ_NO_SOLID_KMER ? "No solid kmer could be found."             // main.cpp:294
+                      : k.status[r] == TALC_READ_ERROR ? "Device scratch exhausted; read left uncorrected." : nullptr;
+    if (msg) { k.logText += "[Read: "; k.logText += k.ids[r]; k.logText += " ]: "; k.logText += msg; k.logText += '\n'; }
+    if (o.readStats && k.stats.size() == 5 * n && k.stats[5 * r]) {   // Read.cpp:425-431
+      k.statsText += "\n" + k.ids[r] + "\t" + std::to_string(k.stats[5 * r + 1]) + "\t" + std::to_string(k.stats[5 * r + 2]) + "\t" +
+                     std::to_string(k.stats[5 * r + 3]) + "\t" + std::to_string(k.stats[5 * r + 4]);
+    }
+    *w++ = '>';
+    memcpy(w, k.ids[r].data(), k.ids[r].size()); w += k.ids[r].size();
+    *w++ = '\n';
+    const char* q = recs + oo[r];
+    const size_t L = (size_t)(oo[r + 1] - oo[r]);
+    for (size_t p = 0; p < L; p += 70) { const size_t m = std::min<size_t>(70, L - p); memcpy(w, q + p, m); w += m; *w++ = '\n'; }
+  }
+  k.text.resize((size_t)(w - k.text.data()));
+}
+
+// no table at all (main.cpp:240, see prepareCounts): pass-through with the reference's statuses; the Dna5 conversion and
+// -rev still apply
+void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
+  const size_t n = c.ids.size();
+  c.status.assign(n, TALC_READ_SKIPPED_SHORT);
+  if (o.readStats) c.stats.assign(5 * n, 0);
+  std::string all;
+  std::vector<uint64_t> oo(n + 1, 0);
+  for (size_t r = 0; r < n; ++r) {
+    std::string q(in.p + c.offsets[r], c.offsets[r + 1] - c.offsets[r]);
+    for (auto& ch : q) { ch = (ch == 'a' || ch == 'A') ? 'A' : (ch == 'c' || ch == 'C') ? 'C' : (ch == 'g' || ch == 'G') ? 'G' : (ch == 't' || ch == 'T') ? 'T' : 'N'; }
+    if (o.p.reverse) {
+      std::string rcs(q.size(), 'N');
+      for (size_t i = 0; i < q.size(); ++i) { char ch = q[q.size() - 1 - i]; rcs[i] = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : 'N'; }
+      q = rcs;
+    }
+    if (q.size() > o.p.k) {
+      c.status[r] = TALC_READ_NO_SOLID_KMER;
+      if (o.readStats) { c.stats[5 * r] = 1; c.stats[5 * r + 1] = (int64_t)q.size(); }
+    }
+    all += q;
+    oo[r + 1] = all.size();
+  }
+  formatChunk(o, c, all.data(), oo.data());
+}
+
+struct Scan {   // what the first pass over the read file found
+  uint64_t nReads = 0;
+  bool fastq = false;
+};
+
+// what one worker's time went into ([talc-timing]: device_busy_s_sum_over_workers and device_parts_s), and the reads it
+// had to leave uncorrected; one per worker, added up once the workers have ended
+struct WorkerTally {
+  double busy = 0, ctx = 0, create = 0, correct = 0, fetch = 0, text = 0, waitChunk = 0;
+  uint64_t readErrors = 0;
+};
+struct PipelineTotals {
+  double readerBusy = 0, writerBusy = 0;   // the three busy times overlap
+  uint64_t bases = 0, batches = 0;
+  WorkerTally workers;
+};
+
+// The correction phase (replaces main.cpp:209-310).  The READER parses batches of --batch-reads reads straight into
+// page-locked buffers of a pool of workers + 2 (input order = batch index); two WORKERS per logical GPU (own context and
+// stream each: one batch's transfers run under the other's kernels) take a batch, correct it and turn the records into
+// the text of <o>.fa themselves, so that formatting runs in parallel; the WRITER appends the finished batches' text
+// strictly by batch index.  At most workers + 2 finished batches wait for the writer, the one it waits for excepted.
+class Pipeline {
+ public:
+  // ndev logical GPUs on nphys devices (logical GPU d on device d mod nphys); ndev == 0: no table, one pass-through worker
+  Pipeline(const Options& o, const talc::Switches& sw, const Files& files, talc_table* table, int ndev, int nphys, const Scan& scan)
+      : o_(o), sw_(sw), files_(files), table_(table), ndev_(ndev), nphys_(nphys), nWorkers_(ndev ? 2 * ndev : 1), nInBufs_(nWorkers_ + 2), inBufs_(nInBufs_) {
+    // what a batch's reads take, from the file's size and the scan's read count
+    struct stat sb;
+    if (ndev && scan.nReads > 0 && stat(o.seqFile.c_str(), &sb) == 0)
+      batchBytesEstimate_ = (uint64_t)((double)sb.st_size / (double)scan.nReads * (double)std::min<uint64_t>(o.batchReads, scan.nReads) * (scan.fastq ? 0.55 : 1.05)) + (1u << 20);
+    for (int i = 0; i < nInBufs_; ++i) q_.freeIn.push_back(i);
+    q_.workersLeft = nWorkers_;
+  }
+  int workers() const { return nWorkers_; }
+  // runs the three kinds of threads to the end of the input, `of` being the open <o>.fa; false: failure() says why
+  bool run(std::ofstream of, PipelineTotals& tot);
+  const std::string& failure() const { return q_.failMsg; }
+
+ private:
+  struct ReaderSide {   // the reader thread's own
+    SeqReader in;
+    double busy = 0;
+    uint64_t bases = 0, batches = 0;
+    explicit ReaderSide(const std::string& file) : in(file) {}
+  };
+  struct WriterSide {   // the writer thread's own
+    std::ofstream of, lf, sf;
+    double busy = 0;
+  };
+  bool fail(std::string msg);
+  void readerMain(ReaderSide& r);
+  void workerMain(int device, WorkerTally& t);
+  void correctChunks(int device, WorkerTally& t);
+  bool correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTally& t);
+  void writerMain(WriterSide& w);   // io.cpp:50-75 + SeqFileOut FASTA writer, io.cpp:105-111 log lines
+
+  // immutable once constructed
+  const Options& o_;
+  const talc::Switches& sw_;
+  const Files& files_;
+  talc_table* const table_;
+  const int ndev_, nphys_, nWorkers_, nInBufs_;
+  uint64_t batchBytesEstimate_ = 0;
+  // input buffer i is used by one thread at a time: the reader once it has taken i off freeIn, then the worker that holds
+  // the Chunk naming it, until that worker puts i back
+  std::vector<HostBuf> inBufs_;
+  struct Shared {
+    std::mutex mu;   // guards every other member of this struct (`failed` is written under it and may be read without)
+    std::condition_variable cvFree, cvReady, cvDone, cvRoom;
+    std::vector<int> freeIn;
+    std::deque<std::unique_ptr<Chunk>> ready;
+    bool readerDone = false;
+    std::map<uint64_t, std::unique_ptr<Chunk>> finished;
+    int workersLeft = 0;
+    uint64_t nextToWrite = 0;
+    std::atomic<bool> failed{false};
+    std::string failMsg;
+  } q_;
+};
+
+// the first message wins; every waiter wakes up and ends.  Always false, for `return fail(...)`.
+bool Pipeline::fail(std::string msg) {
+  std::lock_guard<std::mutex> g(q_.mu);
+  if (!q_.failed) q_.failMsg = std::move(msg);
+  q_.failed = true;
+  q_.cvFree.notify_all(); q_.cvReady.notify_all(); q_.cvDone.notify_all(); q_.cvRoom.notify_all();
+  return false;
+}
+
+bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
+  ReaderSide rd(o_.seqFile);
+  WriterSide wr;
+  wr.of = std::move(of);
+  if (batchBytesEstimate_) {
+    // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
+    // allocation of a few hundred MB takes tens of milliseconds)
+    std::vector<std::thread> th;
+    for (HostBuf& b : inBufs_) th.emplace_back(&HostBuf::reserve, &b, (size_t)batchBytesEstimate_);
+    for (auto& t : th) t.join();
+  }
+  std::vector<WorkerTally> tally(nWorkers_);
+  {
+    std::thread reader(&Pipeline::readerMain, this, std::ref(rd)), writer(&Pipeline::writerMain, this, std::ref(wr));
+    std::vector<std::thread> workers;
+    for (int i = 0; i < nWorkers_; ++i) workers.emplace_back(&Pipeline::workerMain, this, ndev_ ? (i / 2) % nphys_ : -1, std::ref(tally[i]));
+    for (auto& w : workers) w.join();
+    reader.join();
+    writer.join();
+  }
+  wr.of.close();
+  tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
+  tot.writerBusy = wr.busy;
+  for (const WorkerTally& t : tally) {
+    WorkerTally& s = tot.workers;
+    s.busy += t.busy; s.ctx += t.ctx; s.create += t.create; s.correct += t.correct; s.fetch += t.fetch; s.text += t.text; s.waitChunk += t.waitChunk;
+    s.readErrors += t.readErrors;
+  }
+  return !q_.failed;
+}
+
+void Pipeline::readerMain(ReaderSide& r) {
+  std::string id;
+  while (!q_.failed) {
+    int bi = -1;
+    {
+      std::unique_lock<std::mutex> g(q_.mu);
+      q_.cvFree.wait(g, [&] { return q_.failed || !q_.freeIn.empty(); });
+      if (q_.failed) break;
+      bi = q_.freeIn.back(); q_.freeIn.pop_back();
+    }
+    const auto tr0 = Clock::now();
+    std::unique_ptr<Chunk> c(new Chunk());
+    HostBuf& in = inBufs_[bi];
+    in.len = 0;
+    c->inBuf = bi;
+    size_t refused = 0;   // the size the buffer could not grow to
+    auto sink = [&](const char* q, size_t m) { if (!in.append(q, m)) refused = in.len + m; return refused == 0; };
+    while (c->ids.size() < o_.batchReads && r.in.next(id, sink)) {
+      c->ids.push_back(id);
+      c->offsets.push_back(in.len);
+    }
+    r.busy += since(tr0);
+    if (refused) { fail("no host memory: the input buffer of a batch cannot grow to " + std::to_string(refused) + " bytes"); break; }
+    if (c->ids.empty()) { std::lock_guard<std::mutex> g(q_.mu); q_.freeIn.push_back(bi); break; }
+    c->index = r.batches++;
+    r.bases += in.len;
+    std::lock_guard<std::mutex> g(q_.mu);
+    q_.ready.push_back(std::move(c));
+    q_.cvReady.notify_one();
+  }
+  std::lock_guard<std::mutex> g(q_.mu);
+  q_.readerDone = true;
+  q_.cvReady.notify_all();
+}
+
+void Pipeline::workerMain(int device, WorkerTally& t) {
+  correctChunks(device, t);
+  std::lock_guard<std::mutex> g(q_.mu);
+  --q_.workersLeft;
+  q_.cvDone.notify_all();
+}
+
+// device < 0: the pass-through worker
+void Pipeline::correctChunks(int device, WorkerTally& t) {
+  CtxPtr ctx;
+  if (device >= 0) {
+    const auto tc0 = Clock::now();
+    talc_ctx* made = nullptr;
+    if (talc_ctx_create(table_, &o_.p, device, &made) != TALC_OK) { fail(talc_last_error()); return; }
+    ctx.reset(made);
+    t.ctx += since(tc0);
+  }
+  HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
+  if (ctx && batchBytesEstimate_) outb.reserve(batchBytesEstimate_ + batchBytesEstimate_ / 16);   // (one page-locked allocation, not a dozen doublings)
+  while (!q_.failed) {
+    const auto tw0 = Clock::now();
+    std::unique_ptr<Chunk> c;
+    {
+      std::unique_lock<std::mutex> g(q_.mu);
+      q_.cvReady.wait(g, [&] { return q_.failed || !q_.ready.empty() || q_.readerDone; });
+      if (q_.failed || q_.ready.empty()) break;
+      c = std::move(q_.ready.front()); q_.ready.pop_front();
+    }
+    t.waitChunk += since(tw0);
+    if (!ctx) passThrough(o_, *c, inBufs_[c->inBuf]);
+    else if (!correctOnDevice(ctx.get(), *c, outb, t)) return;
+    std::unique_lock<std::mutex> g(q_.mu);
+    q_.freeIn.push_back(c->inBuf); c->inBuf = -1;
+    q_.cvFree.notify_one();
+    // (the batch the writer waits for always gets in; the others wait while the writer is more than a few batches behind)
+    q_.cvRoom.wait(g, [&] { return q_.failed || c->index == q_.nextToWrite || q_.finished.size() < (size_t)nWorkers_ + 2; });
+    q_.finished[c->index] = std::move(c);
+    q_.cvDone.notify_one();
+  }
+}
+
+// one batch through the device and into text; false after fail()
+bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTally& t) {
+  const uint32_t n = (uint32_t)c.ids.size();
+  c.status.assign(n, TALC_READ_SKIPPED_SHORT);
+  const auto td0 = Clock::now();
+  struct Busy { double& sum; Clock::time_point t0; ~Busy() { sum += since(t0); } } busy{t.busy, td0};   // batch create .. the batch's release
+  talc_batch* made = nullptr;
+  if (talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made) != TALC_OK) return fail(talc_last_error());
+  BatchPtr b(made);
+  t.create += since(td0);
+  const auto tk0 = Clock::now();
+  // < 0: a real HIP / argument error stops the run; TALC_WARN_READ_ERRORS (> 0) is a complete batch in which some
+  // reads kept their input sequence (status TALC_READ_ERROR -> a .log line), and the run goes on
+  const int crc = talc_batch_correct(ctx, b.get());
+  if (crc < 0) return fail(talc_last_error());
+  t.correct += since(tk0);
+  const auto tf0 = Clock::now();
+  const uint64_t total = talc_batch_corrected_bytes(b.get());
+  std::vector<uint64_t> oo(n + 1);
+  if (!outb.reserve(std::max<uint64_t>(total, 1))) return fail("no host memory: " + std::to_string(total) + " bytes for the corrected records of a batch");
+  if (talc_batch_fetch_corrected(ctx, b.get(), outb.p, total, oo.data(), c.status.data()) != TALC_OK) return fail(talc_last_error());
+  if (o_.readStats) {
+    c.stats.resize(5ull * n);
+    if (talc_batch_fetch_read_stats(ctx, b.get(), c.stats.data()) != TALC_OK) return fail(talc_last_error());
+  }
+  t.fetch += since(tf0);
+  const auto tu0 = Clock::now();
+  formatChunk(o_, c, outb.p, oo.data());
+  t.text += since(tu0);
+  if (sw_.timing == 2) {   // per batch: where this worker's time went
+    talc_timing tm; talc_ctx_get_timing(ctx, &tm);
+    fprintf(stderr, "[talc-batch] reads %u: create+H2D %.3f s, correct %.3f s (kernels: coverage %.1f structure %.1f search %.1f retry %.1f ms), fetch %.3f s, text %.3f s\n",
+            n, secs(td0, tk0), secs(tk0, tf0), tm.coverage_ms, tm.structure_ms, tm.search_ms, tm.retry_ms, secs(tf0, tu0), since(tu0));
+  }
+  if (crc > 0) for (uint32_t i = 0; i < n; ++i) t.readErrors += c.status[i] == TALC_READ_ERROR ? 1 : 0;
+  return true;
+}
+
+void Pipeline::writerMain(WriterSide& w) {
+  while (true) {
+    std::unique_ptr<Chunk> c;
+    {
+      std::unique_lock<std::mutex> g(q_.mu);
+      auto next = [&] { return !q_.finished.empty() && q_.finished.begin()->first == q_.nextToWrite; };
+      q_.cvDone.wait(g, [&] { return next() || q_.workersLeft == 0 || q_.failed; });
+      if (!next()) break;   // (no worker left, or a failure)
+      c = std::move(q_.finished.begin()->second);
+      q_.finished.erase(q_.finished.begin());
+    }
+    const auto tw0 = Clock::now();
+    if (!c->logText.empty()) { if (!w.lf.is_open()) w.lf.open(files_.log, std::ios_base::app); w.lf << c->logText; w.lf.flush(); }
+    if (!c->statsText.empty()) { if (!w.sf.is_open()) w.sf.open(files_.stats, std::ios_base::app); w.sf << c->statsText; }
+    w.of.write(c->text.data(), (std::streamsize)c->text.size());
+    w.busy += since(tw0);
+    std::lock_guard<std::mutex> g(q_.mu);
+    ++q_.nextToWrite;
+    q_.cvRoom.notify_all();
+  }
+}
+
+// ---- the phases of main(), in the reference's order.  An int result is 0 to go on, else the exit code after a message.
+
+// first pass over the read file: format check and record count only (the reads themselves stream through in batches later)
+bool scanReads(const Options& o, Scan& scan) {
+  std::cout << "[TALC]: Attempting to load sequences." << std::endl;
+  SeqReader probe(o.seqFile);
+  scan.fastq = probe.fastq();
+  if (probe.ok() && !probe.fastq()) {   // FASTA: the records are the lines that start with '>'
+    const long long n = talc::countFastaRecords(o.seqFile);
+    if (n >= 0) scan.nReads = (uint64_t)n;
+  } else if (probe.ok()) {
+    std::string id, seq;
+    while (probe.next(id, seq)) ++scan.nReads;
+  }
+  if (!probe.ok()) {
+    std::cout << "[TALC]: ISSUE WITH INPUT FILES" << std::endl;
+    return false;
+  }
+  std::cout << "[TALC]: Hmm...it seems the sequence file is OK." << std::endl;
+  std::cout << "[TALC]: " << scan.nReads << " long read(s) loaded" << std::endl;
+  return true;
+}
+
+// -qm jellyfish2 (the reference: no table, one `jellyfish query` child per look-up — and never reached):
+// the same counts as ONE table, from the tool's dump when -jf2 names it (o.dump / o.jdump then name the temporary dumps),
+// else from the .jf itself; memory mode takes a .jf too.  haveTable false: a jellyfish2 run that names neither the
+// program nor a .jf keeps the reference's behaviour, main.cpp:240: its loop runs on an EMPTY map (the jellyfish2 code path
+// is dead), every read longer than K logs "No solid kmer could be found."
+int prepareCounts(Options& o, TmpDumps& tmp, bool& haveTable) {
+  haveTable = o.queryMode == "memory";
+  if (o.queryMode == "jellyfish2" && !o.jf2.empty()) {
+    std::string why;
+    const std::string sr = o.outPrefix + ".SRCounts.dump.tmp", jn = o.outPrefix + ".junctions.dump.tmp";
+    std::cout << "[TALC]: jellyfish2 mode: " << o.jf2 << "/jellyfish dump of " << o.dump << std::endl;
+    tmp.files.push_back(sr);
+    bool ok = jellyfishDump(o.jf2, o.dump, o.p.min_count, sr, why);
+    if (ok && o.useJ) { tmp.files.push_back(jn); ok = jellyfishDump(o.jf2, o.jdump, 0, jn, why); }
+    if (!ok) { std::cerr << "talc: " << why << "\n"; return 2; }
+    o.dump = sr;
+    if (o.useJ) o.jdump = jn;
+    haveTable = true;
+  } else if (o.queryMode == "jellyfish2" && isJfFile(o.dump)) {
+    std::cout << "[TALC]: jellyfish2 mode: reading " << o.dump << " natively" << std::endl;
+    haveTable = true;
+  }
+  return 0;
+}
+
+// main.cpp:224-238; tableSize stays 0 without a table
+int buildTable(const Options& o, const talc::Switches& sw, TablePtr& table, uint64_t& tableSize) {
+  int64_t st[3] = {0, 0, 0};
+  int rc = TALC_OK;
+  if (!o.srReads.empty()) {   // --SRReads: counted on the GPU, no count file in between
+    std::cout << "[TALC]: Building the SR-" << (o.useJ ? "cdBG" : "dBG") << " from the k-mers of " << o.srReads.size() << " short-read file(s)";
+    if (o.useJ) std::cout << " and count file: " << o.jdump;
+    std::cout << std::endl;
+    if (const int ec = countShortReads(o, sw, table, st)) return ec;
+  } else {
+    if (o.useJ) std::cout << "[TALC]: Building the SR-cdBG from count files: " << o.dump << " and " << o.jdump << std::endl;
+    else std::cout << "[TALC]: Building the SR-dBG from count file: " << o.dump << std::endl;
+    // the insert loop of buildCDBG runs on the first GPU when there is one (same table, ~10x faster on a 50 M dump)
+    talc_table* built = nullptr;
+    rc = (talc_device_count() > 0)
+             ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &built, st)
+             : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &built, st);
+    table.reset(built);
+  }
+  if (rc != TALC_OK) {
+    // an unreadable dump leaves the reference with an empty map (Jellyfish.cpp:249-251); anything else is fatal
+    libError();
+    if (rc != TALC_ERR_IO) return 2;
+  } else {
+    tableSize = talc_table_size(table.get());
+    std::cout << "There were " << st[0] << " k-mers retrieved from database." << std::endl;
+    std::cout << "In the whole, we have kept " << st[1] << "k-mers, whose counts were over the specified threshold." << std::endl;
+  }
+  std::cout << "[TALC]: SR-dBG contains " << tableSize << " nodes." << std::endl;
+  return 0;
+}
+
+// the devices of this run, the table on each of them, and the batch size when --batch-reads did not give it
+int chooseDevices(Options& o, const talc::Switches& sw, talc_table* table, uint64_t nReads, int& ndev, int& nphys) {
+  nphys = talc_device_count();
+  if (nphys <= 0) return noGpuError();
+  ndev = nphys;
+  // TALC_FAKE_GPUS=n (a rehearsal hook for one-GPU boxes): the sharder runs as if n GPUs were present, logical GPU d on
+  // physical device d mod the real count — the same worker threads, contexts, dealing and ordered merge
+  if (sw.fakeGpus) ndev = (int)sw.fakeGpus;
+  if (o.gpus > 0) ndev = std::min(ndev, o.gpus);
+  for (int d = 0; d < std::min(ndev, nphys); ++d)
+    if (talc_table_upload(table, d) != TALC_OK) { std::cerr << "talc: device error: " << talc_last_error() << "\n"; return 2; }
+  std::cout << "[TALC]: correcting on " << ndev << " GPU(s); k-mer table replicated (" << talc_table_device_bytes(table) / 1e9 << " GB each)" << std::endl;
+  if (!o.haveBatchReads) {
+    // at least two batches per worker (two workers per GPU) so that every worker's transfers find kernels to hide
+    // under and the last batches end together; not below 20000 reads (a small batch leaves k_search's 5120 waves a
+    // long tail), not above 200000
+    const uint64_t per = (nReads + (uint64_t)ndev * 4 - 1) / ((uint64_t)ndev * 4);
+    o.batchReads = (uint32_t)std::min<uint64_t>(200000, std::max<uint64_t>(20000, per));
+  }
+  return 0;
+}
+
+// the reference's own split (main.cpp:213-236: loading the reads, building the graph; :311-313: the correction), in
+// wall-clock seconds instead of CPU minutes, then the same as JSON.  t: start, scanned, table built, uploaded, done.
+void report(const Clock::time_point t[5], const PipelineTotals& p, const Scan& scan, uint32_t batchReads, int ndev, int workers) {
+  const double phase = secs(t[3], t[4]);
+  const WorkerTally& w = p.workers;
+  fprintf(stderr, "[talc] scan=%.3fs table=%.3fs upload=%.3fs read+correct+write=%.3fs (%.3g bases/s, %llu batches of <= %u reads) total=%.3fs\n",
+          secs(t[0], t[1]), secs(t[1], t[2]), secs(t[2], t[3]), phase, phase > 0 ? (double)p.bases / phase : 0.0,
+          (unsigned long long)p.batches, batchReads, secs(t[0], t[4]));
+  fprintf(stderr, "[talc-timing] {\"scan_s\": %.4f, \"table_parse_build_s\": %.4f, \"upload_s\": %.4f, \"correct_phase_s\": %.4f, "
+                  "\"reader_busy_s\": %.4f, \"device_busy_s_sum_over_workers\": %.4f, \"writer_busy_s\": %.4f, \"total_s\": %.4f, "
+                  "\"device_parts_s\": {\"ctx_create\": %.4f, \"batch_create_h2d\": %.4f, \"correct\": %.4f, \"fetch_d2h\": %.4f, \"records_to_text\": %.4f, \"waiting_for_reader\": %.4f}, "
+                  "\"reads\": %llu, \"bases\": %llu, \"batches\": %llu, \"batch_reads\": %u, \"gpus\": %d, \"workers\": %d}\n",
+          secs(t[0], t[1]), secs(t[1], t[2]), secs(t[2], t[3]), phase, p.readerBusy, w.busy, p.writerBusy, secs(t[0], t[4]),
+          w.ctx, w.create, w.correct, w.fetch, w.text, w.waitChunk,
+          (unsigned long long)scan.nReads, (unsigned long long)p.bases, (unsigned long long)p.batches, batchReads, ndev, workers);
 }
 
 }  // namespace
@@ -483,94 +791,27 @@ int main(int argc, const char** argv) {
   std::cout << "[TALC]: Parsing arguments" << std::endl;
   Options o = parse(argc, argv);
   const talc::Switches sw = talc::read_switches();   // (TALC_TIMING, TALC_FAKE_GPUS)
-  const std::string outFile = o.outPrefix + ".fa", statFile = o.outPrefix + ".stats_basics.txt", logFile = o.outPrefix + ".log";
-  outputConfig(o, statFile);          // Settings.cpp:122
-  setBasicReadStatsHeader(statFile);  // main.cpp:204
+  const Files files(o.outPrefix);
+  outputConfig(o, files.stats);          // Settings.cpp:122
+  setBasicReadStatsHeader(files.stats);  // main.cpp:204
 
-  auto t0 = std::chrono::steady_clock::now();
-  std::cout << "[TALC]: Attempting to load sequences." << std::endl;
-  // first pass: format check and record count only (the reads themselves stream through in batches below)
-  uint64_t nReadsTotal = 0;
-  {
-    SeqReader probe(o.seqFile);
-    std::string id, seq;
-    if (probe.ok() && !probe.fastq()) {   // FASTA: the records are the lines that start with '>'
-      const long long n = countFastaRecords(o.seqFile);
-      if (n >= 0) nReadsTotal = (uint64_t)n;
-    } else if (probe.ok()) {
-      while (probe.next(id, seq)) ++nReadsTotal;
-    }
-    if (!probe.ok()) {  // main.cpp:219,323: prints and falls off main
-      std::cout << "[TALC]: ISSUE WITH INPUT FILES" << std::endl;
-      return 0;
-    }
-  }
-  std::cout << "[TALC]: Hmm...it seems the sequence file is OK." << std::endl;
-  std::cout << "[TALC]: " << nReadsTotal << " long read(s) loaded" << std::endl;
-  auto t1 = std::chrono::steady_clock::now();
+  Clock::time_point t[5];
+  t[0] = Clock::now();
+  Scan scan;
+  if (!scanReads(o, scan)) return 0;   // main.cpp:219,323: prints and falls off main
+  t[1] = Clock::now();
 
-  // -qm jellyfish2 (the reference: no table, one `jellyfish query` child per look-up — and never reached):
-  // the same counts as ONE table, from the tool's dump when -jf2 names it, else from the .jf itself; memory mode
-  // takes a .jf too.  A jellyfish2 run with neither keeps the reference's behaviour (below).
-  bool buildTable = (o.queryMode == "memory");
-  std::vector<std::string> tmpFiles;
-  if (o.queryMode == "jellyfish2" && !o.jf2.empty()) {
-    std::string why;
-    const std::string sr = o.outPrefix + ".SRCounts.dump.tmp", jn = o.outPrefix + ".junctions.dump.tmp";
-    std::cout << "[TALC]: jellyfish2 mode: " << o.jf2 << "/jellyfish dump of " << o.dump << std::endl;
-    tmpFiles.push_back(sr);
-    bool ok = jellyfishDump(o.jf2, o.dump, o.p.min_count, sr, why);
-    if (ok && o.useJ) { tmpFiles.push_back(jn); ok = jellyfishDump(o.jf2, o.jdump, 0, jn, why); }
-    if (!ok) {
-      for (const auto& f : tmpFiles) std::remove(f.c_str());
-      std::cerr << "talc: " << why << "\n";
-      return 2;
-    }
-    o.dump = sr;
-    if (o.useJ) o.jdump = jn;
-    buildTable = true;
-  } else if (o.queryMode == "jellyfish2" && isJfFile(o.dump)) {
-    std::cout << "[TALC]: jellyfish2 mode: reading " << o.dump << " natively" << std::endl;
-    buildTable = true;
-  }
-
-  talc_table* table = nullptr;
+  TablePtr table;
   uint64_t tableSize = 0;
-  if (buildTable) {  // main.cpp:224-238
-    int64_t st[3] = {0, 0, 0};
-    int rc = TALC_OK;
-    if (!o.srReads.empty()) {   // --SRReads: counted on the GPU, no count file in between
-      std::cout << "[TALC]: Building the SR-" << (o.useJ ? "cdBG" : "dBG") << " from the k-mers of " << o.srReads.size() << " short-read file(s)";
-      if (o.useJ) std::cout << " and count file: " << o.jdump;
-      std::cout << std::endl;
-      const int ec = countShortReads(o, sw, &table, st);
-      if (ec) return ec;
-    } else {
-      if (o.useJ) std::cout << "[TALC]: Building the SR-cdBG from count files: " << o.dump << " and " << o.jdump << std::endl;
-      else std::cout << "[TALC]: Building the SR-dBG from count file: " << o.dump << std::endl;
-      // the insert loop of buildCDBG runs on the first GPU when there is one (same table, ~10x faster on a 50 M dump)
-      rc = (talc_device_count() > 0)
-               ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &table, st)
-               : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &table, st);
-      for (const auto& f : tmpFiles) std::remove(f.c_str());
-    }
-    if (rc != TALC_OK) {
-      // an unreadable dump leaves the reference with an empty map (Jellyfish.cpp:249-251); anything else is fatal
-      std::cerr << "talc: " << talc_last_error() << "\n";
-      if (rc != TALC_ERR_IO) return 2;
-    } else {
-      tableSize = talc_table_size(table);
-      std::cout << "There were " << st[0] << " k-mers retrieved from database." << std::endl;
-      std::cout << "In the whole, we have kept " << st[1] << "k-mers, whose counts were over the specified threshold." << std::endl;
-    }
-    std::cout << "[TALC]: SR-dBG contains " << tableSize << " nodes." << std::endl;
+  bool haveTable = false;
+  {
+    TmpDumps tmp;
+    if (const int ec = prepareCounts(o, tmp, haveTable)) return ec;
+    if (haveTable)
+      if (const int ec = buildTable(o, sw, table, tableSize)) return ec;
   }
-  auto t2 = std::chrono::steady_clock::now();
-  // main.cpp:240: with -qm jellyfish2 the reference runs the loop on an EMPTY map (the jellyfish2 code
-  // path is dead): every read longer than K logs "No solid kmer could be found."  Kept when the run names
-  // neither the jellyfish program nor a .jf file.
-  const bool emptyRun = !buildTable;
-  if (!emptyRun && tableSize == 0) {
+  t[2] = Clock::now();
+  if (haveTable && tableSize == 0) {
     std::cout << "[TALC]: The de Bruijn Graph is empty...Correction aborted." << std::endl;  // main.cpp:319-320
     return 1;
   }
@@ -578,270 +819,21 @@ int main(int argc, const char** argv) {
   std::cout << "[TALC]: Maybe we can try and correct some long reads, then?" << std::endl;
 
   int ndev = 0, nphys = 0;
-  if (!emptyRun) {
-    nphys = talc_device_count();
-    if (nphys <= 0) { std::cerr << "talc: no MI355X / HIP device visible; the correction path has no CPU fallback\n"; return 2; }
-    ndev = nphys;
-    // TALC_FAKE_GPUS=n (a rehearsal hook for one-GPU boxes): the sharder runs as if n GPUs were present, logical GPU d on
-    // physical device d mod the real count — the same worker threads, contexts, dealing and ordered merge
-    if (sw.fakeGpus) ndev = (int)sw.fakeGpus;
-    if (o.gpus > 0) ndev = std::min(ndev, o.gpus);
-    for (int d = 0; d < std::min(ndev, nphys); ++d)
-      if (talc_table_upload(table, d) != TALC_OK) { std::cerr << "talc: device error: " << talc_last_error() << "\n"; talc_table_destroy(table); return 2; }
-    std::cout << "[TALC]: correcting on " << ndev << " GPU(s); k-mer table replicated (" << talc_table_device_bytes(table) / 1e9 << " GB each)" << std::endl;
-    if (!o.haveBatchReads) {
-      // at least two batches per worker (two workers per GPU) so that every worker's transfers find kernels to hide
-      // under and the last batches end together; not below 20000 reads (a small batch leaves k_search's 5120 waves a
-      // long tail), not above 200000
-      const uint64_t per = (nReadsTotal + (uint64_t)ndev * 4 - 1) / ((uint64_t)ndev * 4);
-      o.batchReads = (uint32_t)std::min<uint64_t>(200000, std::max<uint64_t>(20000, per));
-    }
-  }
-  auto t2b = std::chrono::steady_clock::now();
-  std::cout << "Specified output file name: " << outFile << std::endl;
-  std::ofstream of(outFile, std::ios_base::trunc);
-  if (!of) { std::cerr << "ERROR: Could not open the file " << outFile << "\n"; return 2; }
+  if (haveTable)
+    if (const int ec = chooseDevices(o, sw, table.get(), scan.nReads, ndev, nphys)) return ec;
+  t[3] = Clock::now();
 
-  // ---- the pipeline (replaces the load-everything / OpenMP loop / write-everything of main.cpp:209-310):
-  //   one READER thread parses batches of --batch-reads reads straight into page-locked buffers of a small pool (input order =
-  //   batch index); two WORKERS per GPU (own context and stream each: one batch's transfers run under the other's kernels)
-  //   take a batch, correct it, and turn the records into the text of <o>.fa themselves — '>' id, 70-column lines
-  //   (io.cpp:50-75) — so that formatting runs in parallel; one WRITER thread appends the finished batches' text strictly
-  //   in input order.  At most (workers + 2) batches are in flight.
-  SeqReader reader(o.seqFile);
-  std::atomic<bool> failed{false};
-  uint64_t nextIndex = 0, nextToWrite = 0, basesTotal = 0;
-  std::ofstream lf, sf;
-  std::mutex failMu;
-  std::string failMsg;
-  std::atomic<uint64_t> readErrors{0};
-  const int nWorkers = emptyRun ? 1 : 2 * ndev;
-  const int nInBufs = nWorkers + 2;
-  std::vector<PinnedBuf> inBufs(nInBufs);
-  std::mutex qMu;                                   // guards everything below
-  std::condition_variable cvFree, cvReady, cvDone, cvRoom;
-  std::vector<int> freeIn;
-  for (int i = 0; i < nInBufs; ++i) freeIn.push_back(i);
-  std::deque<std::unique_ptr<Chunk>> ready;
-  bool readerDone = false;
-  std::map<uint64_t, std::unique_ptr<Chunk>> finished;
-  int workersLeft = nWorkers;
-  auto setFailed = [&]() {
-    { std::lock_guard<std::mutex> g(failMu); if (!failed) failMsg = talc_last_error(); failed = true; }
-    std::lock_guard<std::mutex> g(qMu);
-    cvFree.notify_all(); cvReady.notify_all(); cvDone.notify_all(); cvRoom.notify_all();
-  };
-  double readBusy = 0, writeBusy = 0;            // the reader's / the writer's own time
-  std::atomic<long long> deviceBusyUs{0};        // summed over the workers
-  std::atomic<long long> ctxUs{0}, createUs{0}, correctUs{0}, fetchUs{0}, unpackUs{0}, waitChunkUs{0};   // ... and its parts
-  auto usSince = [](std::chrono::steady_clock::time_point t) { return (long long)(1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count()); };
-  // what a batch's reads take, from the file's size and the scan's read count: the page-locked buffers are allocated once,
-  // at that size, by as many threads as there are buffers (an allocation of a few hundred MB takes tens of milliseconds)
-  uint64_t batchBytesEstimate = 0;
-  if (!emptyRun && nReadsTotal > 0) {
-    struct stat sbq;
-    if (stat(o.seqFile.c_str(), &sbq) == 0) batchBytesEstimate = (uint64_t)((double)sbq.st_size / (double)nReadsTotal * (double)std::min<uint64_t>(o.batchReads, nReadsTotal) * (reader.fastq() ? 0.55 : 1.05)) + (1u << 20);
-    std::vector<std::thread> th;
-    for (int i = 0; i < nInBufs; ++i) th.emplace_back([&, i] { inBufs[i].reserve(batchBytesEstimate); });
-    for (auto& t : th) t.join();
-  }
-  auto readerThread = [&]() {
-    std::string id;
-    while (!failed) {
-      int bi = -1;
-      {
-        std::unique_lock<std::mutex> g(qMu);
-        cvFree.wait(g, [&] { return failed.load() || !freeIn.empty(); });
-        if (failed) break;
-        bi = freeIn.back(); freeIn.pop_back();
-      }
-      const auto tr0 = std::chrono::steady_clock::now();
-      std::unique_ptr<Chunk> c(new Chunk());
-      PinnedBuf& in = inBufs[bi];
-      in.len = 0;
-      c->inBuf = bi;
-      bool bad = false;
-      while (c->ids.size() < o.batchReads && reader.next(id, [&](const char* q, size_t m) { if (!in.append(q, m)) { bad = true; return false; } return true; })) {
-        c->ids.push_back(id);
-        c->offsets.push_back(in.len);
-      }
-      readBusy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-      if (bad) { setFailed(); break; }
-      if (c->ids.empty()) { std::lock_guard<std::mutex> g(qMu); freeIn.push_back(bi); break; }
-      c->index = nextIndex++;
-      basesTotal += in.len;
-      std::lock_guard<std::mutex> g(qMu);
-      ready.push_back(std::move(c));
-      cvReady.notify_one();
-    }
-    std::lock_guard<std::mutex> g(qMu);
-    readerDone = true;
-    cvReady.notify_all();
-  };
-  // the text of one batch: '>' id, the sequence wrapped at 70 columns; the log and stats lines of its reads
-  auto formatChunk = [&](Chunk& k, const char* recs, const uint64_t* oo) {
-    const size_t n = k.ids.size();
-    size_t need = 0;
-    for (size_t r = 0; r < n; ++r) { const size_t L = (size_t)(oo[r + 1] - oo[r]); need += k.ids[r].size() + 2 + L + (L + 69) / 70; }
-    k.text.resize(need);
-    char* w = &k.text[0];
-    for (size_t r = 0; r < n; ++r) {
-      // (a read that exhausted the device scratch is written through unchanged, like any read the reference fails on:
-      //  it logs and goes on, main.cpp:298-303)
-      const char* msg = k.status[r] == TALC_READ_NO_STRUCTURE ? "Unable to define convenient structure."       // main.cpp:290
-                        : k.status[r] == TALC_READ_NO_SOLID_KMER ? "No solid kmer could be found."             // main.cpp:294
-                        : k.status[r] == TALC_READ_ERROR ? "Device scratch exhausted; read left uncorrected." : nullptr;
-      if (msg) { k.logText += "[Read: "; k.logText += k.ids[r]; k.logText += " ]: "; k.logText += msg; k.logText += '\n'; }
-      if (o.readStats && k.stats.size() == 5 * n && k.stats[5 * r]) {   // Read.cpp:425-431
-        k.statsText += "\n" + k.ids[r] + "\t" + std::to_string(k.stats[5 * r + 1]) + "\t" + std::to_string(k.stats[5 * r + 2]) + "\t" +
-                       std::to_string(k.stats[5 * r + 3]) + "\t" + std::to_string(k.stats[5 * r + 4]);
-      }
-      *w++ = '>';
-      memcpy(w, k.ids[r].data(), k.ids[r].size()); w += k.ids[r].size();
-      *w++ = '\n';
-      const char* q = recs + oo[r];
-      const size_t L = (size_t)(oo[r + 1] - oo[r]);
-      for (size_t p = 0; p < L; p += 70) { const size_t m = std::min<size_t>(70, L - p); memcpy(w, q + p, m); w += m; *w++ = '\n'; }
-    }
-    k.text.resize((size_t)(w - k.text.data()));
-  };
-  auto passThrough = [&](Chunk& c, const PinnedBuf& in) {
-    // no table at all: pass-through with the reference's statuses (Dna5 conversion / -rev still apply)
-    const size_t n = c.ids.size();
-    c.status.assign(n, TALC_READ_SKIPPED_SHORT);
-    std::string all;
-    std::vector<uint64_t> oo(n + 1, 0);
-    for (size_t r = 0; r < n; ++r) {
-      std::string q(in.p + c.offsets[r], c.offsets[r + 1] - c.offsets[r]);
-      for (auto& ch : q) { ch = (ch == 'a' || ch == 'A') ? 'A' : (ch == 'c' || ch == 'C') ? 'C' : (ch == 'g' || ch == 'G') ? 'G' : (ch == 't' || ch == 'T') ? 'T' : 'N'; }
-      if (o.p.reverse) {
-        std::string rcs(q.size(), 'N');
-        for (size_t i = 0; i < q.size(); ++i) { char ch = q[q.size() - 1 - i]; rcs[i] = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : 'N'; }
-        q = rcs;
-      }
-      c.status[r] = q.size() > o.p.k ? TALC_READ_NO_SOLID_KMER : TALC_READ_SKIPPED_SHORT;
-      if (o.readStats) { c.stats.resize(5 * n, 0); if (q.size() > o.p.k) { c.stats[5 * r] = 1; c.stats[5 * r + 1] = (int64_t)q.size(); } }
-      all += q;
-      oo[r + 1] = all.size();
-    }
-    formatChunk(c, all.data(), oo.data());
-  };
-  auto worker = [&](int device) {
-    talc_ctx* ctx = nullptr;
-    { const auto tc0 = std::chrono::steady_clock::now();
-      if (device >= 0 && talc_ctx_create(table, &o.p, device, &ctx) != TALC_OK) { setFailed(); }
-      ctxUs += usSince(tc0); }
-    PinnedBuf outb;
-    if (device >= 0 && batchBytesEstimate) outb.reserve(batchBytesEstimate + batchBytesEstimate / 16);   // (one page-locked allocation, not a dozen doublings)
-    while (!failed) {
-      const auto tw0 = std::chrono::steady_clock::now();
-      std::unique_ptr<Chunk> c;
-      {
-        std::unique_lock<std::mutex> g(qMu);
-        cvReady.wait(g, [&] { return failed.load() || !ready.empty() || readerDone; });
-        if (failed || ready.empty()) break;
-        c = std::move(ready.front()); ready.pop_front();
-      }
-      waitChunkUs += usSince(tw0);
-      PinnedBuf& in = inBufs[c->inBuf];
-      if (device < 0) {
-        passThrough(*c, in);
-      } else {
-        const uint32_t n = (uint32_t)c->ids.size();
-        c->status.assign(n, TALC_READ_SKIPPED_SHORT);
-        talc_batch* b = nullptr;
-        const auto td0 = std::chrono::steady_clock::now();
-        struct Acc { std::atomic<long long>& a; std::chrono::steady_clock::time_point t; ~Acc() { a += (long long)(1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count()); } } acc{deviceBusyUs, td0};
-        if (talc_batch_create(ctx, in.p, c->offsets.data(), n, &b) != TALC_OK) { setFailed(); break; }
-        createUs += usSince(td0);
-        const auto tk0 = std::chrono::steady_clock::now();
-        // < 0: a real HIP / argument error stops the run; TALC_WARN_READ_ERRORS (> 0) is a complete batch in which some
-        // reads kept their input sequence (status TALC_READ_ERROR -> a .log line), and the run goes on
-        const int crc = talc_batch_correct(ctx, b);
-        if (crc < 0) { setFailed(); talc_batch_destroy(b); break; }
-        correctUs += usSince(tk0);
-        const auto tf0 = std::chrono::steady_clock::now();
-        const uint64_t total = talc_batch_corrected_bytes(b);
-        std::vector<uint64_t> oo(n + 1);
-        if (!outb.reserve(std::max<uint64_t>(total, 1))) { setFailed(); talc_batch_destroy(b); break; }
-        if (talc_batch_fetch_corrected(ctx, b, outb.p, total, oo.data(), c->status.data()) != TALC_OK) { setFailed(); talc_batch_destroy(b); break; }
-        if (o.readStats) { c->stats.resize(5ull * n); if (talc_batch_fetch_read_stats(ctx, b, c->stats.data()) != TALC_OK) { setFailed(); talc_batch_destroy(b); break; } }
-        fetchUs += usSince(tf0);
-        const auto tu0 = std::chrono::steady_clock::now();
-        formatChunk(*c, outb.p, oo.data());
-        unpackUs += usSince(tu0);
-        if (sw.timing == 2) {   // per batch: where this worker's time went
-          talc_timing tm; talc_ctx_get_timing(ctx, &tm);
-          fprintf(stderr, "[talc-batch] reads %u: create+H2D %.3f s, correct %.3f s (kernels: coverage %.1f structure %.1f search %.1f retry %.1f ms), fetch %.3f s, text %.3f s\n",
-                  n, std::chrono::duration<double>(tk0 - td0).count(), std::chrono::duration<double>(tf0 - tk0).count(), tm.coverage_ms, tm.structure_ms, tm.search_ms, tm.retry_ms,
-                  std::chrono::duration<double>(tu0 - tf0).count(), usSince(tu0) / 1e6);
-        }
-        if (crc > 0) for (uint32_t i = 0; i < n; ++i) readErrors += c->status[i] == TALC_READ_ERROR ? 1 : 0;
-        talc_batch_destroy(b);
-      }
-      std::unique_lock<std::mutex> g(qMu);
-      freeIn.push_back(c->inBuf); c->inBuf = -1;
-      cvFree.notify_one();
-      // (the batch the writer waits for always gets in; the others wait while the writer is more than a few batches behind)
-      cvRoom.wait(g, [&] { return failed.load() || c->index == nextToWrite || finished.size() < (size_t)nWorkers + 2; });
-      finished[c->index] = std::move(c);
-      cvDone.notify_one();
-    }
-    if (ctx) talc_ctx_destroy(ctx);
-    std::lock_guard<std::mutex> g(qMu);
-    --workersLeft;
-    cvDone.notify_all();
-  };
-  auto writerThread = [&]() {   // io.cpp:50-75 + SeqFileOut FASTA writer, io.cpp:105-111 log lines
-    while (true) {
-      std::unique_ptr<Chunk> c;
-      {
-        std::unique_lock<std::mutex> g(qMu);
-        cvDone.wait(g, [&] { return (!finished.empty() && finished.begin()->first == nextToWrite) || workersLeft == 0 || failed.load(); });
-        if (!finished.empty() && finished.begin()->first == nextToWrite) { c = std::move(finished.begin()->second); finished.erase(finished.begin()); }
-        else if (workersLeft == 0 || failed) break;
-      }
-      if (!c) continue;
-      const auto tw0 = std::chrono::steady_clock::now();
-      if (!c->logText.empty()) { if (!lf.is_open()) lf.open(logFile, std::ios_base::app); lf << c->logText; lf.flush(); }
-      if (!c->statsText.empty()) { if (!sf.is_open()) sf.open(statFile, std::ios_base::app); sf << c->statsText; }
-      of.write(c->text.data(), (std::streamsize)c->text.size());
-      writeBusy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-      std::lock_guard<std::mutex> g(qMu);
-      ++nextToWrite;
-      cvRoom.notify_all();
-    }
-  };
-  {
-    std::thread rd(readerThread), wr(writerThread);
-    std::vector<std::thread> workers;
-    if (emptyRun) workers.emplace_back(worker, -1);
-    else for (int d = 0; d < ndev; ++d) for (int w = 0; w < 2; ++w) workers.emplace_back(worker, d % nphys);
-    for (auto& w : workers) w.join();
-    rd.join();
-    wr.join();
-  }
-  of.close();
-  auto t3 = std::chrono::steady_clock::now();
-  if (failed) {
-    std::cerr << "talc: device error: " << failMsg << "\n";
-    if (table) talc_table_destroy(table);
-    return 2;
-  }
-  if (table) talc_table_destroy(table);
-  if (readErrors) std::cerr << "talc: " << readErrors << " read(s) exhausted the device scratch and were written uncorrected (see " << logFile << ")\n";
+  std::cout << "Specified output file name: " << files.fa << std::endl;
+  std::ofstream of(files.fa, std::ios_base::trunc);
+  if (!of) { std::cerr << "ERROR: Could not open the file " << files.fa << "\n"; return 2; }
+  Pipeline pipeline(o, sw, files, table.get(), ndev, nphys, scan);
+  PipelineTotals totals;
+  const bool ok = pipeline.run(std::move(of), totals);
+  t[4] = Clock::now();
+  if (!ok) { std::cerr << "talc: device error: " << pipeline.failure() << "\n"; return 2; }
+  if (totals.workers.readErrors)
+    std::cerr << "talc: " << totals.workers.readErrors << " read(s) exhausted the device scratch and were written uncorrected (see " << files.log << ")\n";
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
-  // the reference's own split (main.cpp:213-236: loading the reads, building the graph; :311-313: the correction), in
-  // wall-clock seconds instead of CPU minutes.  The correction phase is a pipeline: its three busy times overlap.
-  fprintf(stderr, "[talc] scan=%.3fs table=%.3fs upload=%.3fs read+correct+write=%.3fs (%.3g bases/s, %llu batches of <= %u reads) total=%.3fs\n",
-          secs(t0, t1), secs(t1, t2), secs(t2, t2b), secs(t2b, t3), secs(t2b, t3) > 0 ? (double)basesTotal / secs(t2b, t3) : 0.0,
-          (unsigned long long)nextIndex, o.batchReads, secs(t0, t3));
-  fprintf(stderr, "[talc-timing] {\"scan_s\": %.4f, \"table_parse_build_s\": %.4f, \"upload_s\": %.4f, \"correct_phase_s\": %.4f, "
-                  "\"reader_busy_s\": %.4f, \"device_busy_s_sum_over_workers\": %.4f, \"writer_busy_s\": %.4f, \"total_s\": %.4f, "
-                  "\"device_parts_s\": {\"ctx_create\": %.4f, \"batch_create_h2d\": %.4f, \"correct\": %.4f, \"fetch_d2h\": %.4f, \"records_to_text\": %.4f, \"waiting_for_reader\": %.4f}, "
-                  "\"reads\": %llu, \"bases\": %llu, \"batches\": %llu, \"batch_reads\": %u, \"gpus\": %d, \"workers\": %d}\n",
-          secs(t0, t1), secs(t1, t2), secs(t2, t2b), secs(t2b, t3), readBusy, (double)deviceBusyUs.load() / 1e6, writeBusy, secs(t0, t3),
-          ctxUs.load() / 1e6, createUs.load() / 1e6, correctUs.load() / 1e6, fetchUs.load() / 1e6, unpackUs.load() / 1e6, waitChunkUs.load() / 1e6,
-          (unsigned long long)nReadsTotal, (unsigned long long)basesTotal, (unsigned long long)nextIndex, o.batchReads, ndev, emptyRun ? 1 : 2 * ndev);
+  report(t, totals, scan, o.batchReads, ndev, pipeline.workers());
   return 0;
 }

@@ -120,6 +120,22 @@ def test_cli_streaming_reader_formats_and_batches(cli, data, tmp_path):
     assert r.returncode == 0 and b"ISSUE WITH INPUT FILES" in r.stdout
 
 
+def test_cli_pass_through_reverse_and_read_stats_match_reference_driver(cli, data, tmp_path):
+    """The pass-through's own Dna5 conversion, reverse complement and per-read stats rows (-qm jellyfish2 with neither
+    -jf2 nor a .jf, so no GPU is needed): multi-line FASTQ in batches of 7 with -rev --read-stats gives the reference
+    driver's <o>.fa, <o>.log and <o>.stats_basics.txt byte for byte."""
+    args = [str(data / "reads.fq"), "-k", "21", "-SR", str(data / "sr.dump"), "-qm", "jellyfish2", "-rev", "--read-stats"]
+    a = run(cli, args + ["--batch-reads", "7", "-o", "gpu"], tmp_path)
+    b = run(TALC_REF, args + ["-o", "ref"], tmp_path)
+    assert a.returncode == 0 and b.returncode == 0, (a.stderr, b.stderr)
+    fa, fb = files(str(tmp_path / "gpu")), files(str(tmp_path / "ref"))
+    rows = fa[".stats_basics.txt"].split(b"\n")[2:]                  # one per read longer than K (Read.cpp:418-433)
+    assert fa[".fa"].count(b">") == 60 and len(rows) >= 55 and all(len(r.split(b"\t")) == 5 for r in rows)
+    assert fa[".fa"] == fb[".fa"]
+    assert fa[".log"] == fb[".log"]
+    assert fa[".stats_basics.txt"] == fb[".stats_basics.txt"]
+
+
 def test_cli_empty_table_aborts_with_exit_1(cli, data, tmp_path):
     (tmp_path / "empty.dump").write_text("ACGTACGTACGTACGTACGTA 1\n")     # below MIN_COUNT
     r = run(cli, [str(data / "reads.fa"), "-k", "21", "-SR", str(tmp_path / "empty.dump")], tmp_path)
