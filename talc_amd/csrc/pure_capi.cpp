@@ -81,4 +81,14 @@ void pure_wfa_xdrop(const uint8_t* q, int qlen, const uint8_t* d, int dlen, int 
   const WfaResult r = wfa_xdrop_scalar(q, qlen, d, dlen, x);
   out4[0] = r.moved; out4[1] = r.extCols; out4[2] = r.extRows; out4[3] = r.score;
 }
+
+// ... as one run of a series over the same pair (talc_wfa.h: WfaKept).  keep130 = level, qlenAt, F[64], E[64]: zeroed
+// before a pair's first run, handed back unchanged to the next; returns 1 if this run resumed from the kept level
+int pure_wfa_xdrop_resume(const uint8_t* q, int qlen, const uint8_t* d, int dlen, int x, int32_t* keep130, int32_t* out4) {
+  static_assert(sizeof(WfaKept) == 130 * sizeof(int32_t), "WfaKept is 130 ints");
+  bool resumed = false;
+  const WfaResult r = wfa_xdrop_scalar_run(q, qlen, d, dlen, x, reinterpret_cast<WfaKept*>(keep130), &resumed);
+  out4[0] = r.moved; out4[1] = r.extCols; out4[2] = r.extRows; out4[3] = r.score;
+  return resumed ? 1 : 0;
+}
 }  // extern "C"

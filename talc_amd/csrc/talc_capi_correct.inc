@@ -158,12 +158,13 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
     if ((rc = ensure_stage(c, c->stage, b->max_len, 1, b->n_reads))) return rc;
     ensure_edge_boxes(c, c->stage);
     EdgeTaskArgs ea = {};
+    ea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
     if (c->stage.boxes) {   // the claim counters sit behind the boxes
       ea.boxes = c->stage.boxes.get();
       ea.avail = (uint32_t*)(c->stage.boxes.get() + (uint64_t)c->stage.n_slots * edge_box_bytes(c->stage.box_seq_cap));
       ea.seqCap = c->stage.box_seq_cap;
       ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
-      ea.lingerMod = c->sw.edgeLingerMod; ea.test = c->sw.edgeRedo ? 1u : 0u;
+      ea.lingerMod = c->sw.edgeLingerMod; ea.test |= c->sw.edgeRedo ? kTestEdgeRedo : 0u;
       ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : c->d_hist.get() + 1024 + 129;   // (switched on: whatever the batch looks like)
       HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)c->stage.n_slots * 4, s));
     }
@@ -199,9 +200,11 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
       HIPCHK(hipMemcpyAsync(b->d_state.get() + r, &b->h_state[r], sizeof(ReadState), hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
+    EdgeTaskArgs rea = {};
+    rea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
     hipLaunchKernelGGL(k_search, dim3(big.n_slots), dim3(64), 0, s, c->dp, c->view, big.caps, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
                        b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), d_retry.get(), (uint32_t)retry.size(),
-                       c->d_queue.get(), big.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), EdgeTaskArgs());
+                       c->d_queue.get(), big.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), rea);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

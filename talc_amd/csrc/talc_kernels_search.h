@@ -676,7 +676,7 @@ enum { PF_PROBE = 0, PF_CHILD, PF_AIMS, PF_CYCLE, PF_FFWD, PF_SCOREBR, PF_GARDEN
        PF_EDGEMISC, PF_ANCHORS, PF_ASSEMBLE, PF_STEPB, PF_STEPE, PF_SRCHB, PF_SRCHE, PF_PROLOG, PF_INITTR, PF_TOTAL, PF_NCALLS, PF_NSTEPS,
        PF_FFLOAD, PF_FFREC, PF_FFFLUSH, PF_FFENTRY, PF_NRECS, PF_RD0, PF_RD1, PF_RD2, PF_RD3, PF_RD4, PF_RD5, PF_RDMAX,
        PF_XSTAGE, PF_XLEV, PF_XSEL, PF_REFB, PF_RESULT, PF_CYQ, PF_CYX, PF_CYHIT, PF_CYFILL,
-       PF_SB11, PF_SB12, PF_SB21, PF_SB10, PF_SBOTHER, PF_SEGEN, PF_XCALLS, PF_XNLEV, PF_FSFORK, PF_FSDEAD, PF_FSFILT, PF_FSLIM, PF_FK1, PF_FK2, PF_FKBAIL, PF_FORK, PF_ANCCALLS, PF_ANCITER, PF_TPUB, PF_TOWN, PF_TSTOLEN, PF_TWAIT, PF_TRUN, PF_EA0, PF_EA1, PF_EA2, PF_EA3, PF_EA4, PF_EASUM3, PF_EASUM4, PF_RANCH, PF_RANCHMAX, PF_RBR, PF_RBRMAX, PF_N };
+       PF_SB11, PF_SB12, PF_SB21, PF_SB10, PF_SBOTHER, PF_SEGEN, PF_XCALLS, PF_XNLEV, PF_FSFORK, PF_FSDEAD, PF_FSFILT, PF_FSLIM, PF_FK1, PF_FK2, PF_FKBAIL, PF_FORK, PF_ANCCALLS, PF_ANCITER, PF_TPUB, PF_TOWN, PF_TSTOLEN, PF_TWAIT, PF_TRUN, PF_EA0, PF_EA1, PF_EA2, PF_EA3, PF_EA4, PF_EASUM3, PF_EASUM4, PF_RANCH, PF_RANCHMAX, PF_RBR, PF_RBRMAX, PF_EDGELANE, PF_N };
 #define TALC_PF_NAMES {"probe", "child", "aims", "cycle", "ffwd", "scorebr", "garden", "evalfull", "xdrop", "extnw", "edgemisc", \
                        "anchors", "assemble", "stepb*", "stepe*", "srchb*", "srche*", "prolog", "inittr", "total", "#ffcalls", "#ffsteps", \
                        "ff.load", "ff.record", "ff.flush", "ff.entry", "#ffrecords", "#reads<0.25ms", "#reads<1ms", "#reads<4ms", \
@@ -685,7 +685,10 @@ enum { PF_PROBE = 0, PF_CHILD, PF_AIMS, PF_CYCLE, PF_FFWD, PF_SCOREBR, PF_GARDEN
                        "#stepb 1->1", "#stepb 1->2", "#stepb 2->1", "#stepb 1->0", "#stepb other", "#stepe generic", "#xdrop calls", "#xdrop levels", \
                        "#ffstop fork", "#ffstop deadend", "#ffstop filter", "#ffstop limit/other", "#forkstep 1 child", "#forkstep fork+deadend", "#forkstep bailed", "forkstep", "#anchor lists", "#anchor level tests", \
                        "#edges published", "#anchors by owner", "#anchors by others", "t.owner waits", "t.run by others", \
-                       "#edge anchors<1ms", "#edge anchors<4ms", "#edge anchors<16ms", "#edge anchors<64ms", "#edge anchors>=64ms", "ticks anchors 16-64ms", "ticks anchors>=64ms", "(per read) anchors", "(per read) longest anchor", "(per read) bridge attempts", "(per read) longest bridge attempt"}
+                       "#edge anchors<1ms", "#edge anchors<4ms", "#edge anchors<16ms", "#edge anchors<64ms", "#edge anchors>=64ms", "ticks anchors 16-64ms", "ticks anchors>=64ms", "(per read) anchors", "(per read) longest anchor", "(per read) bridge attempts", "(per read) longest bridge attempt", "edgelane*"}
+
+// test hooks of a launch (EdgeTaskArgs::test -> Wv::taskTest)
+enum : uint32_t { kTestEdgeRedo = 1u, kTestNoEdgeLane = 2u };
 
 struct Wv {
   // kernel constants
@@ -741,7 +744,8 @@ struct Wv {
   uint32_t stealSeq;               // calls of edge_task_steal (which window of avail[] the next one looks at)
   unsigned long long moreCells, moreSteps;   // of the anchors run for other waves between this wave's reads
   uint32_t nanSeen;                // record_edge has seen a distance that is not a number (the fold is then order-dependent)
-  uint32_t taskTest;               // test hook (TALC_TEST_EDGE_REDO): every anchor another wave has run is flagged for the in-order redo
+  uint32_t taskTest;               // test hooks (EdgeTaskArgs::test).  kTestEdgeRedo: every anchor another wave has run is flagged for the
+                                   // in-order redo; kTestNoEdgeLane: an edge search never enters edge_lane
 };
 
 enum { LOC_HEAD = 0, LOC_INNER = 1, LOC_TAIL = 2 };
@@ -1591,12 +1595,15 @@ TALC_DN bool seed_and_extension_multi(const uint8_t* ref, int refLen, const uint
 // Trail's record is read again after the extension instead of being held across it, so that this function keeps no
 // vector register alive over the call — a vector register held over a call has to be a callee-saved one, and every
 // callee-saved register a function touches costs a scratch store and a load per call of it.)
-TALC_D bool trail_seed_and_extend(int set_, int t_, int len_, int xdrop_) {
+// (leafFell: the edge lane has run the leaf instance for this very scoring and it asked for the general function)
+TALC_D bool trail_seed_and_extend(int set_, int t_, int len_, int xdrop_, bool leafFell = false) {
   const int set = uni(set_), t = uni(t_), len = uni(len_), xdrop = uni(xdrop_);
   WSYNC();   // the Trail's last bases were appended by lane 0: make them visible to the DP lanes
   const uint32_t buf = (uint32_t)uni((int)tr_buf(set, t));
   // (the kept wavefront, talc_wave.h: the pair is this search's reference and the Trail in buffer `buf`)
-  SeedExt e = seed_and_extension_leaf(X.ref, (int)X.refLen, X.seqPool + (uint64_t)buf * X.C.seqCap, len, xdrop, buf + 1u);
+  SeedExt e;   // (with leafFell only `fallback` is set here: the general call below then overwrites every field)
+  e.fallback = true;
+  if (!leafFell) e = seed_and_extension_leaf(X.ref, (int)X.refLen, X.seqPool + (uint64_t)buf * X.C.seqCap, len, xdrop, buf + 1u);
   if (uni((int)e.fallback) != 0) e = seed_and_extension(X.ref, (int)X.refLen, X.seqPool + (uint64_t)buf * X.C.seqCap, len, xdrop, true);
   const int lenHistExt = uni(e.lenHistExt), score = uni(e.score), posOnRef = uni(e.posOnRef);
   const bool stop = uni((int)e.stop) != 0;
@@ -2284,14 +2291,14 @@ TALC_D int step_bridge(int nCur, int len, uint32_t& stepCounter) {
 // are compacted in place; returns their number
 // (ib = the Trail set to score: the new set of a generic step, or the current set when the fast-forward took the step)
 TALC_DNC int score_edges_multi(int ib_, int n_, int len_, int& xdrop_);
-TALC_D int score_edges(int ib_, int n_, int len_, int& xdrop_) {
+TALC_D int score_edges(int ib_, int n_, int len_, int& xdrop_, bool leafFell = false) {
   const int n = uni(n_), len = uni(len_);
   if (n == 0) return 0;
   const int ib = uni(ib_);
   const int xdrop = uni(xdrop_) + 2;
   if (n == 1) {
     // the common case, one live Trail: the same outcome without the survivor flags' trip through memory and its barriers
-    const bool ok = uni((int)trail_seed_and_extend(ib, 0, len, xdrop)) != 0;
+    const bool ok = uni((int)trail_seed_and_extend(ib, 0, len, xdrop, leafFell)) != 0;
     xdrop_ = ok ? (int)((double)uni(tr_get(ib, 0).score) * (-1)) : 0;
     if (!ok) { record_edge(ib, 0, len); pool_free((uint32_t)uni((int)tr_buf(ib, 0))); return 0; }
     return 1;
@@ -2584,78 +2591,24 @@ TALC_D uint32_t dpp_row_shr(uint32_t v, uint32_t old) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x110 + P, 0xF, 0xF, false);
 }
 
-// WIDEF: the search's cycle filter is the wide one in HBM (an instance of its own: the common form's loop stays as it is)
-template <bool dirRight, bool WIDEF>
-TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAXLENGTH_, bool edge_) {
-  PROF_DECL; PROF_DECL2;
-  PROF_BEGIN2();
-  const DevParams& P = X.P;
+// One walk record from the Trail's tip (the loop body of fast_forward_walk and of the edge lane: ONE copy, so that the
+// filter and cycle rules cannot drift apart).  Commits up to `room` steps; returns the number taken, 0 when the walk ends
+// here (no record, a first level that is not "single", a filter hit on the first level).  nOK: the plain steps among them;
+// aimIdx >= 0: the last step taken reached that aim (bridges; nAims == 0 never looks).  `also(position, base)` is run by
+// each committing lane next to its store into the Trail's buffer.
+struct WalkLanes { uint32_t laneOff, laneShift, laneSingle; int lj; };                       // per-lane constants
+struct WalkTip { uint64_t kmer, key; uint32_t hh, cnt; uint32_t ePre; bool havePre; int done, flushed; };   // (ePre: per lane)
+template <bool dirRight, bool WIDEF, class Also>
+TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t TALC_AS1* wtab, uint64_t cap, uint32_t K, gu8 seq, int len0,
+                       uint32_t* recN, int nAims, uint32_t wideMask, unsigned long long* wideBloom, int& nOK, int& aimIdx, Also also) {
+  PROF_DECL;
   const int l = lane_id();
-  const bool edge = uni((int)edge_) != 0;
-  if (uni((int)(X.traceSteps)) != 0) return 0;
-  const TrailRec r0 = tr_get(X.ia, 0);
-  if (uni64(r0.nmask) != 0ull) return 0;
-  const uint32_t K = (uint32_t)uni((int)P.K), CHECK = (uint32_t)uni((int)P.CHECK_INTERVAL);
-  const uint32_t seqCap = (uint32_t)uni((int)X.C.seqCap), PMAX = (uint32_t)uni((int)PATH_MAXLENGTH_);
-  const uint64_t cap = uni64(X.T.capacity);
-  const uint32_t TALC_AS1* wtab = (const uint32_t TALC_AS1*)uni_ptr(dirRight ? X.T.walkRight : X.T.walkLeft);
-  const uint32_t wideMask = WIDEF ? (uint32_t)uni((int)X.wideMask) : 0u;
-  unsigned long long* const wideBloom = WIDEF ? (unsigned long long*)uni_ptr(X.wideBloom) : nullptr;
   const uint64_t kmask = (1ULL << (2 * K)) - 1, m1 = (1ULL << (2 * (K - 1))) - 1;
-  uint64_t kmer = uni64(r0.kmer);
-  uint32_t cnt = (uint32_t)uni((int)r0.cnt);
-  const int len0 = uni(len_);
-  const uint32_t sc0 = (uint32_t)uni((int)stepCounter_);
-  int maxSteps = 0;
-  if (sc0 < PMAX && (uint32_t)len0 < seqCap) {
-    maxSteps = (int)min(PMAX - sc0, seqCap - (uint32_t)len0);
-    if (edge) maxSteps = min(maxSteps, (int)(CHECK - (sc0 % CHECK)));   // up to and including the next scoring step
-  }
-  gu8 seq = (gu8)uni_ptr(X.seqPool + (uint64_t)r0.buf * X.C.seqCap);
-  const int nAims = edge ? 0 : uni(dirRight ? X.nAncR : X.nAncL);
-  int lanc = uni((int)r0.lanc), ranc = uni((int)r0.ranc);
-  bool popped = false;
-  uint32_t* recN = (uint32_t*)g_dp;   // counts of the committed, not yet flushed steps (the DP stage is idle here)
-  uint32_t cFlush = cnt;
-  double dist = r0.dist;
-  int done = 0, flushed = 0;
-
-  auto flush = [&]() {
-    const int n = done - flushed;
-    if (n <= 0) return;
-    PROF_DECL; PROF_BEGIN();
-    // distance terms |c - n| / sqrt(c) (Explorer.cpp:1247): c of step j is n of step j-1
-    const uint32_t cn = (l < n) ? recN[l] : 1u;
-    const uint32_t cprev = (l == 0) ? cFlush : ((l < n) ? recN[l - 1] : 1u);
-    const double term = fabs((double)cprev - (double)cn) / sqrt((double)cprev);
-    // added in path order (the same double additions as step by step): the terms go through LDS, whose reads the
-    // compiler can issue several at a time ahead of the dependent additions
-    double* recT = (double*)(g_dp + 64);
-    recT[l] = term;
-    LSYNC();
-#pragma unroll 8
-    for (int j = 0; j < n; ++j) dist = dist + recT[j];
-    cFlush = (uint32_t)lane_get((int)cn, n - 1);
-    flushed = done;
-    LSYNC();
-    PROF_END(PF_FFFLUSH);
-  };
-
-  // lane j < 12 reads the dword that holds level j (two 16-bit levels per dword), lanes 12 / 13 the two halves of the
-  // key (the lanes above them repeat lane 12)
-  const uint32_t laneOff = (l < TALC_WALK_LEVELS) ? (uint32_t)(2 + (l >> 1)) : (l == TALC_WALK_LEVELS + 1 ? 1u : 0u);
-  const uint32_t laneShift = (l < TALC_WALK_LEVELS && (l & 1)) ? 16u : 0u;
-  const int lj = min(l, TALC_WALK_LEVELS - 1);                // shift amounts stay in range on the idle lanes
-  const uint32_t laneSingle = (l < TALC_WALK_LEVELS) ? kWalkSingle : 0u;
-  uint64_t key = dirRight ? (kmer & m1) : (kmer >> 2);
-  uint32_t hh = (uint32_t)(table_hash(key) >> 32);
-  PROF_END2(PF_FFENTRY);
-  // The record a Trail reaches when it takes all of the current record's steps is requested as soon as the lanes have
-  // hashed their tips — before the filter query, the aim check and the commit — so that its latency runs under that work.
-  uint32_t ePre = 0;
-  bool havePre = false;
-  while (done < maxSteps) {
-    if (done - flushed > 64 - TALC_WALK_LEVELS) flush();
+  const uint32_t laneOff = WL.laneOff, laneShift = WL.laneShift, laneSingle = WL.laneSingle;
+  const int lj = WL.lj;
+  uint64_t& kmer = W.kmer; uint64_t& key = W.key; uint32_t& hh = W.hh; uint32_t& cnt = W.cnt; uint32_t& ePre = W.ePre; bool& havePre = W.havePre;
+  int& done = W.done; const int flushed = W.flushed;
+  nOK = 0; aimIdx = -1;
     PROF_BEGIN();
     uint64_t slot = ((uint64_t)hh * (uint64_t)(uint32_t)cap) >> 32;
     uint32_t e = havePre ? ePre : wtab[slot * 8 + laneOff];
@@ -2672,14 +2625,14 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
 #ifdef TALC_PROF
     if (l == 0) g_prof[PF_NRECS] += 1;
 #endif
-    if (!found) break;
+    if (!found) return 0;
     PROF_BEGIN();
     const uint32_t lev = (e >> laneShift) & 0xFFFFu, top = lev & kWalkTopNone;
 #ifdef TALC_PROF
     {   // why the walk will stop in this record, if it does: the first level that is not "single"
       const unsigned long long pm = ballot64((l < TALC_WALK_LEVELS) && (lev & kWalkSingle) != 0u);
       const int j0 = __builtin_ctzll(~pm);
-      if (j0 < TALC_WALK_LEVELS && j0 < maxSteps - done) {
+      if (j0 < TALC_WALK_LEVELS && j0 < room) {
         const uint32_t t0 = (uint32_t)lane_get((int)top, j0);
         if (l == 0) g_prof[(t0 >= X.P.MIN_COUNT) ? PF_FSFORK : PF_FSDEAD] += 1;
       }
@@ -2688,8 +2641,8 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
     // levels that are "exactly one successor with count >= MIN_COUNT" (decided at upload for the table's MIN_COUNT, which
     // is this context's), from level 0 up to the first that is not
     const unsigned long long passMask = ballot64((lev & laneSingle) != 0u);   // (a plain compare: the ballot is its lane mask)
-    int nOK = min(__builtin_ctzll(~passMask), maxSteps - done);
-    if (nOK == 0) break;
+    nOK = min(__builtin_ctzll(~passMask), room);
+    if (nOK == 0) return 0;
     // lane j's tip after its step: the current tip shifted by j+1 bases, with the bases of levels 0..j
     const uint32_t which = (l < TALC_WALK_LEVELS) ? (lev >> kWalkBaseShift) : 0u;
     uint32_t pre = which << (dirRight ? 2 * (TALC_WALK_LEVELS - 1 - lj) : 2 * lj);
@@ -2736,7 +2689,7 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
     // a filter hit on a level that could otherwise be taken: if its k-mer is an aim, that step is a plain step that
     // also records the bridge (oneMoreStep, Explorer.cpp:566-583) — taken here as well; anything else (a possible
     // cycle, a false positive, aims beyond the LDS copy) is left to the generic step
-    int aimIdx = -1;
+    aimIdx = -1;
     if (nAims > 0 && nAims <= AIMS_LDS && hitLevel < nOK) {
       const uint64_t kmH = ((uint64_t)(uint32_t)lane_get((int)(uint32_t)(km >> 32), hitLevel) << 32) | (uint32_t)lane_get((int)(uint32_t)km, hitLevel);
       const unsigned long long am = ballot64((l < nAims) && (g_aimK[l < AIMS_LDS ? l : 0] == kmH) && (g_aimN[l < AIMS_LDS ? l : 0] == 0ull));
@@ -2747,13 +2700,14 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
 #endif
     nOK = min(nOK, hitLevel);
     const int nTake = nOK + (aimIdx >= 0 ? 1 : 0);
-    if (nTake == 0) break;
+    if (nTake == 0) return 0;
     // ---- commit nTake steps
     if (l < nTake) {
       atomicOr(&g_bloom[bwi], bm);
       if (WIDEF) wide_or(wideW, bmW);
       recN[done - flushed + l] = top;
       seq[len0 + done + l] = (uint8_t)which;
+      also(len0 + done + l, which);
     }
     const int last = nTake - 1;
     kmer = ((uint64_t)(uint32_t)lane_get((int)(uint32_t)(km >> 32), last) << 32) | (uint32_t)lane_get((int)(uint32_t)km, last);
@@ -2764,6 +2718,93 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
     done += nTake;
     LSYNC();
     PROF_END(PF_FFREC);
+  return nTake;
+}
+// the distance terms of the committed, not yet flushed steps (counts in recN), added to dist in path order
+TALC_D void walk_flush(WalkTip& W, uint32_t* recN, uint32_t& cFlush, double& dist) {
+  const int l = lane_id();
+  int& done = W.done; int& flushed = W.flushed;
+  const int n = done - flushed;
+  if (n <= 0) return;
+  PROF_DECL; PROF_BEGIN();
+  // distance terms |c - n| / sqrt(c) (Explorer.cpp:1247): c of step j is n of step j-1
+  const uint32_t cn = (l < n) ? recN[l] : 1u;
+  const uint32_t cprev = (l == 0) ? cFlush : ((l < n) ? recN[l - 1] : 1u);
+  const double term = fabs((double)cprev - (double)cn) / sqrt((double)cprev);
+  // added in path order (the same double additions as step by step): the terms go through LDS, whose reads the
+  // compiler can issue several at a time ahead of the dependent additions
+  double* recT = (double*)(g_dp + 64);
+  recT[l] = term;
+  LSYNC();
+#pragma unroll 8
+  for (int j = 0; j < n; ++j) dist = dist + recT[j];
+  cFlush = (uint32_t)lane_get((int)cn, n - 1);
+  flushed = done;
+  LSYNC();
+  PROF_END(PF_FFFLUSH);
+}
+
+// WIDEF: the search's cycle filter is the wide one in HBM (an instance of its own: the common form's loop stays as it is)
+template <bool dirRight, bool WIDEF>
+TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAXLENGTH_, bool edge_) {
+  PROF_DECL2;
+  PROF_BEGIN2();
+  const DevParams& P = X.P;
+  const int l = lane_id();
+  const bool edge = uni((int)edge_) != 0;
+  if (uni((int)(X.traceSteps)) != 0) return 0;
+  const TrailRec r0 = tr_get(X.ia, 0);
+  if (uni64(r0.nmask) != 0ull) return 0;
+  const uint32_t K = (uint32_t)uni((int)P.K), CHECK = (uint32_t)uni((int)P.CHECK_INTERVAL);
+  const uint32_t seqCap = (uint32_t)uni((int)X.C.seqCap), PMAX = (uint32_t)uni((int)PATH_MAXLENGTH_);
+  const uint64_t cap = uni64(X.T.capacity);
+  const uint32_t TALC_AS1* wtab = (const uint32_t TALC_AS1*)uni_ptr(dirRight ? X.T.walkRight : X.T.walkLeft);
+  const uint32_t wideMask = WIDEF ? (uint32_t)uni((int)X.wideMask) : 0u;
+  unsigned long long* const wideBloom = WIDEF ? (unsigned long long*)uni_ptr(X.wideBloom) : nullptr;
+  const uint64_t m1 = (1ULL << (2 * (K - 1))) - 1;
+  WalkTip W;   // the tip and the step counts: walk_record's state
+  uint64_t& kmer = W.kmer; uint32_t& cnt = W.cnt;
+  kmer = uni64(r0.kmer);
+  cnt = (uint32_t)uni((int)r0.cnt);
+  const int len0 = uni(len_);
+  const uint32_t sc0 = (uint32_t)uni((int)stepCounter_);
+  int maxSteps = 0;
+  if (sc0 < PMAX && (uint32_t)len0 < seqCap) {
+    maxSteps = (int)min(PMAX - sc0, seqCap - (uint32_t)len0);
+    if (edge) maxSteps = min(maxSteps, (int)(CHECK - (sc0 % CHECK)));   // up to and including the next scoring step
+  }
+  gu8 seq = (gu8)uni_ptr(X.seqPool + (uint64_t)r0.buf * X.C.seqCap);
+  const int nAims = edge ? 0 : uni(dirRight ? X.nAncR : X.nAncL);
+  int lanc = uni((int)r0.lanc), ranc = uni((int)r0.ranc);
+  bool popped = false;
+  uint32_t* recN = (uint32_t*)g_dp;   // counts of the committed, not yet flushed steps (the DP stage is idle here)
+  uint32_t cFlush = cnt;
+  double dist = r0.dist;
+  int& done = W.done; int& flushed = W.flushed;
+  done = 0; flushed = 0;
+
+  auto flush = [&]() { walk_flush(W, recN, cFlush, dist); };
+
+  // lane j < 12 reads the dword that holds level j (two 16-bit levels per dword), lanes 12 / 13 the two halves of the
+  // key (the lanes above them repeat lane 12)
+  WalkLanes WL;
+  WL.laneOff = (l < TALC_WALK_LEVELS) ? (uint32_t)(2 + (l >> 1)) : (l == TALC_WALK_LEVELS + 1 ? 1u : 0u);
+  WL.laneShift = (l < TALC_WALK_LEVELS && (l & 1)) ? 16u : 0u;
+  WL.lj = min(l, TALC_WALK_LEVELS - 1);                // shift amounts stay in range on the idle lanes
+  WL.laneSingle = (l < TALC_WALK_LEVELS) ? kWalkSingle : 0u;
+  W.key = dirRight ? (kmer & m1) : (kmer >> 2);
+  W.hh = (uint32_t)(table_hash(W.key) >> 32);
+  PROF_END2(PF_FFENTRY);
+  // The record a Trail reaches when it takes all of the current record's steps is requested as soon as the lanes have
+  // hashed their tips — before the filter query, the aim check and the commit — so that its latency runs under that work.
+  W.ePre = 0;
+  W.havePre = false;
+  while (done < maxSteps) {
+    if (done - flushed > 64 - TALC_WALK_LEVELS) flush();
+    int nOK, aimIdx;
+    const int nTake = walk_record<dirRight, WIDEF>(WL, W, maxSteps - done, wtab, cap, K, seq, len0, recN, nAims, wideMask, wideBloom, nOK, aimIdx,
+                                                   [](int, uint32_t) {});
+    if (nTake == 0) break;
     if (aimIdx >= 0) {
       // recordBridge (Explorer.cpp:1097-1101) for the Trail as it stands after this step
       flush();
@@ -2823,6 +2864,171 @@ TALC_DN int fast_forward(int len, uint32_t& stepCounter, uint32_t PATH_MAXLENGTH
                                 : fast_forward_walk<false, false>(len, stepCounter, PATH_MAXLENGTH, edge);
   }
   [[clang::musttail]] return fast_forward_steps(len, stepCounter, PATH_MAXLENGTH, edge);
+}
+
+// ------------------------------------------------------------------ the edge lane
+// An edge search scores its one live Trail every CHECK_INTERVAL steps, so its loop is: at most CHECK_INTERVAL steps of
+// fast_forward, then score_edges -> trail_seed_and_extend -> seed_and_extension_leaf -> wave_xdrop_wfa<1>, and round
+// again — about 18 rounds per start anchor, each of which fetches the Trail's record, builds the lane constants, evaluates
+// the distance terms, stages both segments of the extension and writes everything back.  None of that changes between
+// rounds: the database segment (the read's edge) is fixed for the whole anchor, the query (the Trail) only grows at its
+// end, the record is wave-uniform.  edge_lane runs "walk up to the scoring step, score, repeat" in one function that
+// makes no call: the record stays in scalar registers (tr_put once, on the way out), the database segment is staged
+// once and the lanes that commit steps write their bases to the stage as well as to the Trail's buffer, the distance
+// terms are evaluated when 64 - TALC_WALK_LEVELS steps are pending or on the way out (added in path order, as ever).
+// The walk is fast_forward_walk's, the scoring wave_xdrop_wfa<1>'s with the kept wavefront (g_keep) as the leaf instance
+// uses it, so whoever takes over finds the state it expects.
+// Like the fast-forward it hands back BEFORE anything that is not the simple round, with the state written back as the
+// separate calls would have left it: a step the walk does not take (the generic step redoes it), a scoring whose band
+// passes 63 diagonals or whose Trail has outgrown the reference (score_edges redoes it: `ff` > 0 on a scoring step), a
+// Trail that fails its scoring (`dead`: the caller records the edge), an extension the leaf instance does not finish
+// (`leafFell`: the caller continues with the general function).
+// LDS: the walk's counts and distance terms keep the first 768 bytes of g_dp, the stage follows: the query at
+// kLaneStageOff, the database segment qpad = (dlen + 16) & ~7 bytes behind it (the query never passes dlen bases here).
+struct EdgeLaneRet { int len; uint32_t stepCounter; int xdrop; int ff; int dead; int leafFell; };
+constexpr int kLaneStageOff = 768;
+
+template <bool dirRight>
+TALC_D EdgeLaneRet edge_lane_dir(int len_, uint32_t stepCounter_, uint32_t PATH_MAXLENGTH_, int xdrop_) {
+  PROF_DECL;
+  const DevParams& P = X.P;
+  const int l = lane_id();
+  EdgeLaneRet R;
+  R.len = uni(len_); R.stepCounter = (uint32_t)uni((int)stepCounter_); R.xdrop = uni(xdrop_); R.ff = 0; R.dead = 0; R.leafFell = 0;
+  if (uni((int)(X.traceSteps)) != 0) return R;
+  const TrailRec r0 = tr_get(X.ia, 0);
+  if (uni64(r0.nmask) != 0ull) return R;
+  const uint32_t K = (uint32_t)uni((int)P.K), CHECK = (uint32_t)uni((int)P.CHECK_INTERVAL);
+  const uint32_t seqCap = (uint32_t)uni((int)X.C.seqCap), PMAX = (uint32_t)uni((int)PATH_MAXLENGTH_);
+  const uint32_t MAXFAIL = (uint32_t)uni((int)P.MAX_BORDER_FAILURES);
+  const uint64_t cap = uni64(X.T.capacity);
+  const uint32_t TALC_AS1* wtab = (const uint32_t TALC_AS1*)uni_ptr(dirRight ? X.T.walkRight : X.T.walkLeft);
+  const uint64_t m1 = (1ULL << (2 * (K - 1))) - 1;
+  WalkTip W;   // the tip and the step counts: walk_record's state
+  uint64_t& kmer = W.kmer; uint32_t& cnt = W.cnt;
+  kmer = uni64(r0.kmer);
+  cnt = (uint32_t)uni((int)r0.cnt);
+  const int len0 = R.len;
+  const uint32_t sc0 = R.stepCounter;
+  const uint32_t buf = (uint32_t)uni((int)r0.buf);
+  gu8 seq = (gu8)uni_ptr(X.seqPool + (uint64_t)buf * X.C.seqCap);
+  int lanc = uni((int)r0.lanc), ranc = uni((int)r0.ranc), score = uni((int)r0.score);
+  uint32_t fail = (uint32_t)uni((int)r0.fail);
+  int xdrop = R.xdrop;
+  uint32_t* recN = (uint32_t*)g_dp;   // counts of the committed, not yet flushed steps
+  uint32_t cFlush = cnt;
+  double dist = r0.dist;
+  int& done = W.done; int& flushed = W.flushed;
+  done = 0; flushed = 0;
+  // the extension's two segments: the reference (database) from S on, the Trail (query) from S on
+  const int S = dirRight ? (int)K - 1 : (int)K;
+  const int refLen = uni((int)X.refLen);
+  const int dlen = refLen - S;
+  const int qpad = (dlen + 16) & ~7;
+  constexpr int STAGE = 3 * LDS_DP_CAP * 4;
+  const bool stageFits = dlen > 0 && kLaneStageOff + qpad + dlen + 16 <= STAGE;
+  uint8_t TALC_AS3* const stage = (uint8_t TALC_AS3*)g_dp + kLaneStageOff;
+  bool staged = false;
+  unsigned long long ncells = 0;
+#ifdef TALC_PROF
+  uint32_t rounds = 0;
+#endif
+
+  auto flush = [&]() { walk_flush(W, recN, cFlush, dist); };
+
+  WalkLanes WL;
+  WL.laneOff = (l < TALC_WALK_LEVELS) ? (uint32_t)(2 + (l >> 1)) : (l == TALC_WALK_LEVELS + 1 ? 1u : 0u);
+  WL.laneShift = (l < TALC_WALK_LEVELS && (l & 1)) ? 16u : 0u;
+  WL.lj = min(l, TALC_WALK_LEVELS - 1);
+  WL.laneSingle = (l < TALC_WALK_LEVELS) ? kWalkSingle : 0u;
+  W.key = dirRight ? (kmer & m1) : (kmer >> 2);
+  W.hh = (uint32_t)(table_hash(W.key) >> 32);
+  W.ePre = 0;
+  W.havePre = false;
+  uint32_t phase = sc0 % CHECK;   // steps since the last scoring step
+
+  while (true) {
+    // ---- one round: the steps up to and including the next scoring step (fast_forward_walk with `edge`, no aims)
+    const uint32_t sc = sc0 + (uint32_t)done;
+    const int roundStart = done;
+    int lim = done;
+    if (sc < PMAX && (uint32_t)(len0 + done) < seqCap)
+      lim = done + (int)min(min(PMAX - sc, seqCap - (uint32_t)(len0 + done)), CHECK - phase);
+#ifdef TALC_PROF
+    ++rounds;
+#endif
+    while (done < lim) {
+      if (done - flushed > 64 - TALC_WALK_LEVELS) flush();
+      // the bases go to the Trail's buffer (record_edge and the generic step read it) and to the stage
+      int nOK, aimIdx;
+      const int nTake = walk_record<dirRight, false>(WL, W, lim - done, wtab, cap, K, seq, len0, recN, 0, 0u, nullptr, nOK, aimIdx,
+                                                     [&](int pos, uint32_t base) { const int qi = pos - S; if (stageFits && qi < dlen) stage[qi] = (uint8_t)base; });
+      if (nTake == 0) break;
+      if (nOK < TALC_WALK_LEVELS) break;
+    }
+    R.ff = done - roundStart;
+    phase += (uint32_t)R.ff;
+    if (phase == CHECK) phase = 0;
+    // ---- is a scoring due, and is it the simple one?  (anything else: back to the caller, which decides as ever)
+    if (R.ff == 0 || phase != 0) break;
+    const int len = len0 + done, x = xdrop + 2;
+    const int qlen = len - S;
+    if (!stageFits || len > refLen) break;                                   // (a Trail longer than its reference is the database)
+    if (min(max(x, 0), qlen) + min(max(x, 0), dlen) + 1 > 63) break;         // the phased instances
+    // ---- Trail::seedAndExtend (trail_seed_and_extend + the leaf instance of getSeedAndExtension) on the kept stage
+    PROF_BEGIN();
+#ifdef TALC_PROF
+    if (l == 0) g_prof[PF_XCALLS] += 1;
+#endif
+    if (!staged) {
+      WSYNC();   // the Trail's bases of before this call are in its buffer only
+      stage_copy(stage, (gcu8)seq + S, qlen);
+      stage_copy(stage + qpad, (gcu8)uni_ptr(X.ref) + S, dlen);
+      if (l == 0) stage[qpad + dlen] = 0xF1;
+      staged = true;
+    }
+    if (l == 0) stage[qlen] = 0xF0;
+    int extCols = 0, extRows = 0, extScore = 0;
+    const int rc = wave_xdrop_wfa<1, true>(nullptr, qlen, nullptr, dlen, x, stage, STAGE - kLaneStageOff, extCols, extRows, extScore, ncells, nullptr, buf + 1u, qpad);
+    PROF_END(PF_XDROP);
+    const int lenRefExt = S + uni(extRows), lenHistExt = S + uni(extCols);
+    const int posOnRef = dirRight ? lenRefExt : (refLen - (int)K - uni(extRows));
+    bool stop = false;
+    int sNew;
+    if (max(lenRefExt, lenHistExt) >= (int)K) {
+      if (uni(rc) != 1) { R.leafFell = 1; break; }
+      sNew = uni(extScore);
+    } else { sNew = -x; stop = true; }
+    fail = (lenHistExt == len) ? 0u : fail + 1u;
+    score = sNew;
+    if (dirRight) ranc = posOnRef; else lanc = posOnRef;
+    if (!((fail <= MAXFAIL) & !stop)) { R.dead = 1; xdrop = 0; break; }
+    xdrop = (int)((double)score * (-1));
+    R.ff = 0;
+    if (!(sc0 + (uint32_t)done < PMAX)) break;
+  }
+
+  flush();
+  R.len = len0 + done; R.stepCounter = sc0 + (uint32_t)done; R.xdrop = xdrop;
+#ifdef TALC_PROF
+  if (l == 0) { g_prof[PF_NCALLS] += rounds; g_prof[PF_NSTEPS] += (uint32_t)done; }
+#endif
+  X.cells += ncells;
+  if (done) {
+    X.steps += (unsigned long long)done;
+    if (l == 0) {
+      TrailRec r;   // (every field from the scalar copy: nothing of r0 stays in vector registers over the loop)
+      r.kmer = kmer; r.nmask = 0ull; r.dist = dist; r.cnt = cnt; r.score = score; r.fail = fail; r.lanc = lanc; r.ranc = ranc; r.buf = buf;
+      tr_put(X.ia, 0, r);
+    }
+  }
+  if (R.dead | R.leafFell) WSYNC();   // what follows reads the Trail's buffer
+  else LSYNC();
+  return R;
+}
+TALC_DN EdgeLaneRet edge_lane(int len, uint32_t stepCounter, uint32_t PATH_MAXLENGTH, int xdrop) {
+  return uni((int)X.dirRight) ? edge_lane_dir<true>(len, stepCounter, PATH_MAXLENGTH, xdrop)
+                              : edge_lane_dir<false>(len, stepCounter, PATH_MAXLENGTH, xdrop);
 }
 
 // ------------------------------------------------------------------ a fork whose second branch ends at once
@@ -3290,15 +3496,33 @@ TALC_D void edge_anchor_search(const AnchorRec* anchors_, int s_) {
   int len = (int)K;
   while ((int)(nCur > 0) & (int)((uint32_t)nCur <= maxInner) & (int)((uint32_t)uni((int)stepCounter) < PATH_MAXLENGTH) & (int)(uni((int)X.overflow) == 0)) {
     if (nCur == 1) {
-      PROF_BEGIN2();
-      const int ff = uni(fast_forward(len, stepCounter, PATH_MAXLENGTH, true));
-      len += ff;
-      PROF_END2(PF_FFWD);
-      if (ff > 0 && ((uint32_t)uni((int)stepCounter) % CHECK == 0)) {
+      int ff;
+      bool leafFell = false;
+      // the walk tables, the search's filter in LDS: the edge lane walks and scores until something is not the simple round
+      if (uni((int)(X.T.walkRight != nullptr && X.P.MIN_COUNT < kWalkTopNone && X.wideMask == 0u && (X.taskTest & kTestNoEdgeLane) == 0u)) != 0) {
+        PROF_BEGIN2();
+        const EdgeLaneRet R = edge_lane(len, stepCounter, PATH_MAXLENGTH, xdrop);
+        len = uni(R.len); stepCounter = (uint32_t)uni((int)R.stepCounter); xdrop = uni(R.xdrop); ff = uni(R.ff);
+        leafFell = uni(R.leafFell) != 0;
+        PROF_END2(PF_EDGELANE);
+        if (uni(R.dead) != 0) {   // its Trail failed a scoring (score_edges, n == 1)
+          PROF_BEGIN2();
+          record_edge(X.ia, 0, len); pool_free((uint32_t)uni((int)tr_buf(X.ia, 0)));
+          nCur = 0;
+          PROF_END2(PF_STEPE);
+          continue;
+        }
+      } else {
+        PROF_BEGIN2();
+        ff = uni(fast_forward(len, stepCounter, PATH_MAXLENGTH, true));
+        len += ff;
+        PROF_END2(PF_FFWD);
+      }
+      if (leafFell || (ff > 0 && ((uint32_t)uni((int)stepCounter) % CHECK == 0))) {
         // the fast-forward took the step after which scoring is due (Explorer.cpp:672-686): the one Trail stays
         // where it is (set ia, slot 0) — score it there; five or fewer survivors means no gardening
         PROF_BEGIN2();
-        nCur = uni(score_edges(X.ia, 1, len, xdrop));
+        nCur = uni(score_edges(X.ia, 1, len, xdrop, leafFell));
         PROF_END2(PF_STEPE);
         continue;
       }
@@ -3364,7 +3588,7 @@ struct EdgeTaskArgs {
   uint32_t minWeak;                  // a border of at least this many bases is published once the work queue is dry ...
   uint32_t heavy, heavyRounds;       // ... and one of at least `heavy` bases from the start of its search, for the reads of the queue's first `heavyRounds` rounds
   uint32_t lingerMod;                // one wave in so many stays when the reads are gone
-  uint32_t test;                     // TALC_TEST_EDGE_REDO
+  uint32_t test;                     // test hooks: kTestEdgeRedo (TALC_TEST_EDGE_REDO) | kTestNoEdgeLane (TALC_TEST_EDGE_LANE=0)
   const uint32_t* autoSwitch;        // not null: the tasks are used when this word is not 0 (k_order_scale: the batch's graph branches)
 };
 TALC_D uint32_t aload32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -3559,7 +3783,7 @@ TALC_DNC void edge_task_run(uint32_t victim_, int old_) {
     WSYNC();
     X.best2[0].have = false; X.best2[1].have = false;
     edge_anchor_search_task(mine, s);
-    if (X.taskTest) X.nanSeen = 1u;
+    if (X.taskTest & kTestEdgeRedo) X.nanSeen = 1u;
     edge_box_store(box, s, X.complexRegion ? 1u : 0u);
   }
   agent_fence();

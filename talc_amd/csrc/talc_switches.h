@@ -24,6 +24,7 @@ struct Switches {
   int edgeTasks = -1;           // TALC_EDGE_TASKS: -1 (unset) the batch's fork share decides, 0 off, 1 on
   uint32_t edgeTaskMin = 150, edgeTaskHeavy = 200, edgeTaskRounds = 0xFFFF, edgeLingerMod = 16;   // TALC_EDGE_TASK_*, TALC_EDGE_LINGER_MOD
   bool edgeRedo = false;        // TALC_TEST_EDGE_REDO: every anchor another wave has run is redone in order
+  bool edgeLane = true;         // TALC_TEST_EDGE_LANE=0: an edge search never enters the fused walk-and-score lane
   bool traceSteps = false;      // TALC_TRACE_STEPS: talc_batch_trace_read records every step
   uint32_t fakeGpus = 0;        // TALC_FAKE_GPUS (the CLI): the sharder runs as on a node with this many GPUs (0: the real count)
   std::string profReads;        // TALC_PROF_READS (the profile build): a file of one row per read
@@ -50,6 +51,7 @@ inline Switches read_switches() {
   s.edgeTaskRounds = clamped("TALC_EDGE_TASK_ROUNDS", 0xFFFF, 0, 0xFFFF);
   s.edgeLingerMod = clamped("TALC_EDGE_LINGER_MOD", 16, 1, 1L << 20);
   s.edgeRedo = given("TALC_TEST_EDGE_REDO");
+  s.edgeLane = num("TALC_TEST_EDGE_LANE", 1) != 0;
   s.traceSteps = num("TALC_TRACE_STEPS", 0) != 0;
   s.fakeGpus = clamped("TALC_FAKE_GPUS", 0, 0, 1L << 20);
   if (const char* e = std::getenv("TALC_PROF_READS")) s.profReads = e;

@@ -712,11 +712,16 @@ __shared__ uint32_t g_wprof[4];   // staging, levels, selection of wave_xdrop_wf
 struct WfaKeep { uint32_t owner; int level; int qlenAt; int pad_; uint16_t F[64]; uint8_t E[64]; };
 __shared__ WfaKeep g_keep;
 
-template <int NR>
+// PRESTAGED (the edge lane, talc_kernels_search.h: edge_lane): the caller keeps both segments in the stage from one run to
+// the next — the query at stage[0 .. qlen) with its sentinel, the WHOLE database segment with its sentinel at
+// stage[qpadPre ..] — so nothing is copied and no global pointer is looked at.  More of the database than the dS bases
+// a run stages for itself changes nothing: database index dS = qlen + X is only ever compared with the query's
+// sentinel.  The caller has checked that the layout fits; qlen <= dlen there, so the query is staged whole (qS = qlen).
+template <int NR, bool PRESTAGED = false>
 TALC_D int wave_xdrop_wfa(const uint8_t* __restrict__ querySeg_, int qlen, const uint8_t* __restrict__ dbSeg_, int dlen, int x,
                           uint8_t TALC_AS3* stage, int stageCap, int& extCols, int& extRows, int& extScore,
-                          unsigned long long& cells, const WfaPhase* ph = nullptr, uint32_t keepKey_ = 0) {
-  gcu8 querySeg = (gcu8)uni_ptr(querySeg_); gcu8 dbSeg = (gcu8)uni_ptr(dbSeg_);
+                          unsigned long long& cells, const WfaPhase* ph = nullptr, uint32_t keepKey_ = 0, int qpadPre = 0) {
+  gcu8 querySeg = PRESTAGED ? nullptr : (gcu8)uni_ptr(querySeg_); gcu8 dbSeg = PRESTAGED ? nullptr : (gcu8)uni_ptr(dbSeg_);
   const int l = lane_id();
   qlen = uni(qlen); dlen = uni(dlen); x = uni(x);
   extCols = extRows = extScore = 0;
@@ -730,15 +735,15 @@ TALC_D int wave_xdrop_wfa(const uint8_t* __restrict__ querySeg_, int qlen, const
   if (nd > 64 * NR - 1) return -1;   // one always-empty lane closes the ring of the lane rotations
   // only cells with |col - row| <= x can be kept: stage that much of each segment, then a sentinel
   const int qS = min(qlen, dlen + X), dS = min(dlen, qlen + X);
-  const int qpad = (qS + 16) & ~7;
-  if (qpad + dS + 16 > stageCap) return -1;
+  const int qpad = PRESTAGED ? qpadPre : (qS + 16) & ~7;
+  if (!PRESTAGED && qpad + dS + 16 > stageCap) return -1;
   const unsigned long long _t0 = WPROF_T();
-  if (fromLevel < 0) {
+  if (!PRESTAGED && fromLevel < 0) {
     stage_copy(stage, querySeg, qS);
     stage_copy(stage + qpad, dbSeg, dS);
     if (l == 0) { stage[qS] = 0xF0; stage[qpad + dS] = 0xF1; }   // differ from each other and from every base code
   }
-  WSYNC();
+  if (PRESTAGED) LSYNC(); else WSYNC();
   WPROF_ADD(0, _t0);
   const unsigned long long _t1 = WPROF_T();
   const int bmax = x >= 2 ? x - 1 : (x == 1 ? 1 : 0);

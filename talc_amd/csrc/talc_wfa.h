@@ -30,16 +30,29 @@ namespace talc {
 
 struct WfaResult { int moved; int extCols; int extRows; int score; };
 
+// A kept wavefront (talc_wave.h: WfaKeep, and the edge lane's runs): run i + 1 of the same pair — the same database
+// segment, the query of run i longer at its end, any x — resumed from a level run i kept.  Level e depends on the
+// segments only up to the furthest points it reaches, on x only through the diagonals |k| = x, and on the query's
+// length only once a diagonal has followed the query to its end: the last level of a run BEFORE any diagonal met the
+// query's end, and below the run's x, is level e of every later run with a longer query and an x above e.  The device
+// keeps levels 1 .. 31 (its first phase, one diagonal per lane); so does this statement.
+// F, E by diagonal: index k + 32, |k| <= level.  level 0: nothing kept.
+struct WfaKept { int level; int qlenAt; int F[64]; int E[64]; };
+constexpr int kWfaMaxKeepLevel = 31;
+
 // q = query segment (columns), d = database segment (rows)
-inline WfaResult wfa_xdrop_scalar(const uint8_t* q, int qlen, const uint8_t* d, int dlen, int x) {
+// keep: nullptr, or the pair's kept wavefront (read: the run resumes from it if it may; written: what this run keeps);
+// resumed (optional): whether this run started from the kept level
+inline WfaResult wfa_xdrop_scalar_run(const uint8_t* q, int qlen, const uint8_t* d, int dlen, int x, WfaKept* keep, bool* resumed) {
   WfaResult res = {0, 0, 0, 0};
+  if (resumed) *resumed = false;
   if (qlen == 0 || dlen == 0) return res;
   const int NEG = -(1 << 29);
   const int bmax = x >= 2 ? x - 1 : (x == 1 ? 1 : 0);
   const int X = x < 0 ? 0 : x;
   const int kmin = -(X < dlen ? X : dlen), kmax = (X < qlen ? X : qlen);
   const int nd = kmax - kmin + 1;
-  std::vector<int> F(nd + 2, NEG), G(nd + 2, NEG), E(nd + 2, 0), amin(nd + 2), amax(nd + 2);
+  std::vector<int> F(nd + 2, NEG), G(nd + 2, NEG), E(nd + 2, 0), EG(nd + 2, 0), amin(nd + 2), amax(nd + 2);
   auto idx = [&](int k) { return k - kmin + 1; };
   for (int k = kmin; k <= kmax; ++k) {
     const int ak = k < 0 ? -k : k;
@@ -53,10 +66,35 @@ inline WfaResult wfa_xdrop_scalar(const uint8_t* q, int qlen, const uint8_t* d, 
     return c + r;
   };
   const int corner = qlen + dlen, kc = qlen - dlen;
-  F[idx(0)] = x >= 0 ? extend(0, 0) : 0;
-  bool cornerHit = (kc >= kmin && kc <= kmax && F[idx(kc)] == corner);
+  bool tracking = keep != nullptr;   // no diagonal has met the query's end yet, and nothing has been kept by this run
+  auto keep_level = [&](int level) {   // F / E are level `level`'s
+    if (level < 1 || level > kWfaMaxKeepLevel) return;
+    keep->level = level; keep->qlenAt = qlen;
+    for (int k = -level; k <= level; ++k) {
+      const bool in = k >= kmin && k <= kmax;
+      keep->F[k + 32] = in ? F[idx(k)] : NEG;
+      keep->E[k + 32] = in ? E[idx(k)] : 0;
+    }
+  };
+  int eStart = 1;
+  bool cornerHit = false;
+  const int lv = keep ? keep->level : 0;
+  if (keep && lv >= 1 && lv < x && lv <= kWfaMaxKeepLevel && lv < keep->qlenAt && keep->qlenAt <= qlen && lv < dlen) {
+    for (int k = -lv; k <= lv; ++k) { F[idx(k)] = keep->F[k + 32] >= 0 ? keep->F[k + 32] : NEG; E[idx(k)] = keep->E[k + 32]; }
+    eStart = lv + 1;
+    if (resumed) *resumed = true;
+  } else {
+    F[idx(0)] = x >= 0 ? extend(0, 0) : 0;
+    cornerHit = (kc >= kmin && kc <= kmax && F[idx(kc)] == corner);
+    if (tracking && F[idx(0)] == 2 * qlen) tracking = false;   // level 0 runs to the query's end: nothing to keep
+  }
   int cornerE = 0;
-  for (int e = 1; e <= x && !cornerHit; ++e) {
+  int eLast = eStart - 1;
+  for (int e = eStart; e <= x && !cornerHit; ++e) {
+    // level x is the one x itself shapes; the device's first phase ends after level kWfaMaxKeepLevel
+    if (tracking && (e == x || e == kWfaMaxKeepLevel + 1)) { keep_level(e - 1); tracking = false; }
+    bool meets = false;
+    EG = E;
     for (int k = kmin; k <= kmax; ++k) {
       const int i = idx(k);
       const int fm = F[i], fl = F[i - 1], fr = F[i + 1];
@@ -65,12 +103,16 @@ inline WfaResult wfa_xdrop_scalar(const uint8_t* q, int qlen, const uint8_t* d, 
       for (int t = 0; t < 3; ++t)
         if (v[t] >= amin[i] && v[t] <= amax[i] && v[t] > best) best = v[t];
       int nv = fm;
-      if (best > fm) { nv = extend(best, k); E[i] = e; }
+      if (best > fm) { nv = extend(best, k); EG[i] = e; meets |= (nv == 2 * qlen - k); }
       G[i] = nv;
     }
+    if (tracking && meets) { keep_level(e - 1); tracking = false; }   // this level meets the query's end: keep the one before
     F.swap(G);
+    E.swap(EG);
     if (kc >= kmin && kc <= kmax && F[idx(kc)] == corner) { cornerHit = true; cornerE = e; }
+    eLast = e;
   }
+  if (tracking && !cornerHit && eLast < x) keep_level(eLast);
   if (cornerHit) { res.moved = 1; res.extCols = qlen; res.extRows = dlen; res.score = -cornerE; return res; }
   // ---- where the original stops, and which cell it reports
   int A = 0;
@@ -129,6 +171,10 @@ inline WfaResult wfa_xdrop_scalar(const uint8_t* q, int qlen, const uint8_t* d, 
   if (A >= 2 && kept(A, c2 - 1)) { take(A, c2 - 1); return res; }
   firstMax(A - 1);
   return res;
+}
+
+inline WfaResult wfa_xdrop_scalar(const uint8_t* q, int qlen, const uint8_t* d, int dlen, int x) {
+  return wfa_xdrop_scalar_run(q, qlen, d, dlen, x, nullptr, nullptr);
 }
 
 }  // namespace talc
