@@ -176,6 +176,13 @@ int talc_table_next_counts_batch(talc_table* t, int device, const uint64_t* kmer
  * builder; works without a GPU, before talc_table_upload or after it). */
 int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uint64_t n, uint32_t* counts,
                                  uint32_t* jcounts);
+/* Test hook, not part of the reference surface: the walk table of one direction (0 = LEFT, 1 = RIGHT) of the copy on
+ * `device`, copied to the host as it stands: talc_table_capacity() records of 32 bytes in bucket order — a 64-bit key
+ * (all ones: unused slot) and twelve 16-bit levels, bits 0-12 the largest successor count (0x1FFF: does not fit), bit
+ * 13 "exactly one successor >= MIN_COUNT", bits 14-15 that successor's base.  `bytes` must be the table's size;
+ * TALC_ERR_STATE when the copy was uploaded without walk tables.  (The in-degree bits an upload writes into the top
+ * three bits of every RIGHT key need no hook: talc_table_export_device after the upload copies them.) */
+int talc_table_fetch_walk(talc_table* t, int device, int direction, void* dst, uint64_t bytes);
 void talc_table_destroy(talc_table* t);
 
 /* ---------------------------------------------------------------- (1b) k-mer counter ------
@@ -233,10 +240,32 @@ int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint
                               uint64_t* kmer_offsets, int32_t* n_in_kmers);
 uint64_t talc_batch_num_kmers(const talc_batch* b);
 uint64_t talc_batch_num_bases(const talc_batch* b);
+/* Test hook, not part of the reference surface: what the coverage kernel leaves beside the colour of every k-mer it
+ * found in the table, in the dense layout of talc_batch_fetch_coverage (one byte per k-mer position): bits 0-2 the
+ * k-mer's out-degree towards RIGHT, bits 3-5 towards LEFT (getOutDegree, Jellyfish.cpp:383-393, 0..4 each), bit 6 "the
+ * degrees are known"; 0 for a position whose k-mer is not in the table.  The structure kernel and the anchor search read
+ * these instead of probing. */
+int talc_batch_fetch_coverage_degrees(talc_ctx* c, talc_batch* b, uint8_t* degrees);
 
 /* The whole hot path on the device: coverage -> structure (defineStructure2) -> path search
  * (correct2) -> reassembly.  Synchronous: returns when the corrected records are in HBM. */
 int talc_batch_correct(talc_ctx* c, talc_batch* b);
+/* Test hooks, not part of the reference surface.  talc_batch_structure runs the hot path up to and including
+ * defineStructure2 (encode, coverage, the structure kernel: the very launches talc_batch_correct starts with) and stops:
+ * nothing of the path search runs, so the region lists are as the structure kernel left them (the search edits them in
+ * place).  talc_batch_fetch_structure then returns, per read: status (TALC_READ_CORRECTED = a structure was defined),
+ * n_regions, lambda (m_priorLambda_noise, Read.cpp:268-269, the double as it is), in_span (sum of end - start + 1 over
+ * the regions); region_offsets[n_reads + 1] and, for region i of the batch, regions[2 i], regions[2 i + 1] = start and
+ * end (k-mer positions) and region_hits[i] = the index of the start's pair among the read's hits (tile base + hits of
+ * the tile below it) with bit 31 set when every position of the region is a hit of one coverage tile; head_counts[16 r
+ * ..] = the counts of read r's first 16 k-mer positions (0 beyond its last; all 0 for reads that are too short or have
+ * no solid k-mer).  Every output may be NULL; region_capacity = room of regions / region_hits in regions
+ * (TALC_ERR_CAPACITY when too small: call once with both NULL to learn region_offsets[n_reads]).  Valid until the next
+ * talc_batch_correct on the batch. */
+int talc_batch_structure(talc_ctx* c, talc_batch* b);
+int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint32_t* n_regions, double* lambda,
+                               uint32_t* in_span, uint64_t* region_offsets, uint32_t* regions, uint32_t* region_hits,
+                               uint64_t region_capacity, uint32_t* head_counts);
 /* Total corrected size (bytes) so the caller can allocate; valid after talc_batch_correct. */
 uint64_t talc_batch_corrected_bytes(const talc_batch* b);
 /* out: corrected (or passed-through) sequences as upper-case ACGTN text, concatenated in input
@@ -288,7 +317,10 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
 
 /* Test hook: one wave-cooperative DP primitive on the device (mode 0: alignment score,
  * 1: seed-and-extend, 2: k-mer window search, 3: successor tagging); out: 12 ints; not part of the
- * reference surface. */
+ * reference surface.  Mode 3 tags by the count model's formula (p1 == 0: a = 4 counts, 4 colours and the count as nine
+ * little-endian 32-bit words, p0 = complex; out = 4 tags and 4 distances), or (p1 != 0) as the search does: through
+ * the context's threshold table for counts below 4096, the formula beyond; a = p2 such records (at least one), out =
+ * max(12, p2) ints, out[i] = the tags of record i in 4 bits each (tag & 15) | "the table was used" << 16. */
 int talc_test_dp(talc_ctx* c, int mode, const char* a, int la, const char* b, int lb, int p0, int p1, int p2, int p3,
                  int32_t* out);
 

@@ -159,6 +159,23 @@ int orc_coverage(void* t, const orc_params* p, const char* bases, uint64_t len, 
   return r.nbInKmers();
 }
 
+// getOutDegree (Jellyfish.cpp:383-393) of every k-mer position of a read, towards LEFT and towards RIGHT:
+// out[2 i] = LEFT, out[2 i + 1] = RIGHT for position i (len - K + 1 positions); 0 0 where the k-mer holds an N
+void orc_out_degrees(void* t, const orc_params* p, const char* bases, uint64_t len, uint8_t* out) {
+  Ctx C; C.P = toParams(p); C.dBG = (Table*)t;
+  const TSeq seq = toDna5(std::string(bases, len));
+  const unsigned K = C.P.K;
+  if (seq.size() < K) return;
+  const long n = (long)(seq.size() - K + 1);
+#pragma omp parallel for schedule(static) if (n > 4096)
+  for (long i = 0; i < n; ++i) {
+    const TSeq kmer(seq.begin() + i, seq.begin() + i + K);
+    const bool hasN = std::find(kmer.begin(), kmer.end(), 'N') != kmer.end();
+    out[2 * i] = hasN ? 0 : (uint8_t)getOutDegree(C, kmer, LEFT);
+    out[2 * i + 1] = hasN ? 0 : (uint8_t)getOutDegree(C, kmer, RIGHT);
+  }
+}
+
 // Read::defineStructure2 inspection: regions (start,end pairs) and the noise threshold
 int orc_structure(void* t, const orc_params* p, const char* bases, uint64_t len, uint32_t* regions,
                   uint32_t max_regions, double* thr, int32_t* ok) {

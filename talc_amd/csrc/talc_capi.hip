@@ -130,6 +130,7 @@ struct talc_batch {
   std::vector<uint64_t> h_outoff;
   uint64_t out_capacity = 0;
   bool encoded = false, covered = false, corrected = false;
+  bool structured = false;   // talc_batch_structure has run and no search has touched the region lists since
   std::vector<ReadState> h_state;
   std::vector<uint64_t> h_dense_off;
   uint64_t dense_cap = 0;
@@ -675,6 +676,20 @@ int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uin
   return TALC_OK;
 }
 
+// Test hook (not part of the reference surface): the walk table of one direction of the copy on `device`, as it is
+int talc_table_fetch_walk(talc_table* t, int device, int direction, void* dst, uint64_t bytes) {
+  if (!t || !dst) return fail(TALC_ERR_INVALID, "null argument");
+  auto it = t->h.dev.find(device);
+  if (it == t->h.dev.end()) return fail(TALC_ERR_STATE, "table not uploaded to device %d", device);
+  const WalkEntry* src = direction ? it->second.walkRight : it->second.walkLeft;
+  if (!src) return fail(TALC_ERR_STATE, "the copy on device %d has no walk tables", device);
+  const uint64_t need = t->h.capacity * sizeof(WalkEntry);
+  if (bytes != need) return fail(TALC_ERR_CAPACITY, "a walk table is %llu bytes, %llu given", (unsigned long long)need, (unsigned long long)bytes);
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+  return TALC_OK;
+}
+
 void talc_table_destroy(talc_table* t) { delete t; }
 
 // ------------------------------------------------------------------ context
@@ -822,38 +837,54 @@ int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
   return TALC_OK;
 }
 
+// the dense vector<colouredCount> of Read.cpp:174-195 exists only here: the device keeps the hits and a bitmap
+// (talc_common.h: CovWord).  counts / jcounts / degrees: one entry per k-mer position, any of them may be null
+static int expand_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint32_t* jcounts, uint8_t* degrees) {
+  if (!b->n_kmers || !(counts || jcounts || degrees)) return TALC_OK;
+  // hipMemcpy on the null stream would not be ordered with the context's stream
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const uint64_t nw = cov_words_total(b->n_kmers, b->n_reads);
+  std::vector<uint2> h(b->n_kmers);
+  std::vector<CovWord> w(nw);
+  HIPCHK(hipMemcpy(h.data(), b->d_cov.get(), b->n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(w.data(), b->d_covw.get(), nw * sizeof(CovWord), hipMemcpyDeviceToHost));
+  for (uint32_t r = 0; r < b->n_reads; ++r) {
+    const uint64_t k0 = b->h_koff[r], nk = b->h_koff[r + 1] - k0;
+    const CovWord* rw = w.data() + cov_word_base(k0, r);
+    for (uint64_t p = 0; p < nk; ++p) {
+      const CovWord& cw = rw[p >> 6];
+      uint32_t cx = 0, cy = 0;
+      if ((cw.bits >> (p & 63)) & 1ull) {
+        const uint64_t idx = (p & ~(uint64_t)(TALC_COV_TILE - 1)) + cw.rank + (uint64_t)__builtin_popcountll(cw.bits & ((1ull << (p & 63)) - 1ull));
+        cx = h[k0 + idx].x; cy = h[k0 + idx].y;
+      }
+      if (counts) counts[k0 + p] = cx;
+      if (jcounts) jcounts[k0 + p] = cy & kCovColourMask;
+      if (degrees) degrees[k0 + p] = (uint8_t)((cy >> kCovDegRShift) & 0x7Fu);   // right degree, left degree, known flag
+    }
+  }
+  return TALC_OK;
+}
+
 int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint32_t* jcounts, uint64_t* kmer_offsets,
                               int32_t* n_in_kmers) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   if (!b->covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
   HIPCHK(hipSetDevice(c->device));
-  if (b->n_kmers && (counts || jcounts)) {
-    // the dense vector<colouredCount> of Read.cpp:174-195 exists only here: the device keeps the hits and a bitmap
-    // (talc_common.h: CovWord); hipMemcpy on the null stream would not be ordered with the context's stream
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint64_t nw = cov_words_total(b->n_kmers, b->n_reads);
-    std::vector<uint2> h(b->n_kmers);
-    std::vector<CovWord> w(nw);
-    HIPCHK(hipMemcpy(h.data(), b->d_cov.get(), b->n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(w.data(), b->d_covw.get(), nw * sizeof(CovWord), hipMemcpyDeviceToHost));
-    for (uint32_t r = 0; r < b->n_reads; ++r) {
-      const uint64_t k0 = b->h_koff[r], nk = b->h_koff[r + 1] - k0;
-      const CovWord* rw = w.data() + cov_word_base(k0, r);
-      for (uint64_t p = 0; p < nk; ++p) {
-        const CovWord& cw = rw[p >> 6];
-        uint32_t cx = 0, cy = 0;
-        if ((cw.bits >> (p & 63)) & 1ull) {
-          const uint64_t idx = (p & ~(uint64_t)(TALC_COV_TILE - 1)) + cw.rank + (uint64_t)__builtin_popcountll(cw.bits & ((1ull << (p & 63)) - 1ull));
-          cx = h[k0 + idx].x; cy = h[k0 + idx].y;
-        }
-        if (counts) counts[k0 + p] = cx;
-        if (jcounts) jcounts[k0 + p] = cy & kCovColourMask;
-      }
-    }
-  }
+  int rc;
+  if ((rc = expand_coverage(c, b, counts, jcounts, nullptr))) return rc;
   if (kmer_offsets) memcpy(kmer_offsets, b->h_koff.data(), (b->n_reads + 1) * 8);
   if (n_in_kmers && b->n_reads) HIPCHK(hipMemcpy(n_in_kmers, b->d_nin.get(), b->n_reads * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
+}
+
+// Test hook (not part of the reference surface): the degree bits k_coverage leaves beside every hit's colour
+static_assert(kCovDegLShift == kCovDegRShift + 3 && kCovDegKnown == (1u << (kCovDegRShift + 6)), "the degree byte of talc_batch_fetch_coverage_degrees");
+int talc_batch_fetch_coverage_degrees(talc_ctx* c, talc_batch* b, uint8_t* degrees) {
+  if (!c || !b || b->ctx != c || !degrees) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
+  if (!b->covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
+  HIPCHK(hipSetDevice(c->device));
+  return expand_coverage(c, b, nullptr, nullptr, degrees);
 }
 
 // ------------------------------------------------------------------ k-mer counter (talc_kernels_count.h)

@@ -120,12 +120,11 @@ static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
 }
 #endif
 
-static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
-  HIPCHK(hipSetDevice(c->device));
+// encode -> coverage -> k_structure on the context's stream, events 0 .. 3 around them: what run_pipeline and the test hook
+// talc_batch_structure share (the hook stops here, so the region lists are still as k_structure left them)
+static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
   int rc;
-  TraceBuf tb = {};
-  if (th) { tb.recs = th->d_recs.get(); tb.nrec = th->d_nrec.get(); tb.cap = th->cap; tb.pool = th->d_pool.get(); tb.npool = th->d_npool.get(); tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   HIPCHK(hipEventRecord(c->ev[0], s));
@@ -139,6 +138,17 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
                        b->d_cov.get(), b->d_covw.get(), b->d_nin.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->n_reads, tb, traceRead, c->d_hist.get() + 1024);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[3], s));
+  return TALC_OK;
+}
+
+static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  int rc;
+  TraceBuf tb = {};
+  if (th) { tb.recs = th->d_recs.get(); tb.nrec = th->d_nrec.get(); tb.cap = th->cap; tb.pool = th->d_pool.get(); tb.npool = th->d_npool.get(); tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
+  b->structured = false;   // (k_search edits the region lists in place)
+  if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
   // ---- the work queue: heaviest reads first, by k_structure's estimate
   if (b->n_reads) {
     HIPCHK(hipMemsetAsync(c->d_hist.get(), 0, 1024 * sizeof(uint32_t), s));
@@ -263,6 +273,65 @@ int talc_batch_correct(talc_ctx* c, talc_batch* b) {
   return run_pipeline(c, b, nullptr, 0xFFFFFFFFu);
 }
 
+// Test hook (not part of the reference surface): the pipeline up to and including k_structure, nothing of the search.
+int talc_batch_structure(talc_ctx* c, talc_batch* b) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  b->structured = false; b->corrected = false;
+  if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
+  b->h_state.resize(b->n_reads);
+  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]));
+  HIPCHK(hipEventElapsedTime(&c->timing.coverage_ms, c->ev[1], c->ev[2]));
+  HIPCHK(hipEventElapsedTime(&c->timing.structure_ms, c->ev[2], c->ev[3]));
+  b->structured = true;
+  return TALC_OK;
+}
+
+// Test hook: what k_structure left for every read of the batch (see include/talc_hip.h)
+int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint32_t* n_regions, double* lambda, uint32_t* in_span,
+                               uint64_t* region_offsets, uint32_t* regions, uint32_t* region_hits, uint64_t region_capacity,
+                               uint32_t* head_counts) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (!b->structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < b->n_reads; ++r) {
+    const ReadState& st = b->h_state[r];
+    if (status) status[r] = st.overflow ? TALC_READ_ERROR : st.status;
+    if (n_regions) n_regions[r] = st.nRegions;
+    if (lambda) lambda[r] = st.lambda;
+    if (in_span) in_span[r] = st.inSpan;
+    if (region_offsets) region_offsets[r] = total;
+    total += st.nRegions;
+  }
+  if (region_offsets) region_offsets[b->n_reads] = total;
+  if ((regions || region_hits) && total) {
+    if (region_capacity < total) return fail(TALC_ERR_CAPACITY, "region buffers too small: need %llu regions", (unsigned long long)total);
+    // a read's slot: regCap starts, regCap ends, regCap hit words (k_structure)
+    std::vector<uint32_t> h(3 * (size_t)b->h_regoff[b->n_reads]);
+    HIPCHK(hipMemcpy(h.data(), b->d_regions.get(), h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < b->n_reads; ++r) {
+      const uint64_t cap = b->h_regoff[r + 1] - b->h_regoff[r];
+      const uint32_t* rs = h.data() + 3 * b->h_regoff[r];
+      for (uint32_t i = 0; i < b->h_state[r].nRegions && i < cap; ++i, ++at) {
+        if (regions) { regions[2 * at] = rs[i]; regions[2 * at + 1] = rs[cap + i]; }
+        if (region_hits) region_hits[at] = rs[2 * cap + i];
+      }
+    }
+  }
+  if (head_counts && b->n_reads) {   // (k_structure leaves the reads it does not analyse without head counts: 0 here)
+    HIPCHK(hipMemcpy(head_counts, b->d_headcov.get(), (size_t)b->n_reads * kHeadCov * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < b->n_reads; ++r)
+      if (b->h_state[r].status == TALC_READ_SKIPPED_SHORT || b->h_state[r].status == TALC_READ_NO_SOLID_KMER)
+        memset(head_counts + (size_t)r * kHeadCov, 0, kHeadCov * sizeof(uint32_t));
+  }
+  return TALC_OK;
+}
+
 uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->corrected) ? b->h_dense_off[b->n_reads] : 0; }
 
 int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
@@ -381,10 +450,13 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
 }
 
 // Test hook (not part of the reference surface): run one wave-cooperative DP primitive on the
-// device.  a, b: Dna5 codes given as ASCII; see k_test_dp for the modes.  out: 6 ints.
+// device.  a, b: Dna5 codes given as ASCII; see k_test_dp for the modes.  out: 12 ints (mode 3 with p1 set: max(12, p2)).
 int talc_test_dp(talc_ctx* c, int mode, const char* a, int la, const char* b, int lb, int p0, int p1, int p2, int p3,
                  int32_t* out) {
   if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
+  const bool tagTable = mode == 3 && p1 != 0;   // one word per record, p2 records
+  if (tagTable && (p2 < 0 || (long long)la < 36ll * std::max(p2, 1))) return fail(TALC_ERR_INVALID, "mode 3: %d records need %lld bytes", p2, 36ll * std::max(p2, 1));
+  const size_t nout = tagTable ? (size_t)std::max(p2, 12) : 12;
   HIPCHK(hipSetDevice(c->device));
   std::vector<uint8_t> ha(std::max(la, 1)), hb(std::max(lb, 1));
   for (int i = 0; i < la; ++i) ha[i] = (mode == 3) ? (uint8_t)a[i] : ascii_to_code((uint8_t)a[i]);
@@ -392,14 +464,14 @@ int talc_test_dp(talc_ctx* c, int mode, const char* a, int la, const char* b, in
   DevBuf<uint8_t> da, db; DevBuf<int> ddp, dout;
   const uint32_t dpCap = (uint32_t)std::max(std::max(la, lb), 2048) + 16;   // (>= 2048: the phased x-drop keeps its hand-over state there)
   HIPCHK(da.alloc(ha.size())); HIPCHK(db.alloc(hb.size()));
-  HIPCHK(ddp.alloc(3ull * dpCap + ROW_MAX_REF + 16)); HIPCHK(dout.alloc(16));   // (+ mode 7's kept row)
+  HIPCHK(ddp.alloc(3ull * dpCap + ROW_MAX_REF + 16)); HIPCHK(dout.alloc(nout + 4));   // (+ mode 7's kept row)
   HIPCHK(hipMemcpy(da.get(), ha.data(), ha.size(), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(db.get(), hb.data(), hb.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(dout.get(), 0, 64, c->stream));   // same stream as the kernel: the null stream is not ordered with it
+  HIPCHK(hipMemsetAsync(dout.get(), 0, (nout + 4) * 4, c->stream));   // same stream as the kernel: the null stream is not ordered with it
   hipLaunchKernelGGL(k_test_dp, dim3(1), dim3(64), 0, c->stream, mode, da.get(), la, db.get(), lb, p0, p1, p2, p3, (int)c->p.k, ddp.get(), dpCap, dout.get(),
-                     c->p.alpha, c->p.sr_error_rate, (int)c->p.min_count);
+                     c->p.alpha, c->p.sr_error_rate, (int)c->p.min_count, c->dp.thr, c->dp.thrN);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out, dout.get(), 12 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, dout.get(), nout * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }

@@ -4282,9 +4282,10 @@ __global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __res
 // mode 2: wave_find_window(a, pattern=b, wantLast=p3)              -> out[0]
 // mode 5: seed_and_extension_multi(a, b, xHi = p0) against seed_and_extension(x) for every x  -> out[0..2]
 // mode 4: edit_and_lcs(a, b, needEdit = !p0, acceptLcs = p1 if p0 == 2) -> out[0] = edit score (0 if not asked), out[1] = LCS
+// mode 3: tag_next_nodes, by the formula (p1 == 0) or through the threshold table (p1 != 0, p2 records): see below
 __global__ void __launch_bounds__(64, TALC_SEARCH_WAVES_PER_SIMD)   // (same register budget as k_search: they share the step functions)
 k_test_dp(int mode, const uint8_t* a, int la, const uint8_t* b, int lb, int p0, int p1, int p2, int p3, int K,
-          int* dpG, uint32_t dpCap, int* out, double alpha, double err, int minc) {
+          int* dpG, uint32_t dpCap, int* out, double alpha, double err, int minc, const uint32_t* thr, uint32_t thrN) {
   if (lane_id() == 0) memset(&g_X, 0, sizeof g_X);
   WSYNC();
   X.P.K = (uint32_t)K; X.P.ALPHA = alpha; X.P.ERR = err; X.P.MIN_COUNT = (uint32_t)minc;
@@ -4387,11 +4388,31 @@ k_test_dp(int mode, const uint8_t* a, int la, const uint8_t* b, int lb, int p0, 
   } else {
     // mode 3: tag_next_nodes on the device.  a = 4 counts + 4 colours + count as 9 little-endian u32 (36 bytes),
     // p0 = complex; out[0..3] = tags, out[4..11] = the 4 distances as raw bits
-    uint32_t w[9];
-    for (int i = 0; i < 9; ++i) w[i] = (uint32_t)a[4 * i] | ((uint32_t)a[4 * i + 1] << 8) | ((uint32_t)a[4 * i + 2] << 16) | ((uint32_t)a[4 * i + 3] << 24);
-    int tg[4]; double ds[4];
-    tag_next_nodes(X.P.ALPHA, X.P.ERR, X.P.MIN_COUNT, w, w + 4, w[8], p0 != 0, tg, ds);
-    if (lane_id() == 0) for (int i = 0; i < 4; ++i) { out[i] = tg[i]; long long bits = __double_as_longlong(ds[i]); out[4 + 2 * i] = (int)(bits & 0xffffffffll); out[5 + 2 * i] = (int)(bits >> 32); }
+    // p1 != 0: the form the search uses (probe_and_tag): through the count model's threshold table where the count and its
+    // lambda_noise are below thrN, the formula beyond.  a = max(p2, 1) such records, one per lane and pass; out[i] = the four
+    // tags of record i (4 bits each, tag & 15) | (the table was used) << 16; no distances
+    X.P.thr = thr; X.P.thrN = thrN;
+    WSYNC();
+    if (p1 != 0) {
+      const int nrec = max(p2, 1);
+      for (int i = lane_id(); i < nrec; i += 64) {
+        const uint8_t* ra = a + 36 * (size_t)i;
+        uint32_t w[9];
+        for (int q = 0; q < 9; ++q) w[q] = (uint32_t)ra[4 * q] | ((uint32_t)ra[4 * q + 1] << 8) | ((uint32_t)ra[4 * q + 2] << 16) | ((uint32_t)ra[4 * q + 3] << 24);
+        int tg[4]; double ds[4];
+        bool inTable;
+        const ModelThresholds mt = model_thresholds(w[8], inTable);
+        if (inTable) tag_next_nodes_with(mt, X.P.ERR, X.P.MIN_COUNT, w, w + 4, w[8], p0 != 0, tg, (double*)nullptr);
+        else tag_next_nodes(X.P.ALPHA, X.P.ERR, X.P.MIN_COUNT, w, w + 4, w[8], p0 != 0, tg, ds);
+        out[i] = (tg[0] & 15) | ((tg[1] & 15) << 4) | ((tg[2] & 15) << 8) | ((tg[3] & 15) << 12) | (inTable ? (1 << 16) : 0);
+      }
+    } else {
+      uint32_t w[9];
+      for (int i = 0; i < 9; ++i) w[i] = (uint32_t)a[4 * i] | ((uint32_t)a[4 * i + 1] << 8) | ((uint32_t)a[4 * i + 2] << 16) | ((uint32_t)a[4 * i + 3] << 24);
+      int tg[4]; double ds[4];
+      tag_next_nodes(X.P.ALPHA, X.P.ERR, X.P.MIN_COUNT, w, w + 4, w[8], p0 != 0, tg, ds);
+      if (lane_id() == 0) for (int i = 0; i < 4; ++i) { out[i] = tg[i]; long long bits = __double_as_longlong(ds[i]); out[4 + 2 * i] = (int)(bits & 0xffffffffll); out[5 + 2 * i] = (int)(bits >> 32); }
+    }
   }
 }
 

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "talc_batch_correct", "talc_batch_corrected_bytes", "talc_batch_fetch_corrected", "talc_batch_fetch_read_stats",
     "talc_batch_copy_corrected_device", "talc_correct_batch",
     "talc_ctx_get_timing", "talc_batch_trace_read", "talc_test_dp",
+    "talc_table_fetch_walk", "talc_batch_fetch_coverage_degrees", "talc_batch_structure", "talc_batch_fetch_structure",
     "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
     "talc_counter_destroy",
 ]
@@ -125,6 +126,7 @@ def lib():
         L.talc_table_lookup_batch.argtypes = [vp, i32, vp, u64, vp, vp]
         L.talc_table_next_counts_batch.argtypes = [vp, i32, vp, u64, i32, vp, vp]
         L.talc_table_lookup_host_batch.argtypes = [vp, vp, u64, vp, vp]
+        L.talc_table_fetch_walk.argtypes = [vp, i32, i32, vp, u64]
         L.talc_table_destroy.argtypes = [vp]
         L.talc_ctx_create.argtypes = [vp, C.POINTER(Params), i32, C.POINTER(vp)]
         L.talc_ctx_destroy.argtypes = [vp]
@@ -132,6 +134,9 @@ def lib():
         L.talc_batch_destroy.argtypes = [vp]
         L.talc_batch_coverage.argtypes = [vp, vp]
         L.talc_batch_fetch_coverage.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.talc_batch_fetch_coverage_degrees.argtypes = [vp, vp, vp]
+        L.talc_batch_structure.argtypes = [vp, vp]
+        L.talc_batch_fetch_structure.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
         L.talc_batch_num_kmers.restype = u64
         L.talc_batch_num_kmers.argtypes = [vp]
         L.talc_batch_num_bases.restype = u64
@@ -297,6 +302,15 @@ class Table:
         _chk(lib().talc_table_next_counts_batch(self._h, device, kmers.ctypes.data, len(kmers), int(direction), c.ctypes.data, j.ctypes.data))
         return c, j
 
+    WALK_DTYPE = np.dtype([("key", "<u8"), ("lvl", "<u2", (12,))])
+
+    def fetch_walk(self, direction, device=0):
+        """Test hook: the walk table of one direction (0 LEFT, 1 RIGHT) of the copy on `device`, one WALK_DTYPE record
+        per bucket; TalcError when that copy has no walk tables."""
+        w = np.empty(self.capacity, dtype=self.WALK_DTYPE)
+        _chk(lib().talc_table_fetch_walk(self._h, int(device), int(direction), w.ctypes.data, w.nbytes))
+        return w
+
     def close(self):
         if self._h:
             lib().talc_table_destroy(self._h)
@@ -382,7 +396,7 @@ class Context:
         return Batch(self, bases, offsets)
 
     def test_dp(self, mode, a, b, p0=0, p1=0, p2=0, p3=0):
-        out = np.zeros(12, dtype=np.int32)
+        out = np.zeros(max(12, p2) if (mode == 3 and p1) else 12, dtype=np.int32)   # (mode 3's table form: one word per record)
         a = a if isinstance(a, bytes) else a.encode()
         b = b if isinstance(b, bytes) else b.encode()
         _chk(lib().talc_test_dp(self._h, mode, a, len(a), b, len(b), p0, p1, p2, p3, out.ctypes.data))
@@ -440,6 +454,35 @@ class Batch:
         nin = np.empty(self.n_reads, dtype=np.int32)
         _chk(lib().talc_batch_fetch_coverage(self.ctx._h, self._h, c.ctypes.data, j.ctypes.data, ko.ctypes.data, nin.ctypes.data))
         return c, j, ko, nin
+
+    def fetch_coverage_degrees(self):
+        """Test hook: uint8 per k-mer position (layout of fetch_coverage): right degree | left degree << 3 | known << 6."""
+        d = np.zeros(max(self.n_kmers, 1), dtype=np.uint8)
+        _chk(lib().talc_batch_fetch_coverage_degrees(self.ctx._h, self._h, d.ctypes.data))
+        return d[: self.n_kmers]
+
+    def structure(self):
+        """Test hook: encode, coverage and the structure kernel; nothing of the search."""
+        _chk(lib().talc_batch_structure(self.ctx._h, self._h))
+
+    def fetch_structure(self):
+        """Test hook, after structure(): dict of status i32[n], n_regions u32[n], lambda f64[n], in_span u32[n],
+        region_offsets u64[n+1], regions u32[R, 2] (start, end), region_hits u32[R], head_counts u32[n, 16]."""
+        n = self.n_reads
+        out = dict(status=np.zeros(n, np.int32), n_regions=np.zeros(n, np.uint32), lam=np.zeros(n, np.float64),
+                   in_span=np.zeros(n, np.uint32), region_offsets=np.zeros(n + 1, np.uint64),
+                   head_counts=np.zeros((n, 16), np.uint32))
+        L, h = lib(), self._h
+        _chk(L.talc_batch_fetch_structure(self.ctx._h, h, out["status"].ctypes.data, out["n_regions"].ctypes.data, out["lam"].ctypes.data,
+                                          out["in_span"].ctypes.data, out["region_offsets"].ctypes.data, None, None, 0,
+                                          out["head_counts"].ctypes.data))
+        R = int(out["region_offsets"][n])
+        out["regions"] = np.zeros((R, 2), np.uint32)
+        out["region_hits"] = np.zeros(R, np.uint32)
+        if R:
+            _chk(L.talc_batch_fetch_structure(self.ctx._h, h, None, None, None, None, None, out["regions"].ctypes.data,
+                                              out["region_hits"].ctypes.data, R, None))
+        return out
 
     def correct(self):
         """0, or WARN_READ_ERRORS when some reads exhausted the device scratch (status READ_ERROR, passed through)."""

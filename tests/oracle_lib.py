@@ -57,6 +57,7 @@ def lib():
         L.orc_table_lookup_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_next_counts.argtypes = [C.c_void_p, C.POINTER(OrcParams), C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_coverage.argtypes = [C.c_void_p, C.POINTER(OrcParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.orc_out_degrees.argtypes = [C.c_void_p, C.POINTER(OrcParams), C.c_void_p, C.c_uint64, C.c_void_p]
         L.orc_structure.argtypes = [C.c_void_p, C.POINTER(OrcParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                     C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.orc_correct_batch.argtypes = [C.c_void_p, C.POINTER(OrcParams), C.c_void_p, C.c_void_p, C.c_uint32,
@@ -154,6 +155,15 @@ class OracleTable:
         j = np.zeros(n, dtype=np.uint32)
         nin = lib().orc_coverage(self._h, C.byref(self.p), b.ctypes.data, len(b), c.ctypes.data, j.ctypes.data)
         return c, j, nin
+
+    def out_degrees(self, seq):
+        """getOutDegree of every k-mer position: (towards LEFT u8[n], towards RIGHT u8[n]); 0 where the k-mer holds an N."""
+        b = np.frombuffer(seq.encode() if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
+        n = max(0, len(b) - self.p.k + 1)
+        d = np.zeros((n, 2), dtype=np.uint8)
+        if n:
+            lib().orc_out_degrees(self._h, C.byref(self.p), b.ctypes.data, len(b), d.ctypes.data)
+        return d[:, 0].copy(), d[:, 1].copy()
 
     def structure(self, seq, max_regions=100000):
         b = np.frombuffer(seq.encode() if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
