@@ -108,8 +108,8 @@ struct talc_ctx {
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
-  DevBuf<uint32_t> d_hist;       // 1024 buckets of the work-queue ordering
-  DevBuf<uint64_t> d_counters;   // [0]=trail steps [1]=dp cells
+  DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
+  DevBuf<uint64_t> d_counters;   // kCounterWords: trail steps, dp cells, the profile build's counters and wave log
   DevBuf<uint32_t> d_thr;        // the count model's thresholds by count (DevParams.thr)
   DevCache cache;       // the device buffers of this context's batches
   ~talc_ctx() {
@@ -720,8 +720,8 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
   HIPCHK(c->d_queue.alloc(kQueueWords));
-  HIPCHK(c->d_hist.alloc(1024 + 256));   // (+ the batch's fork statistics, k_order_scale)
-  HIPCHK(c->d_counters.alloc(128 + 2 * 8192));   // 128 counters + the profile build's record of every wave's last read
+  HIPCHK(c->d_hist.alloc(kHistWords));
+  HIPCHK(c->d_counters.alloc(kCounterWords));
   {   // isExpectedbyMyModel as two thresholds per count (Explorer.cpp:1185-1201), from the formula itself, for this ALPHA
     const uint32_t n = 4096;
     HIPCHK(c->d_thr.alloc(2ull * n));
@@ -821,6 +821,24 @@ static int launch_coverage(talc_ctx* c, talc_batch* b) {
   return TALC_OK;
 }
 
+// the status a caller sees: a read whose scratch ran out is passed through unchanged
+static int32_t read_status(const ReadState& st) { return st.overflow ? TALC_READ_ERROR : st.status; }
+
+// the stage times into c->timing, from the events around the stages.  `last`: the last event recorded and waited for —
+// 2 (coverage), 3 (structure) or 7 (the whole correction; between events 4 and 5 the host looks at the first pass)
+static int read_stage_times(talc_ctx* c, int last) {
+  talc_timing& t = c->timing;
+  HIPCHK(hipEventElapsedTime(&t.encode_ms, c->ev[0], c->ev[1]));
+  HIPCHK(hipEventElapsedTime(&t.coverage_ms, c->ev[1], c->ev[2]));
+  if (last >= 3) HIPCHK(hipEventElapsedTime(&t.structure_ms, c->ev[2], c->ev[3]));
+  if (last >= 7) {
+    HIPCHK(hipEventElapsedTime(&t.search_ms, c->ev[3], c->ev[4]));
+    HIPCHK(hipEventElapsedTime(&t.retry_ms, c->ev[5], c->ev[6]));
+    HIPCHK(hipEventElapsedTime(&t.emit_ms, c->ev[6], c->ev[7]));
+  }
+  return TALC_OK;
+}
+
 int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   HIPCHK(hipSetDevice(c->device));
@@ -831,8 +849,7 @@ int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[2], c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]));
-  HIPCHK(hipEventElapsedTime(&c->timing.coverage_ms, c->ev[1], c->ev[2]));
+  if ((rc = read_stage_times(c, 2))) return rc;
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   return TALC_OK;
 }

@@ -73,7 +73,7 @@ struct TraceHost {
 };
 
 #ifdef TALC_PROF
-// the profile build's report of a corrected batch (TALC_PROF_READS / _PRINT / _SLOW); `counters`: c->d_counters[0 .. 127]
+// the profile build's report of a corrected batch (TALC_PROF_READS / _PRINT / _SLOW); `counters`: the words of c->d_counters below the wave log
 static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
   if (!c->sw.profReads.empty()) {   // one row per read (its last pass): the cost estimate, its inputs, the search's duration
     if (FILE* f = fopen(c->sw.profReads.c_str(), "w")) {
@@ -88,29 +88,29 @@ static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
   }
   if (!c->sw.profPrint) return TALC_OK;
   static const char* nm[] = TALC_PF_NAMES;   // starred entries are totals that contain other entries
-  const uint64_t tot = counters[2 + PF_TOTAL];
-  for (int i = 0; i < PF_N; ++i) fprintf(stderr, "[prof] %-10s %14llu cycles  %5.1f%%\n", nm[i], (unsigned long long)counters[2 + i], tot ? 100.0 * counters[2 + i] / tot : 0.0);
-  if (counters[127] > counters[126] && c->stage.n_slots)
+  const uint64_t* const cat = counters + kCntProf0;
+  const uint64_t tot = cat[PF_TOTAL], t0 = counters[kCntFirstStart], t1 = counters[kCntLastEnd];
+  for (int i = 0; i < PF_N; ++i) fprintf(stderr, "[prof] %-10s %14llu cycles  %5.1f%%\n", nm[i], (unsigned long long)cat[i], tot ? 100.0 * cat[i] / tot : 0.0);
+  if (t1 > t0 && c->stage.n_slots)
     fprintf(stderr, "[prof] wave utilisation: %.1f%% of %u waves x %.3f ms (first start to last end, 100 MHz counter)\n",
-            100.0 * (double)counters[125] / ((double)(counters[127] - counters[126]) * c->stage.n_slots), c->stage.n_slots,
-            (double)(counters[127] - counters[126]) / 1e5);
-  if (counters[124] != ~0ull && counters[124] > counters[126])
-    fprintf(stderr, "[prof] the work queue ran dry %.3f ms after the first wave's start\n", (double)(counters[124] - counters[126]) / 1e5);
+            100.0 * (double)counters[kCntBusy] / ((double)(t1 - t0) * c->stage.n_slots), c->stage.n_slots, (double)(t1 - t0) / 1e5);
+  if (counters[kCntQueueDry] != ~0ull && counters[kCntQueueDry] > t0)
+    fprintf(stderr, "[prof] the work queue ran dry %.3f ms after the first wave's start\n", (double)(counters[kCntQueueDry] - t0) / 1e5);
   if (c->sw.profSlow && c->stage.n_slots) {   // the record of every wave's last read: the waves that end last
-    const uint32_t nw = std::min<uint32_t>(c->stage.n_slots, 8192);
+    const uint32_t nw = std::min<uint32_t>(c->stage.n_slots, kCntMaxWaves);
     std::vector<uint64_t> lg(2 * (size_t)nw);
-    HIPCHK(hipMemcpy(lg.data(), c->d_counters.get() + 128, lg.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lg.data(), c->d_counters.get() + kCntWaveLog, lg.size() * 8, hipMemcpyDeviceToHost));
     std::vector<uint32_t> idx(nw);
     for (uint32_t i = 0; i < nw; ++i) idx[i] = i;
-    const uint32_t t0 = (uint32_t)counters[126];
-    auto endOf = [&](uint32_t w) { return (uint32_t)((uint32_t)lg[2 * w + 1] - t0); };
+    const uint32_t t0w = (uint32_t)t0;   // (the log keeps the low words)
+    auto endOf = [&](uint32_t w) { return (uint32_t)((uint32_t)lg[2 * w + 1] - t0w); };
     std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b2) { return endOf(a) > endOf(b2); });
     fprintf(stderr, "[slow] wave end times (ms), deciles from the last:");
     for (int d = 0; d <= 10; ++d) fprintf(stderr, " %.1f", endOf(idx[std::min<uint32_t>(nw - 1, (uint32_t)((uint64_t)d * nw / 10))]) / 1e5);
     fprintf(stderr, "\n");
     for (uint32_t i = 0; i < std::min<uint32_t>(nw, 24); ++i) {
       const uint32_t w = idx[i];
-      const uint32_t qi = (uint32_t)(lg[2 * w] >> 32), r = (uint32_t)lg[2 * w], st = (uint32_t)(lg[2 * w + 1] >> 32) - t0;
+      const uint32_t qi = (uint32_t)(lg[2 * w] >> 32), r = (uint32_t)lg[2 * w], st = (uint32_t)(lg[2 * w + 1] >> 32) - t0w;
       const uint64_t L = (b->h_offsets.empty() || r >= b->n_reads) ? 0 : b->h_offsets[r + 1] - b->h_offsets[r];
       fprintf(stderr, "[slow] wave %5u ends %8.3f ms: last read %7u (queue %7u, len %6llu) started %8.3f ms\n", w, endOf(w) / 1e5, r, qi,
               (unsigned long long)L, st / 1e5);
@@ -119,6 +119,22 @@ static int prof_report(talc_ctx* c, talc_batch* b, const uint64_t* counters) {
   return TALC_OK;
 }
 #endif
+
+static uint32_t* batch_stats(talc_ctx* c) { return c->d_hist.get() + kBatchStatsOff; }
+
+// the reads' states as the device has them now, into b->h_state (waits for the stream)
+static int fetch_states(talc_ctx* c, talc_batch* b) {
+  b->h_state.resize(b->n_reads);
+  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TALC_OK;
+}
+
+static TraceBuf trace_buf(const talc_ctx* c, const TraceHost* th) {
+  TraceBuf tb = {};
+  if (th) { tb.recs = th->d_recs.get(); tb.nrec = th->d_nrec.get(); tb.cap = th->cap; tb.pool = th->d_pool.get(); tb.npool = th->d_npool.get(); tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
+  return tb;
+}
 
 // encode -> coverage -> k_structure on the context's stream, events 0 .. 3 around them: what run_pipeline and the test hook
 // talc_batch_structure share (the hook stops here, so the region lists are still as k_structure left them)
@@ -132,63 +148,76 @@ static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint
   HIPCHK(hipEventRecord(c->ev[1], s));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[2], s));
-  HIPCHK(hipMemsetAsync(c->d_hist.get() + 1024, 0, 256 * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(batch_stats(c), 0, kBatchStatsWords * sizeof(uint32_t), s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_structure, dim3(b->n_reads), dim3(64), 0, s, c->dp, c->view, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
-                       b->d_cov.get(), b->d_covw.get(), b->d_nin.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->n_reads, tb, traceRead, c->d_hist.get() + 1024);
+                       b->d_cov.get(), b->d_covw.get(), b->d_nin.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->n_reads, tb, traceRead, batch_stats(c));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[3], s));
   return TALC_OK;
 }
 
-static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
-  HIPCHK(hipSetDevice(c->device));
+// the work queue (b->d_order): heaviest reads first, by k_structure's estimate
+static int order_queue(talc_ctx* c, talc_batch* b) {
+  if (!b->n_reads) return TALC_OK;
+  hipStream_t s = c->stream;
+  uint32_t* const hist = c->d_hist.get();
+  HIPCHK(hipMemsetAsync(hist, 0, kOrderBuckets * sizeof(uint32_t), s));
+  const unsigned nb = (b->n_reads + 255) / 256;
+  hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, batch_stats(c));
+  hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, hist, batch_stats(c));
+  hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(kOrderBuckets), 0, s, hist);
+  hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, hist, b->d_order.get(), batch_stats(c));
+  HIPCHK(hipGetLastError());
+  return TALC_OK;
+}
+
+// One k_search launch: the waves of `st` take the `n_work` reads that `d_work` lists.  `edgeTasks`: the waves may hand edge
+// searches to each other through the stage's boxes, where it has them (the first pass; a retry pass searches every edge
+// in its own wave)
+static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint32_t* d_work, uint32_t n_work, const TraceBuf& tb,
+                         uint32_t traceRead, bool edgeTasks) {
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
+  EdgeTaskArgs ea = {};
+  ea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
+  if (edgeTasks && st.boxes) {   // the claim counters sit behind the boxes
+    ea.boxes = st.boxes.get();
+    ea.avail = (uint32_t*)(st.boxes.get() + (uint64_t)st.n_slots * edge_box_bytes(st.box_seq_cap));
+    ea.seqCap = st.box_seq_cap;
+    ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
+    ea.lingerMod = c->sw.edgeLingerMod; ea.test |= c->sw.edgeRedo ? kTestEdgeRedo : 0u;
+    ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : batch_stats(c) + kStatBranching;   // (switched on: whatever the batch looks like)
+    HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)st.n_slots * 4, s));
+  }
+  hipLaunchKernelGGL(k_search, dim3(st.n_slots), dim3(64), 0, s, c->dp, c->view, st.caps, b->d_codes.get(), b->d_offsets.get(),
+                     b->d_koff.get(), b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), d_work,
+                     n_work, c->d_queue.get(), st.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), ea);
+  HIPCHK(hipGetLastError());
+  return TALC_OK;
+}
+
+// the first pass: every read, in queue order, through the context's stage (event 4 after it); leaves the states in b->h_state
+static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
   int rc;
-  TraceBuf tb = {};
-  if (th) { tb.recs = th->d_recs.get(); tb.nrec = th->d_nrec.get(); tb.cap = th->cap; tb.pool = th->d_pool.get(); tb.npool = th->d_npool.get(); tb.poolCap = th->poolCap; tb.steps = c->sw.traceSteps ? 1 : 0; }
-  b->structured = false;   // (k_search edits the region lists in place)
-  if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
-  // ---- the work queue: heaviest reads first, by k_structure's estimate
-  if (b->n_reads) {
-    HIPCHK(hipMemsetAsync(c->d_hist.get(), 0, 1024 * sizeof(uint32_t), s));
-    const unsigned nb = (b->n_reads + 255) / 256;
-    hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, c->d_hist.get() + 1024);
-    hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, c->d_hist.get(), c->d_hist.get() + 1024);
-    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, s, c->d_hist.get());
-    hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, c->d_hist.get(), b->d_order.get(), c->d_hist.get() + 1024);
-    HIPCHK(hipGetLastError());
-  }
-  // ---- search, first pass
-  HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
-  HIPCHK(hipMemsetAsync(c->d_counters.get(), 0, (128 + 2 * 8192) * sizeof(uint64_t), s));
-  HIPCHK(hipMemsetAsync(c->d_counters.get() + 126, 0xFF, sizeof(uint64_t), s));   // (profile build: running minimum)
-  HIPCHK(hipMemsetAsync(c->d_counters.get() + 124, 0xFF, sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(c->d_counters.get(), 0, kCounterWords * sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(c->d_counters.get() + kCntFirstStart, 0xFF, sizeof(uint64_t), s));   // (profile build: running minimum)
+  HIPCHK(hipMemsetAsync(c->d_counters.get() + kCntQueueDry, 0xFF, sizeof(uint64_t), s));
   if (b->n_reads) {
     if ((rc = ensure_stage(c, c->stage, b->max_len, 1, b->n_reads))) return rc;
     ensure_edge_boxes(c, c->stage);
-    EdgeTaskArgs ea = {};
-    ea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
-    if (c->stage.boxes) {   // the claim counters sit behind the boxes
-      ea.boxes = c->stage.boxes.get();
-      ea.avail = (uint32_t*)(c->stage.boxes.get() + (uint64_t)c->stage.n_slots * edge_box_bytes(c->stage.box_seq_cap));
-      ea.seqCap = c->stage.box_seq_cap;
-      ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
-      ea.lingerMod = c->sw.edgeLingerMod; ea.test |= c->sw.edgeRedo ? kTestEdgeRedo : 0u;
-      ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : c->d_hist.get() + 1024 + 129;   // (switched on: whatever the batch looks like)
-      HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)c->stage.n_slots * 4, s));
-    }
-    hipLaunchKernelGGL(k_search, dim3(c->stage.n_slots), dim3(64), 0, s, c->dp, c->view, c->stage.caps, b->d_codes.get(), b->d_offsets.get(),
-                       b->d_koff.get(), b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), b->d_order.get(),
-                       b->n_reads, c->d_queue.get(), c->stage.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), ea);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_search(c, b, c->stage, b->d_order.get(), b->n_reads, tb, traceRead, true))) return rc;
   }
   HIPCHK(hipEventRecord(c->ev[4], s));
-  b->h_state.resize(b->n_reads);
-  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  // ---- retry passes for the reads whose scratch overflowed: buffers sized from the batch's longest read (a path
-  // can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
+  return fetch_states(c, b);
+}
+
+// retry passes for the reads whose scratch overflowed (events 5 and 6 around them): buffers sized from the batch's longest
+// read (a path can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
+static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
+  hipStream_t s = c->stream;
+  int rc;
   std::vector<uint32_t> retry;
   for (uint32_t r = 0; r < b->n_reads; ++r) if (b->h_state[r].overflow) retry.push_back(r);
   c->timing.n_retried = (uint32_t)retry.size();
@@ -209,60 +238,72 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
       b->h_state[r].overflow = 0;
       HIPCHK(hipMemcpyAsync(b->d_state.get() + r, &b->h_state[r], sizeof(ReadState), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
-    EdgeTaskArgs rea = {};
-    rea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
-    hipLaunchKernelGGL(k_search, dim3(big.n_slots), dim3(64), 0, s, c->dp, c->view, big.caps, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
-                       b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), d_retry.get(), (uint32_t)retry.size(),
-                       c->d_queue.get(), big.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), rea);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = launch_search(c, b, big, d_retry.get(), (uint32_t)retry.size(), tb, traceRead, false))) return rc;
+    if ((rc = fetch_states(c, b))) return rc;
     d_retry.reset(); big = Stage();   // (both go before the next, larger stage is sized)
     std::vector<uint32_t> again;
     for (uint32_t r : retry) if (b->h_state[r].overflow) again.push_back(r);
     retry.swap(again);
   }
   HIPCHK(hipEventRecord(c->ev[6], s));
-  // ---- dense packing
-  uint32_t nfail = 0;
-  std::vector<uint64_t> dense_off(b->n_reads + 1);
+  return TALC_OK;
+}
+
+// dense packing: the records' offsets from the states' outLen (host), then k_pack into b->d_dense (event 7 after it)
+static int pack_dense(talc_ctx* c, talc_batch* b) {
+  hipStream_t s = c->stream;
+  b->h_dense_off.resize(b->n_reads + 1);
   uint64_t pos = 0;
   for (uint32_t r = 0; r < b->n_reads; ++r) {
-    dense_off[r] = pos;
+    b->h_dense_off[r] = pos;
     pos += b->h_state[r].outLen;
-    if (b->h_state[r].overflow) nfail++;
   }
-  dense_off[b->n_reads] = pos;
-  b->h_dense_off = dense_off;
+  b->h_dense_off[b->n_reads] = pos;
   // the record buffer of an earlier pass over this batch is kept when it is large enough
   if (b->d_dense && b->dense_cap < pos) b->d_dense.reset();
   if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(pos, 1); HIPCHK(b->d_dense.alloc(c->cache, b->dense_cap)); }
   if (!b->d_dense_off) HIPCHK(b->d_dense_off.alloc(c->cache, b->n_reads + 1));
-  HIPCHK(hipMemcpyAsync(b->d_dense_off.get(), dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(b->d_dense_off.get(), b->h_dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
                        b->n_reads, c->p.reverse ? 1 : 0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[7], s));
-  uint64_t counters[128] = {0};
-  HIPCHK(hipMemcpyAsync(counters, c->d_counters.get(), 128 * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]));
-  HIPCHK(hipEventElapsedTime(&c->timing.coverage_ms, c->ev[1], c->ev[2]));
-  HIPCHK(hipEventElapsedTime(&c->timing.structure_ms, c->ev[2], c->ev[3]));
-  HIPCHK(hipEventElapsedTime(&c->timing.search_ms, c->ev[3], c->ev[4]));
-  HIPCHK(hipEventElapsedTime(&c->timing.retry_ms, c->ev[5], c->ev[6]));
-  HIPCHK(hipEventElapsedTime(&c->timing.emit_ms, c->ev[6], c->ev[7]));
-  c->timing.n_trail_steps = counters[0];
-  c->timing.n_dp_cells = counters[1];
-  c->timing.n_failed = nfail;
+  return TALC_OK;
+}
+
+// waits for the stream; the stage times and the batch's counts into c->timing, the device counters below the wave log into `counters`
+static int read_timing(talc_ctx* c, talc_batch* b, uint64_t* counters) {
+  int rc;
+  HIPCHK(hipMemcpyAsync(counters, c->d_counters.get(), kCntWaveLog * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((rc = read_stage_times(c, 7))) return rc;
+  c->timing.n_trail_steps = counters[kCntSteps];
+  c->timing.n_dp_cells = counters[kCntCells];
+  for (const ReadState& st : b->h_state) c->timing.n_failed += st.overflow ? 1 : 0;
+  return TALC_OK;
+}
+
+static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
+  //  would be a mixture of this run's and the last one's)
+  b->structured = false; b->corrected = false;
+  const TraceBuf tb = trace_buf(c, th);
+  uint64_t counters[kCntWaveLog] = {0};
+  if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
+  if ((rc = order_queue(c, b))) return rc;
+  if ((rc = search_first_pass(c, b, tb, traceRead))) return rc;
+  if ((rc = search_retry_passes(c, b, tb, traceRead))) return rc;
+  if ((rc = pack_dense(c, b))) return rc;
+  if ((rc = read_timing(c, b, counters))) return rc;
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
 #endif
   b->corrected = true;
-  if (nfail) {   // the batch is valid: those reads are passed through unchanged with status TALC_READ_ERROR
-    fail(TALC_WARN_READ_ERRORS, "%u read(s) exhausted the device scratch even in the retry pass (status TALC_READ_ERROR)", nfail);
+  if (c->timing.n_failed) {   // the batch is valid: those reads are passed through unchanged with status TALC_READ_ERROR
+    fail(TALC_WARN_READ_ERRORS, "%u read(s) exhausted the device scratch even in the retry pass (status TALC_READ_ERROR)", c->timing.n_failed);
     return TALC_WARN_READ_ERRORS;
   }
   return TALC_OK;
@@ -280,12 +321,8 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   int rc;
   b->structured = false; b->corrected = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
-  b->h_state.resize(b->n_reads);
-  if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]));
-  HIPCHK(hipEventElapsedTime(&c->timing.coverage_ms, c->ev[1], c->ev[2]));
-  HIPCHK(hipEventElapsedTime(&c->timing.structure_ms, c->ev[2], c->ev[3]));
+  if ((rc = fetch_states(c, b))) return rc;
+  if ((rc = read_stage_times(c, 3))) return rc;
   b->structured = true;
   return TALC_OK;
 }
@@ -300,7 +337,7 @@ int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint
   uint64_t total = 0;
   for (uint32_t r = 0; r < b->n_reads; ++r) {
     const ReadState& st = b->h_state[r];
-    if (status) status[r] = st.overflow ? TALC_READ_ERROR : st.status;
+    if (status) status[r] = read_status(st);
     if (n_regions) n_regions[r] = st.nRegions;
     if (lambda) lambda[r] = st.lambda;
     if (in_span) in_span[r] = st.inSpan;
@@ -334,23 +371,29 @@ int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint
 
 uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->corrected) ? b->h_dense_off[b->n_reads] : 0; }
 
-int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
-                               int32_t* status) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+// the records of a corrected batch into `out` (a host or a device buffer: `kind`; null: offsets and statuses only)
+static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_capacity, uint64_t* out_offsets, int32_t* status,
+                         hipMemcpyKind kind, const char* what) {
   if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t total = b->h_dense_off[b->n_reads];
   if (out_offsets) memcpy(out_offsets, b->h_dense_off.data(), (b->n_reads + 1) * 8);
   if (status)
-    for (uint32_t r = 0; r < b->n_reads; ++r) status[r] = b->h_state[r].overflow ? TALC_READ_ERROR : b->h_state[r].status;
+    for (uint32_t r = 0; r < b->n_reads; ++r) status[r] = read_status(b->h_state[r]);
   if (out) {
-    if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "output buffer too small: need %llu bytes", (unsigned long long)total);
-    if (total) {   // on the context's stream: a DMA transfer when `out` is pinned (talc_pinned_alloc)
-      HIPCHK(hipMemcpyAsync(out, b->d_dense.get(), total, hipMemcpyDeviceToHost, c->stream));
+    if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "%s buffer too small: need %llu bytes", what, (unsigned long long)total);
+    if (total) {   // on the context's stream: a DMA transfer when a host `out` is pinned (talc_pinned_alloc)
+      HIPCHK(hipMemcpyAsync(out, b->d_dense.get(), total, kind, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
     }
   }
   return TALC_OK;
+}
+
+int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
+                               int32_t* status) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output");
 }
 
 // Read::outputBasicReadStats (Read.cpp:418-433) for every read of a corrected batch
@@ -376,18 +419,7 @@ int talc_batch_fetch_read_stats(talc_ctx* c, talc_batch* b, int64_t* stats5) {
 int talc_batch_copy_corrected_device(talc_ctx* c, talc_batch* b, void* device_out, uint64_t out_capacity,
                                      uint64_t* out_offsets, int32_t* status) {
   if (!c || !b || b->ctx != c || !device_out) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
-  if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
-  HIPCHK(hipSetDevice(c->device));
-  const uint64_t total = b->h_dense_off[b->n_reads];
-  if (out_offsets) memcpy(out_offsets, b->h_dense_off.data(), (b->n_reads + 1) * 8);
-  if (status)
-    for (uint32_t r = 0; r < b->n_reads; ++r) status[r] = b->h_state[r].overflow ? TALC_READ_ERROR : b->h_state[r].status;
-  if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "device buffer too small: need %llu bytes", (unsigned long long)total);
-  if (total) {
-    HIPCHK(hipMemcpyAsync(device_out, b->d_dense.get(), total, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return TALC_OK;
+  return corrected_out(c, b, device_out, out_capacity, out_offsets, status, hipMemcpyDeviceToDevice, "device");
 }
 
 int talc_correct_batch(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, char* out,
@@ -429,7 +461,7 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
   std::vector<uint8_t> pool(std::max<uint32_t>(npool, 1));
   if (nrec) HIPCHK(hipMemcpy(recs.data(), th.d_recs.get(), (size_t)nrec * sizeof(TraceRec), hipMemcpyDeviceToHost));
   if (npool) HIPCHK(hipMemcpy(pool.data(), th.d_pool.get(), npool, hipMemcpyDeviceToHost));
-  const int stv = tbch->h_state.empty() ? -1 : (tbch->h_state[0].overflow ? TALC_READ_ERROR : tbch->h_state[0].status);
+  const int stv = tbch->h_state.empty() ? -1 : read_status(tbch->h_state[0]);
   os << "STATUS " << stv << "\n";
   for (auto& e : recs) {
     char x[64];

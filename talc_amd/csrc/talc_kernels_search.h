@@ -61,6 +61,34 @@ struct FullMeta { uint32_t off, len; int32_t lanc, ranc; double dist; };
 // the work queue's counters (uint32 words; 1 KB apart: the waves without a read poll the last two while the others take reads from the first)
 static const uint32_t kQueueWords = 768, kQueueFinished = 256, kQueueOpen = 512;
 
+// the context's histogram buffer (uint32 words): the buckets of the work-queue order (k_order_*), then the batch statistics
+// — 64 pairs of (forking, solid) k-mer sums that k_structure adds to, one pair per read number mod 64, and the two words
+// k_order_scale derives from them: the queue key's gap scale (in 1/256) and the edge tasks' switch (EdgeTaskArgs::autoSwitch)
+static const uint32_t kOrderBuckets = 1024, kBatchStatsOff = kOrderBuckets, kBatchStatsWords = 256, kHistWords = kBatchStatsOff + kBatchStatsWords;
+static const uint32_t kStatGapScale = 128, kStatBranching = 129;   // (indices inside the batch statistics)
+
+// the context's counters (uint64 words).  All but the first two are the profile build's: its categories (PF_*), the
+// launch's utilisation — when the queue first ran dry, the waves' busy time, first start, last end; 100 MHz — and two
+// words per wave on its last read (TALC_PROF_SLOW)
+static const uint32_t kCntSteps = 0, kCntCells = 1, kCntProf0 = 2, kCntQueueDry = 124, kCntBusy = 125, kCntFirstStart = 126, kCntLastEnd = 127;
+static const uint32_t kCntWaveLog = 128, kCntMaxWaves = 8192, kCounterWords = kCntWaveLog + 2 * kCntMaxWaves;
+
+enum { PF_PROBE = 0, PF_CHILD, PF_AIMS, PF_CYCLE, PF_FFWD, PF_SCOREBR, PF_GARDEN, PF_EVALFULL, PF_XDROP, PF_EXTNW,
+       PF_EDGEMISC, PF_ANCHORS, PF_ASSEMBLE, PF_STEPB, PF_STEPE, PF_SRCHB, PF_SRCHE, PF_PROLOG, PF_INITTR, PF_TOTAL, PF_NCALLS, PF_NSTEPS,
+       PF_FFLOAD, PF_FFREC, PF_FFFLUSH, PF_FFENTRY, PF_NRECS, PF_RD0, PF_RD1, PF_RD2, PF_RD3, PF_RD4, PF_RD5, PF_RDMAX,
+       PF_XSTAGE, PF_XLEV, PF_XSEL, PF_REFB, PF_RESULT, PF_CYQ, PF_CYX, PF_CYHIT, PF_CYFILL,
+       PF_SB11, PF_SB12, PF_SB21, PF_SB10, PF_SBOTHER, PF_SEGEN, PF_XCALLS, PF_XNLEV, PF_FSFORK, PF_FSDEAD, PF_FSFILT, PF_FSLIM, PF_FK1, PF_FK2, PF_FKBAIL, PF_FORK, PF_ANCCALLS, PF_ANCITER, PF_TPUB, PF_TOWN, PF_TSTOLEN, PF_TWAIT, PF_TRUN, PF_EA0, PF_EA1, PF_EA2, PF_EA3, PF_EA4, PF_EASUM3, PF_EASUM4, PF_RANCH, PF_RANCHMAX, PF_RBR, PF_RBRMAX, PF_EDGELANE, PF_N };
+#define TALC_PF_NAMES {"probe", "child", "aims", "cycle", "ffwd", "scorebr", "garden", "evalfull", "xdrop", "extnw", "edgemisc", \
+                       "anchors", "assemble", "stepb*", "stepe*", "srchb*", "srche*", "prolog", "inittr", "total", "#ffcalls", "#ffsteps", \
+                       "ff.load", "ff.record", "ff.flush", "ff.entry", "#ffrecords", "#reads<0.25ms", "#reads<1ms", "#reads<4ms", \
+                       "#reads<16ms", "#reads<64ms", "#reads>=64ms", "maxread(10ns)", "x.stage", "x.levels", "x.select", "b.ref", "b.result", \
+                       "#cyc.query", "#cyc.exact", "#cyc.found", "cyc.fill%sum", \
+                       "#stepb 1->1", "#stepb 1->2", "#stepb 2->1", "#stepb 1->0", "#stepb other", "#stepe generic", "#xdrop calls", "#xdrop levels", \
+                       "#ffstop fork", "#ffstop deadend", "#ffstop filter", "#ffstop limit/other", "#forkstep 1 child", "#forkstep fork+deadend", "#forkstep bailed", "forkstep", "#anchor lists", "#anchor level tests", \
+                       "#edges published", "#anchors by owner", "#anchors by others", "t.owner waits", "t.run by others", \
+                       "#edge anchors<1ms", "#edge anchors<4ms", "#edge anchors<16ms", "#edge anchors<64ms", "#edge anchors>=64ms", "ticks anchors 16-64ms", "ticks anchors>=64ms", "(per read) anchors", "(per read) longest anchor", "(per read) bridge attempts", "(per read) longest bridge attempt", "edgelane*"}
+static_assert(kCntProf0 + PF_N <= kCntQueueDry, "the profile categories run into the utilisation counters");
+
 // per-wave scratch layout (byte offsets inside one slot)
 struct SearchLimits {   // (the part the search itself consults: a copy lives in the wave's LDS)
   uint32_t seqCap;      // bytes per Trail sequence (host: the longest possible; device: the current search's stride)
@@ -671,21 +699,6 @@ __shared__ __attribute__((aligned(16))) int g_dp[3 * LDS_DP_CAP];               
 struct EdgeCand {   // best candidate of m_longPaths / m_shortPaths kept online (findBestBORDER is a fold)
   bool have; double score; double dist; double idscore; uint32_t len; uint32_t lanc, ranc;
 };
-
-enum { PF_PROBE = 0, PF_CHILD, PF_AIMS, PF_CYCLE, PF_FFWD, PF_SCOREBR, PF_GARDEN, PF_EVALFULL, PF_XDROP, PF_EXTNW,
-       PF_EDGEMISC, PF_ANCHORS, PF_ASSEMBLE, PF_STEPB, PF_STEPE, PF_SRCHB, PF_SRCHE, PF_PROLOG, PF_INITTR, PF_TOTAL, PF_NCALLS, PF_NSTEPS,
-       PF_FFLOAD, PF_FFREC, PF_FFFLUSH, PF_FFENTRY, PF_NRECS, PF_RD0, PF_RD1, PF_RD2, PF_RD3, PF_RD4, PF_RD5, PF_RDMAX,
-       PF_XSTAGE, PF_XLEV, PF_XSEL, PF_REFB, PF_RESULT, PF_CYQ, PF_CYX, PF_CYHIT, PF_CYFILL,
-       PF_SB11, PF_SB12, PF_SB21, PF_SB10, PF_SBOTHER, PF_SEGEN, PF_XCALLS, PF_XNLEV, PF_FSFORK, PF_FSDEAD, PF_FSFILT, PF_FSLIM, PF_FK1, PF_FK2, PF_FKBAIL, PF_FORK, PF_ANCCALLS, PF_ANCITER, PF_TPUB, PF_TOWN, PF_TSTOLEN, PF_TWAIT, PF_TRUN, PF_EA0, PF_EA1, PF_EA2, PF_EA3, PF_EA4, PF_EASUM3, PF_EASUM4, PF_RANCH, PF_RANCHMAX, PF_RBR, PF_RBRMAX, PF_EDGELANE, PF_N };
-#define TALC_PF_NAMES {"probe", "child", "aims", "cycle", "ffwd", "scorebr", "garden", "evalfull", "xdrop", "extnw", "edgemisc", \
-                       "anchors", "assemble", "stepb*", "stepe*", "srchb*", "srche*", "prolog", "inittr", "total", "#ffcalls", "#ffsteps", \
-                       "ff.load", "ff.record", "ff.flush", "ff.entry", "#ffrecords", "#reads<0.25ms", "#reads<1ms", "#reads<4ms", \
-                       "#reads<16ms", "#reads<64ms", "#reads>=64ms", "maxread(10ns)", "x.stage", "x.levels", "x.select", "b.ref", "b.result", \
-                       "#cyc.query", "#cyc.exact", "#cyc.found", "cyc.fill%sum", \
-                       "#stepb 1->1", "#stepb 1->2", "#stepb 2->1", "#stepb 1->0", "#stepb other", "#stepe generic", "#xdrop calls", "#xdrop levels", \
-                       "#ffstop fork", "#ffstop deadend", "#ffstop filter", "#ffstop limit/other", "#forkstep 1 child", "#forkstep fork+deadend", "#forkstep bailed", "forkstep", "#anchor lists", "#anchor level tests", \
-                       "#edges published", "#anchors by owner", "#anchors by others", "t.owner waits", "t.run by others", \
-                       "#edge anchors<1ms", "#edge anchors<4ms", "#edge anchors<16ms", "#edge anchors<64ms", "#edge anchors>=64ms", "ticks anchors 16-64ms", "ticks anchors>=64ms", "(per read) anchors", "(per read) longest anchor", "(per read) bridge attempts", "(per read) longest bridge attempt", "edgelane*"}
 
 // test hooks of a launch (EdgeTaskArgs::test -> Wv::taskTest)
 enum : uint32_t { kTestEdgeRedo = 1u, kTestNoEdgeLane = 2u };
@@ -4155,7 +4168,7 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
   // no reads left: run published anchors of the edge searches still going on, until every read is finished
 #ifdef TALC_PROF
   _pf_loopEnd = __builtin_amdgcn_s_memrealtime();
-  if (l == 0) atomicMin((unsigned long long*)&counters[124], _pf_loopEnd);   // the first wave to find the queue dry
+  if (l == 0) atomicMin((unsigned long long*)&counters[kCntQueueDry], _pf_loopEnd);   // the first wave to find the queue dry
 #endif
   if (X.boxes != nullptr && blockIdx.x % lingerMod == 0u) {
 #ifdef TALC_PROF
@@ -4165,49 +4178,49 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
   }
   totCells += X.moreCells; totSteps += X.moreSteps;
   if (l == 0) {
-    if (totSteps) atomicAdd((unsigned long long*)&counters[0], totSteps);
-    if (totCells) atomicAdd((unsigned long long*)&counters[1], totCells);
+    if (totSteps) atomicAdd((unsigned long long*)&counters[kCntSteps], totSteps);
+    if (totCells) atomicAdd((unsigned long long*)&counters[kCntCells], totCells);
 #ifdef TALC_PROF
     g_prof[PF_TOTAL] = (uint32_t)(__builtin_amdgcn_s_memtime() - _pf_k0);
     g_prof[PF_XSTAGE] = g_wprof[0]; g_prof[PF_XLEV] = g_wprof[1]; g_prof[PF_XSEL] = g_wprof[2]; g_prof[PF_XNLEV] = g_wprof[3];
     {   // wave utilisation of the launch: sum of the waves' lifetimes against (last end - first start) x waves
       const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-      atomicAdd((unsigned long long*)&counters[125], r1 - _pf_r0 - _pf_idle);   // (counters[2 .. 2 + PF_N) are the categories)
-      atomicMin((unsigned long long*)&counters[126], _pf_r0);
-      atomicMax((unsigned long long*)&counters[127], r1);
+      atomicAdd((unsigned long long*)&counters[kCntBusy], r1 - _pf_r0 - _pf_idle);
+      atomicMin((unsigned long long*)&counters[kCntFirstStart], _pf_r0);
+      atomicMax((unsigned long long*)&counters[kCntLastEnd], r1);
       // the wave's last read: (queue position, read), (its start, the wave's end) — TALC_PROF_SLOW prints the waves that end last
       if (_pf_rd0) state[_pf_prevR].pfTicks = (uint32_t)(r1 - _pf_rd0);
-      if (blockIdx.x < 8192u) {
-        counters[128 + 2 * blockIdx.x] = ((unsigned long long)_pf_prevQi << 32) | _pf_prevR;
-        counters[129 + 2 * blockIdx.x] = ((_pf_lastStart & 0xFFFFFFFFull) << 32) | (_pf_loopEnd & 0xFFFFFFFFull);   // (the end of its last read, not of its stay)
+      if (blockIdx.x < kCntMaxWaves) {
+        counters[kCntWaveLog + 2 * blockIdx.x] = ((unsigned long long)_pf_prevQi << 32) | _pf_prevR;
+        counters[kCntWaveLog + 2 * blockIdx.x + 1] = ((_pf_lastStart & 0xFFFFFFFFull) << 32) | (_pf_loopEnd & 0xFFFFFFFFull);   // (the end of its last read, not of its stay)
       }
-      static_assert(2 + PF_N <= 124, "the profile categories run into the utilisation counters");
     }
     for (int i = 0; i < PF_N; ++i) {
-      if (i == PF_RDMAX) atomicMax((unsigned long long*)&counters[2 + i], (unsigned long long)g_prof[i]);
-      else atomicAdd((unsigned long long*)&counters[2 + i], (unsigned long long)g_prof[i]);
+      if (i == PF_RDMAX) atomicMax((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
+      else atomicAdd((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
     }
 #endif
   }
 }
 
 // ==================================================================== work-queue order
-// Reads by descending cost estimate, without a sort: a 1024-bucket counting sort on a 10-bit logarithmic key (the order
+// Reads by descending cost estimate, without a sort: a counting sort over kOrderBuckets buckets on a logarithmic key (the order
 // inside a bucket is whatever the atomics make it: records do not depend on the order reads are taken in).
 // The key: the estimate, with its inner-gap part weighed by `gapScale` (in 1/256).  Over a branching graph (paralog
 // families: 3.5 % of the solid k-mers of a batch fork, against 1 % over unique sequence with sequencing-error k-mers) a base
 // of an inner gap costs ten to twenty times what it costs elsewhere — the walk carries several Trails — while the edges
 // cost the same, and the edges are the part of a read other waves can take over (edge tasks): the reads with long inner
 // gaps have to start first there.  k_order_scale: 1 up to a fork share of 1.2 %, + 1 per further 1 %, at most 3.
+static_assert(kOrderBuckets == 32 * 32, "the key of order_bucket: five bits of exponent, five of mantissa");
 TALC_D uint32_t order_bucket(const ReadState& st, uint32_t gapScale) {
-  if (st.status != TALC_READ_CORRECTED || st.overflow) return 1023u;   // passed through: last
+  if (st.status != TALC_READ_CORRECTED || st.overflow) return kOrderBuckets - 1;   // passed through: last
   const unsigned long long key = (unsigned long long)st.costEst + (((unsigned long long)st.costGap * (gapScale - 256u)) >> 8);
   const uint32_t c = (uint32_t)min(key, 0xFFFFFFFFull) | 1u;
   const int e = 31 - __builtin_clz(c);                               // 0..31
   const uint32_t m = (e >= 5) ? ((c >> (e - 5)) & 31u) : ((c << (5 - e)) & 31u);
-  return 1022u - min(1022u, (uint32_t)e * 32u + m);                  // heavy first
+  return kOrderBuckets - 2 - min(kOrderBuckets - 2, (uint32_t)e * 32u + m);                  // heavy first
 }
-__global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batchStats) {   // batchStats[128] := the gap scale, [129] := the graph branches
+__global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batchStats) {   // sets the gap scale and whether the graph branches
   const int l = lane_id();
   const unsigned long long fork = wave_sum_u64(batchStats[2 * l]), solid = wave_sum_u64(batchStats[2 * l + 1]);
   uint32_t scale = 256u;
@@ -4215,19 +4228,19 @@ __global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batch
     const unsigned long long perMille10 = fork * 10000ull / solid;   // fork share in 1/10000
     if (perMille10 > 120ull) scale = 256u + (uint32_t)min((perMille10 - 120ull) * 256ull / 100ull, 512ull);
   }
-  if (l == 0) { batchStats[128] = scale; batchStats[129] = scale > 256u ? 1u : 0u; }   // [129]: the edge tasks' switch
+  if (l == 0) { batchStats[kStatGapScale] = scale; batchStats[kStatBranching] = scale > 256u ? 1u : 0u; }   // (the edge tasks' switch)
 }
 __global__ void k_order_hist(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ hist, const uint32_t* __restrict__ batchStats) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) atomicAdd(&hist[order_bucket(state[r], batchStats[128])], 1u);
+  if (r < n) atomicAdd(&hist[order_bucket(state[r], batchStats[kStatGapScale])], 1u);
 }
-__global__ void __launch_bounds__(1024) k_order_scan(uint32_t* __restrict__ hist) {   // hist[b] := first position of bucket b
-  __shared__ uint32_t s[1024];
+__global__ void __launch_bounds__(kOrderBuckets) k_order_scan(uint32_t* __restrict__ hist) {   // hist[b] := first position of bucket b
+  __shared__ uint32_t s[kOrderBuckets];
   const uint32_t t = threadIdx.x;
   const uint32_t v = hist[t];
   s[t] = v;
   __syncthreads();
-  for (uint32_t off = 1; off < 1024; off <<= 1) {
+  for (uint32_t off = 1; off < kOrderBuckets; off <<= 1) {
     const uint32_t add = (t >= off) ? s[t - off] : 0u;
     __syncthreads();
     s[t] += add;
@@ -4238,7 +4251,7 @@ __global__ void __launch_bounds__(1024) k_order_scan(uint32_t* __restrict__ hist
 __global__ void k_order_scatter(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
                                 const uint32_t* __restrict__ batchStats) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) order[atomicAdd(&cursor[order_bucket(state[r], batchStats[128])], 1u)] = r;
+  if (r < n) order[atomicAdd(&cursor[order_bucket(state[r], batchStats[kStatGapScale])], 1u)] = r;
 }
 
 // ==================================================================== the count model's thresholds (DevParams.thr)
