@@ -2,7 +2,12 @@
 //
 // Device restatement of the reference's per-read correction:
 //   k_structure : Read::defineStructure2           Read.cpp:260-276, 440-600, 214-258
-//   k_search    : Read::correct2                   Read.cpp:336-386
+//   k_search    : Read::correct2                   Read.cpp:336-386, per read of the work queue:
+//                   begin_read       the read and its regions into the wave's context X (bind_slot, bind_launch: once per wave)
+//                   correct_inner    :346-360 initializeINNER, the RIGHT then the LEFT attempt, updateINNER (:294-303)
+//                   correct_border   :361-374 head and tail, updateHEAD / updateTAIL (:305-318)
+//                   corrected_length, reassemble   updateCorrSeq :320-326 (piece_after: what follows a region)
+//                   pass_through     the read leaves as it came (main.cpp:310)
 //                 Explorer::searchBridge/searchEdge Explorer.cpp:868-1081 and everything below them
 //                 (anchors :413-543, oneMoreStep :546-612, oneMoreStepInTheDark :615-687,
 //                  scoreBridges :689-706, scoreEdges :709-740, gardening :773-865, Trail.cpp,
@@ -768,16 +773,42 @@ enum { LOC_HEAD = 0, LOC_INNER = 1, LOC_TAIL = 2 };
 // and lets the heavy routines be real (non-inlined) functions without passing anything.
 __shared__ Wv g_X;
 #define X g_X
+// every scratch pointer of the wave, from its slot (a new scratch region: SearchCaps, make_caps and here)
+TALC_D void bind_slot(uint8_t* slot, const SearchCaps& C, const TraceBuf& trace) {
+  X.C = (const SearchLimits&)C;
+  X.G[0] = make_set(slot + C.o_setA);
+  X.G[1] = make_set(slot + C.o_setB);
+  X.ia = 0;
+  X.seqPool = slot + C.o_seqPool;
+  X.refBuf = slot + C.o_ref; X.ref = X.refBuf; X.ancL = (AnchorRec*)(slot + C.o_ancL); X.ancR = (AnchorRec*)(slot + C.o_ancR);
+  X.ancPos = (uint32_t*)(slot + C.o_ancPos);
+  X.fullMeta = (FullMeta*)(slot + C.o_fullMeta); X.fullPool = slot + C.o_fullPoolB;
+  X.edgeLong = slot + C.o_edgeLong; X.edgeShort = slot + C.o_edgeShort; X.edgeTmp = slot + C.o_edgeTmp;
+  X.dpG = (int*)(slot + C.o_dp);
+  X.wideBloom = (unsigned long long*)(slot + C.o_wideBloom); X.wideMask = 0;
+  X.rowPool = (int*)(slot + C.o_rowPool); X.rowStride = 0; X.rowAvail = 0;
+  {
+    uint8_t* g = slot + C.o_gard;
+    X.gScores = (double*)g; g += 8ull * (TCAP + 64);
+    X.gDists = (double*)g; g += 8ull * (TCAP + 64);
+    X.gVal = (ValIdx*)g; g += 16ull * (TCAP + 64);
+    X.gRank = (Rank4*)g; g += 32ull * (TCAP + 64);
+    X.gKept = (uint32_t*)g;
+  }
+  X.regS = (uint32_t*)(slot + C.o_regS); X.regE = (uint32_t*)(slot + C.o_regE); X.regH = (uint32_t*)(slot + C.o_regH);
+  X.wOff = (uint32_t*)(slot + C.o_wOff); X.wLen = (uint32_t*)(slot + C.o_wLen);
+  X.weak = slot + C.o_weak;
+  if (lane_id() == 0) *(TraceBuf*)(slot + C.o_trace) = trace;
+  X.tracep = (const TraceBuf*)(slot + C.o_trace);
+}
 #ifdef TALC_PROF
-__shared__ uint32_t g_prof[PF_N];   // per wave, in cycles: 2^32 cycles = 1.9 s (32 bits keep the build in the product's LDS size class:
+__shared__ uint32_t g_prof[PF_N];  // per wave, in cycles: 2^32 cycles = 1.9 s (32 bits keep the build in the product's LDS size class:
                                      // LDS is handed out in steps of 1280 bytes, and one step more costs three of the 21 waves a CU holds)
 #endif
 
 // ---- optional in-kernel cycle accounting (diagnostic build only: -DTALC_PROF) ----
 #ifdef TALC_PROF
 #define PROF_DECL unsigned long long _pf_t
-#define PF_EDGE_T0() (_pf_e0 = __builtin_amdgcn_s_memrealtime())
-#define PF_EDGE_T1() (_pf_edge += (uint32_t)(__builtin_amdgcn_s_memrealtime() - _pf_e0))
 #define PROF_BEGIN() (_pf_t = __builtin_amdgcn_s_memtime())
 #define PROF_END(cat) (g_prof[cat] += (uint32_t)(__builtin_amdgcn_s_memtime() - _pf_t))
 #define PROF_DECL2 unsigned long long _pf_t2
@@ -786,14 +817,85 @@ __shared__ uint32_t g_prof[PF_N];   // per wave, in cycles: 2^32 cycles = 1.9 s 
 #define PROF_END2(cat) (g_prof[cat] += (uint32_t)(__builtin_amdgcn_s_memtime() - _pf_t2))
 #else
 #define PROF_DECL
-#define PF_EDGE_T0() ((void)0)
-#define PF_EDGE_T1() ((void)0)
 #define PROF_BEGIN() ((void)0)
 #define PROF_END(cat) ((void)0)
 #define PROF_DECL2
 #define PROF_COUNT(cat, n) ((void)0)
 #define PROF_BEGIN2() ((void)0)
 #define PROF_END2(cat) ((void)0)
+#endif
+
+// The profile build's bookkeeping of one k_search wave (ticks: 100 MHz, the same counter on every CU); in the product
+// build every call is empty
+#ifdef TALC_PROF
+struct SearchProf {
+  unsigned long long k0, r0;                                      // the wave's start: cycles, ticks
+  unsigned long long rd0 = 0, lastStart = 0, loopEnd = 0, e0 = 0;   // starts of the read under way and of the last one finished, the queue found dry, search_edge entered
+  unsigned long long idle = 0;                                    // asleep without a read, waiting for anchors to be published
+  uint32_t prevQi = 0, prevR = 0, edge = 0;                       // the read under way (or the last one): queue position, number, ticks inside search_edge
+  TALC_D void wave_begins() {
+    if (lane_id() == 0) { for (int i = 0; i < PF_N; ++i) g_prof[i] = 0; for (int i = 0; i < 4; ++i) g_wprof[i] = 0; }
+    k0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime();
+  }
+  TALC_D void read_begins(ReadState* state, uint32_t qi, uint32_t r) {
+    rd0 = __builtin_amdgcn_s_memrealtime(); prevQi = qi; prevR = r; edge = 0;
+    if (lane_id() == 0) state[r].pfStart = (uint32_t)rd0;
+  }
+  TALC_D void edge_begins() { e0 = __builtin_amdgcn_s_memrealtime(); }
+  TALC_D void edge_ends() { edge += (uint32_t)(__builtin_amdgcn_s_memrealtime() - e0); }
+  TALC_D void read_searched(ReadState* state) {   // what the search of the read took (TALC_PROF_READS)
+    if (lane_id() != 0) return;
+    ReadState& st = state[prevR];
+    st.pfSteps = (uint32_t)X.steps; st.pfEdgeTicks = edge; st.pfAnchors = g_prof[PF_RANCH]; st.pfAnchorMax = g_prof[PF_RANCHMAX]; g_prof[PF_RANCH] = 0; g_prof[PF_RANCHMAX] = 0;
+    st.pfBridges = g_prof[PF_RBR]; st.pfBridgeMax = g_prof[PF_RBRMAX]; g_prof[PF_RBR] = 0; g_prof[PF_RBRMAX] = 0;
+  }
+  TALC_D void read_ends(ReadState* state) {   // (whichever way the read left the loop's body: called before the next one is taken)
+    if (lane_id() == 0 && rd0) {
+      const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - rd0;
+      const int bk = dt < 25000ull ? 0 : dt < 100000ull ? 1 : dt < 400000ull ? 2 : dt < 1600000ull ? 3 : dt < 6400000ull ? 4 : 5;
+      g_prof[PF_RD0 + bk] += 1;
+      if (dt > g_prof[PF_RDMAX]) g_prof[PF_RDMAX] = (uint32_t)dt;
+      state[prevR].pfTicks = (uint32_t)dt;
+      lastStart = rd0; rd0 = 0;
+    }
+  }
+  TALC_D void queue_dry(uint64_t* counters) {
+    loopEnd = __builtin_amdgcn_s_memrealtime();
+    if (lane_id() == 0) atomicMin((unsigned long long*)&counters[kCntQueueDry], loopEnd);   // the first wave to find the queue dry
+  }
+  TALC_D void lingered(unsigned long long slept) { idle = slept; }
+  TALC_D void wave_ends(ReadState* state, uint64_t* counters) {   // (lane 0)
+    g_prof[PF_TOTAL] = (uint32_t)(__builtin_amdgcn_s_memtime() - k0);
+    g_prof[PF_XSTAGE] = g_wprof[0]; g_prof[PF_XLEV] = g_wprof[1]; g_prof[PF_XSEL] = g_wprof[2]; g_prof[PF_XNLEV] = g_wprof[3];
+    // wave utilisation of the launch: sum of the waves' lifetimes against (last end - first start) x waves
+    const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
+    atomicAdd((unsigned long long*)&counters[kCntBusy], r1 - r0 - idle);
+    atomicMin((unsigned long long*)&counters[kCntFirstStart], r0);
+    atomicMax((unsigned long long*)&counters[kCntLastEnd], r1);
+    // the wave's last read: (queue position, read), (its start, the wave's end) — TALC_PROF_SLOW prints the waves that end last
+    if (rd0) state[prevR].pfTicks = (uint32_t)(r1 - rd0);
+    if (blockIdx.x < kCntMaxWaves) {
+      counters[kCntWaveLog + 2 * blockIdx.x] = ((unsigned long long)prevQi << 32) | prevR;
+      counters[kCntWaveLog + 2 * blockIdx.x + 1] = ((lastStart & 0xFFFFFFFFull) << 32) | (loopEnd & 0xFFFFFFFFull);   // (the end of its last read, not of its stay)
+    }
+    for (int i = 0; i < PF_N; ++i) {
+      if (i == PF_RDMAX) atomicMax((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
+      else atomicAdd((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
+    }
+  }
+};
+#else
+struct SearchProf {
+  TALC_D void wave_begins() {}
+  TALC_D void read_begins(ReadState*, uint32_t, uint32_t) {}
+  TALC_D void edge_begins() {}
+  TALC_D void edge_ends() {}
+  TALC_D void read_searched(ReadState*) {}
+  TALC_D void read_ends(ReadState*) {}
+  TALC_D void queue_dry(uint64_t*) {}
+  TALC_D void lingered(unsigned long long) {}
+  TALC_D void wave_ends(ReadState*, uint64_t*) {}
+};
 #endif
 
 // count / colour word of the k-mer at position i of the current read (0 when it is not in the table)
@@ -1225,9 +1327,7 @@ TALC_D bool build_anchors_body(int side) {
 #define RUNY(pos) ((LEAF || inRegs) ? run_y(pos) : (clean ? (*(const v2u32 TALC_AS1*)(cr.hits + hbase + ((pos) - rs))).y : COVY(pos)))
 #define HEADX(a) (((a) < (uint32_t)kHeadCov) ? (uint32_t)uni((int)park[128u + (a)]) : (LEAF ? 0u : COVX(a)))
   uint32_t current_count = (uint32_t)uni((int)RUNX(pivot));
-#ifdef TALC_PROF
-  if (l == 0) g_prof[PF_ANCCALLS] += 1;
-#endif
+  PROF_COUNT(PF_ANCCALLS, 1);
   uint32_t nPos = 0;
   if (l == 0) anchorPos[0] = pivot;
   nPos = 1;
@@ -1243,9 +1343,7 @@ TALC_D bool build_anchors_body(int side) {
       const bool inRange = valid & (nc >= MINC) & ((double)nc < P.MAX_IN_COUNT);
       int from = 0;
       while (from < 64) {
-#ifdef TALC_PROF
-        if (l == 0) g_prof[PF_ANCITER] += 1;
-#endif
+        PROF_COUNT(PF_ANCITER, 1);
         const bool go = inRange && is_expected_by_last_node(P.ALPHA, nc, current_count);
         const unsigned long long stops = ballot64(valid && !go) & (~0ull << from);
         if (stops == 0ull) break;
@@ -1436,9 +1534,7 @@ TALC_D SeedExt seed_and_extension_body(const uint8_t* ref, int refLen, const uin
   const int qlen = len2 - S, dlen = len1 - S;
   if (qlen > 0 && dlen > 0) {
     PROF_BEGIN();
-#ifdef TALC_PROF
-    if (lane_id() == 0) g_prof[PF_XCALLS] += 1;
-#endif
+    PROF_COUNT(PF_XCALLS, 1);
     constexpr int STAGE = 3 * LDS_DP_CAP * 4;
     uint8_t TALC_AS3* stage = (uint8_t TALC_AS3*)g_dp;
     // furthest-reaching wavefronts, 1 / 2 / 4 diagonals per lane (x up to 31 / 63 / 127)
@@ -1900,9 +1996,7 @@ TALC_D bool is_cycle(int t, int c, int len, uint64_t km2, uint64_t nm2, uint32_t
   if (!(len > K)) return false;
   if (!maybe) return false;   // the k-mer occurs nowhere in this search so far
   const bool found = uni((int)is_cycle_exact(t, c, len)) != 0;
-#ifdef TALC_PROF
-  if (lane_id() == 0 && found) g_prof[PF_CYHIT] += 1;
-#endif
+  if (found) PROF_COUNT(PF_CYHIT, 1);
   return found;
 }
 TALC_D void swap_sets() { X.ia ^= 1; }
@@ -2174,9 +2268,7 @@ TALC_DN int bridge_children_by_lane(int tags_, uint32_t nc0, uint32_t nc1, uint3
       if (!uni((int)record_bridge_at_aim(nNew + f, hitF, len, kmF, nmF))) popM |= 1ull << f;   // :579-582 pop_back
     } else {
       const bool cyc = uni((int)is_cycle_exact(lane_get(t, f), nNew + f, len)) != 0;
-#ifdef TALC_PROF
-      if (l == 0 && cyc) g_prof[PF_CYHIT] += 1;
-#endif
+      if (cyc) PROF_COUNT(PF_CYHIT, 1);
       if (cyc) { pool_free((uint32_t)lane_get((int)ch.buf, f)); popM |= 1ull << f; }          // :586-587 pop_back
     }
   }
@@ -2280,9 +2372,7 @@ TALC_D int step_bridge(int nCur, int len, uint32_t& stepCounter) {
   bloom_flush(pend, nPend);
   const bool complex = ((uint32_t)nNew > P.MAXB);
   ++stepCounter;
-#ifdef TALC_PROF
-  if (l == 0) g_prof[(nCur == 1 && nNew == 1) ? PF_SB11 : (nCur == 1 && nNew == 2) ? PF_SB12 : (nCur == 2 && nNew == 1) ? PF_SB21 : (nCur == 1 && nNew == 0) ? PF_SB10 : PF_SBOTHER] += 1;
-#endif
+  PROF_COUNT((nCur == 1 && nNew == 1) ? PF_SB11 : (nCur == 1 && nNew == 2) ? PF_SB12 : (nCur == 2 && nNew == 1) ? PF_SB21 : (nCur == 1 && nNew == 0) ? PF_SB10 : PF_SBOTHER, 1);
   int nOut;
   if (complex & (stepCounter % P.CHECK_INTERVAL == 0)) {
     PROF_BEGIN();
@@ -2425,9 +2515,7 @@ TALC_DN int step_edge(int nCur, int len, uint32_t& stepCounter, uint32_t PATH_MA
   }
   bloom_flush(pend, nPend);
   ++stepCounter;
-#ifdef TALC_PROF
-  if (l == 0) g_prof[PF_SEGEN] += 1;
-#endif
+  PROF_COUNT(PF_SEGEN, 1);
   int nOut;
   if ((stepCounter % P.CHECK_INTERVAL == 0) || ((uint32_t)nNew >= P.MAX_BORDER_PATHS)) {
     nNew = uni(score_edges(X.ia ^ 1, nNew, len + 1, xdrop));
@@ -2576,9 +2664,7 @@ TALC_D int fast_forward_dir(int len_, uint32_t& stepCounter_, uint32_t PATH_MAXL
   g_bloom[l] = ((unsigned long long)(uint32_t)bwHi << 32) | (uint32_t)bwLo;
   g_bloom[l + 64] = ((unsigned long long)(uint32_t)bxHi << 32) | (uint32_t)bxLo;
   stepCounter_ = sc0 + (uint32_t)done;
-#ifdef TALC_PROF
-  if (l == 0) { g_prof[PF_NCALLS] += 1; g_prof[PF_NSTEPS] += (uint32_t)done; }
-#endif
+  PROF_COUNT(PF_NCALLS, 1); PROF_COUNT(PF_NSTEPS, done);
   if (done) {
     X.steps += (unsigned long long)done;
     if (l == 0) {
@@ -2635,9 +2721,7 @@ TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t
       e = wtab[slot * 8 + laneOff];
     }
     PROF_END(PF_FFLOAD);
-#ifdef TALC_PROF
-    if (l == 0) g_prof[PF_NRECS] += 1;
-#endif
+    PROF_COUNT(PF_NRECS, 1);
     if (!found) return 0;
     PROF_BEGIN();
     const uint32_t lev = (e >> laneShift) & 0xFFFFu, top = lev & kWalkTopNone;
@@ -2708,9 +2792,7 @@ TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t
       const unsigned long long am = ballot64((l < nAims) && (g_aimK[l < AIMS_LDS ? l : 0] == kmH) && (g_aimN[l < AIMS_LDS ? l : 0] == 0ull));
       if (am != 0ull) aimIdx = (int)__builtin_ctzll(am);   // checkAims takes the first aim that matches (Trail.cpp:273-285)
     }
-#ifdef TALC_PROF
-    if (hitLevel < nOK && aimIdx < 0 && l == 0) g_prof[PF_FSFILT] += 1;
-#endif
+    if (hitLevel < nOK && aimIdx < 0) PROF_COUNT(PF_FSFILT, 1);
     nOK = min(nOK, hitLevel);
     const int nTake = nOK + (aimIdx >= 0 ? 1 : 0);
     if (nTake == 0) return 0;
@@ -2842,9 +2924,7 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
   }
   flush();
   stepCounter_ = sc0 + (uint32_t)done;
-#ifdef TALC_PROF
-  if (l == 0) { g_prof[PF_NCALLS] += 1; g_prof[PF_NSTEPS] += (uint32_t)done; }
-#endif
+  PROF_COUNT(PF_NCALLS, 1); PROF_COUNT(PF_NSTEPS, done);
   if (done) {
     X.steps += (unsigned long long)done;
     if (l == 0) {
@@ -2990,9 +3070,7 @@ TALC_D EdgeLaneRet edge_lane_dir(int len_, uint32_t stepCounter_, uint32_t PATH_
     if (min(max(x, 0), qlen) + min(max(x, 0), dlen) + 1 > 63) break;         // the phased instances
     // ---- Trail::seedAndExtend (trail_seed_and_extend + the leaf instance of getSeedAndExtension) on the kept stage
     PROF_BEGIN();
-#ifdef TALC_PROF
-    if (l == 0) g_prof[PF_XCALLS] += 1;
-#endif
+    PROF_COUNT(PF_XCALLS, 1);
     if (!staged) {
       WSYNC();   // the Trail's bases of before this call are in its buffer only
       stage_copy(stage, (gcu8)seq + S, qlen);
@@ -3023,9 +3101,7 @@ TALC_D EdgeLaneRet edge_lane_dir(int len_, uint32_t stepCounter_, uint32_t PATH_
 
   flush();
   R.len = len0 + done; R.stepCounter = sc0 + (uint32_t)done; R.xdrop = xdrop;
-#ifdef TALC_PROF
-  if (l == 0) { g_prof[PF_NCALLS] += rounds; g_prof[PF_NSTEPS] += (uint32_t)done; }
-#endif
+  PROF_COUNT(PF_NCALLS, rounds); PROF_COUNT(PF_NSTEPS, done);
   X.cells += ncells;
   if (done) {
     X.steps += (unsigned long long)done;
@@ -3188,9 +3264,7 @@ TALC_DN int fork_step(int len_, uint32_t sc_, uint32_t PMAX_) {
       LSYNC();
     }
   }
-#ifdef TALC_PROF
-  if (l == 0) g_prof[taken == 1 ? PF_FK1 : taken == 2 ? PF_FK2 : PF_FKBAIL] += 1;
-#endif
+  PROF_COUNT(taken == 1 ? PF_FK1 : taken == 2 ? PF_FK2 : PF_FKBAIL, 1);
   PROF_END(PF_FORK);
   return taken;
 }
@@ -3916,6 +3990,147 @@ TALC_DNC void trace_search_cold() {
   for (int i = 0; i < nR; ++i) trace_rec(TR_ANCHOR, 1, (int)X.ancR[i].pos, (int)X.ancR[i].count, 0, 0.0, X.read + X.ancR[i].pos, K, false);
 }
 
+// the launch's constants -> X; returns the one-wave-in-so-many that stays when the reads are gone
+TALC_D uint32_t bind_launch(const DevParams& P, const TableView& T, uint32_t* queue, uint32_t n_work, uint32_t launchStamp, EdgeTaskArgs E) {
+  X.P = P; X.T = T;
+  X.launchStamp = launchStamp;
+  // (over a graph that does not branch the queue's order alone keeps the waves busy 95 % of the launch, and the tasks'
+  //  bookkeeping and the waves that stay cost config 2 0.7 %: the batch's fork share decides, k_order_scale)
+  if (E.boxes != nullptr && E.autoSwitch != nullptr && *E.autoSwitch == 0u) E.boxes = nullptr;
+  X.boxes = E.boxes; X.avail = E.avail; X.qwords = queue; X.boxSeqCap = E.seqCap; X.boxBytes = (uint32_t)edge_box_bytes(E.seqCap);
+  X.nSlots = gridDim.x; X.mySlot = blockIdx.x; X.nWork = n_work; X.taskMinWeak = E.minWeak; X.nanSeen = 0u; X.taskTest = E.test;
+  X.taskHeavy = E.heavy; X.heavyUpTo = (E.heavyRounds >= 0xFFFFu) ? 0xFFFFFFFFu : E.heavyRounds * gridDim.x;
+  X.qi = 0; X.holding = 0u; X.stealSeq = 0u; X.moreCells = 0; X.moreSteps = 0;
+  X.searchNo = 16u;   // (stamps below 16 << ROW_COV_BITS could be matrix values)
+  return max(E.lingerMod, 1u);   // (5120 waves polling two words kept a memory channel busy: config 2 + 0.7 ms with nothing ever published)
+}
+
+static const uint32_t kNotCorrected = 0xFFFFFFFFu;   // in wLen[i]: no search has replaced what follows region i
+struct Piece { const uint8_t* p; uint32_t n; };      // a stretch of the corrected read: bases of the read itself or of X.weak
+TALC_D Piece uni_piece(const uint8_t* p, uint32_t n) { return Piece{uni_ptr(p), (uint32_t)uni((int)n)}; }   // (in scalar registers: a border's piece lives across the searches)
+
+// Read `r` into X, and its regions into the wave's arrays (an edge task run between two reads overwrites part of X: every
+// per-read field is set here).  False: the read is not to be searched
+TALC_D bool begin_read(uint32_t r, const ReadState& st, uint32_t regCap, const uint8_t* codes, const uint64_t* offsets,
+                       const uint64_t* koff, const uint2* covAll, const CovWord* covWords, const uint32_t* headCovAll,
+                       const uint32_t* regions, const uint64_t* regoff, const TraceBuf& trace, uint32_t traceRead) {
+  const uint64_t rb = offsets[r];
+  const uint32_t L = (uint32_t)(offsets[r + 1] - rb), K = X.P.K;
+  X.read = codes + rb; X.L = L; X.n = L >= K ? L - K + 1 : 0; X.cov = covAll + koff[r]; X.covw = covWords + cov_word_base(koff[r], r); X.headCov = headCovAll + (uint64_t)r * kHeadCov; X.lambda = st.lambda;
+  X.cells = 0; X.steps = 0; X.overflow = 0; X.complexRegion = false; X.ffPopped = false;
+  X.tracing = (trace.recs != nullptr) && (r == traceRead);
+  X.traceSteps = X.tracing && (trace.steps != 0);
+  if (st.status != TALC_READ_CORRECTED || st.overflow) return false;
+  const uint32_t R = st.nRegions;
+  if (R > regCap) { X.overflow |= OVF_REGIONS; }
+  else {
+    const uint32_t* gS = regions + 3 * regoff[r];
+    const uint32_t gCap = (uint32_t)(regoff[r + 1] - regoff[r]);
+    const uint32_t* gE = gS + gCap;
+    const uint32_t* gH = gE + gCap;
+    for (uint32_t i = lane_id(); i < R; i += 64) { X.regS[i] = gS[i]; X.regE[i] = gE[i]; X.regH[i] = gH[i]; X.wLen[i] = kNotCorrected; X.wOff[i] = 0; }
+  }
+  WSYNC();
+  return true;
+}
+
+// the gap between regions `reg` and `reg + 1` (Read.cpp:346-360): the RIGHT attempt, then the LEFT one
+TALC_D void correct_inner(uint32_t reg, uint32_t& weakUsed) {
+  const uint32_t K = X.P.K;
+  PROF_DECL2;
+  uint32_t wo = 0, wl = 0;
+  bool success = false;
+  for (int attempt = 0; attempt < 2 && !success && !X.overflow; ++attempt) {
+    // initializeINNER (Explorer.cpp:228-243)
+    X.location = LOC_INNER; X.dirRight = (attempt == 0) ? 1 : 0;
+    X.Ls = X.regS[reg]; X.Le = X.regE[reg]; X.Rs = X.regS[reg + 1]; X.Re = X.regE[reg + 1];
+    X.LH = X.regH[reg]; X.RH = X.regH[reg + 1];
+    X.weakLen = (X.Rs > X.Le + K) ? (X.Rs - (X.Le + K)) : 0;
+    // (the LEFT attempt after a failed RIGHT one starts from the same two regions — a failed search changes
+    //  neither — so anchorLEFTHandSide / anchorRIGHTHandSide, Explorer.cpp:239-240, would return the lists again)
+    if (attempt == 0) { build_anchors(0); build_anchors(1); }
+    if (uni((int)X.tracing)) trace_search_cold();
+    PROF_BEGIN2(); success = search_bridge(wo, wl, weakUsed); PROF_END2(PF_SRCHB);
+    if (uni((int)X.tracing)) {
+      if (success) trace_rec(TR_RESULT, 1, 1, (int)X.Le, (int)X.Rs, 0.0, X.weak + wo, wl, false);
+      else trace_rec(TR_RESULT, 1, 0, (int)X.regE[reg], (int)X.regS[reg + 1], 0.0, X.read + X.regE[reg] + K, X.weakLen, false);
+    }
+  }
+  // updateINNER (Read.cpp:294-303)
+  WSYNC();
+  // (a region's start only ever moves inward: its hit index moves with it)
+  if (success && lane_id() == 0) { X.regE[reg] = X.Le; X.regH[reg + 1] += X.Rs - X.regS[reg + 1]; X.regS[reg + 1] = X.Rs; X.wOff[reg] = wo; X.wLen[reg] = wl; }
+  WSYNC();
+}
+
+// the head (Read.cpp:361-367: leftwards from the first region) or the tail (:368-374: rightwards from the last of the R);
+// `border` is the read's own bases there and becomes the corrected sequence when the search finds one
+template <int LOC>
+TALC_D void correct_border(Piece& border, uint32_t R, uint32_t& weakUsed, SearchProf& pf) {
+  constexpr bool HEAD = (LOC == LOC_HEAD);
+  const uint32_t reg = HEAD ? 0 : R - 1;   // the region the border hangs on
+  PROF_DECL2;
+  X.location = LOC; X.dirRight = HEAD ? 0 : 1;
+  if (HEAD) { X.Rs = X.regS[reg]; X.Re = X.regE[reg]; X.Ls = 0; X.Le = 0; X.RH = X.regH[reg]; X.LH = 0; X.weakLen = X.Rs; X.nAncL = 0; }
+  else { X.Ls = X.regS[reg]; X.Le = X.regE[reg]; X.Rs = 0; X.Re = 0; X.LH = X.regH[reg]; X.RH = 0; X.weakLen = X.L - (X.Le + X.P.K); X.nAncR = 0; }
+  build_anchors(HEAD ? 1 : 0);
+  if (uni((int)X.tracing)) trace_search_cold();
+  uint32_t off = 0, len = 0;
+  PROF_BEGIN2(); pf.edge_begins(); const bool found = search_edge(off, len, weakUsed); pf.edge_ends(); PROF_END2(PF_SRCHE);
+  if (uni((int)X.tracing)) {
+    if (found) trace_rec(TR_RESULT, LOC, 1, HEAD ? 0 : (int)X.Le, HEAD ? (int)X.Rs : 0, 0.0, X.weak + off, len, false);
+    else trace_rec(TR_RESULT, LOC, 0, HEAD ? 0 : (int)X.regE[reg], HEAD ? (int)X.regS[reg] : 0, 0.0, border.p, X.weakLen, false);
+  }
+  WSYNC();
+  if (found && lane_id() == 0) {
+    if (HEAD) { X.regH[reg] += X.Rs - X.regS[reg]; X.regS[reg] = X.Rs; }   // updateHEAD (Read.cpp:305-311)
+    else X.regE[reg] = X.Le;                                               // updateTAIL (Read.cpp:313-318)
+  }
+  WSYNC();
+  if (found) border = uni_piece(X.weak + off, len);
+}
+
+// what follows region i of R in the corrected read: the corrected weak sequence, or the read's own bases, or nothing
+TALC_D Piece piece_after(uint32_t i, uint32_t R, uint32_t K) {
+  if (i + 1 >= R) return Piece{nullptr, 0};
+  if (X.wLen[i] != kNotCorrected) return Piece{X.weak + X.wOff[i], X.wLen[i]};
+  const uint32_t from = X.regE[i] + K, to = X.regS[i + 1];
+  return Piece{X.read + from, to > from ? to - from : 0};
+}
+
+// updateCorrSeq (Read.cpp:320-326): head + (solid, weak)* + solid + tail.  Its length ...
+TALC_D unsigned long long corrected_length(const Piece& head, const Piece& tail, uint32_t R) {
+  const uint32_t K = X.P.K;
+  unsigned long long part = 0;
+  for (uint32_t i = lane_id(); i < R; i += 64) part += (unsigned long long)X.regE[i] + K - X.regS[i] + piece_after(i, R, K).n;
+  return head.n + wave_sum_u64(part) + tail.n;
+}
+// ... and the sequence itself, with the read's length and the stats row's span (Read.cpp:423 on the regions as correct2 leaves them)
+TALC_D void reassemble(uint8_t* out, const Piece& head, const Piece& tail, uint32_t R, ReadState* rs) {
+  const uint32_t K = X.P.K;
+  uint32_t pos = 0;
+  auto put = [&](const uint8_t* p, uint32_t n) { copy_bytes(out + pos, p, n, false); pos += n; };
+  if (head.n) put(head.p, head.n);
+  for (uint32_t i = 0; i < R; ++i) {
+    const uint32_t s = X.regS[i];
+    put(X.read + s, X.regE[i] + K - s);
+    const Piece w = piece_after(i, R, K);
+    if (w.n) put(w.p, w.n);
+  }
+  if (tail.n) put(tail.p, tail.n);
+  unsigned long long part = 0;
+  for (uint32_t i = lane_id(); i < R; i += 64) part += (unsigned long long)X.regE[i] - X.regS[i] + 1;
+  const uint32_t span = (uint32_t)wave_sum_u64(part);
+  if (lane_id() == 0) { rs->outLen = pos; rs->inSpan = span; }
+}
+
+// the read leaves as it came (main.cpp:310 writes mySeqs[r] unchanged): not to be searched (overflow 0), scratch exhausted
+// during the search, or the corrected read longer than its out slot (OVF_OUT)
+TALC_D void pass_through(uint8_t* out, ReadState* rs, uint32_t overflow) {
+  copy_bytes(out, X.read, X.L, false);
+  if (lane_id() == 0) { rs->outLen = X.L; if (overflow) rs->overflow = overflow; }
+}
+
 #ifndef TALC_SEARCH_WAVES_PER_SIMD
 #define TALC_SEARCH_WAVES_PER_SIMD 5   /* 20 waves per CU: <= 96 VGPRs and <= 8 KB of LDS per wave */
 #endif
@@ -3930,276 +4145,58 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
          uint32_t traceRead, uint32_t launchStamp, EdgeTaskArgs E) {
   __shared__ uint32_t s_next;
   const int l = lane_id();
-  uint8_t* slot = scratchAll + (uint64_t)blockIdx.x * C.slotBytes;
-  X.P = P; X.T = T; X.C = (const SearchLimits&)C;
-  X.G[0] = make_set(slot + C.o_setA);
-  X.G[1] = make_set(slot + C.o_setB);
-  X.ia = 0;
-  X.seqPool = slot + C.o_seqPool;
-  X.refBuf = slot + C.o_ref; X.ref = X.refBuf; X.ancL = (AnchorRec*)(slot + C.o_ancL); X.ancR = (AnchorRec*)(slot + C.o_ancR);
-  X.ancPos = (uint32_t*)(slot + C.o_ancPos);
-  X.fullMeta = (FullMeta*)(slot + C.o_fullMeta); X.fullPool = slot + C.o_fullPoolB;
-  X.edgeLong = slot + C.o_edgeLong; X.edgeShort = slot + C.o_edgeShort; X.edgeTmp = slot + C.o_edgeTmp;
-  X.dpG = (int*)(slot + C.o_dp);
-  X.wideBloom = (unsigned long long*)(slot + C.o_wideBloom); X.wideMask = 0;
-  X.rowPool = (int*)(slot + C.o_rowPool); X.rowStride = 0; X.rowAvail = 0;
-  X.launchStamp = launchStamp;
-  // (over a graph that does not branch the queue's order alone keeps the waves busy 95 % of the launch, and the tasks'
-  //  bookkeeping and the waves that stay cost config 2 0.7 %: the batch's fork share decides, k_order_scale)
-  if (E.boxes != nullptr && E.autoSwitch != nullptr && *E.autoSwitch == 0u) E.boxes = nullptr;
-  X.boxes = E.boxes; X.avail = E.avail; X.qwords = queue; X.boxSeqCap = E.seqCap; X.boxBytes = (uint32_t)edge_box_bytes(E.seqCap);
-  X.nSlots = gridDim.x; X.mySlot = blockIdx.x; X.nWork = n_work; X.taskMinWeak = E.minWeak; X.nanSeen = 0u; X.taskTest = E.test;
-  X.taskHeavy = E.heavy; X.heavyUpTo = (E.heavyRounds >= 0xFFFFu) ? 0xFFFFFFFFu : E.heavyRounds * gridDim.x;
-  X.qi = 0; X.holding = 0u; X.stealSeq = 0u; X.moreCells = 0; X.moreSteps = 0;
-  const uint32_t lingerMod = max(E.lingerMod, 1u);   // (5120 waves polling two words kept a memory channel busy: config 2 + 0.7 ms with nothing ever published)
-  X.searchNo = 16u;   // (stamps below 16 << ROW_COV_BITS could be matrix values)
-  {
-    uint8_t* g = slot + C.o_gard;
-    X.gScores = (double*)g; g += 8ull * (TCAP + 64);
-    X.gDists = (double*)g; g += 8ull * (TCAP + 64);
-    X.gVal = (ValIdx*)g; g += 16ull * (TCAP + 64);
-    X.gRank = (Rank4*)g; g += 32ull * (TCAP + 64);
-    X.gKept = (uint32_t*)g;
-  }
-  X.regS = (uint32_t*)(slot + C.o_regS); X.regE = (uint32_t*)(slot + C.o_regE); X.regH = (uint32_t*)(slot + C.o_regH);
-  X.wOff = (uint32_t*)(slot + C.o_wOff); X.wLen = (uint32_t*)(slot + C.o_wLen);
-  X.weak = slot + C.o_weak;
-  if (l == 0) *(TraceBuf*)(slot + C.o_trace) = trace;
-  X.tracep = (const TraceBuf*)(slot + C.o_trace);
+  bind_slot(scratchAll + (uint64_t)blockIdx.x * C.slotBytes, C, trace);
+  const uint32_t lingerMod = bind_launch(P, T, queue, n_work, launchStamp, E);
   unsigned long long totCells = 0, totSteps = 0;
   PROF_DECL2;
-#ifdef TALC_PROF
-  if (l == 0) { for (int i = 0; i < PF_N; ++i) g_prof[i] = 0; for (int i = 0; i < 4; ++i) g_wprof[i] = 0; }
-  const unsigned long long _pf_k0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long _pf_r0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz, the same counter on every CU
-  unsigned long long _pf_rd0 = 0, _pf_lastStart = 0, _pf_loopEnd = 0, _pf_idle = 0;   // (_pf_idle: asleep without a read, waiting for anchors to be published)
-  uint32_t _pf_prevQi = 0, _pf_prevR = 0;
-#endif
+  SearchProf pf;
+  pf.wave_begins();
 
   while (true) {
     WSYNC();
-#ifdef TALC_PROF
-    if (l == 0 && _pf_rd0) {   // duration of the previous read of this wave (100 MHz ticks)
-      const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - _pf_rd0;
-      const int bk = dt < 25000ull ? 0 : dt < 100000ull ? 1 : dt < 400000ull ? 2 : dt < 1600000ull ? 3 : dt < 6400000ull ? 4 : 5;
-      g_prof[PF_RD0 + bk] += 1;
-      if (dt > g_prof[PF_RDMAX]) g_prof[PF_RDMAX] = (uint32_t)dt;
-      state[_pf_prevR].pfTicks = (uint32_t)dt;
-      _pf_lastStart = _pf_rd0; _pf_rd0 = 0;
-    }
-#endif
+    pf.read_ends(state);
     if (X.boxes != nullptr) edge_between_reads();
     if (l == 0) s_next = atomicAdd(queue, 1u);
     WSYNC();
     const uint32_t qi = s_next;
     if (qi >= n_work) break;
     X.qi = qi;
-#ifdef TALC_PROF
-    _pf_rd0 = __builtin_amdgcn_s_memrealtime();
-#endif
     PROF_BEGIN2();
     const uint32_t r = order[qi];
-#ifdef TALC_PROF
-    if (l == 0) state[r].pfStart = (uint32_t)_pf_rd0;
-#endif
-#ifdef TALC_PROF
-    _pf_prevQi = qi; _pf_prevR = r;
-#endif
-    const uint64_t rb = offsets[r];
-    const uint32_t L = (uint32_t)(offsets[r + 1] - rb);
+    pf.read_begins(state, qi, r);
+    ReadState* const rs = state + r;
     uint8_t* out = outAll + outoff[r];
     const uint32_t outCap = (uint32_t)(outoff[r + 1] - outoff[r]);
-    ReadState st = state[r];
-    X.read = codes + rb; X.L = L; X.n = L >= P.K ? L - P.K + 1 : 0; X.cov = covAll + koff[r]; X.covw = covWords + cov_word_base(koff[r], r); X.headCov = headCovAll + (uint64_t)r * kHeadCov; X.lambda = st.lambda;
-    X.cells = 0; X.steps = 0; X.overflow = 0; X.complexRegion = false; X.ffPopped = false;
-    X.tracing = (trace.recs != nullptr) && (r == traceRead);
-    X.traceSteps = X.tracing && (trace.steps != 0);
-
-    if (st.status != TALC_READ_CORRECTED || st.overflow) {
-      // not corrected: pass the (encoded) read through (main.cpp:310 writes mySeqs[r] unchanged)
-      copy_bytes(out, X.read, L, false);
-      if (l == 0) { state[r].outLen = L; }
-      continue;
-    }
-    const uint32_t K = P.K;
+    const ReadState st = *rs;
+    if (!begin_read(r, st, C.regCap, codes, offsets, koff, covAll, covWords, headCovAll, regions, regoff, trace, traceRead)) { pass_through(out, rs, 0u); continue; }
     const uint32_t R = st.nRegions;
-    if (R > C.regCap) { X.overflow |= OVF_REGIONS; }
-    else {
-      const uint32_t* gS = regions + 3 * regoff[r];
-      const uint32_t gCap = (uint32_t)(regoff[r + 1] - regoff[r]);
-      const uint32_t* gE = gS + gCap;
-      const uint32_t* gH = gE + gCap;
-      for (uint32_t i = l; i < R; i += 64) { X.regS[i] = gS[i]; X.regE[i] = gE[i]; X.regH[i] = gH[i]; X.wLen[i] = 0xFFFFFFFFu; X.wOff[i] = 0; }
-    }
-    WSYNC();
     uint32_t weakUsed = 0;
-#ifdef TALC_PROF
-    uint32_t _pf_edge = 0; unsigned long long _pf_e0 = 0; (void)_pf_e0;
-#endif
     PROF_END2(PF_PROLOG);
-    // head / tail presence as set by setInitialStructure (Read.cpp:223-237)
-    bool headPresent = false, tailPresent = false;
-    uint32_t headLen = 0, tailLen = 0;
-    bool headCorr = false, tailCorr = false;
-    uint32_t headOff = 0, headCLen = 0, tailOff = 0, tailCLen = 0;
+    Piece head = {nullptr, 0}, tail = head;
     if (!X.overflow) {
-      headPresent = X.regS[0] > 0; headLen = X.regS[0];
-      const uint32_t eLast = X.regE[R - 1];
-      tailPresent = (eLast + 1 < X.n); tailLen = tailPresent ? (L - (eLast + K)) : 0;
-      // ---- inner regions (Read.cpp:346-360)
-      for (uint32_t reg = 0; reg + 1 < R && !X.overflow; ++reg) {
-        uint32_t wo = 0, wl = 0;
-        bool success = false;
-        for (int attempt = 0; attempt < 2 && !success && !X.overflow; ++attempt) {
-          // initializeINNER (Explorer.cpp:228-243)
-          X.location = LOC_INNER; X.dirRight = (attempt == 0) ? 1 : 0;
-          X.Ls = X.regS[reg]; X.Le = X.regE[reg]; X.Rs = X.regS[reg + 1]; X.Re = X.regE[reg + 1];
-          X.LH = X.regH[reg]; X.RH = X.regH[reg + 1];
-          X.weakLen = (X.Rs > X.Le + K) ? (X.Rs - (X.Le + K)) : 0;
-          // (the LEFT attempt after a failed RIGHT one starts from the same two regions — a failed search changes
-          //  neither — so anchorLEFTHandSide / anchorRIGHTHandSide, Explorer.cpp:239-240, would return the lists again)
-          if (attempt == 0) { build_anchors(0); build_anchors(1); }
-          if (uni((int)X.tracing)) trace_search_cold();
-          PROF_BEGIN2(); success = search_bridge(wo, wl, weakUsed); PROF_END2(PF_SRCHB);
-          if (uni((int)X.tracing)) {
-            if (success) trace_rec(TR_RESULT, 1, 1, (int)X.Le, (int)X.Rs, 0.0, X.weak + wo, wl, false);
-            else trace_rec(TR_RESULT, 1, 0, (int)X.regE[reg], (int)X.regS[reg + 1], 0.0, X.read + X.regE[reg] + K, X.weakLen, false);
-          }
-        }
-        // updateINNER (Read.cpp:294-303)
-        WSYNC();
-        // (a region's start only ever moves inward: its hit index moves with it)
-        if (success && l == 0) { X.regE[reg] = X.Le; X.regH[reg + 1] += X.Rs - X.regS[reg + 1]; X.regS[reg + 1] = X.Rs; X.wOff[reg] = wo; X.wLen[reg] = wl; }
-        WSYNC();
-      }
-      // ---- head (Read.cpp:361-367)
-      if (!X.overflow && headPresent && headLen <= P.MAX_BORDER_LEN) {
-        X.location = LOC_HEAD; X.dirRight = 0;
-        X.Rs = X.regS[0]; X.Re = X.regE[0]; X.Ls = 0; X.Le = 0; X.RH = X.regH[0]; X.LH = 0;
-        X.weakLen = X.Rs;
-        X.nAncL = 0;
-        build_anchors(1);
-        if (uni((int)X.tracing)) trace_search_cold();
-        PROF_BEGIN2(); PF_EDGE_T0(); headCorr = search_edge(headOff, headCLen, weakUsed); PF_EDGE_T1(); PROF_END2(PF_SRCHE);
-        if (uni((int)X.tracing)) {
-          if (headCorr) trace_rec(TR_RESULT, 0, 1, 0, (int)X.Rs, 0.0, X.weak + headOff, headCLen, false);
-          else trace_rec(TR_RESULT, 0, 0, 0, (int)X.regS[0], 0.0, X.read, X.weakLen, false);
-        }
-        WSYNC();
-        if (headCorr && l == 0) { X.regH[0] += X.Rs - X.regS[0]; X.regS[0] = X.Rs; }   // updateHEAD (Read.cpp:305-311)
-        WSYNC();
-      }
-      // ---- tail (Read.cpp:368-374)
-      if (!X.overflow && tailPresent && tailLen <= P.MAX_BORDER_LEN) {
-        X.location = LOC_TAIL; X.dirRight = 1;
-        X.Ls = X.regS[R - 1]; X.Le = X.regE[R - 1]; X.Rs = 0; X.Re = 0; X.LH = X.regH[R - 1]; X.RH = 0;
-        X.weakLen = L - (X.Le + K);
-        X.nAncR = 0;
-        build_anchors(0);
-        if (uni((int)X.tracing)) trace_search_cold();
-        PROF_BEGIN2(); PF_EDGE_T0(); tailCorr = search_edge(tailOff, tailCLen, weakUsed); PF_EDGE_T1(); PROF_END2(PF_SRCHE);
-        if (uni((int)X.tracing)) {
-          if (tailCorr) trace_rec(TR_RESULT, 2, 1, (int)X.Le, 0, 0.0, X.weak + tailOff, tailCLen, false);
-          else trace_rec(TR_RESULT, 2, 0, (int)X.regE[R - 1], 0, 0.0, X.read + X.regE[R - 1] + K, X.weakLen, false);
-        }
-        WSYNC();
-        if (tailCorr && l == 0) X.regE[R - 1] = X.Le;   // updateTAIL (Read.cpp:313-318)
-        WSYNC();
-      }
+      // head and tail as set by setInitialStructure (Read.cpp:223-237): what lies before the first region and after the last
+      const uint32_t tailLen = X.L - (X.regE[R - 1] + P.K);
+      head = uni_piece(X.read, X.regS[0]); tail = uni_piece(X.read + (X.L - tailLen), tailLen);
+      for (uint32_t reg = 0; reg + 1 < R && !X.overflow; ++reg) correct_inner(reg, weakUsed);
+      if (!X.overflow && head.n > 0 && head.n <= P.MAX_BORDER_LEN) correct_border<LOC_HEAD>(head, R, weakUsed, pf);
+      if (!X.overflow && tail.n > 0 && tail.n <= P.MAX_BORDER_LEN) correct_border<LOC_TAIL>(tail, R, weakUsed, pf);
     }
     totCells += X.cells; totSteps += X.steps;
-#ifdef TALC_PROF
-    if (l == 0) { state[r].pfSteps = (uint32_t)X.steps; state[r].pfEdgeTicks = _pf_edge; state[r].pfAnchors = g_prof[PF_RANCH]; state[r].pfAnchorMax = g_prof[PF_RANCHMAX]; g_prof[PF_RANCH] = 0; g_prof[PF_RANCHMAX] = 0;
-                  state[r].pfBridges = g_prof[PF_RBR]; state[r].pfBridgeMax = g_prof[PF_RBRMAX]; g_prof[PF_RBR] = 0; g_prof[PF_RBRMAX] = 0; }
-#endif
-    if (X.overflow) {
-      copy_bytes(out, X.read, L, false);
-      if (l == 0) { state[r].outLen = L; state[r].overflow = X.overflow; }
-      continue;
-    }
-    // ---- updateCorrSeq (Read.cpp:320-326): head + (solid, weak)* + solid + tail
-    // total length first
-    unsigned long long total = 0;
-    total += headPresent ? (headCorr ? headCLen : headLen) : 0;
-    {
-      unsigned long long part = 0;
-      for (uint32_t i = l; i < R; i += 64) {
-        part += (unsigned long long)X.regE[i] + K - X.regS[i];
-        if (i + 1 < R) {
-          if (X.wLen[i] != 0xFFFFFFFFu) part += X.wLen[i];
-          else part += (X.regS[i + 1] > X.regE[i] + K) ? (X.regS[i + 1] - (X.regE[i] + K)) : 0;
-        }
-      }
-      total += wave_sum_u64(part);
-    }
-    total += tailPresent ? (tailCorr ? tailCLen : tailLen) : 0;
-    if (total > outCap) {
-      copy_bytes(out, X.read, L, false);
-      if (l == 0) { state[r].outLen = L; state[r].overflow = OVF_OUT; }
-      continue;
-    }
-    uint32_t pos = 0;
+    pf.read_searched(state);
+    if (X.overflow) { pass_through(out, rs, X.overflow); continue; }
+    if (corrected_length(head, tail, R) > outCap) { pass_through(out, rs, OVF_OUT); continue; }
     PROF_BEGIN2();
-    if (headPresent) {
-      if (headCorr) { copy_bytes(out + pos, X.weak + headOff, headCLen, false); pos += headCLen; }
-      else { copy_bytes(out + pos, X.read, headLen, false); pos += headLen; }
-    }
-    for (uint32_t i = 0; i < R; ++i) {
-      const uint32_t s = X.regS[i], e = X.regE[i];
-      const uint32_t sl = e + K - s;
-      copy_bytes(out + pos, X.read + s, sl, false); pos += sl;
-      if (i + 1 < R) {
-        if (X.wLen[i] != 0xFFFFFFFFu) { copy_bytes(out + pos, X.weak + X.wOff[i], X.wLen[i], false); pos += X.wLen[i]; }
-        else if (X.regS[i + 1] > e + K) { const uint32_t wl = X.regS[i + 1] - (e + K); copy_bytes(out + pos, X.read + e + K, wl, false); pos += wl; }
-      }
-    }
-    if (tailPresent) {
-      if (tailCorr) { copy_bytes(out + pos, X.weak + tailOff, tailCLen, false); pos += tailCLen; }
-      else { copy_bytes(out + pos, X.read + (L - tailLen), tailLen, false); pos += tailLen; }
-    }
-    {   // Read.cpp:423 on the regions as correct2 leaves them
-      unsigned long long part = 0;
-      for (uint32_t i = l; i < R; i += 64) part += (unsigned long long)X.regE[i] - X.regS[i] + 1;
-      const uint32_t span = (uint32_t)wave_sum_u64(part);
-      if (l == 0) { state[r].outLen = pos; state[r].inSpan = span; }
-    }
+    reassemble(out, head, tail, R, rs);
     PROF_END2(PF_ASSEMBLE);
   }
   // no reads left: run published anchors of the edge searches still going on, until every read is finished
-#ifdef TALC_PROF
-  _pf_loopEnd = __builtin_amdgcn_s_memrealtime();
-  if (l == 0) atomicMin((unsigned long long*)&counters[kCntQueueDry], _pf_loopEnd);   // the first wave to find the queue dry
-#endif
-  if (X.boxes != nullptr && blockIdx.x % lingerMod == 0u) {
-#ifdef TALC_PROF
-    _pf_idle =
-#endif
-    edge_linger(n_work);
-  }
+  pf.queue_dry(counters);
+  if (X.boxes != nullptr && blockIdx.x % lingerMod == 0u) pf.lingered(edge_linger(n_work));
   totCells += X.moreCells; totSteps += X.moreSteps;
   if (l == 0) {
     if (totSteps) atomicAdd((unsigned long long*)&counters[kCntSteps], totSteps);
     if (totCells) atomicAdd((unsigned long long*)&counters[kCntCells], totCells);
-#ifdef TALC_PROF
-    g_prof[PF_TOTAL] = (uint32_t)(__builtin_amdgcn_s_memtime() - _pf_k0);
-    g_prof[PF_XSTAGE] = g_wprof[0]; g_prof[PF_XLEV] = g_wprof[1]; g_prof[PF_XSEL] = g_wprof[2]; g_prof[PF_XNLEV] = g_wprof[3];
-    {   // wave utilisation of the launch: sum of the waves' lifetimes against (last end - first start) x waves
-      const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-      atomicAdd((unsigned long long*)&counters[kCntBusy], r1 - _pf_r0 - _pf_idle);
-      atomicMin((unsigned long long*)&counters[kCntFirstStart], _pf_r0);
-      atomicMax((unsigned long long*)&counters[kCntLastEnd], r1);
-      // the wave's last read: (queue position, read), (its start, the wave's end) — TALC_PROF_SLOW prints the waves that end last
-      if (_pf_rd0) state[_pf_prevR].pfTicks = (uint32_t)(r1 - _pf_rd0);
-      if (blockIdx.x < kCntMaxWaves) {
-        counters[kCntWaveLog + 2 * blockIdx.x] = ((unsigned long long)_pf_prevQi << 32) | _pf_prevR;
-        counters[kCntWaveLog + 2 * blockIdx.x + 1] = ((_pf_lastStart & 0xFFFFFFFFull) << 32) | (_pf_loopEnd & 0xFFFFFFFFull);   // (the end of its last read, not of its stay)
-      }
-    }
-    for (int i = 0; i < PF_N; ++i) {
-      if (i == PF_RDMAX) atomicMax((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
-      else atomicAdd((unsigned long long*)&counters[kCntProf0 + i], (unsigned long long)g_prof[i]);
-    }
-#endif
+    pf.wave_ends(state, counters);
   }
 }
 
