@@ -227,6 +227,7 @@ int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64
 // lines below MIN_COUNT themselves), `kept` = how many reach MIN_COUNT (sizes the tables).  Takes ownership of dK / dC.
 static int build_table_from_device_arrays(DevBuf<uint64_t> dK, DevBuf<uint32_t> dC, uint64_t n, uint64_t kept, const talc_params* p, int device,
                                           talc_table** out, double h2d_seconds, double h2d_megabytes, const Switches& sw) {
+  if (n >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "the device builder takes fewer than 2^32-2 entries");   // (a bid is index + 1 < 0xFFFFFFFF)
   auto t = std::make_unique<talc_table>();
   t->h.p = *p;
   {   // (sparser than load 0.5 when the device has the room: HostTable::capacity_for)
@@ -251,13 +252,17 @@ static int build_table_from_device_arrays(DevBuf<uint64_t> dK, DevBuf<uint32_t> 
   HIPCHK(hipMemset(dR.get(), 0xFF, bytes)); HIPCHK(hipMemset(dL.get(), 0xFF, bytes)); HIPCHK(hipMemset(dStats.get(), 0, 3 * 8));
   HIPCHK(hipDeviceSynchronize());
   const auto td2 = tnow();
+  // claim, resolve, finalize, write.  Finalize comes before the counts are written: a stored count may be any value from
+  // MIN_COUNT to 0xFFFFFFFF, a bid may not be 0xFFFFFFFF.  Without lines there is only the finalize pass.
+  const unsigned nb = (unsigned)((n + 255) / 256), nbCap = (unsigned)((cap + 255) / 256);
   if (n) {
-    const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_build_claim, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), cap, p->k, dK.get(), dC.get(), n, p->min_count, dSR.get(), dSL.get());
     hipLaunchKernelGGL(k_build_resolve, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), p->k, dK.get(), n, dSR.get(), dSL.get());
+    hipLaunchKernelGGL(k_build_finalize, dim3(nbCap), dim3(256), 0, 0, dR.get(), dL.get(), cap, dStats.get());
     hipLaunchKernelGGL(k_build_write, dim3(nb), dim3(256), 0, 0, dR.get(), dL.get(), p->k, dK.get(), dC.get(), n, dSR.get(), dSL.get());
+  } else {
+    hipLaunchKernelGGL(k_build_finalize, dim3(nbCap), dim3(256), 0, 0, dR.get(), dL.get(), cap, dStats.get());
   }
-  hipLaunchKernelGGL(k_build_finalize, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, dR.get(), dL.get(), cap, dStats.get());
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   unsigned long long st[3];

@@ -7,8 +7,10 @@
 //             probing from the same home slot the lookups use) and bids for its count slot with atomicMin(index+1)
 //             — the count words, preset to 0xFFFFFFFF, hold the smallest bidding index after this pass;
 //   resolve   an entry whose index is not the one left in the slot lost to an earlier line: it forgets its slot;
-//   write     the winners store their counts;
-//   finalize  untouched count words and colour fields become 0; stored k-mers and buckets are counted.
+//   finalize  untouched count words (still 0xFFFFFFFF: a bid is index + 1 of fewer than 2^32 - 2 entries, never that
+//             value) and colour fields become 0; the count words that hold a bid (each gets a count >= MIN_COUNT >= 1)
+//             and the buckets are counted;
+//   write     the winners store their counts — any value, 0xFFFFFFFF included, which is why finalize runs first.
 // Bucket placement along a probe sequence depends on the order the CASes land in, which is not the host builder's
 // order; lookups do not depend on it (no deletions, probing stops at the first empty bucket).
 #pragma once
@@ -67,7 +69,8 @@ __global__ void k_build_write(Bucket* right, Bucket* left, uint32_t K, const uin
   if (sl != kNoSlot) left[sl].cnt[(km >> (2 * (K - 1))) & 3] = counts[i];
 }
 
-// stats: [0] stored k-mers (RIGHT table), [1] buckets RIGHT, [2] buckets LEFT
+// stats: [0] stored k-mers (RIGHT table), [1] buckets RIGHT, [2] buckets LEFT.  Runs between resolve and write: a count
+// word is 0xFFFFFFFF (no entry bid for it) or the winning bid.
 __global__ void k_build_finalize(Bucket* right, Bucket* left, uint64_t cap, unsigned long long* stats) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long nk = 0, nr = 0, nl = 0;
