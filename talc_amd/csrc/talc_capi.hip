@@ -44,42 +44,60 @@ static int fail(int code, const char* fmt, ...) {
     if (_e != hipSuccess) return fail(TALC_ERR_DEVICE, "%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
 
+// seconds on the steady clock, since the start or since the last lap (where a build's wall time goes, TALC_TIMING)
+struct Stopwatch {
+  using Clock = std::chrono::steady_clock;
+  Clock::time_point t0 = Clock::now();
+  double seconds() const { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+  double lap() { const auto t1 = Clock::now(); const double s = std::chrono::duration<double>(t1 - t0).count(); t0 = t1; return s; }
+};
+
 // The table lives where it was built.  A host-built table has a host image (h.right / h.left) that uploads copy; a
 // table built (or imported) on a GPU has a *staged* device image there — colouring and de-colouring run on it as
 // kernels, talc_table_upload to that same GPU adopts it without any copy, and the host image is only materialised
 // when something asks for it (host lookups, an upload to another GPU).
-struct DeviceImage {   // what one upload allocated; h.dev[device] (DeviceCopy) is the view of it that the host-only code knows
+struct DeviceImage {   // everything the table owns on one GPU
   DevBuf<Bucket> right, left;
-  DevBuf<uint64_t> filter;
-  DevBuf<WalkEntry> walkRight, walkLeft;
+  DevBuf<uint64_t> filter;                 // presence filter of filterWords words
+  uint64_t filterWords = 0;
+  DevBuf<WalkEntry> walkRight, walkLeft;   // optional (talc_table_upload decides)
+  // staged (buckets only: built or imported, still editable) until an upload derives the filter, the in-degree bits in
+  // the RIGHT keys and perhaps the walk tables
+  bool uploaded() const { return (bool)filter; }
+  void drop_derived() { filter.reset(); filterWords = 0; walkRight.reset(); walkLeft.reset(); }   // staged again
+  uint64_t bytes(uint64_t capacity) const { return 2 * capacity * sizeof(Bucket) + filterWords * 8 + (walkRight ? 2 * capacity * sizeof(WalkEntry) : 0); }
+  TableView view(uint64_t capacity, uint32_t k) const { return TableView{right.get(), left.get(), capacity, k, filter.get(), filterWords, walkRight.get(), walkLeft.get()}; }
 };
 struct talc_table {
   HostTable h;
   bool hostValid = true;       // h.right / h.left hold the current table
-  int stagedDev = -1;          // GPU holding the built, not yet uploaded image (-1: none)
-  DevBuf<Bucket> stR, stL;
-  std::map<int, DeviceImage> images;   // device -> the uploaded copy
-  ~talc_table() {
-    for (auto& kv : images) { (void)hipSetDevice(kv.first); kv.second = DeviceImage(); }
-    if (stagedDev >= 0) (void)hipSetDevice(stagedDev);
+  // device -> its image.  A device build or an import leaves one staged image, uploads leave uploaded ones; every image
+  // holds the current table (a staged one is the only place edits go, and nothing is edited once an upload has happened)
+  using Images = std::map<int, DeviceImage>;
+  Images images;
+  ~talc_table() { for (auto& kv : images) { (void)hipSetDevice(kv.first); kv.second = DeviceImage(); } }
+  // (device, image) on `device`, or on whichever GPU has one; nullptr when there is none
+  Images::value_type* image(int device) { auto it = images.find(device); return it == images.end() ? nullptr : &*it; }
+  Images::value_type* any_image() { return images.empty() ? nullptr : &*images.begin(); }
+  const DeviceImage* first_uploaded() const {
+    for (auto& kv : images) if (kv.second.uploaded()) return &kv.second;
+    return nullptr;
   }
+  bool frozen() const { return first_uploaded() != nullptr; }   // some upload has happened: the table is immutable
 };
 
-// make the host image current (device-built tables: copy it back from the GPU that holds it)
+// make the host image current (device-built tables: copy it back from a GPU that holds it)
 static int ensure_host(talc_table* t) {
   if (t->hostValid) return TALC_OK;
-  const Bucket *srcR = nullptr, *srcL = nullptr;
-  int dev = -1;
-  if (t->stagedDev >= 0) { srcR = t->stR.get(); srcL = t->stL.get(); dev = t->stagedDev; }
-  else if (!t->h.dev.empty()) { srcR = t->h.dev.begin()->second.right; srcL = t->h.dev.begin()->second.left; dev = t->h.dev.begin()->first; }
-  if (!srcR) return fail(TALC_ERR_STATE, "the table has neither a host image nor a device image");
+  auto* at = t->any_image();
+  if (!at) return fail(TALC_ERR_STATE, "the table has neither a host image nor a device image");
   const uint64_t bytes = t->h.capacity * sizeof(Bucket);
   if (!t->h.right) t->h.right = (Bucket*)malloc(bytes);
   if (!t->h.left) t->h.left = (Bucket*)malloc(bytes);
   if (!t->h.right || !t->h.left) return fail(TALC_ERR_NOMEM, "cannot allocate the host image (%llu bytes)", (unsigned long long)(2 * bytes));
-  HIPCHK(hipSetDevice(dev));
-  HIPCHK(hipMemcpy(t->h.right, srcR, bytes, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(t->h.left, srcL, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipSetDevice(at->first));
+  HIPCHK(hipMemcpy(t->h.right, at->second.right.get(), bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(t->h.left, at->second.left.get(), bytes, hipMemcpyDeviceToHost));
   t->hostValid = true;
   return TALC_OK;
 }
@@ -206,14 +224,23 @@ static int check_params(const talc_params* p) {
 }
 
 // ------------------------------------------------------------------ table
+// Tables travel between the builders as unique_ptr; a raw talc_table* exists only where one crosses the ABI.
+using TablePtr = std::unique_ptr<talc_table>;
+
+// the dump lines at or above MIN_COUNT: what a table of these lines stores, duplicates aside (sizes the tables)
+static uint64_t count_kept(const uint32_t* counts, uint64_t n, uint32_t min_count) {
+  uint64_t kept = 0;
+#pragma omp parallel for reduction(+ : kept)
+  for (long i = 0; i < (long)n; ++i) kept += counts[i] >= min_count ? 1 : 0;
+  return kept;
+}
+
 int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64_t n, const talc_params* p,
                            talc_table** out) {
   int rc = check_params(p);
   if (rc) return rc;
   if (!out || (n && (!kmers || !counts))) return fail(TALC_ERR_INVALID, "null argument");
-  uint64_t kept = 0;
-#pragma omp parallel for reduction(+ : kept)
-  for (long i = 0; i < (long)n; ++i) kept += counts[i] >= p->min_count ? 1 : 0;
+  const uint64_t kept = count_kept(counts, n, p->min_count);
   auto t = std::make_unique<talc_table>();
   t->h.p = *p;
   if (!t->h.allocate(kept, read_switches().tableSlotsX10)) return fail(TALC_ERR_NOMEM, "cannot allocate host table for %llu k-mers", (unsigned long long)kept);
@@ -222,36 +249,29 @@ int talc_table_from_arrays(const uint64_t* kmers, const uint32_t* counts, uint64
   return TALC_OK;
 }
 
-// the table built on `device` (talc_kernels_build.h); the image stays there (staged) until talc_table_upload adopts it
-// the device builder's core: n dump lines as device arrays dK / dC (line i of the dump at index i; the kernels drop the
-// lines below MIN_COUNT themselves), `kept` = how many reach MIN_COUNT (sizes the tables).  Takes ownership of dK / dC.
+// The device builder's core (talc_kernels_build.h): n dump lines as device arrays dK / dC (line i of the dump at index i;
+// the kernels drop the lines below MIN_COUNT themselves), `kept` = how many reach MIN_COUNT (sizes the tables).  Takes
+// ownership of dK / dC.  The image stays on `device`, staged, until talc_table_upload adopts it.
 static int build_table_from_device_arrays(DevBuf<uint64_t> dK, DevBuf<uint32_t> dC, uint64_t n, uint64_t kept, const talc_params* p, int device,
-                                          talc_table** out, double h2d_seconds, double h2d_megabytes, const Switches& sw) {
+                                          TablePtr& out, double h2d_seconds, double h2d_megabytes, const Switches& sw) {
   if (n >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "the device builder takes fewer than 2^32-2 entries");   // (a bid is index + 1 < 0xFFFFFFFF)
   auto t = std::make_unique<talc_table>();
   t->h.p = *p;
-  {   // (sparser than load 0.5 when the device has the room: HostTable::capacity_for)
-    hipDeviceProp_t prop;
-    uint64_t devBytes = 0;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) devBytes = (uint64_t)prop.totalGlobalMem;
-    t->h.capacity = HostTable::capacity_for(kept, devBytes, sw.tableSlotsX10);
-  }
+  hipDeviceProp_t prop;   // (sparser than load 0.5 when the device has the room: HostTable::capacity_for)
+  const uint64_t devBytes = hipGetDeviceProperties(&prop, device) == hipSuccess ? (uint64_t)prop.totalGlobalMem : 0;
+  t->h.capacity = HostTable::capacity_for(kept, devBytes, sw.tableSlotsX10);
   if (t->h.capacity >= (1ULL << 32)) return fail(TALC_ERR_NOMEM, "table of %llu k-mers exceeds 2^32 buckets", (unsigned long long)kept);
   t->hostValid = false;
   const uint64_t cap = t->h.capacity, bytes = cap * sizeof(Bucket);
-  DevBuf<uint32_t> dSR, dSL;
-  DevBuf<unsigned long long> dStats;
-  DevBuf<Bucket> dR, dL;
-  auto tnow = []() { return std::chrono::steady_clock::now(); };
-  auto tsec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  const auto td1 = tnow();
+  DevBuf<uint32_t> dSR, dSL; DevBuf<unsigned long long> dStats; DevBuf<Bucket> dR, dL;
+  Stopwatch watch;
   HIPCHK(hipSetDevice(device));
   HIPCHK(dR.alloc(cap)); HIPCHK(dL.alloc(cap));
   HIPCHK(dSR.alloc(std::max<uint64_t>(n, 1))); HIPCHK(dSL.alloc(std::max<uint64_t>(n, 1)));
   HIPCHK(dStats.alloc(3));
   HIPCHK(hipMemset(dR.get(), 0xFF, bytes)); HIPCHK(hipMemset(dL.get(), 0xFF, bytes)); HIPCHK(hipMemset(dStats.get(), 0, 3 * 8));
   HIPCHK(hipDeviceSynchronize());
-  const auto td2 = tnow();
+  const double tClear = watch.lap();
   // claim, resolve, finalize, write.  Finalize comes before the counts are written: a stored count may be any value from
   // MIN_COUNT to 0xFFFFFFFF, a bid may not be 0xFFFFFFFF.  Without lines there is only the finalize pass.
   const unsigned nb = (unsigned)((n + 255) / 256), nbCap = (unsigned)((cap + 255) / 256);
@@ -267,13 +287,14 @@ static int build_table_from_device_arrays(DevBuf<uint64_t> dK, DevBuf<uint32_t> 
   HIPCHK(hipDeviceSynchronize());
   unsigned long long st[3];
   HIPCHK(hipMemcpy(st, dStats.get(), 3 * 8, hipMemcpyDeviceToHost));
-  const auto td3 = tnow();
+  const double tKernels = watch.lap();
   dK.reset(); dC.reset(); dSR.reset(); dSL.reset(); dStats.reset();   // (before the caller colours: only the image stays)
   if (sw.timing) fprintf(stderr, "[talc-lib] device build: %.0f MB to the device %.3f s, table allocations + clears %.3f s, kernels %.3f s, frees %.3f s\n",
-                      h2d_megabytes, h2d_seconds, tsec(td1, td2), tsec(td2, td3), tsec(td3, tnow()));
-  t->stagedDev = device; t->stR = std::move(dR); t->stL = std::move(dL);
+                      h2d_megabytes, h2d_seconds, tClear, tKernels, watch.lap());
+  DeviceImage& staged = t->images[device];
+  staged.right = std::move(dR); staged.left = std::move(dL);
   t->h.nkmers = st[0]; t->h.nbuckets_right = st[1]; t->h.nbuckets_left = st[2];
-  *out = t.release();
+  out = std::move(t);
   return TALC_OK;
 }
 
@@ -282,18 +303,18 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
   int rc = check_params(p);
   if (rc) return rc;
   if (!out || (n && (!kmers || !counts))) return fail(TALC_ERR_INVALID, "null argument");
-  if (n >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "the device builder takes fewer than 2^32-2 entries");
-  uint64_t kept = 0;
-#pragma omp parallel for reduction(+ : kept)
-  for (long i = 0; i < (long)n; ++i) kept += counts[i] >= p->min_count ? 1 : 0;
+  const uint64_t kept = count_kept(counts, n, p->min_count);
   DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
-  const auto t0 = std::chrono::steady_clock::now();
+  Stopwatch watch;
   HIPCHK(hipSetDevice(device));
   HIPCHK(hip_runtime_start());
   HIPCHK(dK.alloc(std::max<uint64_t>(n, 1))); HIPCHK(dC.alloc(std::max<uint64_t>(n, 1)));
   if (n) { HIPCHK(hipMemcpy(dK.get(), kmers, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dC.get(), counts, n * 4, hipMemcpyHostToDevice)); }
-  const double h2d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return build_table_from_device_arrays(std::move(dK), std::move(dC), n, kept, p, device, out, h2d, (double)n * 12 / 1e6, read_switches());
+  const double h2d = watch.seconds();
+  TablePtr t;
+  if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), n, kept, p, device, t, h2d, (double)n * 12 / 1e6, read_switches()))) return rc;
+  *out = t.release();
+  return TALC_OK;
 }
 
 // The text dump parsed ON the device (talc_kernels_build.h): the file's bytes are read by a few host threads into
@@ -301,7 +322,7 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
 // a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory):
 // the caller then parses on the host, as before.
 static int parse_on_host_instead() { (void)hipGetLastError(); return 1; }   // (an allocation or a copy failed: no error is left behind)
-static int table_from_text_on_device(const char* path, const talc_params* p, int device, talc_table** out, DumpStats& ds, const Switches& sw) {
+static int table_from_text_on_device(const char* path, const talc_params* p, int device, TablePtr& out, DumpStats& ds, const Switches& sw) {
   struct stat sb;
   if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
   const uint64_t size = (uint64_t)sb.st_size;
@@ -314,8 +335,7 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
     fclose(f);
     if (jfLooksLike(head, got)) return 1;
   }
-  const auto t0 = std::chrono::steady_clock::now();
-  auto secs = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+  Stopwatch watch;
   if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
   DevBuf<uint8_t> dText;
   if (dText.alloc(size + 64) != hipSuccess) return parse_on_host_instead();
@@ -345,9 +365,8 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
     if (fd >= 0) close(fd);
   }
   if (err.load()) return parse_on_host_instead();
-  const double tUp = secs(t0);
+  const double tUp = watch.lap();
   // ---- lines per tile, the tiles' first line numbers, the lines themselves
-  const auto t1 = std::chrono::steady_clock::now();
   const uint64_t ntiles = (size + kParseTile - 1) / kParseTile;
   DevBuf<uint32_t> dCount; DevBuf<uint64_t> dFirst; DevBuf<ParseStats> dPS;
   DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
@@ -371,16 +390,17 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
     return 1;
   }
   if (sw.timing) fprintf(stderr, "[talc-lib] dump parsed on the device: %.0f MB of text to the device in %.3f s (%d reader threads), %llu lines parsed in %.3f s\n",
-                      (double)size / 1e6, tUp, T, (unsigned long long)nlines, secs(t1));
+                      (double)size / 1e6, tUp, T, (unsigned long long)nlines, watch.seconds());
   ds.nread += (int64_t)nlines; ds.nkept += (int64_t)ps.kept;
   return build_table_from_device_arrays(std::move(dK), std::move(dC), nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
 }
 
 // Junction colouring (Jellyfish.cpp:273-290) on the staged device image: last line wins, both strands.
-static int colour_on_device(talc_table* t, const uint64_t* jkmers, const int64_t* jcounts, uint64_t n) {
+static int colour_on_device(talc_table* t, talc_table::Images::value_type& staged, const uint64_t* jkmers, const int64_t* jcounts, uint64_t n) {
   if (n == 0) return TALC_OK;
   if (n >= (1ull << 31)) return fail(TALC_ERR_INVALID, "the device colouring takes fewer than 2^31 junction lines");
-  HIPCHK(hipSetDevice(t->stagedDev));
+  HIPCHK(hipSetDevice(staged.first));
+  Bucket *right = staged.second.right.get(), *left = staged.second.left.get();
   uint64_t hsize = 1024;
   while (hsize < 4 * n) hsize *= 2;   // two bids per line at most: load <= 0.5
   DevBuf<uint64_t> dJ, dIds; DevBuf<int64_t> dC; DevBuf<unsigned long long> dHK; DevBuf<uint32_t> dHS;
@@ -389,18 +409,18 @@ static int colour_on_device(talc_table* t, const uint64_t* jkmers, const int64_t
   HIPCHK(hipMemcpy(dJ.get(), jkmers, n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dC.get(), jcounts, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dHK.get(), 0xFF, hsize * 8)); HIPCHK(hipMemset(dHS.get(), 0, hsize * 4));
   const unsigned nb = (unsigned)((2 * n + 255) / 256);
-  hipLaunchKernelGGL(k_colour_claim, dim3(nb), dim3(256), 0, 0, t->stR.get(), t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, t->h.p.coloured_count_thr,
+  hipLaunchKernelGGL(k_colour_claim, dim3(nb), dim3(256), 0, 0, right, t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, t->h.p.coloured_count_thr,
                      dIds.get(), dHK.get(), dHS.get(), hsize - 1);
-  hipLaunchKernelGGL(k_colour_write, dim3(nb), dim3(256), 0, 0, t->stR.get(), t->stL.get(), t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, dIds.get(), dHK.get(), dHS.get(),
+  hipLaunchKernelGGL(k_colour_write, dim3(nb), dim3(256), 0, 0, right, left, t->h.capacity, t->h.p.k, dJ.get(), dC.get(), n, dIds.get(), dHK.get(), dHS.get(),
                      hsize - 1);
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   t->hostValid = false;
   return TALC_OK;
 }
-static int decolour_on_device(talc_table* t) {
-  HIPCHK(hipSetDevice(t->stagedDev));
-  hipLaunchKernelGGL(k_decolour_repeats, dim3(1), dim3(64), 0, 0, t->stR.get(), t->stL.get(), t->h.capacity, t->h.p.k);
+static int decolour_on_device(talc_table* t, talc_table::Images::value_type& staged) {
+  HIPCHK(hipSetDevice(staged.first));
+  hipLaunchKernelGGL(k_decolour_repeats, dim3(1), dim3(64), 0, 0, staged.second.right.get(), staged.second.left.get(), t->h.capacity, t->h.p.k);
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   t->hostValid = false;
@@ -409,7 +429,7 @@ static int decolour_on_device(talc_table* t) {
 
 // The tail every table build shares: junction colouring (Jellyfish.cpp:273-290), then the homopolymer de-colouring
 // (main.cpp:232); stats = {lines read, lines kept, malformed lines}.  Sets *out on success.
-static int table_finish(std::unique_ptr<talc_table> t, const char* junction_path, const talc_params* p, DumpStats& ds, talc_table** out,
+static int table_finish(TablePtr t, const char* junction_path, const talc_params* p, DumpStats& ds, talc_table** out,
                         int64_t stats[3]) {
   int rc;
   if (junction_path && junction_path[0]) {  // Jellyfish.cpp:273-290
@@ -439,31 +459,31 @@ static int table_build_impl(const char* dump_path, const char* junction_path, co
   DumpStats ds;
   std::string why;
   const Switches sw = read_switches();   // (TALC_TIMING: where a table build's wall time goes, on stderr)
-  const auto tb0 = std::chrono::steady_clock::now();
-  talc_table* t = nullptr;
+  Stopwatch watch;
+  TablePtr t;
   int viaDevice = 1;   // > 0: not taken
   if (device >= 0) {
-    viaDevice = table_from_text_on_device(dump_path, p, device, &t, ds, sw);
+    viaDevice = table_from_text_on_device(dump_path, p, device, t, ds, sw);
     if (viaDevice < 0) return viaDevice;
     if (viaDevice == 0 && sw.timing)
-      fprintf(stderr, "[talc-lib] dump to table on the device %.3f s (%llu lines)\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count(), (unsigned long long)ds.nread);
+      fprintf(stderr, "[talc-lib] dump to table on the device %.3f s (%llu lines)\n", watch.seconds(), (unsigned long long)ds.nread);
   }
   if (viaDevice > 0) {
     if (!parseDumpFile(dump_path, p->k, p->min_count, true, kmers, &counts, nullptr, ds, &why))
       return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", dump_path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
-    const auto tb1 = std::chrono::steady_clock::now();
-    rc = (device >= 0) ? talc_table_from_arrays_device(kmers.data(), counts.data(), kmers.size(), p, device, &t)
-                       : talc_table_from_arrays(kmers.data(), counts.data(), kmers.size(), p, &t);
-    if (sw.timing) {
-      const auto tb2 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[talc-lib] dump parse %.3f s (%llu lines), table build on %s %.3f s\n", std::chrono::duration<double>(tb1 - tb0).count(),
-              (unsigned long long)ds.nread, device >= 0 ? "the device (incl. its first HIP call)" : "the host", std::chrono::duration<double>(tb2 - tb1).count());
-    }
+    const double tParse = watch.lap();
+    talc_table* built = nullptr;   // (through the ABI's own two builders)
+    rc = (device >= 0) ? talc_table_from_arrays_device(kmers.data(), counts.data(), kmers.size(), p, device, &built)
+                       : talc_table_from_arrays(kmers.data(), counts.data(), kmers.size(), p, &built);
+    t.reset(built);
+    if (sw.timing)
+      fprintf(stderr, "[talc-lib] dump parse %.3f s (%llu lines), table build on %s %.3f s\n", tParse,
+              (unsigned long long)ds.nread, device >= 0 ? "the device (incl. its first HIP call)" : "the host", watch.seconds());
     if (rc) return rc;
   }
   std::vector<uint64_t>().swap(kmers);
   std::vector<uint32_t>().swap(counts);
-  return table_finish(std::unique_ptr<talc_table>(t), junction_path, p, ds, out, stats);
+  return table_finish(std::move(t), junction_path, p, ds, out, stats);
 }
 
 int talc_table_build(const char* dump_path, const char* junction_path, const talc_params* p, talc_table** out,
@@ -478,15 +498,15 @@ int talc_table_build_device(const char* dump_path, const char* junction_path, co
 
 int talc_table_colour(talc_table* t, const uint64_t* jkmers, const int64_t* jcounts, uint64_t n) {
   if (!t || (n && (!jkmers || !jcounts))) return fail(TALC_ERR_INVALID, "null argument");
-  if (t->h.frozen) return fail(TALC_ERR_STATE, "table already uploaded (immutable)");
-  if (t->stagedDev >= 0) return colour_on_device(t, jkmers, jcounts, n);
+  if (t->frozen()) return fail(TALC_ERR_STATE, "table already uploaded (immutable)");
+  if (auto* staged = t->any_image()) return colour_on_device(t, *staged, jkmers, jcounts, n);   // (not frozen: an image is a staged one)
   t->h.colour(jkmers, jcounts, n);
   return TALC_OK;
 }
 int talc_table_decolour_repeats(talc_table* t) {
   if (!t) return fail(TALC_ERR_INVALID, "null argument");
-  if (t->h.frozen) return fail(TALC_ERR_STATE, "table already uploaded (immutable)");
-  if (t->stagedDev >= 0) return decolour_on_device(t);
+  if (t->frozen()) return fail(TALC_ERR_STATE, "table already uploaded (immutable)");
+  if (auto* staged = t->any_image()) return decolour_on_device(t, *staged);
   t->h.decolourRepeats();
   return TALC_OK;
 }
@@ -499,79 +519,72 @@ static uint64_t filter_words_for(uint64_t nkmers, uint64_t bitsPerKmer) {
 // would make without the walk tables (whether those are built is decided then, from the free memory)
 uint64_t talc_table_device_bytes(const talc_table* t) {
   if (!t) return 0;
-  if (!t->h.dev.empty()) {
-    const DeviceCopy& dc = t->h.dev.begin()->second;
-    return 2 * t->h.capacity * sizeof(Bucket) + dc.filterWords * 8 + (dc.walkRight ? 2 * t->h.capacity * sizeof(WalkEntry) : 0);
-  }
+  if (const DeviceImage* img = t->first_uploaded()) return img->bytes(t->h.capacity);
   return 2 * t->h.capacity * sizeof(Bucket) + filter_words_for(t->h.nkmers, read_switches().filterBits) * 8;
 }
 
-int talc_table_upload(talc_table* t, int device) {
-  if (!t) return fail(TALC_ERR_INVALID, "null table");
-  if (t->h.dev.count(device)) return TALC_OK;
-  const Switches sw = read_switches();
-  const uint64_t bytes = t->h.capacity * sizeof(Bucket);
-  const bool adopt = (t->stagedDev == device);
-  // everything this call allocates is freed again when a later step fails; an adopted image stays the table's staged one
-  // until the copy is complete (a failed upload leaves the table as it was)
-  DeviceImage img;
-  DeviceCopy dc;
-  if (adopt) {   // built (or imported) on this GPU: the image is adopted as it stands
-    HIPCHK(hipSetDevice(device));
-    dc.right = t->stR.get(); dc.left = t->stL.get();
-  } else {
-    int rc = ensure_host(t);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(img.right.alloc(t->h.capacity));
-    HIPCHK(img.left.alloc(t->h.capacity));
-    dc.right = img.right.get(); dc.left = img.left.get();
-    HIPCHK(hipMemcpy(dc.right, t->h.right, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dc.left, t->h.left, bytes, hipMemcpyHostToDevice));
-  }
-  {   // presence filter, from the RIGHT table
-    dc.filterWords = filter_words_for(t->h.nkmers, sw.filterBits);
-    HIPCHK(img.filter.alloc(dc.filterWords));
-    dc.filter = img.filter.get();
-    HIPCHK(hipMemset(dc.filter, 0, dc.filterWords * 8));
-    if (t->h.capacity)
-      hipLaunchKernelGGL(k_build_filter, dim3((unsigned)((t->h.capacity + 255) / 256)), dim3(256), 0, 0, dc.right, t->h.capacity,
-                         t->h.p.k, (unsigned long long*)dc.filter, dc.filterWords);
-    HIPCHK(hipGetLastError());
-    // ... and every RIGHT bucket's in-degree into its key word (talc_common.h: the coverage kernel's left degrees)
-    if (t->h.capacity)
-      hipLaunchKernelGGL(k_build_indegree, dim3((unsigned)((t->h.capacity + 255) / 256)), dim3(256), 0, 0, dc.right, dc.left, t->h.capacity,
-                         (uint32_t)t->h.p.min_count);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-  }
+// What an upload adds to the buckets of an image on the current device: the presence filter, the in-degree bits, and the
+// walk tables when they fit.  On failure the caller drops what was made (DeviceImage::drop_derived).
+static int derive_tables(DeviceImage& img, const HostTable& h, const Switches& sw) {
+  Bucket *right = img.right.get(), *left = img.left.get();
+  const unsigned nbCap = (unsigned)((h.capacity + 255) / 256);
+  // presence filter, from the RIGHT table
+  img.filterWords = filter_words_for(h.nkmers, sw.filterBits);
+  HIPCHK(img.filter.alloc(img.filterWords));
+  HIPCHK(hipMemset(img.filter.get(), 0, img.filterWords * 8));
+  if (h.capacity)
+    hipLaunchKernelGGL(k_build_filter, dim3(nbCap), dim3(256), 0, 0, right, h.capacity, h.p.k, (unsigned long long*)img.filter.get(), img.filterWords);
+  HIPCHK(hipGetLastError());
+  // ... and every RIGHT bucket's in-degree into its key word (talc_common.h: the coverage kernel's left degrees)
+  if (h.capacity) hipLaunchKernelGGL(k_build_indegree, dim3(nbCap), dim3(256), 0, 0, right, left, h.capacity, (uint32_t)h.p.min_count);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
   // walk tables (WalkEntry, talc_common.h).  Built when they leave the correction batches and their scratch a reserve
   // (64 GB, or a quarter of the device if that is less).  TALC_WALK=0 turns them off, TALC_WALK=1 insists.
-  {
-    const uint64_t wbytes = t->h.capacity * sizeof(WalkEntry);
-    size_t freeB = 0, totalB = 0;
-    HIPCHK(hipMemGetInfo(&freeB, &totalB));
-    const uint64_t reserve = std::min<uint64_t>(64ull << 30, (uint64_t)totalB / 4);
-    const bool want = sw.walk >= 0 ? sw.walk != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
-    if (want && t->h.capacity) {
-      if (img.walkRight.alloc(t->h.capacity) != hipSuccess || img.walkLeft.alloc(t->h.capacity) != hipSuccess) {
-        (void)hipGetLastError();
-        img.walkRight.reset(); img.walkLeft.reset();
-        if (sw.walk == 1) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
-      } else {
-        dc.walkRight = img.walkRight.get(); dc.walkLeft = img.walkLeft.get();
-        const uint64_t nthr = 2 * t->h.capacity;
-        hipLaunchKernelGGL(k_build_walk, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, dc.right, dc.left, t->h.capacity,
-                           t->h.p.k, (uint32_t)t->h.p.min_count, dc.walkRight, dc.walkLeft);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-      }
-    }
+  const uint64_t wbytes = h.capacity * sizeof(WalkEntry);
+  size_t freeB = 0, totalB = 0;
+  HIPCHK(hipMemGetInfo(&freeB, &totalB));
+  const uint64_t reserve = std::min<uint64_t>(64ull << 30, (uint64_t)totalB / 4);
+  const bool want = sw.walk >= 0 ? sw.walk != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
+  if (!want || !h.capacity) return TALC_OK;
+  if (img.walkRight.alloc(h.capacity) != hipSuccess || img.walkLeft.alloc(h.capacity) != hipSuccess) {
+    (void)hipGetLastError();
+    img.walkRight.reset(); img.walkLeft.reset();
+    if (sw.walk == 1) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
+    return TALC_OK;
   }
-  if (adopt) { img.right = std::move(t->stR); img.left = std::move(t->stL); t->stagedDev = -1; }
-  t->h.dev[device] = dc;
-  t->images[device] = std::move(img);
-  t->h.frozen = true;
+  const uint64_t nthr = 2 * h.capacity;
+  hipLaunchKernelGGL(k_build_walk, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, 0, right, left, h.capacity, h.p.k, (uint32_t)h.p.min_count,
+                     img.walkRight.get(), img.walkLeft.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return TALC_OK;
+}
+
+// The staged image of `device` is completed where it is (adopted: no copy); any other GPU gets a copy of the host image,
+// completed in a record of its own that joins the table only when it is whole.  A failed upload leaves the table as it
+// was: a staged image staged, without filter or walk tables.
+int talc_table_upload(talc_table* t, int device) {
+  if (!t) return fail(TALC_ERR_INVALID, "null table");
+  auto* held = t->image(device);
+  if (held && held->second.uploaded()) return TALC_OK;
+  const Switches sw = read_switches();
+  DeviceImage copy;
+  DeviceImage& img = held ? held->second : copy;
+  int rc;
+  if (held) {
+    HIPCHK(hipSetDevice(device));
+  } else {
+    const uint64_t bytes = t->h.capacity * sizeof(Bucket);
+    if ((rc = ensure_host(t))) return rc;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(copy.right.alloc(t->h.capacity));
+    HIPCHK(copy.left.alloc(t->h.capacity));
+    HIPCHK(hipMemcpy(copy.right.get(), t->h.right, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(copy.left.get(), t->h.left, bytes, hipMemcpyHostToDevice));
+  }
+  if ((rc = derive_tables(img, t->h, sw))) { img.drop_derived(); return rc; }
+  if (!held) t->images.emplace(device, std::move(copy));
   return TALC_OK;
 }
 
@@ -582,15 +595,12 @@ uint64_t talc_table_image_bytes(const talc_table* t) { return t ? t->h.capacity 
 
 int talc_table_export_device(talc_table* t, int device, void* dst_right, void* dst_left) {
   if (!t || !dst_right || !dst_left) return fail(TALC_ERR_INVALID, "null argument");
-  const Bucket *srcR = nullptr, *srcL = nullptr;
-  auto it = t->h.dev.find(device);
-  if (it != t->h.dev.end()) { srcR = it->second.right; srcL = it->second.left; }
-  else if (t->stagedDev == device) { srcR = t->stR.get(); srcL = t->stL.get(); }
-  else return fail(TALC_ERR_STATE, "the table has no image on device %d", device);
+  auto* at = t->image(device);
+  if (!at) return fail(TALC_ERR_STATE, "the table has no image on device %d", device);
   HIPCHK(hipSetDevice(device));
   const uint64_t bytes = t->h.capacity * sizeof(Bucket);
-  HIPCHK(hipMemcpy(dst_right, srcR, bytes, hipMemcpyDeviceToDevice));
-  HIPCHK(hipMemcpy(dst_left, srcL, bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipMemcpy(dst_right, at->second.right.get(), bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipMemcpy(dst_left, at->second.left.get(), bytes, hipMemcpyDeviceToDevice));
   HIPCHK(hipDeviceSynchronize());
   return TALC_OK;
 }
@@ -604,10 +614,10 @@ int talc_table_import_device(const talc_params* p, uint64_t capacity, uint64_t n
   t->h.p = *p; t->h.capacity = capacity; t->h.nkmers = n_kmers; t->hostValid = false;
   const uint64_t bytes = capacity * sizeof(Bucket);
   HIPCHK(hipSetDevice(device));
-  t->stagedDev = device;
-  HIPCHK(t->stR.alloc(capacity)); HIPCHK(t->stL.alloc(capacity));
-  HIPCHK(hipMemcpy(t->stR.get(), src_right, bytes, hipMemcpyDeviceToDevice));
-  HIPCHK(hipMemcpy(t->stL.get(), src_left, bytes, hipMemcpyDeviceToDevice));
+  DeviceImage& staged = t->images[device];
+  HIPCHK(staged.right.alloc(capacity)); HIPCHK(staged.left.alloc(capacity));
+  HIPCHK(hipMemcpy(staged.right.get(), src_right, bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipMemcpy(staged.left.get(), src_left, bytes, hipMemcpyDeviceToDevice));
   HIPCHK(hipDeviceSynchronize());
   // an image carries no parameters of its own: what the kernels rely on — every stored count >= MIN_COUNT, keys of K - 1
   // bases — is checked against the parameters given (an image filtered with a lower MIN_COUNT would give wrong regions)
@@ -615,7 +625,7 @@ int talc_table_import_device(const talc_params* p, uint64_t capacity, uint64_t n
   DevBuf<unsigned long long> dChk;
   HIPCHK(dChk.alloc(2));
   HIPCHK(hipMemcpy(dChk.get(), chk, sizeof chk, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_image_check, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, 0, t->stR.get(), capacity, dChk.get());
+  hipLaunchKernelGGL(k_image_check, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, 0, staged.right.get(), capacity, dChk.get());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(chk, dChk.get(), sizeof chk, hipMemcpyDeviceToHost));
   const unsigned long long keyBits = 2ull * (p->k - 1);
@@ -626,49 +636,41 @@ int talc_table_import_device(const talc_params* p, uint64_t capacity, uint64_t n
   return TALC_OK;
 }
 
+// what the kernels read of the uploaded image on `device`
 static int table_view(talc_table* t, int device, TableView& v) {
-  auto it = t->h.dev.find(device);
-  if (it == t->h.dev.end()) return fail(TALC_ERR_STATE, "table not uploaded to device %d", device);
-  v.right = it->second.right; v.left = it->second.left; v.capacity = t->h.capacity; v.k = t->h.p.k;
-  v.filter = it->second.filter; v.filterWords = it->second.filterWords;
-  v.walkRight = it->second.walkRight; v.walkLeft = it->second.walkLeft;
+  auto* at = t->image(device);
+  if (!at || !at->second.uploaded()) return fail(TALC_ERR_STATE, "table not uploaded to device %d", device);
+  v = at->second.view(t->h.capacity, t->h.p.k);
   return TALC_OK;
 }
 
-int talc_table_lookup_batch(talc_table* t, int device, const uint64_t* kmers, uint64_t n, uint32_t* counts,
-                            uint32_t* jcounts) {
+// the body of the two device lookup calls.  direction < 0: k_lookup, one (count, colour) per k-mer; 0 / 1: k_next_counts, four
+static int lookup_on_device(talc_table* t, int device, const uint64_t* kmers, uint64_t n, int direction, uint32_t* counts, uint32_t* jcounts) {
   if (!t || !kmers || !counts || !jcounts) return fail(TALC_ERR_INVALID, "null argument");
   TableView v;
   int rc = table_view(t, device, v);
   if (rc) return rc;
   if (n == 0) return TALC_OK;
   HIPCHK(hipSetDevice(device));
+  const uint64_t width = direction < 0 ? 1 : 4;
+  const dim3 grid((unsigned)((n + 255) / 256));
   DevBuf<uint64_t> dk; DevBuf<uint32_t> dc, dj;
-  HIPCHK(dk.alloc(n)); HIPCHK(dc.alloc(n)); HIPCHK(dj.alloc(n));
+  HIPCHK(dk.alloc(n)); HIPCHK(dc.alloc(width * n)); HIPCHK(dj.alloc(width * n));
   HIPCHK(hipMemcpy(dk.get(), kmers, n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk.get(), n, dc.get(), dj.get());
+  if (direction < 0) hipLaunchKernelGGL(k_lookup, grid, dim3(256), 0, 0, v, dk.get(), n, dc.get(), dj.get());
+  else hipLaunchKernelGGL(k_next_counts, grid, dim3(256), 0, 0, v, dk.get(), n, direction, dc.get(), dj.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(counts, dc.get(), n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(jcounts, dj.get(), n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(counts, dc.get(), n * width * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(jcounts, dj.get(), n * width * 4, hipMemcpyDeviceToHost));
   return TALC_OK;
 }
-
+int talc_table_lookup_batch(talc_table* t, int device, const uint64_t* kmers, uint64_t n, uint32_t* counts,
+                            uint32_t* jcounts) {
+  return lookup_on_device(t, device, kmers, n, -1, counts, jcounts);
+}
 int talc_table_next_counts_batch(talc_table* t, int device, const uint64_t* kmers, uint64_t n, int direction,
                                  uint32_t* counts4, uint32_t* jcounts4) {
-  if (!t || !kmers || !counts4 || !jcounts4) return fail(TALC_ERR_INVALID, "null argument");
-  TableView v;
-  int rc = table_view(t, device, v);
-  if (rc) return rc;
-  if (n == 0) return TALC_OK;
-  HIPCHK(hipSetDevice(device));
-  DevBuf<uint64_t> dk; DevBuf<uint32_t> dc, dj;
-  HIPCHK(dk.alloc(n)); HIPCHK(dc.alloc(4 * n)); HIPCHK(dj.alloc(4 * n));
-  HIPCHK(hipMemcpy(dk.get(), kmers, n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_next_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, dk.get(), n, direction ? 1 : 0, dc.get(), dj.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(counts4, dc.get(), n * 16, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(jcounts4, dj.get(), n * 16, hipMemcpyDeviceToHost));
-  return TALC_OK;
+  return lookup_on_device(t, device, kmers, n, direction ? 1 : 0, counts4, jcounts4);
 }
 
 int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uint64_t n, uint32_t* counts,
@@ -684,9 +686,10 @@ int talc_table_lookup_host_batch(const talc_table* t, const uint64_t* kmers, uin
 // Test hook (not part of the reference surface): the walk table of one direction of the copy on `device`, as it is
 int talc_table_fetch_walk(talc_table* t, int device, int direction, void* dst, uint64_t bytes) {
   if (!t || !dst) return fail(TALC_ERR_INVALID, "null argument");
-  auto it = t->h.dev.find(device);
-  if (it == t->h.dev.end()) return fail(TALC_ERR_STATE, "table not uploaded to device %d", device);
-  const WalkEntry* src = direction ? it->second.walkRight : it->second.walkLeft;
+  TableView v;
+  int rc = table_view(t, device, v);
+  if (rc) return rc;
+  const WalkEntry* src = direction ? v.walkRight : v.walkLeft;
   if (!src) return fail(TALC_ERR_STATE, "the copy on device %d has no walk tables", device);
   const uint64_t need = t->h.capacity * sizeof(WalkEntry);
   if (bytes != need) return fail(TALC_ERR_CAPACITY, "a walk table is %llu bytes, %llu given", (unsigned long long)need, (unsigned long long)bytes);
@@ -976,7 +979,7 @@ static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32
 
 // a larger power of two that holds `need` distinct k-mers at load <= 0.7; the old slots are rehashed on the device
 static int counter_grow(talc_counter* c, uint64_t need) {
-  const auto t0 = std::chrono::steady_clock::now();
+  Stopwatch watch;
   uint64_t nc = c->cap;
   while ((double)need > 0.7 * (double)nc) nc *= 2;
   DevBuf<CountSlot> nt;
@@ -992,7 +995,7 @@ static int counter_grow(talc_counter* c, uint64_t need) {
   c->tab = std::move(nt);   // (frees the old slots)
   c->cap = nc;
   ++c->nGrows;
-  c->growS += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->growS += watch.seconds();
   return TALC_OK;
 }
 
@@ -1053,7 +1056,7 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
     if ((double)(c->distinctKnown + wins) > 0.7 * (double)c->cap && (rc = counter_grow(c, c->distinctKnown + wins))) return rc;
   }
   // staging buffer: free once the copy that last read it is done
-  const auto tp0 = std::chrono::steady_clock::now();
+  Stopwatch packing;
   const int b = c->next;
   c->next ^= 1;
   if (c->stageBusy[b]) { HIPCHK(hipEventSynchronize(c->stageEv[b])); c->stageBusy[b] = false; }
@@ -1073,7 +1076,7 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
     memcpy(dst + at, bases + offsets[r], offsets[r + 1] - offsets[r]);
     dst[at + offsets[r + 1] - offsets[r]] = '\n';
   }
-  c->packS += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count();
+  c->packS += packing.seconds();
   if (c->dTextCap < nbytes) {   // (the previous kernel may still read the old buffer)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->dText.reset(); c->dTextCap = 0;
@@ -1150,11 +1153,11 @@ int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uin
 int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]) {
   if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
   if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
-  const auto t0 = std::chrono::steady_clock::now();
+  Stopwatch watch;
   unsigned long long st[2];
   int rc = counter_sync(c, st);
   if (rc) return rc;
-  const auto t1 = std::chrono::steady_clock::now();
+  const double tWait = watch.lap();
   uint64_t kept = 0;
   if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept))) return rc;
   if (kept >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
@@ -1167,7 +1170,7 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
   c->tab.reset(); c->cap = 0;
   c->dText.reset(); c->dTextCap = 0;
   c->spent = true;
-  const auto t2 = std::chrono::steady_clock::now();
+  const double tCompact = watch.lap();
   if (c->sw.timing) {
     double kms = 0;
     for (auto& ev : c->kev) { float ms = 0; if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) kms += ms; }
@@ -1175,14 +1178,14 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
                     "(%.3f ms per batch), %llu grows %.3f s, last batch wait %.3f s, compaction %.3f s\n",
             (unsigned long long)c->nBatches, (double)c->nBytes / 1e6, st[0], st[1], (unsigned long long)kept, c->packS, kms,
             c->nBatches ? kms / (double)c->nBatches : 0.0, (unsigned long long)c->nGrows, c->growS,
-            std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t2 - t1).count());
+            tWait, tCompact);
   }
-  talc_table* t = nullptr;
-  if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, &t, 0.0, 0.0, c->sw))) return rc;
+  TablePtr t;
+  if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, t, 0.0, 0.0, c->sw))) return rc;
   DumpStats ds;
   ds.nread = (int64_t)st[1];
   ds.nkept = (int64_t)kept;
-  return table_finish(std::unique_ptr<talc_table>(t), junction_path, &c->p, ds, out, stats);
+  return table_finish(std::move(t), junction_path, &c->p, ds, out, stats);
 }
 
 void talc_counter_destroy(talc_counter* c) {

@@ -11,7 +11,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -20,24 +19,13 @@
 
 namespace talc {
 
-struct DeviceCopy {
-  Bucket* right = nullptr;
-  Bucket* left = nullptr;
-  uint64_t* filter = nullptr;
-  uint64_t filterWords = 0;
-  WalkEntry* walkRight = nullptr;
-  WalkEntry* walkLeft = nullptr;
-};
-
 struct HostTable {
   talc_params p;
   uint64_t capacity = 0;     // buckets per table
   uint64_t nkmers = 0;       // stored k-mers == SR_DBG.size()
   uint64_t nbuckets_right = 0, nbuckets_left = 0;
-  Bucket* right = nullptr;   // host images (calloc'ed; released after the last upload on request)
+  Bucket* right = nullptr;   // the host image (malloc'ed), when there is one
   Bucket* left = nullptr;
-  std::map<int, DeviceCopy> dev;
-  bool frozen = false;
 
   ~HostTable() { free(right); free(left); }
 
