@@ -275,6 +275,41 @@ uint64_t talc_batch_corrected_bytes(const talc_batch* b);
 int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity,
                                uint64_t* out_offsets, int32_t* status);
 
+/* The correction map (docs/correction_map.md): which stretches of every record are solid stretches of the read, which were
+ * replaced by a path through the short-read graph, and which are weak stretches that stayed as they came — what LoRDEC
+ * reports as lower case.  talc_ctx_set_map(c, 1) makes every later talc_batch_correct of the context keep it (default off;
+ * the records, statuses and counters of a correction do not depend on it).
+ *
+ * A read with status TALC_READ_CORRECTED has exactly 2 R + 1 segments, R its number of IN regions: head, solid 0, between 0,
+ * solid 1, ..., solid R-1, tail, segments of length 0 included.  With regS / regE the regions' first and last k-mer
+ * positions as correct2 leaves them (accepted anchors move region ends inward):
+ *   solid i    raw [regS[i], regE[i] + K), kind SOLID, out_len = raw_len
+ *   between i  raw_start = regE[i] + K, raw_len = max(0, regS[i+1] - raw_start); CORRECTED with the bridge's length as
+ *              out_len (which may be 0: the K < len < 2K rule of cutAnchors) when a bridge was accepted, else RAW with
+ *              out_len = raw_len
+ *   head       raw [0, regS[0]);  tail  raw [regE[R-1] + K, L): CORRECTED with the edge's length when the edge search
+ *              succeeded, else RAW — a failed search, an absent border, one longer than max_border_length
+ * Every other read (too short, no solid k-mer, no structure, TALC_READ_ERROR) has one RAW segment {0, L, 0, L}.
+ * out_start runs on without gaps and the out_len of a read add up to its record's length.  Coordinates are those of the
+ * read as the caller gave it and of the record as talc_batch_fetch_corrected returns it: under -rev the segments of a
+ * corrected read are flipped (order reversed, raw_start = L - raw_start - raw_len, out_start = outLen - out_start - out_len). */
+typedef enum talc_segment_kind { TALC_SEG_SOLID = 0, TALC_SEG_CORRECTED = 1, TALC_SEG_RAW = 2 } talc_segment_kind;
+typedef struct talc_segment { uint32_t kind, raw_start, raw_len, out_start, out_len; } talc_segment;
+int talc_ctx_set_map(talc_ctx* c, int on);
+/* segments of the whole batch; 0 unless the batch's last correction ran with the map on */
+uint64_t talc_batch_num_segments(const talc_batch* b);
+/* segs: the batch's segments, reads in input order; seg_offsets[n_reads + 1] (may be NULL).  segs == NULL fills only the
+ * offsets.  TALC_ERR_CAPACITY (the message names the count needed) when capacity is too small, TALC_ERR_STATE when the
+ * batch's last correction ran with the map off. */
+int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_t capacity, uint64_t* seg_offsets);
+/* talc_batch_fetch_corrected with every base of a RAW segment in lower case: same offsets, same statuses, same bytes but
+ * for the case.  Needs the map (TALC_ERR_STATE without).  The masked records are a second device buffer, made on first use. */
+int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
+                                      int32_t* status);
+/* Measurement: device time (ms) of the context's last map kernels — k_pack_map (the last mapped correction) and
+ * k_mask_case (the last masked fetch that had to make its buffer).  Either pointer may be NULL. */
+int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_case_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

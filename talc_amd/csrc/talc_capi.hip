@@ -120,10 +120,12 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[11] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
+  bool map = false;     // talc_ctx_set_map: corrections keep the correction map
+  float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -152,8 +154,16 @@ struct talc_batch {
   std::vector<ReadState> h_state;
   std::vector<uint64_t> h_dense_off;
   uint64_t dense_cap = 0;
+  // the correction map of the last correction, when the context kept one (talc_ctx_set_map)
+  bool mapped = false, masked = false;   // d_segs holds that correction's map; d_masked its records, RAW stretches in lower case
+  std::vector<uint64_t> h_seg_off;
+  uint64_t segs_cap = 0, masked_cap = 0;
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  CachedBuf<uint8_t> d_masked;       // the dense records again, RAW stretches in lower case (k_mask_case; made on first use)
+  CachedBuf<MapSeg> d_segs;          // the dense correction map (k_pack_map) and the reads' offsets into it
+  CachedBuf<uint64_t> d_seg_off;
+  CachedBuf<uint32_t> d_mapedge;     // 2 x u32 per read: what k_search made of its head and its tail (leave_outcome)
   CachedBuf<uint32_t> d_headcov;     // 16 x u32 per read: dense counts of its first positions (k_structure -> k_search)
   CachedBuf<uint64_t> d_dense_off;
   CachedBuf<uint8_t> d_dense;
@@ -173,6 +183,9 @@ struct talc_batch {
   CachedBuf<uint8_t> d_raw;
   ~talc_batch() { if (ctx) (void)hipSetDevice(ctx->device); }
 };
+
+static_assert(sizeof(MapSeg) == sizeof(talc_segment) && TALC_SEG_SOLID == SEG_SOLID && TALC_SEG_CORRECTED == SEG_CORRECTED && TALC_SEG_RAW == SEG_RAW,
+              "k_pack_map writes talc_segment records");
 
 template <typename T>
 static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
@@ -743,6 +756,19 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
 }
 
 void talc_ctx_destroy(talc_ctx* c) { delete c; }
+
+int talc_ctx_set_map(talc_ctx* c, int on) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  c->map = on != 0;
+  return TALC_OK;
+}
+
+int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_case_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (pack_map_ms) *pack_map_ms = c->pack_map_ms;
+  if (mask_case_ms) *mask_case_ms = c->mask_case_ms;
+  return TALC_OK;
+}
 
 int talc_ctx_get_timing(const talc_ctx* c, talc_timing* out) {
   if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");

@@ -191,7 +191,8 @@ static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint
     HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)st.n_slots * 4, s));
   }
   hipLaunchKernelGGL(k_search, dim3(st.n_slots), dim3(64), 0, s, c->dp, c->view, st.caps, b->d_codes.get(), b->d_offsets.get(),
-                     b->d_koff.get(), b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->d_out.get(), b->d_outoff.get(), d_work,
+                     b->d_koff.get(), b->d_cov.get(), b->d_covw.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(),
+                     c->map ? b->d_regions.get() : nullptr, c->map ? b->d_mapedge.get() : nullptr, b->d_out.get(), b->d_outoff.get(), d_work,
                      n_work, c->d_queue.get(), st.scratch.get(), c->d_counters.get(), tb, traceRead, next_launch_stamp(), ea);
   HIPCHK(hipGetLastError());
   return TALC_OK;
@@ -272,6 +273,29 @@ static int pack_dense(talc_ctx* c, talc_batch* b) {
   return TALC_OK;
 }
 
+// the correction map (talc_ctx_set_map): the reads' segment counts from the states (host: 2 R + 1 for a read k_search
+// reassembled, 1 for every other), then k_pack_map into b->d_segs (event 8 after it)
+static int pack_map(talc_ctx* c, talc_batch* b) {
+  hipStream_t s = c->stream;
+  b->h_seg_off.resize(b->n_reads + 1);
+  uint64_t n = 0;
+  for (uint32_t r = 0; r < b->n_reads; ++r) {
+    b->h_seg_off[r] = n;
+    n += map_has_outcome(b->h_state[r]) ? 2ull * b->h_state[r].nRegions + 1 : 1;
+  }
+  b->h_seg_off[b->n_reads] = n;
+  if (b->d_segs && b->segs_cap < n) b->d_segs.reset();
+  if (!b->d_segs) { b->segs_cap = std::max<uint64_t>(n, 1); HIPCHK(b->d_segs.alloc(c->cache, b->segs_cap)); }
+  if (!b->d_seg_off) HIPCHK(b->d_seg_off.alloc(c->cache, b->n_reads + 1));
+  HIPCHK(hipMemcpyAsync(b->d_seg_off.get(), b->h_seg_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  if (b->n_reads)
+    hipLaunchKernelGGL(k_pack_map, dim3(b->n_reads), dim3(64), 0, s, b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_mapedge.get(),
+                       b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[8], s));
+  return TALC_OK;
+}
+
 // waits for the stream; the stage times and the batch's counts into c->timing, the device counters below the wave log into `counters`
 static int read_timing(talc_ctx* c, talc_batch* b, uint64_t* counters) {
   int rc;
@@ -289,7 +313,9 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   int rc;
   // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
   //  would be a mixture of this run's and the last one's)
-  b->structured = false; b->corrected = false;
+  b->structured = false; b->corrected = false; b->mapped = false; b->masked = false;
+  const bool map = c->map;
+  if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
   uint64_t counters[kCntWaveLog] = {0};
   if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
@@ -297,11 +323,13 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   if ((rc = search_first_pass(c, b, tb, traceRead))) return rc;
   if ((rc = search_retry_passes(c, b, tb, traceRead))) return rc;
   if ((rc = pack_dense(c, b))) return rc;
+  if (map && (rc = pack_map(c, b))) return rc;
   if ((rc = read_timing(c, b, counters))) return rc;
+  if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[7], c->ev[8]));
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
 #endif
-  b->corrected = true;
+  b->corrected = true; b->mapped = map;
   if (c->timing.n_failed) {   // the batch is valid: those reads are passed through unchanged with status TALC_READ_ERROR
     fail(TALC_WARN_READ_ERRORS, "%u read(s) exhausted the device scratch even in the retry pass (status TALC_READ_ERROR)", c->timing.n_failed);
     return TALC_WARN_READ_ERRORS;
@@ -373,7 +401,7 @@ uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->corre
 
 // the records of a corrected batch into `out` (a host or a device buffer: `kind`; null: offsets and statuses only)
 static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_capacity, uint64_t* out_offsets, int32_t* status,
-                         hipMemcpyKind kind, const char* what) {
+                         hipMemcpyKind kind, const char* what, bool masked = false) {
   if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t total = b->h_dense_off[b->n_reads];
@@ -383,7 +411,7 @@ static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_cap
   if (out) {
     if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "%s buffer too small: need %llu bytes", what, (unsigned long long)total);
     if (total) {   // on the context's stream: a DMA transfer when a host `out` is pinned (talc_pinned_alloc)
-      HIPCHK(hipMemcpyAsync(out, b->d_dense.get(), total, kind, c->stream));
+      HIPCHK(hipMemcpyAsync(out, masked ? b->d_masked.get() : b->d_dense.get(), total, kind, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
     }
   }
@@ -394,6 +422,60 @@ int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t o
                                int32_t* status) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output");
+}
+
+uint64_t talc_batch_num_segments(const talc_batch* b) { return (b && b->corrected && b->mapped) ? b->h_seg_off[b->n_reads] : 0; }
+
+static int need_map(const talc_batch* b) {
+  if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
+  if (!b->mapped) return fail(TALC_ERR_STATE, "the batch's last correction kept no correction map (talc_ctx_set_map)");
+  return TALC_OK;
+}
+
+int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_t capacity, uint64_t* seg_offsets) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  int rc;
+  if ((rc = need_map(b))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const uint64_t total = b->h_seg_off[b->n_reads];
+  if (seg_offsets) memcpy(seg_offsets, b->h_seg_off.data(), (b->n_reads + 1) * 8);
+  if (segs) {
+    if (capacity < total) return fail(TALC_ERR_CAPACITY, "segment buffer too small: need %llu segments", (unsigned long long)total);
+    if (total) {
+      HIPCHK(hipMemcpyAsync(segs, b->d_segs.get(), total * sizeof(talc_segment), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+  }
+  return TALC_OK;
+}
+
+// the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (events 9, 10)
+static int mask_dense(talc_ctx* c, talc_batch* b) {
+  if (b->masked) return TALC_OK;
+  hipStream_t s = c->stream;
+  const uint64_t total = b->h_dense_off[b->n_reads];
+  if (b->d_masked && b->masked_cap < total) b->d_masked.reset();
+  if (!b->d_masked) { b->masked_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_masked.alloc(c->cache, b->masked_cap)); }
+  if (total) HIPCHK(hipMemcpyAsync(b->d_masked.get(), b->d_dense.get(), total, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipEventRecord(c->ev[9], s));
+  if (b->n_reads)
+    hipLaunchKernelGGL(k_mask_case, dim3(b->n_reads), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), b->d_dense_off.get(), b->d_masked.get(), b->n_reads);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[10], s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventElapsedTime(&c->mask_case_ms, c->ev[9], c->ev[10]));
+  b->masked = true;
+  return TALC_OK;
+}
+
+int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
+                                      int32_t* status) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  int rc;
+  if ((rc = need_map(b))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (out && (rc = mask_dense(c, b))) return rc;
+  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output", true);
 }
 
 // Read::outputBasicReadStats (Read.cpp:418-433) for every read of a corrected batch

@@ -755,6 +755,7 @@ struct Wv {
   uint8_t* refBuf;                 // the scratch buffer a search's reference is assembled in (ref points there, or into the read)
   // edge tasks (the start anchors of a head / tail search handed to waves that have run out of reads; nullptr: none)
   uint8_t* boxes; uint32_t* avail; uint32_t* qwords;
+  uint32_t* mapRegions; uint32_t* mapEdge;   // the launch keeps the correction map (leave_outcome); nullptr: it does not
   uint32_t boxBytes, boxSeqCap, nSlots, mySlot, nWork, taskMinWeak;
   uint32_t taskHeavy;              // a border of at least this many bases is published when its search starts (queue positions below heavyUpTo)
   uint32_t qi, heavyUpTo;          // the current read's position in the work queue; `taskHeavy` applies below this position
@@ -4124,6 +4125,26 @@ TALC_D void reassemble(uint8_t* out, const Piece& head, const Piece& tail, uint3
   if (lane_id() == 0) { rs->outLen = pos; rs->inSpan = span; }
 }
 
+// The correction map (docs/correction_map.md).  A read that has just been reassembled leaves its outcome for k_pack_map: the
+// regions as correct2 left them and, per gap, the accepted bridge's length (kNotCorrected: the read's own bases stayed) go
+// back into the read's own slot of the region lists — starts, ends, and the gap word where the hit indices were —, which
+// nobody reads again once the read is reassembled (a retry pass only takes reads that never got here); head and tail
+// leave two words in mapEdge: a border that a search replaced is a piece of X.weak, one that stayed a piece of the read.
+// (`regions` is the kernel's second, writable pointer to the lists, mapRegions; the one the reads go through stays
+// const __restrict__: one pointer for both measured + 0.06 ms per config-2 launch with the map off.)
+TALC_D void leave_outcome(uint32_t r, const Piece& head, const Piece& tail, uint32_t R, uint32_t* regions, const uint64_t* regoff,
+                          uint32_t* mapEdge) {
+  uint32_t* gS = regions + 3 * regoff[r];
+  const uint32_t gCap = (uint32_t)(regoff[r + 1] - regoff[r]);
+  uint32_t* gE = gS + gCap;
+  uint32_t* gW = gE + gCap;
+  for (uint32_t i = lane_id(); i < R; i += 64) { gS[i] = X.regS[i]; gE[i] = X.regE[i]; gW[i] = X.wLen[i]; }
+  if (lane_id() == 0) {
+    mapEdge[2ull * r] = (head.p == X.read) ? kNotCorrected : head.n;
+    mapEdge[2ull * r + 1] = (tail.p + tail.n == X.read + X.L) ? kNotCorrected : tail.n;
+  }
+}
+
 // the read leaves as it came (main.cpp:310 writes mySeqs[r] unchanged): not to be searched (overflow 0), scratch exhausted
 // during the search, or the corrected read longer than its out slot (OVF_OUT)
 TALC_D void pass_through(uint8_t* out, ReadState* rs, uint32_t overflow) {
@@ -4138,7 +4159,8 @@ __global__ void __launch_bounds__(64, TALC_SEARCH_WAVES_PER_SIMD)
 k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ codes, const uint64_t* __restrict__ offsets,
          const uint64_t* __restrict__ koff, const uint2* __restrict__ covAll, const CovWord* __restrict__ covWords,
          ReadState* __restrict__ state,
-         const uint32_t* __restrict__ regions, const uint64_t* __restrict__ regoff, const uint32_t* __restrict__ headCovAll,
+         const uint32_t* regions, const uint64_t* __restrict__ regoff, const uint32_t* __restrict__ headCovAll,
+         uint32_t* mapRegions, uint32_t* __restrict__ mapEdge,   // the correction map (leave_outcome): `regions` again, to be written, and the borders' words; null: no map is kept
          uint8_t* __restrict__ outAll,
          const uint64_t* __restrict__ outoff, const uint32_t* __restrict__ order, uint32_t n_work,
          uint32_t* __restrict__ queue, uint8_t* __restrict__ scratchAll, uint64_t* __restrict__ counters, TraceBuf trace,
@@ -4147,6 +4169,7 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
   const int l = lane_id();
   bind_slot(scratchAll + (uint64_t)blockIdx.x * C.slotBytes, C, trace);
   const uint32_t lingerMod = bind_launch(P, T, queue, n_work, launchStamp, E);
+  X.mapRegions = mapRegions; X.mapEdge = mapEdge;   // (kept in the wave's context: the searches between here and its one use need the registers)
   unsigned long long totCells = 0, totSteps = 0;
   PROF_DECL2;
   SearchProf pf;
@@ -4187,6 +4210,7 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
     if (corrected_length(head, tail, R) > outCap) { pass_through(out, rs, OVF_OUT); continue; }
     PROF_BEGIN2();
     reassemble(out, head, tail, R, rs);
+    if (uni_ptr(X.mapEdge) != nullptr) leave_outcome(r, head, tail, R, uni_ptr(X.mapRegions), regoff, uni_ptr(X.mapEdge));
     PROF_END2(PF_ASSEMBLE);
   }
   // no reads left: run published anchors of the edge searches still going on, until every read is finished
@@ -4282,6 +4306,77 @@ __global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __res
   for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) {
     if (rc) dst[i] = (uint8_t)code_to_ascii(complement_code(src[len - 1 - i]));
     else dst[i] = (uint8_t)code_to_ascii(src[i]);
+  }
+}
+
+// ==================================================================== k_pack_map, k_mask_case
+// The correction map as the caller sees it (talc_segment, include/talc_hip.h): one wave per read turns what leave_outcome
+// left into the read's 2 R + 1 segments — head, (solid, between)*, solid, tail; empty ones are kept — at segOff[r] of the
+// dense array.  out_start is the running sum of out_len: 64 segments per pass, a wave scan inside the pass and a carry
+// between passes.  Under -rev the kernel's coordinates are those of the reverse complement: the segments of a corrected
+// read are flipped (order, raw_start, out_start).  Every other read is one RAW segment over the whole record.
+struct MapSeg { uint32_t kind, rawStart, rawLen, outStart, outLen; };
+enum : uint32_t { SEG_SOLID = 0, SEG_CORRECTED = 1, SEG_RAW = 2 };
+__host__ __device__ inline bool map_has_outcome(const ReadState& st) { return st.status == TALC_READ_CORRECTED && st.overflow == 0 && st.nRegions > 0; }
+__global__ void __launch_bounds__(64)
+k_pack_map(const ReadState* __restrict__ state, const uint32_t* __restrict__ regions, const uint64_t* __restrict__ regoff,
+           const uint32_t* __restrict__ mapEdge, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ segOff,
+           MapSeg* __restrict__ segs, uint32_t n_reads, uint32_t K, int reverse) {
+  const uint32_t r = blockIdx.x;
+  if (r >= n_reads) return;
+  const uint32_t l = (uint32_t)lane_id();
+  const uint32_t L = (uint32_t)(offsets[r + 1] - offsets[r]);
+  const ReadState st = state[r];
+  MapSeg* const o = segs + segOff[r];
+  if (!map_has_outcome(st)) {
+    if (l == 0) o[0] = MapSeg{SEG_RAW, 0u, L, 0u, L};
+    return;
+  }
+  const uint32_t R = st.nRegions, nseg = 2 * R + 1, outLen = st.outLen;
+  const uint32_t* gS = regions + 3 * regoff[r];
+  const uint32_t gCap = (uint32_t)(regoff[r + 1] - regoff[r]);
+  const uint32_t* gE = gS + gCap;
+  const uint32_t* gW = gE + gCap;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < nseg; base += 64) {
+    const uint32_t j = base + l;
+    MapSeg s = {SEG_RAW, 0u, 0u, 0u, 0u};
+    if (j < nseg) {
+      uint32_t w = kNotCorrected;   // the length of what replaced the stretch, if anything did
+      if (j == 0) { s.rawLen = gS[0]; w = mapEdge[2ull * r]; }
+      else if (j == 2 * R) { s.rawStart = gE[R - 1] + K; s.rawLen = L - s.rawStart; w = mapEdge[2ull * r + 1]; }
+      else {
+        const uint32_t i = (j - 1) >> 1;
+        if (j & 1u) { s.kind = SEG_SOLID; s.rawStart = gS[i]; s.rawLen = gE[i] + K - s.rawStart; }
+        else { const uint32_t to = gS[i + 1]; s.rawStart = gE[i] + K; s.rawLen = to > s.rawStart ? to - s.rawStart : 0u; w = gW[i]; }   // (piece_after's clamp)
+      }
+      s.outLen = s.rawLen;
+      if (w != kNotCorrected) { s.kind = SEG_CORRECTED; s.outLen = w; }
+    }
+    uint32_t incl = s.outLen;   // inclusive scan over the pass's lanes
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (l >= (uint32_t)off) incl += t; }
+    s.outStart = carry + incl - s.outLen;
+    carry += (uint32_t)__shfl((int)incl, 63, 64);
+    if (j < nseg) {
+      if (reverse) { s.rawStart = L - s.rawStart - s.rawLen; s.outStart = outLen - s.outStart - s.outLen; o[nseg - 1 - j] = s; }
+      else o[j] = s;
+    }
+  }
+}
+
+// the masked copy of the dense records: the bases of every RAW segment in lower case.  One block per read, over its segments
+__global__ void __launch_bounds__(256)
+k_mask_case(const MapSeg* __restrict__ segs, const uint64_t* __restrict__ segOff, const uint64_t* __restrict__ dense_off,
+            uint8_t* __restrict__ masked, uint32_t n_reads) {
+  const uint32_t r = blockIdx.x;
+  if (r >= n_reads) return;
+  uint8_t* const rec = masked + dense_off[r];
+  const uint32_t recLen = (uint32_t)(dense_off[r + 1] - dense_off[r]);
+  for (uint64_t k = segOff[r]; k < segOff[r + 1]; ++k) {
+    const MapSeg s = segs[k];
+    if (s.kind != SEG_RAW) continue;
+    for (uint32_t i = threadIdx.x; i < s.outLen && s.outStart + i < recLen; i += blockDim.x) rec[s.outStart + i] |= 0x20u;
   }
 }
 

@@ -12,6 +12,9 @@
 //   --batch-reads N  reads per device batch (default: two or more batches per worker — two workers per GPU —, 20000..200000)
 //   --read-stats     append the per-read rows of Read::outputBasicReadStats (Read.cpp:418-433) to <o>.stats_basics.txt
 //                    (the reference has that call commented out, main.cpp:305, and only ever writes the header)
+//   --corr-map       write <o>.map.tsv, the correction map (docs/correction_map.md): one line per segment of every read,
+//                    in input order: read_name kind(S|C|R) raw_start raw_len out_start out_len
+//   --soft-mask      the bases of <o>.fa that were not corrected (RAW segments) in lower case, as LoRDEC writes them
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -89,6 +92,7 @@ struct Options {
   uint32_t batchReads = 200000;
   bool haveBatchReads = false;
   bool readStats = false;
+  bool corrMap = false, softMask = false;   // --corr-map, --soft-mask
 };
 
 void usage(FILE* f) {
@@ -118,6 +122,9 @@ void usage(FILE* f) {
           "  --gpus INT                  GPUs to use (default: all)\n"
           "  --batch-reads INT           reads per device batch (default: at least two batches per worker, 20000..200000)\n"
           "  --read-stats                append per-read rows to <o>.stats_basics.txt (Read.cpp:418-433)\n"
+          "  --corr-map                  write <o>.map.tsv: read_name, kind (S solid, C corrected, R raw), raw_start, raw_len,\n"
+          "                              out_start, out_len for every stretch of every read (docs/correction_map.md)\n"
+          "  --soft-mask                 write the bases that stayed uncorrected (R stretches) in lower case\n"
           "  -h, --help / --version\n");
 }
 
@@ -167,6 +174,8 @@ Options parse(int argc, const char** argv) {
     else if (a == "--gpus") { o.gpus = (int)num(need(i), "gpus"); range(o.gpus, 1, 64, "gpus"); }
     else if (a == "--batch-reads") { double v = num(need(i), "batch-reads"); range(v, 1, 4e9, "batch-reads"); o.batchReads = (uint32_t)v; o.haveBatchReads = true; }
     else if (a == "--read-stats") o.readStats = true;
+    else if (a == "--corr-map") o.corrMap = true;
+    else if (a == "--soft-mask") o.softMask = true;
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
     else if (a.size() > 1 && a[0] == '-') parse_error("unknown option: " + a);
@@ -216,8 +225,8 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log;
-  explicit Files(const std::string& prefix) : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log") {}
+  const std::string fa, stats, log, map;
+  explicit Files(const std::string& prefix) : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -347,7 +356,23 @@ struct Chunk {
   std::vector<int32_t> status;
   std::vector<int64_t> stats;           // 5 per read (--read-stats)
   std::string text, logText, statsText; // what the writer appends to <o>.fa / <o>.log / <o>.stats_basics.txt
+  std::string mapText;                  // ... and to <o>.map.tsv (--corr-map)
 };
+
+// the lines of <o>.map.tsv for one batch: the segments of read r are segs[so[r] .. so[r + 1]); those with both lengths 0
+// are left out
+void formatMap(Chunk& k, const talc_segment* segs, const uint64_t* so) {
+  char num[96];
+  for (size_t r = 0; r < k.ids.size(); ++r)
+    for (uint64_t i = so[r]; i < so[r + 1]; ++i) {
+      const talc_segment& g = segs[i];
+      if (g.raw_len == 0 && g.out_len == 0) continue;
+      const int m = snprintf(num, sizeof num, "\t%c\t%u\t%u\t%u\t%u\n", g.kind == TALC_SEG_SOLID ? 'S' : g.kind == TALC_SEG_CORRECTED ? 'C' : 'R',
+                             g.raw_start, g.raw_len, g.out_start, g.out_len);
+      k.mapText += k.ids[r];
+      k.mapText.append(num, (size_t)m);
+    }
+}
 
 // the text of one batch: '>' id, the sequence wrapped at 70 columns (io.cpp:50-75); the log and stats lines of its reads
 void formatChunk(const Options& o, Chunk& k, const char* recs, const uint64_t* oo) {
@@ -397,8 +422,16 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
       c.status[r] = TALC_READ_NO_SOLID_KMER;
       if (o.readStats) { c.stats[5 * r] = 1; c.stats[5 * r + 1] = (int64_t)q.size(); }
     }
+    if (o.softMask) for (auto& ch : q) ch = (char)(ch | 0x20);   // (nothing was corrected: one RAW segment per read)
     all += q;
     oo[r + 1] = all.size();
+  }
+  if (o.corrMap) {
+    std::vector<talc_segment> segs(n);
+    std::vector<uint64_t> so(n + 1);
+    for (size_t r = 0; r <= n; ++r) so[r] = r;
+    for (size_t r = 0; r < n; ++r) { const uint32_t L = (uint32_t)(oo[r + 1] - oo[r]); segs[r] = talc_segment{TALC_SEG_RAW, 0u, L, 0u, L}; }
+    formatMap(c, segs.data(), so.data());
   }
   formatChunk(o, c, all.data(), oo.data());
 }
@@ -450,7 +483,7 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf;
+    std::ofstream of, lf, sf, mf;
     double busy = 0;
   };
   bool fail(std::string msg);
@@ -497,6 +530,10 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   ReaderSide rd(o_.seqFile);
   WriterSide wr;
   wr.of = std::move(of);
+  if (o_.corrMap) {
+    wr.mf.open(files_.map, std::ios_base::trunc);
+    if (!wr.mf) return fail("cannot write " + files_.map);
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -514,6 +551,7 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     writer.join();
   }
   wr.of.close();
+  if (wr.mf.is_open()) wr.mf.close();
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
   for (const WorkerTally& t : tally) {
@@ -574,6 +612,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     talc_ctx* made = nullptr;
     if (talc_ctx_create(table_, &o_.p, device, &made) != TALC_OK) { fail(talc_last_error()); return; }
     ctx.reset(made);
+    if ((o_.corrMap || o_.softMask) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -620,7 +659,15 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
   const uint64_t total = talc_batch_corrected_bytes(b.get());
   std::vector<uint64_t> oo(n + 1);
   if (!outb.reserve(std::max<uint64_t>(total, 1))) return fail("no host memory: " + std::to_string(total) + " bytes for the corrected records of a batch");
-  if (talc_batch_fetch_corrected(ctx, b.get(), outb.p, total, oo.data(), c.status.data()) != TALC_OK) return fail(talc_last_error());
+  const int frc = o_.softMask ? talc_batch_fetch_corrected_masked(ctx, b.get(), outb.p, total, oo.data(), c.status.data())
+                              : talc_batch_fetch_corrected(ctx, b.get(), outb.p, total, oo.data(), c.status.data());
+  if (frc != TALC_OK) return fail(talc_last_error());
+  if (o_.corrMap) {   // fetched here, beside the records; the writer appends the lines in batch order
+    std::vector<talc_segment> segs(std::max<uint64_t>(talc_batch_num_segments(b.get()), 1));
+    std::vector<uint64_t> so(n + 1);
+    if (talc_batch_fetch_map(ctx, b.get(), segs.data(), segs.size(), so.data()) != TALC_OK) return fail(talc_last_error());
+    formatMap(c, segs.data(), so.data());
+  }
   if (o_.readStats) {
     c.stats.resize(5ull * n);
     if (talc_batch_fetch_read_stats(ctx, b.get(), c.stats.data()) != TALC_OK) return fail(talc_last_error());
@@ -653,6 +700,7 @@ void Pipeline::writerMain(WriterSide& w) {
     if (!c->logText.empty()) { if (!w.lf.is_open()) w.lf.open(files_.log, std::ios_base::app); w.lf << c->logText; w.lf.flush(); }
     if (!c->statsText.empty()) { if (!w.sf.is_open()) w.sf.open(files_.stats, std::ios_base::app); w.sf << c->statsText; }
     w.of.write(c->text.data(), (std::streamsize)c->text.size());
+    if (w.mf.is_open()) w.mf.write(c->mapText.data(), (std::streamsize)c->mapText.size());
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;

@@ -34,7 +34,14 @@ ABI_SYMBOLS = [
     "talc_table_fetch_walk", "talc_batch_fetch_coverage_degrees", "talc_batch_structure", "talc_batch_fetch_structure",
     "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
     "talc_counter_destroy",
+    "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
+    "talc_ctx_get_map_timing",
 ]
+
+SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
+SEG_LETTERS = "SCR"
+# talc_segment (docs/correction_map.md)
+SEGMENT_DTYPE = np.dtype([("kind", "<u4"), ("raw_start", "<u4"), ("raw_len", "<u4"), ("out_start", "<u4"), ("out_len", "<u4")])
 
 
 class TalcError(RuntimeError):
@@ -158,6 +165,14 @@ def lib():
         L.talc_counter_fetch.argtypes = [vp, u32, vp, vp, u64, vp]
         L.talc_counter_build_table.argtypes = [vp, C.c_char_p, C.POINTER(vp), vp]
         L.talc_counter_destroy.argtypes = [vp]
+        # (a build from before the correction map, selected with TALC_LIB for an A/B, loads; asking it for a map raises)
+        if hasattr(L, "talc_ctx_set_map"):
+            L.talc_ctx_set_map.argtypes = [vp, i32]
+            L.talc_batch_num_segments.restype = u64
+            L.talc_batch_num_segments.argtypes = [vp]
+            L.talc_batch_fetch_map.argtypes = [vp, vp, vp, u64, vp]
+            L.talc_batch_fetch_corrected_masked.argtypes = [vp, vp, vp, u64, vp, vp]
+            L.talc_ctx_get_map_timing.argtypes = [vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -392,6 +407,16 @@ class Context:
         _chk(lib().talc_ctx_get_timing(self._h, C.byref(t)))
         return t
 
+    def record_map(self, on=True):
+        """Later corrections of this context keep the correction map (Batch.fetch_map, fetch_corrected(soft_mask=True))."""
+        _chk(lib().talc_ctx_set_map(self._h, 1 if on else 0))
+
+    def map_timing(self):
+        """(k_pack_map ms, k_mask_case ms) of the context's last map kernels."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_map_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def batch(self, bases, offsets):
         return Batch(self, bases, offsets)
 
@@ -488,15 +513,30 @@ class Batch:
         """0, or WARN_READ_ERRORS when some reads exhausted the device scratch (status READ_ERROR, passed through)."""
         return _chk(lib().talc_batch_correct(self.ctx._h, self._h))
 
-    def fetch_corrected(self, out=None):
-        """(records uint8 ASCII, offsets, status); `out`: a caller's uint8 buffer to fill (e.g. PinnedArray.array)."""
+    def fetch_corrected(self, out=None, soft_mask=False):
+        """(records uint8 ASCII, offsets, status); `out`: a caller's uint8 buffer to fill (e.g. PinnedArray.array).
+        soft_mask: the bases of RAW segments in lower case (needs Context.record_map() before the correction)."""
         total = int(lib().talc_batch_corrected_bytes(self._h))
         if out is None or len(out) < total:
             out = np.empty(max(total, 1), dtype=np.uint8)
         oo = np.empty(self.n_reads + 1, dtype=np.uint64)
         st = np.empty(self.n_reads, dtype=np.int32)
-        _chk(lib().talc_batch_fetch_corrected(self.ctx._h, self._h, out.ctypes.data, total, oo.ctypes.data, st.ctypes.data))
+        fetch = lib().talc_batch_fetch_corrected_masked if soft_mask else lib().talc_batch_fetch_corrected
+        _chk(fetch(self.ctx._h, self._h, out.ctypes.data, total, oo.ctypes.data, st.ctypes.data))
         return out[:total], oo, st
+
+    @property
+    def n_segments(self):
+        return int(lib().talc_batch_num_segments(self._h))
+
+    def fetch_map(self):
+        """(segments as a SEGMENT_DTYPE array, offsets u64[n_reads + 1]): the correction map of the last correction."""
+        so = np.empty(self.n_reads + 1, dtype=np.uint64)
+        _chk(lib().talc_batch_fetch_map(self.ctx._h, self._h, None, 0, so.ctypes.data))
+        n = int(so[self.n_reads])
+        segs = np.empty(max(n, 1), dtype=SEGMENT_DTYPE)
+        _chk(lib().talc_batch_fetch_map(self.ctx._h, self._h, segs.ctypes.data, n, so.ctypes.data))
+        return segs[:n], so
 
     def fetch_read_stats(self):
         """int64[n, 5]: {row written, raw length, IN-region span, IN regions, corrected length} (Read.cpp:418-433)."""
