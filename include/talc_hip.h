@@ -310,6 +310,33 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
  * k_mask_case (the last masked fetch that had to make its buffer).  Either pointer may be NULL. */
 int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_case_ms);
 
+/* The solidity report (docs/solidity.md): how much of every read the short reads support, before and after the correction —
+ * what lordec-stat reports, and what the last column of the reference's stats header (nbInKmers2, Read.cpp:392,413) was to hold.
+ * For a sequence S of L bases: n = max(0, L - K + 1); c[i] = the table count of S[i, i + K), 0 when the k-mer is absent or
+ * holds an N; position i is solid when c[i] >= MIN_COUNT. */
+typedef struct talc_solidity {
+  uint32_t n_kmers;       /* n */
+  uint32_t n_solid;       /* #{i : c[i] >= MIN_COUNT}                      (header: nbSolidKmers) */
+  uint32_t n_in;          /* #{i : c[i] >  MIN_COUNT}, Read.cpp:190        (header: nbInKmers / nbInKmers2) */
+  uint32_t n_regions;     /* maximal runs of solid positions               (header: nbSolidReg; no n > 1 condition) */
+  uint32_t solid_bases;   /* bases of S covered by at least one solid k-mer: | U [i, i+K) | */
+  uint32_t longest_weak;  /* longest run of consecutive non-solid positions, 0 when none */
+} talc_solidity;
+/* One device pass per row, nothing written per position.  Every read gets a raw row — S = the read as the correction sees
+ * it: Dna5-converted, reverse-complemented under -rev — and, when the batch has been corrected, a corrected row: S = its
+ * record as talc_batch_fetch_corrected returns it, in that same orientation (under -rev the reverse complement of a
+ * corrected read's record; a passed-through record already is in it).  A read that was passed through (too short, no solid
+ * k-mer, no structure, TALC_READ_ERROR) has a corrected row equal to its raw row; a read with L < K has all zeros.
+ * May be called on any batch: before a correction it computes the raw rows only.  It changes nothing a later
+ * talc_batch_correct, talc_batch_fetch_map or talc_batch_fetch_corrected reads. */
+int talc_batch_solidity(talc_ctx* c, talc_batch* b);
+/* raw / corrected: n_reads rows each, either may be NULL.  TALC_ERR_STATE when talc_batch_solidity has not run since the
+ * batch's last correction, and when `corrected` is asked for and the batch had not been corrected when it ran. */
+int talc_batch_fetch_solidity(talc_ctx* c, talc_batch* b, talc_solidity* raw, talc_solidity* corrected);
+/* Measurement: device time (ms) of the two k_solidity launches of the context's last talc_batch_solidity (corrected: 0 when
+ * there were no records).  Either pointer may be NULL. */
+int talc_ctx_get_solidity_timing(const talc_ctx* c, float* raw_ms, float* corrected_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

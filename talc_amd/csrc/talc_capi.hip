@@ -22,6 +22,7 @@
 #include "talc_kernels_count.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
+#include "talc_kernels_solidity.h"
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -120,12 +121,13 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[11] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case
+  hipEvent_t ev[14] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
   float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
+  float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -158,8 +160,11 @@ struct talc_batch {
   bool mapped = false, masked = false;   // d_segs holds that correction's map; d_masked its records, RAW stretches in lower case
   std::vector<uint64_t> h_seg_off;
   uint64_t segs_cap = 0, masked_cap = 0;
+  // the solidity report (talc_batch_solidity): rows of the reads, and of the records of the correction before it
+  bool solidity = false, solidityCorrected = false;
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  CachedBuf<SolidityRow> d_sol_corr, d_sol_raw;   // one row per read (k_solidity): of its record, of the read itself
   CachedBuf<uint8_t> d_masked;       // the dense records again, RAW stretches in lower case (k_mask_case; made on first use)
   CachedBuf<MapSeg> d_segs;          // the dense correction map (k_pack_map) and the reads' offsets into it
   CachedBuf<uint64_t> d_seg_off;
@@ -186,6 +191,7 @@ struct talc_batch {
 
 static_assert(sizeof(MapSeg) == sizeof(talc_segment) && TALC_SEG_SOLID == SEG_SOLID && TALC_SEG_CORRECTED == SEG_CORRECTED && TALC_SEG_RAW == SEG_RAW,
               "k_pack_map writes talc_segment records");
+static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 
 template <typename T>
 static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
@@ -767,6 +773,13 @@ int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_c
   if (!c) return fail(TALC_ERR_INVALID, "null context");
   if (pack_map_ms) *pack_map_ms = c->pack_map_ms;
   if (mask_case_ms) *mask_case_ms = c->mask_case_ms;
+  return TALC_OK;
+}
+
+int talc_ctx_get_solidity_timing(const talc_ctx* c, float* raw_ms, float* corrected_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (raw_ms) *raw_ms = c->sol_raw_ms;
+  if (corrected_ms) *corrected_ms = c->sol_corr_ms;
   return TALC_OK;
 }
 

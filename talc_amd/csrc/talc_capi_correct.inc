@@ -314,6 +314,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
   //  would be a mixture of this run's and the last one's)
   b->structured = false; b->corrected = false; b->mapped = false; b->masked = false;
+  b->solidity = false; b->solidityCorrected = false;
   const bool map = c->map;
   if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
@@ -348,6 +349,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipSetDevice(c->device));
   int rc;
   b->structured = false; b->corrected = false;
+  b->solidity = false; b->solidityCorrected = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
   if ((rc = read_stage_times(c, 3))) return rc;
@@ -476,6 +478,52 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
   HIPCHK(hipSetDevice(c->device));
   if (out && (rc = mask_dense(c, b))) return rc;
   return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output", true);
+}
+
+// ---- the solidity report (docs/solidity.md): k_solidity over the batch's codes (the raw rows) and, once the batch is
+// corrected, over the dense records as talc_batch_fetch_corrected returns them (the corrected rows)
+static int launch_solidity(talc_ctx* c, talc_batch* b, bool records) {
+  CachedBuf<SolidityRow>& rows = records ? b->d_sol_corr : b->d_sol_raw;
+  if (!rows) HIPCHK(rows.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
+  if (b->n_reads)
+    hipLaunchKernelGGL(k_solidity, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, records ? b->d_dense.get() : b->d_codes.get(),
+                       records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
+                       c->p.reverse ? 1 : 0, c->p.min_count, b->n_reads, rows.get());
+  HIPCHK(hipGetLastError());
+  return TALC_OK;
+}
+
+int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  int rc;
+  const bool records = b->corrected;
+  b->solidity = false; b->solidityCorrected = false;
+  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  HIPCHK(hipEventRecord(c->ev[11], s));
+  if ((rc = launch_solidity(c, b, false))) return rc;
+  HIPCHK(hipEventRecord(c->ev[12], s));
+  if (records && (rc = launch_solidity(c, b, true))) return rc;
+  HIPCHK(hipEventRecord(c->ev[13], s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventElapsedTime(&c->sol_raw_ms, c->ev[11], c->ev[12]));
+  c->sol_corr_ms = 0;
+  if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[12], c->ev[13]));
+  b->solidity = true; b->solidityCorrected = records;
+  return TALC_OK;
+}
+
+int talc_batch_fetch_solidity(talc_ctx* c, talc_batch* b, talc_solidity* raw, talc_solidity* corrected) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (!b->solidity) return fail(TALC_ERR_STATE, "talc_batch_solidity has not run on this batch since its last correction");
+  if (corrected && !b->solidityCorrected) return fail(TALC_ERR_STATE, "the batch had not been corrected when talc_batch_solidity ran: it has no corrected rows");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t bytes = (size_t)b->n_reads * sizeof(talc_solidity);
+  if (raw && bytes) HIPCHK(hipMemcpyAsync(raw, b->d_sol_raw.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+  if (corrected && bytes) HIPCHK(hipMemcpyAsync(corrected, b->d_sol_corr.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TALC_OK;
 }
 
 // Read::outputBasicReadStats (Read.cpp:418-433) for every read of a corrected batch

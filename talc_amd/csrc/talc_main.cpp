@@ -15,6 +15,8 @@
 //   --corr-map       write <o>.map.tsv, the correction map (docs/correction_map.md): one line per segment of every read,
 //                    in input order: read_name kind(S|C|R) raw_start raw_len out_start out_len
 //   --soft-mask      the bases of <o>.fa that were not corrected (RAW segments) in lower case, as LoRDEC writes them
+//   --solidity       write <o>.solidity.tsv, the solidity report (docs/solidity.md): one line per read, in input order, with
+//                    the short-read support of the read and of its record; one summary line on stdout
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -93,6 +95,7 @@ struct Options {
   bool haveBatchReads = false;
   bool readStats = false;
   bool corrMap = false, softMask = false;   // --corr-map, --soft-mask
+  bool solidity = false;                    // --solidity
 };
 
 void usage(FILE* f) {
@@ -125,6 +128,7 @@ void usage(FILE* f) {
           "  --corr-map                  write <o>.map.tsv: read_name, kind (S solid, C corrected, R raw), raw_start, raw_len,\n"
           "                              out_start, out_len for every stretch of every read (docs/correction_map.md)\n"
           "  --soft-mask                 write the bases that stayed uncorrected (R stretches) in lower case\n"
+          "  --solidity                  write <o>.solidity.tsv: k-mers and bases the short reads support, per read, raw and corrected\n"
           "  -h, --help / --version\n");
 }
 
@@ -176,6 +180,7 @@ Options parse(int argc, const char** argv) {
     else if (a == "--read-stats") o.readStats = true;
     else if (a == "--corr-map") o.corrMap = true;
     else if (a == "--soft-mask") o.softMask = true;
+    else if (a == "--solidity") o.solidity = true;
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
     else if (a.size() > 1 && a[0] == '-') parse_error("unknown option: " + a);
@@ -225,8 +230,9 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map;
-  explicit Files(const std::string& prefix) : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv") {}
+  const std::string fa, stats, log, map, solidity;
+  explicit Files(const std::string& prefix)
+      : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -357,7 +363,27 @@ struct Chunk {
   std::vector<int64_t> stats;           // 5 per read (--read-stats)
   std::string text, logText, statsText; // what the writer appends to <o>.fa / <o>.log / <o>.stats_basics.txt
   std::string mapText;                  // ... and to <o>.map.tsv (--corr-map)
+  std::string solText;                  // ... and to <o>.solidity.tsv (--solidity)
+  uint64_t solSums[4] = {0, 0, 0, 0};   // of the batch's lines: raw solid_bases, raw_length, corrected solid_bases, corr_length
 };
+
+// the lines of <o>.solidity.tsv for one batch (k.status filled; oo: the records' offsets): read_name status raw_length
+// corr_length, the six fields of the raw row, the six of the corrected row; and the batch's share of the summary line
+const char* const kSolidityHeader = "read_name\tstatus\traw_length\tcorr_length\traw_n_kmers\traw_n_solid\traw_n_in\traw_n_regions\traw_solid_bases\t"
+                                    "raw_longest_weak\tcorr_n_kmers\tcorr_n_solid\tcorr_n_in\tcorr_n_regions\tcorr_solid_bases\tcorr_longest_weak\n";
+void formatSolidity(Chunk& k, const talc_solidity* raw, const talc_solidity* cor, const uint64_t* oo) {
+  char num[256];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const uint64_t rawLen = k.offsets[r + 1] - k.offsets[r], corLen = oo[r + 1] - oo[r];
+    const talc_solidity &a = raw[r], &b = cor[r];
+    const int m = snprintf(num, sizeof num, "\t%d\t%llu\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", k.status[r], (unsigned long long)rawLen,
+                           (unsigned long long)corLen, a.n_kmers, a.n_solid, a.n_in, a.n_regions, a.solid_bases, a.longest_weak, b.n_kmers, b.n_solid,
+                           b.n_in, b.n_regions, b.solid_bases, b.longest_weak);
+    k.solText += k.ids[r];
+    k.solText.append(num, (size_t)m);
+    k.solSums[0] += a.solid_bases; k.solSums[1] += rawLen; k.solSums[2] += b.solid_bases; k.solSums[3] += corLen;
+  }
+}
 
 // the lines of <o>.map.tsv for one batch: the segments of read r are segs[so[r] .. so[r + 1]); those with both lengths 0
 // are left out
@@ -433,6 +459,11 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
     for (size_t r = 0; r < n; ++r) { const uint32_t L = (uint32_t)(oo[r + 1] - oo[r]); segs[r] = talc_segment{TALC_SEG_RAW, 0u, L, 0u, L}; }
     formatMap(c, segs.data(), so.data());
   }
+  if (o.solidity) {   // (no table: every count is 0, every position weak; the record is the read)
+    std::vector<talc_solidity> rows(n, talc_solidity{0u, 0u, 0u, 0u, 0u, 0u});
+    for (size_t r = 0; r < n; ++r) { const uint64_t L = oo[r + 1] - oo[r]; rows[r].n_kmers = rows[r].longest_weak = L >= o.p.k ? (uint32_t)(L - o.p.k + 1) : 0u; }
+    formatSolidity(c, rows.data(), rows.data(), oo.data());
+  }
   formatChunk(o, c, all.data(), oo.data());
 }
 
@@ -450,6 +481,7 @@ struct WorkerTally {
 struct PipelineTotals {
   double readerBusy = 0, writerBusy = 0;   // the three busy times overlap
   uint64_t bases = 0, batches = 0;
+  uint64_t solSums[4] = {0, 0, 0, 0};      // --solidity: the sums of four columns of <o>.solidity.tsv (Chunk::solSums)
   WorkerTally workers;
 };
 
@@ -483,8 +515,9 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf;
+    std::ofstream of, lf, sf, mf, yf;
     double busy = 0;
+    uint64_t solSums[4] = {0, 0, 0, 0};
   };
   bool fail(std::string msg);
   void readerMain(ReaderSide& r);
@@ -534,6 +567,11 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     wr.mf.open(files_.map, std::ios_base::trunc);
     if (!wr.mf) return fail("cannot write " + files_.map);
   }
+  if (o_.solidity) {
+    wr.yf.open(files_.solidity, std::ios_base::trunc);
+    if (!wr.yf) return fail("cannot write " + files_.solidity);
+    wr.yf << kSolidityHeader;
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -552,6 +590,8 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   }
   wr.of.close();
   if (wr.mf.is_open()) wr.mf.close();
+  if (wr.yf.is_open()) wr.yf.close();
+  for (int i = 0; i < 4; ++i) tot.solSums[i] = wr.solSums[i];
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
   for (const WorkerTally& t : tally) {
@@ -668,6 +708,11 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
     if (talc_batch_fetch_map(ctx, b.get(), segs.data(), segs.size(), so.data()) != TALC_OK) return fail(talc_last_error());
     formatMap(c, segs.data(), so.data());
   }
+  if (o_.solidity) {   // one more device pass over the reads and over the records, while both are in HBM
+    std::vector<talc_solidity> raw(std::max<uint32_t>(n, 1)), cor(std::max<uint32_t>(n, 1));
+    if (talc_batch_solidity(ctx, b.get()) != TALC_OK || talc_batch_fetch_solidity(ctx, b.get(), raw.data(), cor.data()) != TALC_OK) return fail(talc_last_error());
+    formatSolidity(c, raw.data(), cor.data(), oo.data());
+  }
   if (o_.readStats) {
     c.stats.resize(5ull * n);
     if (talc_batch_fetch_read_stats(ctx, b.get(), c.stats.data()) != TALC_OK) return fail(talc_last_error());
@@ -701,6 +746,10 @@ void Pipeline::writerMain(WriterSide& w) {
     if (!c->statsText.empty()) { if (!w.sf.is_open()) w.sf.open(files_.stats, std::ios_base::app); w.sf << c->statsText; }
     w.of.write(c->text.data(), (std::streamsize)c->text.size());
     if (w.mf.is_open()) w.mf.write(c->mapText.data(), (std::streamsize)c->mapText.size());
+    if (w.yf.is_open()) {
+      w.yf.write(c->solText.data(), (std::streamsize)c->solText.size());
+      for (int i = 0; i < 4; ++i) w.solSums[i] += c->solSums[i];
+    }
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -881,6 +930,13 @@ int main(int argc, const char** argv) {
   if (!ok) { std::cerr << "talc: device error: " << pipeline.failure() << "\n"; return 2; }
   if (totals.workers.readErrors)
     std::cerr << "talc: " << totals.workers.readErrors << " read(s) exhausted the device scratch and were written uncorrected (see " << files.log << ")\n";
+  if (o.solidity) {
+    const uint64_t* y = totals.solSums;
+    char line[200];
+    snprintf(line, sizeof line, "[TALC]: solid bases: raw %llu of %llu (%.2f %%), corrected %llu of %llu (%.2f %%)", (unsigned long long)y[0], (unsigned long long)y[1],
+             y[1] ? 100.0 * (double)y[0] / (double)y[1] : 0.0, (unsigned long long)y[2], (unsigned long long)y[3], y[3] ? 100.0 * (double)y[2] / (double)y[3] : 0.0);
+    std::cout << line << std::endl;
+  }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   report(t, totals, scan, o.batchReads, ndev, pipeline.workers());
   return 0;

@@ -36,12 +36,16 @@ ABI_SYMBOLS = [
     "talc_counter_destroy",
     "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
     "talc_ctx_get_map_timing",
+    "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
 SEG_LETTERS = "SCR"
 # talc_segment (docs/correction_map.md)
 SEGMENT_DTYPE = np.dtype([("kind", "<u4"), ("raw_start", "<u4"), ("raw_len", "<u4"), ("out_start", "<u4"), ("out_len", "<u4")])
+# talc_solidity (docs/solidity.md)
+SOLIDITY_FIELDS = ("n_kmers", "n_solid", "n_in", "n_regions", "solid_bases", "longest_weak")
+SOLIDITY_DTYPE = np.dtype([(f, "<u4") for f in SOLIDITY_FIELDS])
 
 
 class TalcError(RuntimeError):
@@ -173,6 +177,10 @@ def lib():
             L.talc_batch_fetch_map.argtypes = [vp, vp, vp, u64, vp]
             L.talc_batch_fetch_corrected_masked.argtypes = [vp, vp, vp, u64, vp, vp]
             L.talc_ctx_get_map_timing.argtypes = [vp, vp, vp]
+        if hasattr(L, "talc_batch_solidity"):   # (likewise: a build from before the solidity report)
+            L.talc_batch_solidity.argtypes = [vp, vp]
+            L.talc_batch_fetch_solidity.argtypes = [vp, vp, vp, vp]
+            L.talc_ctx_get_solidity_timing.argtypes = [vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -417,6 +425,12 @@ class Context:
         _chk(lib().talc_ctx_get_map_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def solidity_timing(self):
+        """(raw ms, corrected ms): device time of the two k_solidity launches of the context's last Batch.solidity()."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_solidity_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def batch(self, bases, offsets):
         return Batch(self, bases, offsets)
 
@@ -459,6 +473,7 @@ class Batch:
         h = C.c_void_p()
         _chk(lib().talc_batch_create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
         self._h = h
+        self._corrected = False   # the batch holds the records of a correction (solidity() then has corrected rows)
 
     @property
     def n_kmers(self):
@@ -488,6 +503,7 @@ class Batch:
 
     def structure(self):
         """Test hook: encode, coverage and the structure kernel; nothing of the search."""
+        self._corrected = False
         _chk(lib().talc_batch_structure(self.ctx._h, self._h))
 
     def fetch_structure(self):
@@ -511,7 +527,10 @@ class Batch:
 
     def correct(self):
         """0, or WARN_READ_ERRORS when some reads exhausted the device scratch (status READ_ERROR, passed through)."""
-        return _chk(lib().talc_batch_correct(self.ctx._h, self._h))
+        self._corrected = False
+        rc = _chk(lib().talc_batch_correct(self.ctx._h, self._h))
+        self._corrected = True
+        return rc
 
     def fetch_corrected(self, out=None, soft_mask=False):
         """(records uint8 ASCII, offsets, status); `out`: a caller's uint8 buffer to fill (e.g. PinnedArray.array).
@@ -537,6 +556,16 @@ class Batch:
         segs = np.empty(max(n, 1), dtype=SEGMENT_DTYPE)
         _chk(lib().talc_batch_fetch_map(self.ctx._h, self._h, segs.ctypes.data, n, so.ctypes.data))
         return segs[:n], so
+
+    def solidity(self):
+        """The solidity report (docs/solidity.md): (raw, corrected) as SOLIDITY_DTYPE arrays of one row per read — how
+        much of the read, and of its record, the short reads support.  corrected is None on a batch that has not been
+        corrected."""
+        _chk(lib().talc_batch_solidity(self.ctx._h, self._h))
+        raw = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE)
+        cor = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE) if self._corrected else None
+        _chk(lib().talc_batch_fetch_solidity(self.ctx._h, self._h, raw.ctypes.data, cor.ctypes.data if self._corrected else None))
+        return raw, cor
 
     def fetch_read_stats(self):
         """int64[n, 5]: {row written, raw length, IN-region span, IN regions, corrected length} (Read.cpp:418-433)."""
