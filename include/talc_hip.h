@@ -337,6 +337,38 @@ int talc_batch_fetch_solidity(talc_ctx* c, talc_batch* b, talc_solidity* raw, ta
  * there were no records).  Either pointer may be NULL. */
 int talc_ctx_get_solidity_timing(const talc_ctx* c, float* raw_ms, float* corrected_ms);
 
+/* Trimmed and split output (docs/trim_split.md): the records of a corrected batch cut at their uncorrected stretches, on
+ * the device, so that only the kept bytes cross to the host — what lordec-trim and lordec-trim-split make of LoRDEC's
+ * lower case.  Everything is in record coordinates: the record as talc_batch_fetch_corrected returns it, the segments as
+ * talc_batch_fetch_map returns them.  A byte of a record is weak when it lies in a RAW segment, trusted when it lies in a
+ * SOLID or CORRECTED one; segments with out_len 0 hold no byte and never start, end or split anything.
+ *   TALC_PIECES_SPLIT  the pieces of a read are its maximal runs of trusted bytes, in record order
+ *   TALC_PIECES_TRIM   at most one piece per read: from its first trusted byte to its last, inclusive; weak stretches inside
+ *                      it stay (with soft_mask in lower case: the bytes talc_batch_fetch_corrected_masked has there)
+ * A piece of fewer than min_len bytes is dropped (0 keeps all).  A read without a trusted byte — every read that was passed
+ * through — has no piece.  The pieces of a batch are ordered by read (input order), then by out_start.
+ *
+ * talc_batch_pieces needs a correction that kept the map (TALC_ERR_STATE otherwise); a mode outside the enum is
+ * TALC_ERR_INVALID; soft_mask is ignored in split mode (a piece has no weak byte).  A later call on the same batch replaces
+ * the earlier result.  It changes nothing that talc_batch_fetch_corrected, talc_batch_fetch_corrected_masked,
+ * talc_batch_fetch_map, talc_batch_solidity or a later talc_batch_correct reads. */
+typedef enum talc_piece_mode { TALC_PIECES_TRIM = 1, TALC_PIECES_SPLIT = 2 } talc_piece_mode;
+typedef struct talc_piece { uint32_t read, out_start, out_len; } talc_piece;   /* read index in the batch; range of its record */
+int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, int soft_mask);
+/* pieces / their bytes of the whole batch; 0 unless talc_batch_pieces ran since the batch's last correction */
+uint64_t talc_batch_num_pieces(const talc_batch* b);
+uint64_t talc_batch_pieces_bytes(const talc_batch* b);
+/* out: the bytes of the pieces, concatenated; piece_offsets[n_pieces + 1] into it; pieces[n_pieces]; read_piece_offsets[n_reads
+ * + 1]: the pieces of read r are pieces[read_piece_offsets[r] .. read_piece_offsets[r + 1]).  Every output may be NULL (out ==
+ * NULL with pieces == NULL fills only the offsets).  TALC_ERR_CAPACITY (the message names the size needed) when out_capacity
+ * (bytes) or piece_capacity (entries) is too small; TALC_ERR_STATE when talc_batch_pieces has not run since the batch's last
+ * correction. */
+int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* piece_offsets,
+                            talc_piece* pieces, uint64_t piece_capacity, uint64_t* read_piece_offsets);
+/* Measurement: device time (ms) of k_piece_count and k_piece_pack of the context's last talc_batch_pieces.  Either pointer
+ * may be NULL. */
+int talc_ctx_get_pieces_timing(const talc_ctx* c, float* count_ms, float* pack_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

@@ -20,6 +20,7 @@
 #include "talc_hip.h"
 #include "talc_kernels_build.h"
 #include "talc_kernels_count.h"
+#include "talc_kernels_pieces.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
 #include "talc_kernels_solidity.h"
@@ -121,13 +122,15 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[14] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity
+  hipEvent_t ev[18] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
+                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
   float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
   float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
+  float piece_count_ms = 0, piece_pack_ms = 0;   // the last talc_batch_pieces: k_piece_count, k_piece_pack
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -162,8 +165,17 @@ struct talc_batch {
   uint64_t segs_cap = 0, masked_cap = 0;
   // the solidity report (talc_batch_solidity): rows of the reads, and of the records of the correction before it
   bool solidity = false, solidityCorrected = false;
+  // trimmed / split output (talc_batch_pieces): the pieces of the last correction's records, made since that correction
+  bool pieced = false;
+  std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte
+  uint64_t pieces_cap = 0, piece_bytes_cap = 0;
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  CachedBuf<uint8_t> d_piece_bytes;  // the kept pieces' bytes, dense (k_piece_pack), sized exactly
+  CachedBuf<uint64_t> d_piece_off;   // one per piece: where its bytes start in d_piece_bytes
+  CachedBuf<OutPiece> d_pieces;         // the talc_piece entries, reads in input order
+  CachedBuf<uint64_t> d_read_byte_off, d_read_piece_off;   // h_read_byte_off / h_read_piece_off on the device
+  CachedBuf<PieceCount> d_piece_count;   // per read: kept pieces and their bytes (k_piece_count)
   CachedBuf<SolidityRow> d_sol_corr, d_sol_raw;   // one row per read (k_solidity): of its record, of the read itself
   CachedBuf<uint8_t> d_masked;       // the dense records again, RAW stretches in lower case (k_mask_case; made on first use)
   CachedBuf<MapSeg> d_segs;          // the dense correction map (k_pack_map) and the reads' offsets into it
@@ -191,6 +203,8 @@ struct talc_batch {
 
 static_assert(sizeof(MapSeg) == sizeof(talc_segment) && TALC_SEG_SOLID == SEG_SOLID && TALC_SEG_CORRECTED == SEG_CORRECTED && TALC_SEG_RAW == SEG_RAW,
               "k_pack_map writes talc_segment records");
+static_assert(sizeof(OutPiece) == sizeof(talc_piece) && sizeof(talc_piece) == 12 && sizeof(PieceCount) == 8 && TALC_PIECES_TRIM == PIECES_TRIM &&
+              TALC_PIECES_SPLIT == PIECES_SPLIT, "k_piece_pack writes talc_piece records");
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 
 template <typename T>
@@ -773,6 +787,13 @@ int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_c
   if (!c) return fail(TALC_ERR_INVALID, "null context");
   if (pack_map_ms) *pack_map_ms = c->pack_map_ms;
   if (mask_case_ms) *mask_case_ms = c->mask_case_ms;
+  return TALC_OK;
+}
+
+int talc_ctx_get_pieces_timing(const talc_ctx* c, float* count_ms, float* pack_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (count_ms) *count_ms = c->piece_count_ms;
+  if (pack_ms) *pack_ms = c->piece_pack_ms;
   return TALC_OK;
 }
 

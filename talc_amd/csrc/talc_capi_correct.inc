@@ -314,7 +314,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
   //  would be a mixture of this run's and the last one's)
   b->structured = false; b->corrected = false; b->mapped = false; b->masked = false;
-  b->solidity = false; b->solidityCorrected = false;
+  b->solidity = false; b->solidityCorrected = false; b->pieced = false;
   const bool map = c->map;
   if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
@@ -349,7 +349,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipSetDevice(c->device));
   int rc;
   b->structured = false; b->corrected = false;
-  b->solidity = false; b->solidityCorrected = false;
+  b->solidity = false; b->solidityCorrected = false; b->pieced = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
   if ((rc = read_stage_times(c, 3))) return rc;
@@ -478,6 +478,82 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
   HIPCHK(hipSetDevice(c->device));
   if (out && (rc = mask_dense(c, b))) return rc;
   return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output", true);
+}
+
+// ---- trimmed and split output (docs/trim_split.md): k_piece_count over the map, the reads' offsets on the host (as
+// pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (events 14 .. 17 around the two kernels)
+int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, int soft_mask) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (mode != TALC_PIECES_TRIM && mode != TALC_PIECES_SPLIT) return fail(TALC_ERR_INVALID, "piece mode %d is neither TALC_PIECES_TRIM nor TALC_PIECES_SPLIT", mode);
+  int rc;
+  if ((rc = need_map(b))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const uint32_t n = b->n_reads;
+  b->pieced = false;
+  const bool masked = mode == TALC_PIECES_TRIM && soft_mask;   // (a split piece has no weak byte)
+  if (masked && (rc = mask_dense(c, b))) return rc;
+  if (!b->d_piece_count) HIPCHK(b->d_piece_count.alloc(c->cache, std::max<uint32_t>(n, 1)));
+  HIPCHK(hipEventRecord(c->ev[14], s));
+  if (n) hipLaunchKernelGGL(k_piece_count, dim3(n), dim3(64), 0, s, b->d_segs.get(), b->d_seg_off.get(), n, mode, min_len, b->d_piece_count.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[15], s));
+  std::vector<PieceCount> counts(n);
+  if (n) HIPCHK(hipMemcpyAsync(counts.data(), b->d_piece_count.get(), (size_t)n * sizeof(PieceCount), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  b->h_read_piece_off.resize(n + 1); b->h_read_byte_off.resize(n + 1);
+  uint64_t np = 0, nb = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    b->h_read_piece_off[r] = np; b->h_read_byte_off[r] = nb;
+    np += counts[r].n; nb += counts[r].bytes;
+  }
+  b->h_read_piece_off[n] = np; b->h_read_byte_off[n] = nb;
+  // exactly what the pieces take; the buffers of an earlier call are kept when they are large enough
+  if (b->d_pieces && b->pieces_cap < np) { b->d_pieces.reset(); b->d_piece_off.reset(); }
+  if (!b->d_pieces) {
+    b->pieces_cap = std::max<uint64_t>(np, 1);
+    HIPCHK(b->d_pieces.alloc(c->cache, b->pieces_cap)); HIPCHK(b->d_piece_off.alloc(c->cache, b->pieces_cap));
+  }
+  if (b->d_piece_bytes && b->piece_bytes_cap < nb) b->d_piece_bytes.reset();
+  if (!b->d_piece_bytes) { b->piece_bytes_cap = std::max<uint64_t>(nb, 1); HIPCHK(b->d_piece_bytes.alloc(c->cache, b->piece_bytes_cap)); }
+  if (!b->d_read_piece_off) { HIPCHK(b->d_read_piece_off.alloc(c->cache, n + 1)); HIPCHK(b->d_read_byte_off.alloc(c->cache, n + 1)); }
+  HIPCHK(hipMemcpyAsync(b->d_read_piece_off.get(), b->h_read_piece_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(b->d_read_byte_off.get(), b->h_read_byte_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c->ev[16], s));
+  if (n && np)
+    hipLaunchKernelGGL(k_piece_pack, dim3(n), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), masked ? b->d_masked.get() : b->d_dense.get(),
+                       b->d_dense_off.get(), n, mode, min_len, b->d_read_piece_off.get(), b->d_read_byte_off.get(), b->d_pieces.get(),
+                       b->d_piece_off.get(), b->d_piece_bytes.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[17], s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventElapsedTime(&c->piece_count_ms, c->ev[14], c->ev[15]));
+  HIPCHK(hipEventElapsedTime(&c->piece_pack_ms, c->ev[16], c->ev[17]));
+  b->pieced = true;
+  return TALC_OK;
+}
+
+uint64_t talc_batch_num_pieces(const talc_batch* b) { return (b && b->corrected && b->pieced) ? b->h_read_piece_off[b->n_reads] : 0; }
+uint64_t talc_batch_pieces_bytes(const talc_batch* b) { return (b && b->corrected && b->pieced) ? b->h_read_byte_off[b->n_reads] : 0; }
+
+int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* piece_offsets, talc_piece* pieces,
+                            uint64_t piece_capacity, uint64_t* read_piece_offsets) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (!b->corrected || !b->pieced) return fail(TALC_ERR_STATE, "talc_batch_pieces has not run on this batch since its last correction");
+  HIPCHK(hipSetDevice(c->device));
+  const uint64_t np = b->h_read_piece_off[b->n_reads], nb = b->h_read_byte_off[b->n_reads];
+  if (read_piece_offsets) memcpy(read_piece_offsets, b->h_read_piece_off.data(), (b->n_reads + 1) * 8);
+  if (out && out_capacity < nb) return fail(TALC_ERR_CAPACITY, "piece byte buffer too small: need %llu bytes", (unsigned long long)nb);
+  if (pieces && piece_capacity < np) return fail(TALC_ERR_CAPACITY, "piece buffer too small: need %llu pieces", (unsigned long long)np);
+  hipStream_t s = c->stream;
+  if (piece_offsets) {
+    if (np) HIPCHK(hipMemcpyAsync(piece_offsets, b->d_piece_off.get(), np * 8, hipMemcpyDeviceToHost, s));
+    piece_offsets[np] = nb;
+  }
+  if (pieces && np) HIPCHK(hipMemcpyAsync(pieces, b->d_pieces.get(), np * sizeof(talc_piece), hipMemcpyDeviceToHost, s));
+  if (out && nb) HIPCHK(hipMemcpyAsync(out, b->d_piece_bytes.get(), nb, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TALC_OK;
 }
 
 // ---- the solidity report (docs/solidity.md): k_solidity over the batch's codes (the raw rows) and, once the batch is

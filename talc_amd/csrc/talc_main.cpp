@@ -17,6 +17,10 @@
 //   --soft-mask      the bases of <o>.fa that were not corrected (RAW segments) in lower case, as LoRDEC writes them
 //   --solidity       write <o>.solidity.tsv, the solidity report (docs/solidity.md): one line per read, in input order, with
 //                    the short-read support of the read and of its record; one summary line on stdout
+//   --trim          write <o>.trim.fa: every read cut down to the stretch from its first to its last trusted (solid or
+//                    corrected) base, cut on the device (docs/trim_split.md); reads without one are left out
+//   --split         write <o>.split.fa: every read split at its uncorrected stretches, pieces named name_1, name_2, ...
+//   --min-piece-len N  with --trim / --split: pieces of fewer than N bases are dropped (default 0)
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -96,6 +100,8 @@ struct Options {
   bool readStats = false;
   bool corrMap = false, softMask = false;   // --corr-map, --soft-mask
   bool solidity = false;                    // --solidity
+  bool trim = false, split = false;         // --trim, --split
+  uint32_t minPieceLen = 0;                 // --min-piece-len
 };
 
 void usage(FILE* f) {
@@ -129,6 +135,10 @@ void usage(FILE* f) {
           "                              out_start, out_len for every stretch of every read (docs/correction_map.md)\n"
           "  --soft-mask                 write the bases that stayed uncorrected (R stretches) in lower case\n"
           "  --solidity                  write <o>.solidity.tsv: k-mers and bases the short reads support, per read, raw and corrected\n"
+          "  --trim                      write <o>.trim.fa: each read from its first to its last solid or corrected base (reads\n"
+          "                              without one are left out; with --soft-mask the uncorrected stretches inside in lower case)\n"
+          "  --split                     write <o>.split.fa: each read cut at its uncorrected stretches, pieces named name_1, name_2, ...\n"
+          "  --min-piece-len INT         with --trim / --split: drop pieces of fewer bases, default 0 (docs/trim_split.md)\n"
           "  -h, --help / --version\n");
 }
 
@@ -181,6 +191,9 @@ Options parse(int argc, const char** argv) {
     else if (a == "--corr-map") o.corrMap = true;
     else if (a == "--soft-mask") o.softMask = true;
     else if (a == "--solidity") o.solidity = true;
+    else if (a == "--trim") o.trim = true;
+    else if (a == "--split") o.split = true;
+    else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
     else if (a.size() > 1 && a[0] == '-') parse_error("unknown option: " + a);
@@ -230,9 +243,10 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity;
+  const std::string fa, stats, log, map, solidity, trim, split;
   explicit Files(const std::string& prefix)
-      : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv") {}
+      : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
+        trim(prefix + ".trim.fa"), split(prefix + ".split.fa") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -365,7 +379,23 @@ struct Chunk {
   std::string mapText;                  // ... and to <o>.map.tsv (--corr-map)
   std::string solText;                  // ... and to <o>.solidity.tsv (--solidity)
   uint64_t solSums[4] = {0, 0, 0, 0};   // of the batch's lines: raw solid_bases, raw_length, corrected solid_bases, corr_length
+  std::string trimText, splitText;      // ... and to <o>.trim.fa / <o>.split.fa (--trim, --split)
+  uint64_t pieceSums[4] = {0, 0, 0, 0}; // of the batch: trimmed reads, their bases, split pieces, their bases
 };
+
+// the records of <o>.trim.fa or <o>.split.fa for one batch: the pieces of read r are po[rpo[r]] .. po[rpo[r + 1]] of
+// `bytes`; a trimmed read keeps its name, split pieces are name_1, name_2, ... counting the kept ones; lines of 70 columns
+void formatPieces(const Chunk& k, bool split, const char* bytes, const uint64_t* po, const uint64_t* rpo, std::string& text, uint64_t sums[2]) {
+  for (size_t r = 0; r < k.ids.size(); ++r)
+    for (uint64_t i = rpo[r]; i < rpo[r + 1]; ++i) {
+      text += '>'; text += k.ids[r];
+      if (split) { text += '_'; text += std::to_string(i - rpo[r] + 1); }
+      text += '\n';
+      const size_t L = (size_t)(po[i + 1] - po[i]);
+      for (size_t p = 0; p < L; p += 70) { text.append(bytes + po[i] + p, std::min<size_t>(70, L - p)); text += '\n'; }
+      sums[0] += 1; sums[1] += L;
+    }
+}
 
 // the lines of <o>.solidity.tsv for one batch (k.status filled; oo: the records' offsets): read_name status raw_length
 // corr_length, the six fields of the raw row, the six of the corrected row; and the batch's share of the summary line
@@ -482,6 +512,7 @@ struct PipelineTotals {
   double readerBusy = 0, writerBusy = 0;   // the three busy times overlap
   uint64_t bases = 0, batches = 0;
   uint64_t solSums[4] = {0, 0, 0, 0};      // --solidity: the sums of four columns of <o>.solidity.tsv (Chunk::solSums)
+  uint64_t pieceSums[4] = {0, 0, 0, 0};    // --trim / --split: trimmed reads, their bases, split pieces, their bases
   WorkerTally workers;
 };
 
@@ -515,15 +546,16 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf;
     double busy = 0;
-    uint64_t solSums[4] = {0, 0, 0, 0};
+    uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0};
   };
   bool fail(std::string msg);
   void readerMain(ReaderSide& r);
   void workerMain(int device, WorkerTally& t);
   void correctChunks(int device, WorkerTally& t);
   bool correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTally& t);
+  bool fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split);
   void writerMain(WriterSide& w);   // io.cpp:50-75 + SeqFileOut FASTA writer, io.cpp:105-111 log lines
 
   // immutable once constructed
@@ -572,6 +604,14 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     if (!wr.yf) return fail("cannot write " + files_.solidity);
     wr.yf << kSolidityHeader;
   }
+  if (o_.trim) {   // (without a table both files exist and stay empty: nothing has a trusted base)
+    wr.tf.open(files_.trim, std::ios_base::trunc);
+    if (!wr.tf) return fail("cannot write " + files_.trim);
+  }
+  if (o_.split) {
+    wr.pf.open(files_.split, std::ios_base::trunc);
+    if (!wr.pf) return fail("cannot write " + files_.split);
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -591,7 +631,9 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   wr.of.close();
   if (wr.mf.is_open()) wr.mf.close();
   if (wr.yf.is_open()) wr.yf.close();
-  for (int i = 0; i < 4; ++i) tot.solSums[i] = wr.solSums[i];
+  if (wr.tf.is_open()) wr.tf.close();
+  if (wr.pf.is_open()) wr.pf.close();
+  for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; }
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
   for (const WorkerTally& t : tally) {
@@ -652,7 +694,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     talc_ctx* made = nullptr;
     if (talc_ctx_create(table_, &o_.p, device, &made) != TALC_OK) { fail(talc_last_error()); return; }
     ctx.reset(made);
-    if ((o_.corrMap || o_.softMask) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
+    if ((o_.corrMap || o_.softMask || o_.trim || o_.split) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -677,6 +719,17 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     q_.finished[c->index] = std::move(c);
     q_.cvDone.notify_one();
   }
+}
+
+// --trim / --split: the batch's records cut on the device, only the kept bytes fetched, and turned into the file's text
+bool Pipeline::fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split) {
+  if (talc_batch_pieces(ctx, b, split ? TALC_PIECES_SPLIT : TALC_PIECES_TRIM, o_.minPieceLen, o_.softMask ? 1 : 0) != TALC_OK) return fail(talc_last_error());
+  const uint64_t np = talc_batch_num_pieces(b), nb = talc_batch_pieces_bytes(b);
+  std::vector<char> bytes(std::max<uint64_t>(nb, 1));
+  std::vector<uint64_t> po(np + 1), rpo(c.ids.size() + 1);
+  if (talc_batch_fetch_pieces(ctx, b, bytes.data(), nb, po.data(), nullptr, 0, rpo.data()) != TALC_OK) return fail(talc_last_error());
+  formatPieces(c, split, bytes.data(), po.data(), rpo.data(), split ? c.splitText : c.trimText, c.pieceSums + (split ? 2 : 0));
+  return true;
 }
 
 // one batch through the device and into text; false after fail()
@@ -713,6 +766,8 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
     if (talc_batch_solidity(ctx, b.get()) != TALC_OK || talc_batch_fetch_solidity(ctx, b.get(), raw.data(), cor.data()) != TALC_OK) return fail(talc_last_error());
     formatSolidity(c, raw.data(), cor.data(), oo.data());
   }
+  if (o_.trim && !fetchPieces(ctx, b.get(), c, false)) return false;
+  if (o_.split && !fetchPieces(ctx, b.get(), c, true)) return false;
   if (o_.readStats) {
     c.stats.resize(5ull * n);
     if (talc_batch_fetch_read_stats(ctx, b.get(), c.stats.data()) != TALC_OK) return fail(talc_last_error());
@@ -750,6 +805,9 @@ void Pipeline::writerMain(WriterSide& w) {
       w.yf.write(c->solText.data(), (std::streamsize)c->solText.size());
       for (int i = 0; i < 4; ++i) w.solSums[i] += c->solSums[i];
     }
+    if (w.tf.is_open()) w.tf.write(c->trimText.data(), (std::streamsize)c->trimText.size());
+    if (w.pf.is_open()) w.pf.write(c->splitText.data(), (std::streamsize)c->splitText.size());
+    for (int i = 0; i < 4; ++i) w.pieceSums[i] += c->pieceSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -935,6 +993,14 @@ int main(int argc, const char** argv) {
     char line[200];
     snprintf(line, sizeof line, "[TALC]: solid bases: raw %llu of %llu (%.2f %%), corrected %llu of %llu (%.2f %%)", (unsigned long long)y[0], (unsigned long long)y[1],
              y[1] ? 100.0 * (double)y[0] / (double)y[1] : 0.0, (unsigned long long)y[2], (unsigned long long)y[3], y[3] ? 100.0 * (double)y[2] / (double)y[3] : 0.0);
+    std::cout << line << std::endl;
+  }
+  if (o.trim || o.split) {
+    const uint64_t* y = totals.pieceSums;
+    std::string line = "[TALC]: ";
+    if (o.trim) line += "trimmed: " + std::to_string(y[0]) + " reads, " + std::to_string(y[1]) + " bases";
+    if (o.trim && o.split) line += "; ";
+    if (o.split) line += "split: " + std::to_string(y[2]) + " pieces, " + std::to_string(y[3]) + " bases";
     std::cout << line << std::endl;
   }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
     "talc_ctx_get_map_timing",
     "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
+    "talc_batch_pieces", "talc_batch_num_pieces", "talc_batch_pieces_bytes", "talc_batch_fetch_pieces", "talc_ctx_get_pieces_timing",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -46,6 +47,9 @@ SEGMENT_DTYPE = np.dtype([("kind", "<u4"), ("raw_start", "<u4"), ("raw_len", "<u
 # talc_solidity (docs/solidity.md)
 SOLIDITY_FIELDS = ("n_kmers", "n_solid", "n_in", "n_regions", "solid_bases", "longest_weak")
 SOLIDITY_DTYPE = np.dtype([(f, "<u4") for f in SOLIDITY_FIELDS])
+# talc_piece_mode, talc_piece (docs/trim_split.md)
+PIECES_TRIM, PIECES_SPLIT = 1, 2
+PIECE_DTYPE = np.dtype([("read", "<u4"), ("out_start", "<u4"), ("out_len", "<u4")])
 
 
 class TalcError(RuntimeError):
@@ -181,6 +185,14 @@ def lib():
             L.talc_batch_solidity.argtypes = [vp, vp]
             L.talc_batch_fetch_solidity.argtypes = [vp, vp, vp, vp]
             L.talc_ctx_get_solidity_timing.argtypes = [vp, vp, vp]
+        if hasattr(L, "talc_batch_pieces"):     # (likewise: a build from before the trimmed / split output)
+            L.talc_batch_pieces.argtypes = [vp, vp, i32, u32, i32]
+            L.talc_batch_num_pieces.restype = u64
+            L.talc_batch_num_pieces.argtypes = [vp]
+            L.talc_batch_pieces_bytes.restype = u64
+            L.talc_batch_pieces_bytes.argtypes = [vp]
+            L.talc_batch_fetch_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
+            L.talc_ctx_get_pieces_timing.argtypes = [vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -431,6 +443,12 @@ class Context:
         _chk(lib().talc_ctx_get_solidity_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def pieces_timing(self):
+        """(k_piece_count ms, k_piece_pack ms) of the context's last Batch.pieces()."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_pieces_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def batch(self, bases, offsets):
         return Batch(self, bases, offsets)
 
@@ -566,6 +584,21 @@ class Batch:
         cor = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE) if self._corrected else None
         _chk(lib().talc_batch_fetch_solidity(self.ctx._h, self._h, raw.ctypes.data, cor.ctypes.data if self._corrected else None))
         return raw, cor
+
+    def pieces(self, mode, min_len=0, soft_mask=False):
+        """Trimmed (PIECES_TRIM) or split (PIECES_SPLIT) output of the last correction (docs/trim_split.md; needs
+        Context.record_map() before it): (bytes uint8, piece_offsets u64[n_pieces + 1], pieces as a PIECE_DTYPE array,
+        read_piece_offsets u64[n_reads + 1]).  Pieces shorter than min_len are dropped; soft_mask: the weak stretches
+        inside a trimmed piece in lower case."""
+        L = lib()
+        _chk(L.talc_batch_pieces(self.ctx._h, self._h, int(mode), int(min_len), 1 if soft_mask else 0))
+        n, nb = int(L.talc_batch_num_pieces(self._h)), int(L.talc_batch_pieces_bytes(self._h))
+        out = np.empty(max(nb, 1), dtype=np.uint8)
+        po = np.empty(n + 1, dtype=np.uint64)
+        pc = np.empty(max(n, 1), dtype=PIECE_DTYPE)
+        rpo = np.empty(self.n_reads + 1, dtype=np.uint64)
+        _chk(L.talc_batch_fetch_pieces(self.ctx._h, self._h, out.ctypes.data, nb, po.ctypes.data, pc.ctypes.data, n, rpo.ctypes.data))
+        return out[:nb], po, pc[:n], rpo
 
     def fetch_read_stats(self):
         """int64[n, 5]: {row written, raw length, IN-region span, IN regions, corrected length} (Read.cpp:418-433)."""
