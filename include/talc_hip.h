@@ -369,6 +369,56 @@ int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_
  * may be NULL. */
 int talc_ctx_get_pieces_timing(const talc_ctx* c, float* count_ms, float* pack_ms);
 
+/* The edit scripts of a correction (docs/correction_edits.md): for every read the run-length list of operations that turns
+ * `raw` — the read as the caller gave it, Dna5-converted to upper case — into `rec`, its record as talc_batch_fetch_corrected
+ * returns it, segment by segment of the map as talc_batch_fetch_map returns it (under -rev: already in the caller's
+ * orientation).  An op is one uint32_t, len << 4 | code, with BAM's codes: I 1 (a base of rec that raw has not), D 2 (a base
+ * of raw that rec has not), = 7, X 8.  The script of a read is the concatenation, in segment order, of one part per segment:
+ *   SOLID or RAW   out_len x '='; nothing is compared (in a corrected read these stretches of raw and rec are equal)
+ *   CORRECTED      with a = raw[raw_start, +raw_len), b = rec[out_start, +out_len), n = |a|, m = |b|:
+ *                  n == 0: m x I;  m == 0: n x D;  both 0: nothing;
+ *                  n m > max_cells: not aligned — n x D, then m x I, and the segment counts as unaligned;
+ *                  otherwise the canonical optimal alignment under unit costs, bytes compared as they are (N == N): with
+ *                  D[i][j] the edit distance of a[:i] and b[:j], walk back from (n, m); take the diagonal ('=' or X) when
+ *                  i, j > 0 and D[i-1][j-1] + (a[i-1] != b[j-1]) == D[i][j]; else D when i > 0 and D[i-1][j] + 1 ==
+ *                  D[i][j]; else I; reverse.  The rule is applied in the caller's orientation.
+ * Adjacent equal ops are merged over the whole read, across segment boundaries; an empty read has no op.
+ * A read that was passed through has one RAW segment and the script L '='.  Under -rev its record is the reverse complement
+ * of the input (main.cpp:253), so that script relates the record to the read as the correction sees it, not as the caller
+ * gave it.
+ * Row: n_ins and n_del include the bases of unaligned segments, n_unaligned counts those segments, n_ops the read's ops;
+ * n_match + n_mismatch + n_del is the read's length, n_match + n_mismatch + n_ins its record's.
+ *
+ * talc_batch_edits needs a correction that kept the map (TALC_ERR_STATE otherwise).  max_cells: 0 is the default, 1 << 26.
+ * One deviation from "every pair of at most max_cells cells is aligned": the alignment's device scratch is bounded by 1 GiB
+ * whatever the batch, and one pair may take half of it, so a max_cells beyond 1 << 29 acts as 1 << 29 — a pair of more cells
+ * than that is not aligned (n x D, m x I, counted in n_unaligned) however large max_cells is.  A later call on the same batch
+ * replaces the earlier result.  It changes nothing that talc_batch_fetch_corrected,
+ * talc_batch_fetch_corrected_masked, talc_batch_fetch_map, talc_batch_solidity, talc_batch_pieces or a later
+ * talc_batch_correct reads. */
+typedef struct talc_edit_row { uint32_t n_match, n_mismatch, n_ins, n_del, n_ops, n_unaligned; } talc_edit_row;
+int talc_batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells);
+/* ops of the whole batch; 0 unless talc_batch_edits ran since the batch's last correction */
+uint64_t talc_batch_num_edit_ops(const talc_batch* b);
+/* ops: the batch's ops, reads in input order; op_offsets[n_reads + 1]: the ops of read r are ops[op_offsets[r] ..
+ * op_offsets[r + 1]); rows[n_reads].  Each may be NULL (ops == NULL fills only offsets and rows).  TALC_ERR_CAPACITY (the
+ * message names the count needed) when op_capacity is too small; TALC_ERR_STATE when talc_batch_edits has not run since the
+ * batch's last correction. */
+int talc_batch_fetch_edits(talc_ctx* c, talc_batch* b, uint32_t* ops, uint64_t op_capacity, uint64_t* op_offsets,
+                           talc_edit_row* rows);
+/* Measurement: device time (ms) of the context's last edit scripts — align_ms both runs of k_edit_align (the first counts a
+ * part's runs, the second writes them), pack_ms k_edit_count and k_edit_pack.  Either pointer may be NULL. */
+int talc_ctx_get_edits_timing(const talc_ctx* c, float* align_ms, float* pack_ms);
+/* Test hook, not part of the reference surface: the device routine on one pair of ASCII sequences, as the one CORRECTED
+ * segment of a one-read batch: its merged script (ops may be NULL: only *n_ops; TALC_ERR_CAPACITY when op_capacity is too
+ * small) and *distance = the edit distance the alignment found (la + lb when a side is empty, -1 when the pair is over
+ * max_cells and was not aligned).  n_ops and distance may be NULL. */
+int talc_test_edit_script(talc_ctx* c, const char* a, uint32_t la, const char* b, uint32_t lb, uint64_t max_cells,
+                          uint32_t* ops, uint64_t op_capacity, uint64_t* n_ops, int32_t* distance);
+/* Test hook: talc_batch_edits with scratch_bytes (128 .. 1 << 30) in place of the 1 GiB budget, so that the alignments of a
+ * small batch run in several rounds; TALC_ERR_INVALID when one pair alone does not fit.  Same result as talc_batch_edits. */
+int talc_test_batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells, uint64_t scratch_bytes);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "talc_edit_plan.h"
 #include "talc_pure.h"
 #include "talc_wfa.h"
 
@@ -91,4 +92,24 @@ int pure_wfa_xdrop_resume(const uint8_t* q, int qlen, const uint8_t* d, int dlen
   out4[0] = r.moved; out4[1] = r.extCols; out4[2] = r.extRows; out4[3] = r.score;
   return resumed ? 1 : 0;
 }
+
+// the edit scripts' planner (talc_edit_plan.h) on `count` pairs n[i] x m[i], in order: kind[i] = edit_part_kind; for a DP
+// word[i] = where its delta words start (all ones: LDS) and round[i] = its round; *most = the largest round's words.
+// Returns the number of rounds, -1 when a pair alone is beyond budget_words.
+int pure_edit_plan(const uint32_t* n, const uint32_t* m, uint32_t count, uint64_t max_cells, uint64_t budget_words, int32_t* kind,
+                   uint64_t* word, int32_t* round, uint64_t* most) {
+  EditPlan plan(budget_words);
+  for (uint32_t i = 0; i < count; ++i) {
+    kind[i] = edit_part_kind(n[i], m[i], max_cells); word[i] = 0; round[i] = -1;
+    if (kind[i] == EDIT_PART_DP && !plan.add(i, 0, n[i], m[i])) return -1;
+  }
+  plan.finish();
+  size_t t = 0;
+  for (size_t r = 0; r < plan.roundEnd.size(); ++r)
+    for (; t < plan.roundEnd[r]; ++t) { word[plan.tasks[t].seg] = plan.tasks[t].scratchWord; round[plan.tasks[t].seg] = (int32_t)r; }
+  *most = plan.mostWords;
+  return (int)plan.roundEnd.size();
+}
+uint64_t pure_edit_scratch_words(uint32_t n, uint32_t m) { return edit_scratch_words(n, m); }
+int pure_edit_in_lds(uint32_t n, uint32_t m) { return edit_in_lds(n, m) ? 1 : 0; }
 }  // extern "C"

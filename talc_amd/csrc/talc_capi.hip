@@ -20,6 +20,7 @@
 #include "talc_hip.h"
 #include "talc_kernels_build.h"
 #include "talc_kernels_count.h"
+#include "talc_kernels_edits.h"
 #include "talc_kernels_pieces.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
@@ -122,8 +123,8 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[18] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
-                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack
+  hipEvent_t ev[24] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
+                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack; 18 .. 23: the edit scripts (run_edits)
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
@@ -131,6 +132,7 @@ struct talc_ctx {
   float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
   float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
   float piece_count_ms = 0, piece_pack_ms = 0;   // the last talc_batch_pieces: k_piece_count, k_piece_pack
+  float edit_align_ms = 0, edit_pack_ms = 0;     // the last edit scripts: both k_edit_align runs, k_edit_count + k_edit_pack
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -142,6 +144,14 @@ struct talc_ctx {
     for (auto& e : ev) if (e) hipEventDestroy(e);
     if (stream) hipStreamDestroy(stream);
   }
+};
+
+// the edit scripts of a batch (talc_batch_edits; talc_capi_edits.inc)
+struct EditOut {
+  std::vector<uint64_t> h_op_off;    // n_reads + 1: the reads' first op
+  std::vector<EditRow> h_rows;       // n_reads
+  uint64_t ops_cap = 0;
+  CachedBuf<uint32_t> d_ops;         // the ops of all reads, dense, sized exactly
 };
 
 struct talc_batch {
@@ -169,8 +179,11 @@ struct talc_batch {
   bool pieced = false;
   std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte
   uint64_t pieces_cap = 0, piece_bytes_cap = 0;
+  // the edit scripts (talc_batch_edits) of the last correction, made since that correction
+  bool edited = false;
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  EditOut edits;
   CachedBuf<uint8_t> d_piece_bytes;  // the kept pieces' bytes, dense (k_piece_pack), sized exactly
   CachedBuf<uint64_t> d_piece_off;   // one per piece: where its bytes start in d_piece_bytes
   CachedBuf<OutPiece> d_pieces;         // the talc_piece entries, reads in input order
@@ -205,6 +218,7 @@ static_assert(sizeof(MapSeg) == sizeof(talc_segment) && TALC_SEG_SOLID == SEG_SO
               "k_pack_map writes talc_segment records");
 static_assert(sizeof(OutPiece) == sizeof(talc_piece) && sizeof(talc_piece) == 12 && sizeof(PieceCount) == 8 && TALC_PIECES_TRIM == PIECES_TRIM &&
               TALC_PIECES_SPLIT == PIECES_SPLIT, "k_piece_pack writes talc_piece records");
+static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) == 24 && sizeof(EditPart) == 32 && sizeof(EditTask) == 16, "k_edit_count writes talc_edit_row records");
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 
 template <typename T>
@@ -1256,5 +1270,6 @@ void talc_counter_destroy(talc_counter* c) {
 }
 
 #include "talc_capi_correct.inc"
+#include "talc_capi_edits.inc"
 
 }  // extern "C"

@@ -21,6 +21,9 @@
 //                    corrected) base, cut on the device (docs/trim_split.md); reads without one are left out
 //   --split         write <o>.split.fa: every read split at its uncorrected stretches, pieces named name_1, name_2, ...
 //   --min-piece-len N  with --trim / --split: pieces of fewer than N bases are dropped (default 0)
+//   --corr-edits    write <o>.edits.tsv, the edit script of every read (docs/correction_edits.md): one line per read, in
+//                    input order, with the counts of matches, mismatches, insertions and deletions and a CIGAR string
+//   --max-edit-cells N  with --corr-edits: a corrected stretch of more than N cells (raw x corrected length) is not aligned
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -102,6 +105,8 @@ struct Options {
   bool solidity = false;                    // --solidity
   bool trim = false, split = false;         // --trim, --split
   uint32_t minPieceLen = 0;                 // --min-piece-len
+  bool corrEdits = false;                   // --corr-edits
+  uint64_t maxEditCells = 0;                // --max-edit-cells (0: the library's default)
 };
 
 void usage(FILE* f) {
@@ -139,6 +144,9 @@ void usage(FILE* f) {
           "                              without one are left out; with --soft-mask the uncorrected stretches inside in lower case)\n"
           "  --split                     write <o>.split.fa: each read cut at its uncorrected stretches, pieces named name_1, name_2, ...\n"
           "  --min-piece-len INT         with --trim / --split: drop pieces of fewer bases, default 0 (docs/trim_split.md)\n"
+          "  --corr-edits                write <o>.edits.tsv: matches, mismatches, insertions, deletions and a CIGAR string per read\n"
+          "  --max-edit-cells INT        with --corr-edits: do not align a corrected stretch of more cells (raw x corrected\n"
+          "                              length), default 67108864; beyond 536870912 it acts as that (docs/correction_edits.md)\n"
           "  -h, --help / --version\n");
 }
 
@@ -193,6 +201,8 @@ Options parse(int argc, const char** argv) {
     else if (a == "--solidity") o.solidity = true;
     else if (a == "--trim") o.trim = true;
     else if (a == "--split") o.split = true;
+    else if (a == "--corr-edits") o.corrEdits = true;
+    else if (a == "--max-edit-cells") { double v = num(need(i), "max-edit-cells"); range(v, 1, 9e18, "max-edit-cells"); o.maxEditCells = (uint64_t)v; }
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -243,10 +253,10 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split;
+  const std::string fa, stats, log, map, solidity, trim, split, edits;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
-        trim(prefix + ".trim.fa"), split(prefix + ".split.fa") {}
+        trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -381,7 +391,33 @@ struct Chunk {
   uint64_t solSums[4] = {0, 0, 0, 0};   // of the batch's lines: raw solid_bases, raw_length, corrected solid_bases, corr_length
   std::string trimText, splitText;      // ... and to <o>.trim.fa / <o>.split.fa (--trim, --split)
   uint64_t pieceSums[4] = {0, 0, 0, 0}; // of the batch: trimmed reads, their bases, split pieces, their bases
+  std::string editText;                 // ... and to <o>.edits.tsv (--corr-edits)
+  uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch's corrected reads: =, X, I, D bases, the reads, segments not aligned
 };
+
+// the lines of <o>.edits.tsv for one batch (k.status filled; oo: the records' offsets; the ops of read r are ops[po[r] ..
+// po[r + 1])): read_name status raw_length corr_length, five fields of the row, as_seen — '-' when the record is in the
+// orientation the correction worked in rather than the caller's (-rev, passed through) —, and the ops as text
+const char* const kEditsHeader = "read_name\tstatus\traw_length\tcorr_length\tn_match\tn_mismatch\tn_ins\tn_del\tn_unaligned\tas_seen\tcigar\n";
+void formatEdits(const Options& o, Chunk& k, const uint32_t* ops, const uint64_t* po, const talc_edit_row* rows, const uint64_t* oo) {
+  char num[256];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const talc_edit_row& w = rows[r];
+    const bool corrected = k.status[r] == TALC_READ_CORRECTED;
+    const int m = snprintf(num, sizeof num, "\t%d\t%llu\t%llu\t%u\t%u\t%u\t%u\t%u\t%c\t", k.status[r], (unsigned long long)(k.offsets[r + 1] - k.offsets[r]),
+                           (unsigned long long)(oo[r + 1] - oo[r]), w.n_match, w.n_mismatch, w.n_ins, w.n_del, w.n_unaligned, (o.p.reverse && !corrected) ? '-' : '+');
+    k.editText += k.ids[r];
+    k.editText.append(num, (size_t)m);
+    if (po[r] == po[r + 1]) k.editText += '*';
+    for (uint64_t i = po[r]; i < po[r + 1]; ++i) {
+      const uint32_t code = ops[i] & 15u;
+      k.editText += std::to_string(ops[i] >> 4);
+      k.editText += code == 7u ? '=' : code == 8u ? 'X' : code == 1u ? 'I' : 'D';
+    }
+    k.editText += '\n';
+    if (corrected) { k.editSums[0] += w.n_match; k.editSums[1] += w.n_mismatch; k.editSums[2] += w.n_ins; k.editSums[3] += w.n_del; k.editSums[4] += 1; k.editSums[5] += w.n_unaligned; }
+  }
+}
 
 // the records of <o>.trim.fa or <o>.split.fa for one batch: the pieces of read r are po[rpo[r]] .. po[rpo[r + 1]] of
 // `bytes`; a trimmed read keeps its name, split pieces are name_1, name_2, ... counting the kept ones; lines of 70 columns
@@ -494,6 +530,17 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
     for (size_t r = 0; r < n; ++r) { const uint64_t L = oo[r + 1] - oo[r]; rows[r].n_kmers = rows[r].longest_weak = L >= o.p.k ? (uint32_t)(L - o.p.k + 1) : 0u; }
     formatSolidity(c, rows.data(), rows.data(), oo.data());
   }
+  if (o.corrEdits) {   // (nothing was corrected: every read is L '=')
+    std::vector<uint32_t> ops;
+    std::vector<uint64_t> po(n + 1, 0);
+    std::vector<talc_edit_row> rows(n, talc_edit_row{0u, 0u, 0u, 0u, 0u, 0u});
+    for (size_t r = 0; r < n; ++r) {
+      const uint32_t L = (uint32_t)(oo[r + 1] - oo[r]);
+      if (L) { ops.push_back(L << 4 | 7u); rows[r].n_match = L; rows[r].n_ops = 1; }
+      po[r + 1] = ops.size();
+    }
+    formatEdits(o, c, ops.data(), po.data(), rows.data(), oo.data());
+  }
   formatChunk(o, c, all.data(), oo.data());
 }
 
@@ -513,6 +560,7 @@ struct PipelineTotals {
   uint64_t bases = 0, batches = 0;
   uint64_t solSums[4] = {0, 0, 0, 0};      // --solidity: the sums of four columns of <o>.solidity.tsv (Chunk::solSums)
   uint64_t pieceSums[4] = {0, 0, 0, 0};    // --trim / --split: trimmed reads, their bases, split pieces, their bases
+  uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // --corr-edits: Chunk::editSums
   WorkerTally workers;
 };
 
@@ -546,9 +594,9 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef;
     double busy = 0;
-    uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0};
+    uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
   };
   bool fail(std::string msg);
   void readerMain(ReaderSide& r);
@@ -612,6 +660,11 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     wr.pf.open(files_.split, std::ios_base::trunc);
     if (!wr.pf) return fail("cannot write " + files_.split);
   }
+  if (o_.corrEdits) {
+    wr.ef.open(files_.edits, std::ios_base::trunc);
+    if (!wr.ef) return fail("cannot write " + files_.edits);
+    wr.ef << kEditsHeader;
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -633,7 +686,9 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.yf.is_open()) wr.yf.close();
   if (wr.tf.is_open()) wr.tf.close();
   if (wr.pf.is_open()) wr.pf.close();
+  if (wr.ef.is_open()) wr.ef.close();
   for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; }
+  for (int i = 0; i < 6; ++i) tot.editSums[i] = wr.editSums[i];
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
   for (const WorkerTally& t : tally) {
@@ -694,7 +749,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     talc_ctx* made = nullptr;
     if (talc_ctx_create(table_, &o_.p, device, &made) != TALC_OK) { fail(talc_last_error()); return; }
     ctx.reset(made);
-    if ((o_.corrMap || o_.softMask || o_.trim || o_.split) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
+    if ((o_.corrMap || o_.softMask || o_.trim || o_.split || o_.corrEdits) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -768,6 +823,15 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
   }
   if (o_.trim && !fetchPieces(ctx, b.get(), c, false)) return false;
   if (o_.split && !fetchPieces(ctx, b.get(), c, true)) return false;
+  if (o_.corrEdits) {   // aligned on the device while the reads and the records are in HBM; only the ops cross
+    if (talc_batch_edits(ctx, b.get(), o_.maxEditCells) != TALC_OK) return fail(talc_last_error());
+    const uint64_t nops = talc_batch_num_edit_ops(b.get());
+    std::vector<uint32_t> ops(std::max<uint64_t>(nops, 1));
+    std::vector<uint64_t> po(n + 1);
+    std::vector<talc_edit_row> rows(std::max<uint32_t>(n, 1));
+    if (talc_batch_fetch_edits(ctx, b.get(), ops.data(), nops, po.data(), rows.data()) != TALC_OK) return fail(talc_last_error());
+    formatEdits(o_, c, ops.data(), po.data(), rows.data(), oo.data());
+  }
   if (o_.readStats) {
     c.stats.resize(5ull * n);
     if (talc_batch_fetch_read_stats(ctx, b.get(), c.stats.data()) != TALC_OK) return fail(talc_last_error());
@@ -808,6 +872,8 @@ void Pipeline::writerMain(WriterSide& w) {
     if (w.tf.is_open()) w.tf.write(c->trimText.data(), (std::streamsize)c->trimText.size());
     if (w.pf.is_open()) w.pf.write(c->splitText.data(), (std::streamsize)c->splitText.size());
     for (int i = 0; i < 4; ++i) w.pieceSums[i] += c->pieceSums[i];
+    if (w.ef.is_open()) w.ef.write(c->editText.data(), (std::streamsize)c->editText.size());
+    for (int i = 0; i < 6; ++i) w.editSums[i] += c->editSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -1002,6 +1068,11 @@ int main(int argc, const char** argv) {
     if (o.trim && o.split) line += "; ";
     if (o.split) line += "split: " + std::to_string(y[2]) + " pieces, " + std::to_string(y[3]) + " bases";
     std::cout << line << std::endl;
+  }
+  if (o.corrEdits) {
+    const uint64_t* y = totals.editSums;
+    std::cout << "[TALC]: edits: " << y[0] << " matches, " << y[1] << " mismatches, " << y[2] << " insertions, " << y[3] << " deletions in " << y[4]
+              << " corrected reads (" << y[5] << " segments not aligned)" << std::endl;
   }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   report(t, totals, scan, o.batchReads, ndev, pipeline.workers());

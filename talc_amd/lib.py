@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
     "talc_ctx_get_map_timing",
     "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
     "talc_batch_pieces", "talc_batch_num_pieces", "talc_batch_pieces_bytes", "talc_batch_fetch_pieces", "talc_ctx_get_pieces_timing",
+    "talc_batch_edits", "talc_batch_num_edit_ops", "talc_batch_fetch_edits", "talc_ctx_get_edits_timing", "talc_test_edit_script",
+    "talc_test_batch_edits",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -50,6 +52,16 @@ SOLIDITY_DTYPE = np.dtype([(f, "<u4") for f in SOLIDITY_FIELDS])
 # talc_piece_mode, talc_piece (docs/trim_split.md)
 PIECES_TRIM, PIECES_SPLIT = 1, 2
 PIECE_DTYPE = np.dtype([("read", "<u4"), ("out_start", "<u4"), ("out_len", "<u4")])
+# talc_edit_row and the op codes (docs/correction_edits.md): an op is len << 4 | code, the codes are BAM's
+EDIT_ROW_FIELDS = ("n_match", "n_mismatch", "n_ins", "n_del", "n_ops", "n_unaligned")
+EDIT_ROW_DTYPE = np.dtype([(f, "<u4") for f in EDIT_ROW_FIELDS])
+EDIT_I, EDIT_D, EDIT_EQ, EDIT_X = 1, 2, 7, 8
+EDIT_LETTERS = {EDIT_I: "I", EDIT_D: "D", EDIT_EQ: "=", EDIT_X: "X"}
+
+
+def cigar_text(ops):
+    """The ops of one read as text, e.g. 812=1X40=2D; '*' for none."""
+    return "".join("%d%s" % (int(o) >> 4, EDIT_LETTERS[int(o) & 15]) for o in ops) or "*"
 
 
 class TalcError(RuntimeError):
@@ -193,6 +205,14 @@ def lib():
             L.talc_batch_pieces_bytes.argtypes = [vp]
             L.talc_batch_fetch_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
             L.talc_ctx_get_pieces_timing.argtypes = [vp, vp, vp]
+        if hasattr(L, "talc_batch_edits"):      # (likewise: a build from before the edit scripts)
+            L.talc_batch_edits.argtypes = [vp, vp, u64]
+            L.talc_batch_num_edit_ops.restype = u64
+            L.talc_batch_num_edit_ops.argtypes = [vp]
+            L.talc_batch_fetch_edits.argtypes = [vp, vp, vp, u64, vp, vp]
+            L.talc_ctx_get_edits_timing.argtypes = [vp, vp, vp]
+            L.talc_test_batch_edits.argtypes = [vp, vp, u64, u64]
+            L.talc_test_edit_script.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, u64, vp, u64, vp, vp]
         _LIB = L
     return _LIB
 
@@ -449,6 +469,24 @@ class Context:
         _chk(lib().talc_ctx_get_pieces_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def edits_timing(self):
+        """(align ms, pack ms) of the context's last Batch.edits(): both runs of k_edit_align, k_edit_count + k_edit_pack."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_edits_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def test_edit_script(self, a, b, max_cells=0):
+        """Test hook: (ops uint32[], distance) of one pair of ASCII sequences as one CORRECTED segment; distance -1 when
+        the pair is over max_cells and was not aligned."""
+        a = a if isinstance(a, bytes) else a.encode()
+        b = b if isinstance(b, bytes) else b.encode()
+        n, d = C.c_uint64(), C.c_int32()
+        L = lib()
+        _chk(L.talc_test_edit_script(self._h, a, len(a), b, len(b), int(max_cells), None, 0, C.byref(n), C.byref(d)))
+        ops = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _chk(L.talc_test_edit_script(self._h, a, len(a), b, len(b), int(max_cells), ops.ctypes.data, n.value, C.byref(n), C.byref(d)))
+        return ops[:n.value], d.value
+
     def batch(self, bases, offsets):
         return Batch(self, bases, offsets)
 
@@ -599,6 +637,22 @@ class Batch:
         rpo = np.empty(self.n_reads + 1, dtype=np.uint64)
         _chk(L.talc_batch_fetch_pieces(self.ctx._h, self._h, out.ctypes.data, nb, po.ctypes.data, pc.ctypes.data, n, rpo.ctypes.data))
         return out[:nb], po, pc[:n], rpo
+
+    def edits(self, max_cells=0, scratch_bytes=None):
+        """The edit scripts of the last correction (docs/correction_edits.md; needs Context.record_map() before it): (ops
+        uint32[] — len << 4 | code —, op_offsets u64[n_reads + 1], rows as an EDIT_ROW_DTYPE array).  A CORRECTED segment
+        of more than max_cells cells (0: 1 << 26) is not aligned.  scratch_bytes: test hook, another scratch budget."""
+        L = lib()
+        if scratch_bytes is None:
+            _chk(L.talc_batch_edits(self.ctx._h, self._h, int(max_cells)))
+        else:
+            _chk(L.talc_test_batch_edits(self.ctx._h, self._h, int(max_cells), int(scratch_bytes)))
+        n = int(L.talc_batch_num_edit_ops(self._h))
+        ops = np.empty(max(n, 1), dtype=np.uint32)
+        oo = np.empty(self.n_reads + 1, dtype=np.uint64)
+        rows = np.zeros(self.n_reads, dtype=EDIT_ROW_DTYPE)
+        _chk(L.talc_batch_fetch_edits(self.ctx._h, self._h, ops.ctypes.data, n, oo.ctypes.data, rows.ctypes.data))
+        return ops[:n], oo, rows
 
     def fetch_read_stats(self):
         """int64[n, 5]: {row written, raw length, IN-region span, IN regions, corrected length} (Read.cpp:418-433)."""
