@@ -418,6 +418,19 @@ int talc_test_edit_script(talc_ctx* c, const char* a, uint32_t la, const char* b
 /* Test hook: talc_batch_edits with scratch_bytes (128 .. 1 << 30) in place of the 1 GiB budget, so that the alignments of a
  * small batch run in several rounds; TALC_ERR_INVALID when one pair alone does not fit.  Same result as talc_batch_edits. */
 int talc_test_batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells, uint64_t scratch_bytes);
+/* Test hook: the text-dump parser alone, on a file of any size (talc_table_build_device takes the device route only from
+ * 8 MiB on, with chunks of 32 MiB and at most 8 reader threads).  where = 1: the file goes to GPU `device` in chunks of
+ * chunk_bytes (1 .. 1 << 30) read by at most reader_threads (1 .. 64) threads and is parsed there; line i of the file at
+ * index i of kmers_out / counts_out, lines below min_count included; *kept_out = lines with count >= min_count, *flags_out
+ * != 0 when some line is not canonical (the arrays then mean nothing).  where = 0: the host parser, unfiltered, no GPU
+ * needed (device, chunk_bytes, reader_threads ignored): one entry per line it read whose k-mer is K letters of ACGT;
+ * *kept_out = entries with count >= min_count, *flags_out = (lines read that gave no entry) << 32 | lines without two
+ * tokens, so that lines read = *n_lines_out + (*flags_out >> 32).  *n_lines_out = entries; kmers_out and counts_out NULL:
+ * only the three numbers (each of those pointers may be NULL); TALC_ERR_CAPACITY when capacity (entries) is too small,
+ * with the three numbers set. */
+int talc_test_parse_text(const char* path, uint32_t k, uint32_t min_count, int where, int device, uint64_t chunk_bytes,
+                         int reader_threads, uint64_t* kmers_out, uint32_t* counts_out, uint64_t capacity,
+                         uint64_t* n_lines_out, uint64_t* kept_out, uint64_t* flags_out);
 
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.

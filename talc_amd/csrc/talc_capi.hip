@@ -369,27 +369,15 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
 // a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory):
 // the caller then parses on the host, as before.
 static int parse_on_host_instead() { (void)hipGetLastError(); return 1; }   // (an allocation or a copy failed: no error is left behind)
-static int table_from_text_on_device(const char* path, const talc_params* p, int device, TablePtr& out, DumpStats& ds, const Switches& sw) {
-  struct stat sb;
-  if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
-  const uint64_t size = (uint64_t)sb.st_size;
-  if (size < (8u << 20) || sw.hostParse) return 1;
-  {   // a Jellyfish 2 count file goes the host's way (talc_jf.h)
-    char head[64] = {0};
-    FILE* f = fopen(path, "rb");
-    if (!f) return fail(TALC_ERR_IO, "cannot open %s", path);
-    const size_t got = fread(head, 1, sizeof head, f);
-    fclose(f);
-    if (jfLooksLike(head, got)) return 1;
-  }
-  Stopwatch watch;
-  if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
-  DevBuf<uint8_t> dText;
+
+// Step 1, the file's bytes to the device as they are: reader threads (one per chunk of chunkBytes, at most maxReaders),
+// each with its own descriptor, page-locked buffer and stream, claim the chunks in turn; chunk i lands at byte
+// i * chunkBytes of dText (size + 64 bytes).  0, or a positive value when memory or a read failed.
+static int text_to_device(const char* path, uint64_t size, uint64_t chunkBytes, int maxReaders, int device, DevBuf<uint8_t>& dText, int* readers) {
   if (dText.alloc(size + 64) != hipSuccess) return parse_on_host_instead();
-  // ---- the file's bytes to the device: reader threads, each with its own descriptor, page-locked buffer and stream
-  const uint64_t CH = 32ull << 20;
+  const uint64_t CH = chunkBytes;
   const uint64_t nch = (size + CH - 1) / CH;
-  const int T = (int)std::min<uint64_t>(nch, 8);
+  const int T = (int)std::min<uint64_t>(nch, (uint64_t)maxReaders);
   std::atomic<uint64_t> next{0};
   std::atomic<int> err{0};
 #pragma omp parallel num_threads(T)
@@ -412,14 +400,21 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
     if (fd >= 0) close(fd);
   }
   if (err.load()) return parse_on_host_instead();
-  const double tUp = watch.lap();
-  // ---- lines per tile, the tiles' first line numbers, the lines themselves
+  *readers = T;
+  return 0;
+}
+
+// Step 2, the device text to the builder's arrays (talc_kernels_build.h): lines per tile, the tiles' first line numbers,
+// the lines themselves; line i of the text at index i of out.kmers / out.counts, lines below minc included (out.stats.kept
+// counts the others).  The one place the parse kernels are launched from.  0, or a positive value when the text has no
+// line, too many, or memory failed; out.stats.flags != 0 when a line is not canonical (the arrays then mean nothing).
+struct ParsedText { DevBuf<uint64_t> kmers; DevBuf<uint32_t> counts; uint64_t nlines = 0; ParseStats stats = {0, 0}; };
+static int parse_device_text(const uint8_t* dText, uint64_t size, uint32_t K, uint32_t minc, ParsedText& out) {
   const uint64_t ntiles = (size + kParseTile - 1) / kParseTile;
   DevBuf<uint32_t> dCount; DevBuf<uint64_t> dFirst; DevBuf<ParseStats> dPS;
-  DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
-  if (ntiles >= (1ull << 31) || dCount.alloc(ntiles) != hipSuccess || dFirst.alloc(ntiles) != hipSuccess ||
+  if (ntiles == 0 || ntiles >= (1ull << 31) || dCount.alloc(ntiles) != hipSuccess || dFirst.alloc(ntiles) != hipSuccess ||
       dPS.alloc(1) != hipSuccess || hipMemset(dPS.get(), 0, sizeof(ParseStats)) != hipSuccess) return parse_on_host_instead();
-  hipLaunchKernelGGL(k_parse_count, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText.get(), size, dCount.get());
+  hipLaunchKernelGGL(k_parse_count, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dCount.get());
   std::vector<uint32_t> hCount(ntiles);
   if (hipMemcpy(hCount.data(), dCount.get(), ntiles * 4, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
   std::vector<uint64_t> hFirst(ntiles);
@@ -427,11 +422,40 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
   for (uint64_t i = 0; i < ntiles; ++i) { hFirst[i] = nlines; nlines += hCount[i]; }
   if (nlines == 0 || nlines >= 0xFFFFFFFEull) return parse_on_host_instead();
   if (hipMemcpy(dFirst.get(), hFirst.data(), ntiles * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      dK.alloc(nlines) != hipSuccess || dC.alloc(nlines) != hipSuccess) return parse_on_host_instead();
-  hipLaunchKernelGGL(k_parse_lines, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText.get(), size, dFirst.get(), p->k, p->min_count, dK.get(), dC.get(), dPS.get());
-  ParseStats ps;
-  if (hipGetLastError() != hipSuccess || hipMemcpy(&ps, dPS.get(), sizeof ps, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
-  dText.reset(); dCount.reset(); dFirst.reset(); dPS.reset();   // (the text goes before the builder allocates its buckets)
+      out.kmers.alloc(nlines) != hipSuccess || out.counts.alloc(nlines) != hipSuccess) return parse_on_host_instead();
+  hipLaunchKernelGGL(k_parse_lines, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dFirst.get(), K, minc, out.kmers.get(), out.counts.get(), dPS.get());
+  if (hipGetLastError() != hipSuccess || hipMemcpy(&out.stats, dPS.get(), sizeof out.stats, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
+  out.nlines = nlines;
+  return 0;
+}
+
+constexpr uint64_t kDumpChunkBytes = 32ull << 20;   // of the production upload
+constexpr int kDumpReaders = 8;
+
+static int table_from_text_on_device(const char* path, const talc_params* p, int device, TablePtr& out, DumpStats& ds, const Switches& sw) {
+  struct stat sb;
+  if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
+  const uint64_t size = (uint64_t)sb.st_size;
+  if (size < (8u << 20) || sw.hostParse) return 1;
+  {   // a Jellyfish 2 count file goes the host's way (talc_jf.h)
+    char head[64] = {0};
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(TALC_ERR_IO, "cannot open %s", path);
+    const size_t got = fread(head, 1, sizeof head, f);
+    fclose(f);
+    if (jfLooksLike(head, got)) return 1;
+  }
+  Stopwatch watch;
+  if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
+  DevBuf<uint8_t> dText;
+  int T = 0;
+  if (text_to_device(path, size, kDumpChunkBytes, kDumpReaders, device, dText, &T)) return 1;
+  const double tUp = watch.lap();
+  ParsedText parsed;
+  if (parse_device_text(dText.get(), size, p->k, p->min_count, parsed)) return 1;
+  dText.reset();   // (the text goes before the builder allocates its buckets)
+  const ParseStats ps = parsed.stats;
+  const uint64_t nlines = parsed.nlines;
   if (ps.flags != 0) {   // a line the device parser does not take: the host's tokeniser decides what every line means
     if (sw.timing) fprintf(stderr, "[talc-lib] the dump has lines that are not 'KMER count': parsing on the host\n");
     return 1;
@@ -439,7 +463,54 @@ static int table_from_text_on_device(const char* path, const talc_params* p, int
   if (sw.timing) fprintf(stderr, "[talc-lib] dump parsed on the device: %.0f MB of text to the device in %.3f s (%d reader threads), %llu lines parsed in %.3f s\n",
                       (double)size / 1e6, tUp, T, (unsigned long long)nlines, watch.seconds());
   ds.nread += (int64_t)nlines; ds.nkept += (int64_t)ps.kept;
-  return build_table_from_device_arrays(std::move(dK), std::move(dC), nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
+  return build_table_from_device_arrays(std::move(parsed.kmers), std::move(parsed.counts), nlines, ps.kept, p, device, out, 0.0, 0.0, sw);
+}
+
+// Test hook (include/talc_hip.h): the two steps above on a file of any size with the caller's chunk size and reader count
+// (where = 1), or parseDumpFile unfiltered (where = 0).
+int talc_test_parse_text(const char* path, uint32_t k, uint32_t min_count, int where, int device, uint64_t chunk_bytes, int reader_threads,
+                         uint64_t* kmers_out, uint32_t* counts_out, uint64_t capacity, uint64_t* n_lines_out, uint64_t* kept_out,
+                         uint64_t* flags_out) {
+  if (!path || k < 18 || k > 31 || (where != 0 && where != 1)) return fail(TALC_ERR_INVALID, "bad argument");
+  uint64_t n = 0, kept = 0, flags = 0;
+  auto report = [&] { if (n_lines_out) *n_lines_out = n; if (kept_out) *kept_out = kept; if (flags_out) *flags_out = flags; };   // (before a capacity error too)
+  if (where == 0) {
+    std::vector<uint64_t> kmers;
+    std::vector<uint32_t> counts;
+    DumpStats ds;
+    std::string why;
+    if (!parseDumpFile(path, k, min_count, false, kmers, &counts, nullptr, ds, &why))
+      return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
+    n = kmers.size();
+    for (uint64_t i = 0; i < n; ++i) kept += counts[i] >= min_count ? 1 : 0;
+    flags = ((uint64_t)ds.nread - n) << 32 | (uint64_t)ds.nbad;   // lines read that gave no entry | lines without two tokens
+    report();
+    if (kmers_out || counts_out) {
+      if (capacity < n) return fail(TALC_ERR_CAPACITY, "line buffers too small: need %llu entries", (unsigned long long)n);
+      if (kmers_out && n) memcpy(kmers_out, kmers.data(), n * 8);
+      if (counts_out && n) memcpy(counts_out, counts.data(), n * 4);
+    }
+  } else {
+    if (device < 0 || chunk_bytes == 0 || chunk_bytes > (1ull << 30) || reader_threads < 1 || reader_threads > 64) return fail(TALC_ERR_INVALID, "bad argument");
+    struct stat sb;
+    if (stat(path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", path);
+    const uint64_t size = (uint64_t)sb.st_size;
+    if (size == 0) return fail(TALC_ERR_INVALID, "%s is empty", path);
+    if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
+    DevBuf<uint8_t> dText;
+    int T = 0;
+    if (text_to_device(path, size, chunk_bytes, reader_threads, device, dText, &T)) return fail(TALC_ERR_DEVICE, "the text of %s did not reach the device", path);
+    ParsedText parsed;
+    if (parse_device_text(dText.get(), size, k, min_count, parsed)) return fail(TALC_ERR_DEVICE, "the text of %s was not parsed on the device", path);
+    n = parsed.nlines; kept = parsed.stats.kept; flags = parsed.stats.flags;
+    report();
+    if (kmers_out || counts_out) {
+      if (capacity < n) return fail(TALC_ERR_CAPACITY, "line buffers too small: need %llu entries", (unsigned long long)n);
+      if (kmers_out) HIPCHK(hipMemcpy(kmers_out, parsed.kmers.get(), n * 8, hipMemcpyDeviceToHost));
+      if (counts_out) HIPCHK(hipMemcpy(counts_out, parsed.counts.get(), n * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  return TALC_OK;
 }
 
 // Junction colouring (Jellyfish.cpp:273-290) on the staged device image: last line wins, both strands.

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
     "talc_batch_pieces", "talc_batch_num_pieces", "talc_batch_pieces_bytes", "talc_batch_fetch_pieces", "talc_ctx_get_pieces_timing",
     "talc_batch_edits", "talc_batch_num_edit_ops", "talc_batch_fetch_edits", "talc_ctx_get_edits_timing", "talc_test_edit_script",
-    "talc_test_batch_edits",
+    "talc_test_batch_edits", "talc_test_parse_text",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -213,6 +213,8 @@ def lib():
             L.talc_ctx_get_edits_timing.argtypes = [vp, vp, vp]
             L.talc_test_batch_edits.argtypes = [vp, vp, u64, u64]
             L.talc_test_edit_script.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, u64, vp, u64, vp, vp]
+        if hasattr(L, "talc_test_parse_text"):  # (likewise: a build from before the parser's test hook)
+            L.talc_test_parse_text.argtypes = [C.c_char_p, u32, u32, i32, i32, u64, i32, vp, vp, u64, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -239,6 +241,28 @@ def default_params(**kw):
 
 def device_count():
     return int(lib().talc_device_count())
+
+
+def parse_text_hook(path, k, min_count=2, where=1, device=0, chunk_bytes=32 << 20, reader_threads=8, arrays=True):
+    """Test hook: the text-dump parser alone on a file of any size.  where=1: the file goes to GPU `device` in chunks of
+    chunk_bytes read by at most reader_threads threads and is parsed there; where=0: the host parser, unfiltered (no GPU).
+    Returns a dict: kmers u64[n] and counts u32[n] in file order (None with arrays=False), n_lines, kept, and flags (device:
+    != 0 when a line is not canonical) or nread / nbad (host)."""
+    L = lib()
+    n, kept, flags = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    args = (path.encode(), int(k), int(min_count), int(where), int(device), int(chunk_bytes), int(reader_threads))
+    _chk(L.talc_test_parse_text(*args, None, None, 0, C.byref(n), C.byref(kept), C.byref(flags)))
+    out = {"kmers": None, "counts": None}
+    if arrays:
+        km, ct = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
+        _chk(L.talc_test_parse_text(*args, km.ctypes.data, ct.ctypes.data, n.value, C.byref(n), C.byref(kept), C.byref(flags)))
+        out = {"kmers": km[:n.value], "counts": ct[:n.value]}
+    out.update(n_lines=n.value, kept=kept.value)
+    if where:
+        out["flags"] = flags.value
+    else:
+        out.update(nread=n.value + (flags.value >> 32), nbad=flags.value & 0xFFFFFFFF)
+    return out
 
 
 class PinnedArray:
