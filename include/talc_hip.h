@@ -432,6 +432,38 @@ int talc_test_parse_text(const char* path, uint32_t k, uint32_t min_count, int w
                          int reader_threads, uint64_t* kmers_out, uint32_t* counts_out, uint64_t capacity,
                          uint64_t* n_lines_out, uint64_t* kept_out, uint64_t* flags_out);
 
+/* Auto strand (docs/auto_strand.md): the k-mer table is directional and a long cDNA read arrives in either orientation; -rev
+ * (talc_params.reverse) turns the whole file.  With auto strand every read is corrected in the orientation the short reads
+ * support, chosen on the device before the read is encoded.  For a read of L raw bytes, S its Dna5 conversion (acgt accepted
+ * in lower case, every other byte N): n = max(0, L - K + 1); f[i] = the table count of S[i, i + K), r[i] = the table count of
+ * the reverse complement of S[i, i + K); a count is 0 when the k-mer is absent or holds an N; a palindromic k-mer (even K)
+ * counts in both.  The multiset {r[i]} is that of the forward counts of revcomp(S): the rc fields are what a -rev context's
+ * raw solidity row reports. */
+typedef struct talc_strand {
+  uint32_t n_kmers;     /* n */
+  uint32_t fwd_solid;   /* #{i : f[i] >= MIN_COUNT} */
+  uint32_t fwd_in;      /* #{i : f[i] >  MIN_COUNT}  (Read.cpp:190: what reCoverage counts) */
+  uint32_t rc_solid;    /* #{i : r[i] >= MIN_COUNT} */
+  uint32_t rc_in;       /* #{i : r[i] >  MIN_COUNT} */
+  uint32_t reverse;     /* the choice: 1 iff rc_in > fwd_in, or rc_in == fwd_in and rc_solid > fwd_solid; else 0 */
+} talc_strand;
+/* A read with L < K has an all-zero row; every tie chooses forward; with an empty table every row is zero apart from n_kmers.
+ * With auto strand on, every entry point that needs the batch's codes (talc_batch_coverage, _structure, _correct, _solidity,
+ * talc_correct_batch) first runs the vote if it has not yet run on that batch, and from then on read r is treated exactly as
+ * a -rev context treats it when rows[r].reverse is 1 and exactly as a plain context does when it is 0: everything fetched —
+ * record, status, masked record, map segments, both solidity rows, pieces, edit ops and row, read-stats row — is byte for
+ * byte what the chosen one of the two fixed contexts returns for that read, the reference's quirk included that a read passed
+ * through under -rev comes out reverse-complemented (main.cpp:253).  Toggling the setting between two calls on one batch has
+ * the batch encoded again at the next call that needs codes, as if it were new (what it held from earlier calls is gone).
+ * Default off: nothing changes.  TALC_ERR_INVALID when the context's params have reverse set. */
+int talc_ctx_set_auto_strand(talc_ctx* c, int on);
+/* The vote alone, on any batch, auto strand on or off (once per batch: a later call finds the rows there). */
+int talc_batch_strand(talc_ctx* c, talc_batch* b);
+/* rows: n_reads rows.  TALC_ERR_STATE when no vote has run on b. */
+int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows);
+/* Measurement: device time (ms) of the context's last k_strand_vote. */
+int talc_ctx_get_strand_timing(const talc_ctx* c, float* vote_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

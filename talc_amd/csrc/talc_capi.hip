@@ -25,6 +25,7 @@
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
 #include "talc_kernels_solidity.h"
+#include "talc_kernels_strand.h"
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -123,12 +124,16 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[24] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
-                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack; 18 .. 23: the edit scripts (run_edits)
+  hipEvent_t ev[26] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
+                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack; 18 .. 23: the edit scripts (run_edits);
+                            // 24, 25: around k_strand_vote
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
+  bool autoStrand = false;   // talc_ctx_set_auto_strand: every read in the orientation k_strand_vote chooses
+  float vote_ms = 0;         // the last k_strand_vote of this context
+  bool votePending = false;  // ... has been launched and its events not yet read (vote_time)
   float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
   float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
   float piece_count_ms = 0, piece_pack_ms = 0;   // the last talc_batch_pieces: k_piece_count, k_piece_pack
@@ -181,8 +186,14 @@ struct talc_batch {
   uint64_t pieces_cap = 0, piece_bytes_cap = 0;
   // the edit scripts (talc_batch_edits) of the last correction, made since that correction
   bool edited = false;
+  // auto strand: k_strand_vote has run on d_raw (d_strand, d_strand_flag hold its result: the raw bytes never change, so
+  // it runs once per batch); encodedAuto: d_codes were made with the flags, and k_pack, k_pack_map, k_solidity take them too
+  bool voted = false, encodedAuto = false;
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
+  CachedBuf<uint8_t> d_strand_flag;   // ... and its choice as one byte per read: what the four kernels that orient a read take
+  const uint8_t* rev_flags() const { return encodedAuto ? d_strand_flag.get() : nullptr; }
   EditOut edits;
   CachedBuf<uint8_t> d_piece_bytes;  // the kept pieces' bytes, dense (k_piece_pack), sized exactly
   CachedBuf<uint64_t> d_piece_off;   // one per piece: where its bytes start in d_piece_bytes
@@ -220,6 +231,7 @@ static_assert(sizeof(OutPiece) == sizeof(talc_piece) && sizeof(talc_piece) == 12
               TALC_PIECES_SPLIT == PIECES_SPLIT, "k_piece_pack writes talc_piece records");
 static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) == 24 && sizeof(EditPart) == 32 && sizeof(EditTask) == 16, "k_edit_count writes talc_edit_row records");
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
+static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
 
 template <typename T>
 static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
@@ -868,6 +880,19 @@ int talc_ctx_set_map(talc_ctx* c, int on) {
   return TALC_OK;
 }
 
+int talc_ctx_set_auto_strand(talc_ctx* c, int on) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (c->p.reverse) return fail(TALC_ERR_INVALID, "auto strand chooses every read's orientation: it does not go with reverse set in the context's params");
+  c->autoStrand = on != 0;
+  return TALC_OK;
+}
+
+int talc_ctx_get_strand_timing(const talc_ctx* c, float* vote_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (vote_ms) *vote_ms = c->vote_ms;
+  return TALC_OK;
+}
+
 int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_case_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
   if (pack_map_ms) *pack_map_ms = c->pack_map_ms;
@@ -955,13 +980,64 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
 uint64_t talc_batch_num_kmers(const talc_batch* b) { return b ? b->n_kmers : 0; }
 uint64_t talc_batch_num_bases(const talc_batch* b) { return b ? b->n_bases : 0; }
 
+// ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes, events 24 and 25 around it
+static int launch_vote(talc_ctx* c, talc_batch* b) {
+  if (!b->d_strand) HIPCHK(b->d_strand.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
+  if (!b->d_strand_flag) HIPCHK(b->d_strand_flag.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
+  HIPCHK(hipEventRecord(c->ev[24], c->stream));
+  if (b->n_reads)
+    hipLaunchKernelGGL(k_strand_vote, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, b->d_raw.get(), b->d_offsets.get(), c->p.min_count, b->n_reads,
+                       b->d_strand.get(), b->d_strand_flag.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[25], c->stream));
+  c->votePending = true;
+  b->voted = true;
+  return TALC_OK;
+}
+// the last vote's device time into c->vote_ms, once the stream has been waited for
+static int vote_time(talc_ctx* c) {
+  if (!c->votePending) return TALC_OK;
+  HIPCHK(hipEventElapsedTime(&c->vote_ms, c->ev[24], c->ev[25]));
+  c->votePending = false;
+  return TALC_OK;
+}
+// What every entry point that needs the batch's codes does first: codes made under the other setting are dropped with
+// everything that came of them (the batch is as if it were new), and with auto strand on the vote runs before k_encode
+static int prepare_strand(talc_ctx* c, talc_batch* b) {
+  if (b->encoded && b->encodedAuto != c->autoStrand) {
+    b->encoded = b->covered = b->structured = b->corrected = b->mapped = b->masked = false;
+    b->solidity = b->solidityCorrected = b->pieced = b->edited = false;
+  }
+  if (c->autoStrand && !b->voted) return launch_vote(c, b);
+  return TALC_OK;
+}
+
 static int launch_encode(talc_ctx* c, talc_batch* b) {
+  b->encodedAuto = c->autoStrand;
   if (!b->h_chunk_read.empty())
     hipLaunchKernelGGL(k_encode, dim3((unsigned)b->h_chunk_read.size()), dim3(256), 0, c->stream, b->d_raw.get(), b->d_codes.get(),
-                       b->d_offsets.get(), b->d_chunk_read.get(), b->d_chunk_start.get(), c->p.reverse ? 1 : 0);
+                       b->d_offsets.get(), b->d_chunk_read.get(), b->d_chunk_start.get(), c->p.reverse ? 1 : 0, b->rev_flags());
   HIPCHK(hipGetLastError());
   b->encoded = true;
   return TALC_OK;
+}
+
+int talc_batch_strand(talc_ctx* c, talc_batch* b) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if (!b->voted && (rc = launch_vote(c, b))) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return vote_time(c);
+}
+
+int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (!b->voted) return fail(TALC_ERR_STATE, "no strand vote has run on this batch (talc_batch_strand, or auto strand and a call that needs the batch's codes)");
+  HIPCHK(hipSetDevice(c->device));
+  if (rows && b->n_reads) HIPCHK(hipMemcpyAsync(rows, b->d_strand.get(), (size_t)b->n_reads * sizeof(talc_strand), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return vote_time(c);
 }
 static int launch_coverage(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipMemsetAsync(b->d_nin.get(), 0, std::max<uint32_t>(b->n_reads, 1) * sizeof(int32_t), c->stream));
@@ -996,13 +1072,14 @@ int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   HIPCHK(hipSetDevice(c->device));
   int rc;
+  if ((rc = prepare_strand(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[0], c->stream));
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[1], c->stream));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[2], c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((rc = read_stage_times(c, 2))) return rc;
+  if ((rc = read_stage_times(c, 2)) || (rc = vote_time(c))) return rc;
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   return TALC_OK;
 }

@@ -143,6 +143,7 @@ static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint
   int rc;
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
+  if ((rc = prepare_strand(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[0], s));
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[1], s));
@@ -267,7 +268,7 @@ static int pack_dense(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipMemcpyAsync(b->d_dense_off.get(), b->h_dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
-                       b->n_reads, c->p.reverse ? 1 : 0);
+                       b->n_reads, c->p.reverse ? 1 : 0, b->rev_flags());
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[7], s));
   return TALC_OK;
@@ -290,7 +291,8 @@ static int pack_map(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipMemcpyAsync(b->d_seg_off.get(), b->h_seg_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack_map, dim3(b->n_reads), dim3(64), 0, s, b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_mapedge.get(),
-                       b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0);
+                       b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0,
+                       b->rev_flags());
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[8], s));
   return TALC_OK;
@@ -325,7 +327,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   if ((rc = search_retry_passes(c, b, tb, traceRead))) return rc;
   if ((rc = pack_dense(c, b))) return rc;
   if (map && (rc = pack_map(c, b))) return rc;
-  if ((rc = read_timing(c, b, counters))) return rc;
+  if ((rc = read_timing(c, b, counters)) || (rc = vote_time(c))) return rc;
   if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[7], c->ev[8]));
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
@@ -352,7 +354,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
-  if ((rc = read_stage_times(c, 3))) return rc;
+  if ((rc = read_stage_times(c, 3)) || (rc = vote_time(c))) return rc;
   b->structured = true;
   return TALC_OK;
 }
@@ -564,7 +566,7 @@ static int launch_solidity(talc_ctx* c, talc_batch* b, bool records) {
   if (b->n_reads)
     hipLaunchKernelGGL(k_solidity, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, records ? b->d_dense.get() : b->d_codes.get(),
                        records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
-                       c->p.reverse ? 1 : 0, c->p.min_count, b->n_reads, rows.get());
+                       c->p.reverse ? 1 : 0, b->rev_flags(), c->p.min_count, b->n_reads, rows.get());
   HIPCHK(hipGetLastError());
   return TALC_OK;
 }
@@ -574,6 +576,7 @@ int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int rc;
+  if ((rc = prepare_strand(c, b))) return rc;   // (a batch encoded under the other setting is no longer corrected either)
   const bool records = b->corrected;
   b->solidity = false; b->solidityCorrected = false;
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
@@ -586,6 +589,7 @@ int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipEventElapsedTime(&c->sol_raw_ms, c->ev[11], c->ev[12]));
   c->sol_corr_ms = 0;
   if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[12], c->ev[13]));
+  if ((rc = vote_time(c))) return rc;
   b->solidity = true; b->solidityCorrected = records;
   return TALC_OK;
 }

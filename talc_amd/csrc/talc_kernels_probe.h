@@ -87,10 +87,13 @@ __global__ void k_next_counts(TableView T, const uint64_t* kmers, uint64_t n, in
 
 // ------------------------------------------------------------------ encode
 // raw ASCII -> Dna5 codes (SeqAn Dna5 conversion), with the -rev reverse complement of
-// main.cpp:253 applied per read.  One block per (read, 4096-base chunk).
+// main.cpp:253 applied per read.  One block per (read, 4096-base chunk).  rev_flags: one byte per read (auto strand,
+// k_strand_vote): a read whose byte is set is taken as under -rev; nullptr: `reverse` alone decides.
 __global__ void k_encode(const uint8_t* __restrict__ raw, uint8_t* __restrict__ codes, const uint64_t* __restrict__ offsets,
-                         const uint32_t* __restrict__ chunk_read, const uint32_t* __restrict__ chunk_start, int reverse) {
+                         const uint32_t* __restrict__ chunk_read, const uint32_t* __restrict__ chunk_start, int reverse,
+                         const uint8_t* __restrict__ rev_flags) {
   const uint32_t r = chunk_read[blockIdx.x];
+  if (rev_flags) reverse |= rev_flags[r];
   const uint64_t b = offsets[r], e = offsets[r + 1];
   const uint64_t L = e - b;
   const uint64_t s0 = chunk_start[blockIdx.x];

@@ -4294,11 +4294,13 @@ __global__ void k_build_thresholds(double ALPHA, uint32_t n, uint32_t* __restric
 
 // ==================================================================== k_pack
 // dense output: codes -> ASCII, with the reverse complement of main.cpp:286 for corrected reads
-// under -rev.  One block per (read, 4096-base chunk) of the OUTPUT.
+// under -rev.  One block per (read, 4096-base chunk) of the OUTPUT.  rev_flags: as k_encode's.
 __global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __restrict__ outoff, const ReadState* __restrict__ state,
-                       const uint64_t* __restrict__ dense_off, uint8_t* __restrict__ dense, uint32_t n_reads, int reverse) {
+                       const uint64_t* __restrict__ dense_off, uint8_t* __restrict__ dense, uint32_t n_reads, int reverse,
+                       const uint8_t* __restrict__ rev_flags) {
   const uint32_t r = blockIdx.x;
   if (r >= n_reads) return;
+  if (rev_flags) reverse |= rev_flags[r];
   const uint8_t* src = outAll + outoff[r];
   const uint32_t len = state[r].outLen;
   uint8_t* dst = dense + dense_off[r];
@@ -4321,9 +4323,10 @@ __host__ __device__ inline bool map_has_outcome(const ReadState& st) { return st
 __global__ void __launch_bounds__(64)
 k_pack_map(const ReadState* __restrict__ state, const uint32_t* __restrict__ regions, const uint64_t* __restrict__ regoff,
            const uint32_t* __restrict__ mapEdge, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ segOff,
-           MapSeg* __restrict__ segs, uint32_t n_reads, uint32_t K, int reverse) {
+           MapSeg* __restrict__ segs, uint32_t n_reads, uint32_t K, int reverse, const uint8_t* __restrict__ rev_flags) {
   const uint32_t r = blockIdx.x;
   if (r >= n_reads) return;
+  if (rev_flags) reverse |= rev_flags[r];   // (as k_encode's)
   const uint32_t l = (uint32_t)lane_id();
   const uint32_t L = (uint32_t)(offsets[r + 1] - offsets[r]);
   const ReadState st = state[r];

@@ -59,7 +59,7 @@ TALC_D uint32_t longest_run(uint64_t x) {
 
 __global__ void __launch_bounds__(64)
 k_solidity(TableView T, const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ offsets, const ReadState* __restrict__ state,
-           int ascii, int reverse, uint32_t min_count, uint32_t n_reads, SolidityRow* __restrict__ rows) {
+           int ascii, int reverse, const uint8_t* __restrict__ rev_flags, uint32_t min_count, uint32_t n_reads, SolidityRow* __restrict__ rows) {
   __shared__ uint64_t s_pack[SOL_TILE / 32 + 8];    // base i of the window at bits [63 - 2 (i % 32) - 1, 63 - 2 (i % 32)] of word i / 32
   __shared__ uint64_t s_nmask[SOL_TILE / 64 + 4];   // bit (i % 64) of word i / 64: base i is N
   static_assert(sizeof(s_pack) == 64 * 2 && sizeof(s_nmask) == 64, "one 8-base group per lane fills both arrays");
@@ -73,7 +73,8 @@ k_solidity(TableView T, const uint8_t* __restrict__ seqs, const uint64_t* __rest
   const uint32_t n = L >= K ? L - K + 1 : 0;
   // a record k_pack reverse complemented (a corrected read under -rev) is read back to front: the sequence the kernels
   // worked on, the orientation the table's directional counts belong to
-  const bool flip = state != nullptr && reverse && state[r].status == TALC_READ_CORRECTED && state[r].overflow == 0;
+  // (rev_flags: one byte per read, auto strand: a read whose byte is set is taken as under -rev)
+  const bool flip = state != nullptr && (reverse || (rev_flags && rev_flags[r])) && state[r].status == TALC_READ_CORRECTED && state[r].overflow == 0;
   const uint8_t TALC_AS1* src = (const uint8_t TALC_AS1*)(seqs + rb);
   // base i (< L) of the sequence sits at byte at_byte(i); code_of turns the byte into a Dna5 code: ascii_to_code and
   // complement_code as selects (the staging below asks for a lane's 8 bytes at once and must not branch between them)

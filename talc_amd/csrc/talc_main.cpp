@@ -24,6 +24,8 @@
 //   --corr-edits    write <o>.edits.tsv, the edit script of every read (docs/correction_edits.md): one line per read, in
 //                    input order, with the counts of matches, mismatches, insertions and deletions and a CIGAR string
 //   --max-edit-cells N  with --corr-edits: a corrected stretch of more than N cells (raw x corrected length) is not aligned
+//   --auto-strand    every read is corrected in the orientation the short reads support, chosen on the device (docs/
+//                    auto_strand.md); writes <o>.strand.tsv: one line per read, in input order, with the vote and the choice
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -107,6 +109,7 @@ struct Options {
   uint32_t minPieceLen = 0;                 // --min-piece-len
   bool corrEdits = false;                   // --corr-edits
   uint64_t maxEditCells = 0;                // --max-edit-cells (0: the library's default)
+  bool autoStrand = false;                  // --auto-strand
 };
 
 void usage(FILE* f) {
@@ -147,6 +150,8 @@ void usage(FILE* f) {
           "  --corr-edits                write <o>.edits.tsv: matches, mismatches, insertions, deletions and a CIGAR string per read\n"
           "  --max-edit-cells INT        with --corr-edits: do not align a corrected stretch of more cells (raw x corrected\n"
           "                              length), default 67108864; beyond 536870912 it acts as that (docs/correction_edits.md)\n"
+          "  --auto-strand               correct every read in the orientation the short reads support (not with -rev); write\n"
+          "                              <o>.strand.tsv: solid and IN k-mers of the read and of its reverse complement, + or -\n"
           "  -h, --help / --version\n");
 }
 
@@ -203,6 +208,7 @@ Options parse(int argc, const char** argv) {
     else if (a == "--split") o.split = true;
     else if (a == "--corr-edits") o.corrEdits = true;
     else if (a == "--max-edit-cells") { double v = num(need(i), "max-edit-cells"); range(v, 1, 9e18, "max-edit-cells"); o.maxEditCells = (uint64_t)v; }
+    else if (a == "--auto-strand") o.autoStrand = true;
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -218,6 +224,7 @@ Options parse(int argc, const char** argv) {
   if (o.haveSR && !o.srReads.empty()) parse_error("-SR and --SRReads exclude each other: give the counts or the short reads");
   if (!o.srReads.empty() && o.queryMode == "jellyfish2") parse_error("--SRReads counts the k-mers itself: it does not go with -qm jellyfish2");
   if (!o.srCountsOut.empty() && o.srReads.empty()) parse_error("--SRCountsOut needs --SRReads");
+  if (o.autoStrand && o.p.reverse) parse_error("--auto-strand chooses every read's orientation: it does not go with -rev");
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
 }
@@ -253,10 +260,10 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
-        trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv") {}
+        trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -393,11 +400,30 @@ struct Chunk {
   uint64_t pieceSums[4] = {0, 0, 0, 0}; // of the batch: trimmed reads, their bases, split pieces, their bases
   std::string editText;                 // ... and to <o>.edits.tsv (--corr-edits)
   uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch's corrected reads: =, X, I, D bases, the reads, segments not aligned
+  std::vector<talc_strand> strand;      // --auto-strand: the vote of every read (empty without)
+  std::string strandText;               // ... and the lines of <o>.strand.tsv
+  uint64_t strandSums[2] = {0, 0};      // reads taken forward, reverse
+  // the read was corrected as under -rev: the whole file's -rev, or the read's own vote
+  bool reversed(const talc_params& p, size_t r) const { return p.reverse || (!strand.empty() && strand[r].reverse); }
 };
+
+// the lines of <o>.strand.tsv for one batch (k.status, k.strand filled)
+const char* const kStrandHeader = "read_name\tstatus\tn_kmers\tfwd_solid\tfwd_in\trc_solid\trc_in\tstrand\n";
+void formatStrand(Chunk& k) {
+  char num[128];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const talc_strand& w = k.strand[r];
+    const int m = snprintf(num, sizeof num, "\t%d\t%u\t%u\t%u\t%u\t%u\t%c\n", k.status[r], w.n_kmers, w.fwd_solid, w.fwd_in, w.rc_solid, w.rc_in, w.reverse ? '-' : '+');
+    k.strandText += k.ids[r];
+    k.strandText.append(num, (size_t)m);
+    k.strandSums[w.reverse ? 1 : 0] += 1;
+  }
+}
 
 // the lines of <o>.edits.tsv for one batch (k.status filled; oo: the records' offsets; the ops of read r are ops[po[r] ..
 // po[r + 1])): read_name status raw_length corr_length, five fields of the row, as_seen — '-' when the record is in the
-// orientation the correction worked in rather than the caller's (-rev, passed through) —, and the ops as text
+// orientation the correction worked in rather than the caller's (-rev or a read voted reverse, passed through) —, and the
+// ops as text
 const char* const kEditsHeader = "read_name\tstatus\traw_length\tcorr_length\tn_match\tn_mismatch\tn_ins\tn_del\tn_unaligned\tas_seen\tcigar\n";
 void formatEdits(const Options& o, Chunk& k, const uint32_t* ops, const uint64_t* po, const talc_edit_row* rows, const uint64_t* oo) {
   char num[256];
@@ -405,7 +431,7 @@ void formatEdits(const Options& o, Chunk& k, const uint32_t* ops, const uint64_t
     const talc_edit_row& w = rows[r];
     const bool corrected = k.status[r] == TALC_READ_CORRECTED;
     const int m = snprintf(num, sizeof num, "\t%d\t%llu\t%llu\t%u\t%u\t%u\t%u\t%u\t%c\t", k.status[r], (unsigned long long)(k.offsets[r + 1] - k.offsets[r]),
-                           (unsigned long long)(oo[r + 1] - oo[r]), w.n_match, w.n_mismatch, w.n_ins, w.n_del, w.n_unaligned, (o.p.reverse && !corrected) ? '-' : '+');
+                           (unsigned long long)(oo[r + 1] - oo[r]), w.n_match, w.n_mismatch, w.n_ins, w.n_del, w.n_unaligned, (k.reversed(o.p, r) && !corrected) ? '-' : '+');
     k.editText += k.ids[r];
     k.editText.append(num, (size_t)m);
     if (po[r] == po[r + 1]) k.editText += '*';
@@ -502,6 +528,10 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
   if (o.readStats) c.stats.assign(5 * n, 0);
   std::string all;
   std::vector<uint64_t> oo(n + 1, 0);
+  if (o.autoStrand) {   // (no table: every count is 0, every read stays forward)
+    c.strand.assign(n, talc_strand{0u, 0u, 0u, 0u, 0u, 0u});
+    for (size_t r = 0; r < n; ++r) { const uint64_t L = c.offsets[r + 1] - c.offsets[r]; c.strand[r].n_kmers = L >= o.p.k ? (uint32_t)(L - o.p.k + 1) : 0u; }
+  }
   for (size_t r = 0; r < n; ++r) {
     std::string q(in.p + c.offsets[r], c.offsets[r + 1] - c.offsets[r]);
     for (auto& ch : q) { ch = (ch == 'a' || ch == 'A') ? 'A' : (ch == 'c' || ch == 'C') ? 'C' : (ch == 'g' || ch == 'G') ? 'G' : (ch == 't' || ch == 'T') ? 'T' : 'N'; }
@@ -541,6 +571,7 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
     }
     formatEdits(o, c, ops.data(), po.data(), rows.data(), oo.data());
   }
+  if (o.autoStrand) formatStrand(c);
   formatChunk(o, c, all.data(), oo.data());
 }
 
@@ -558,6 +589,7 @@ struct WorkerTally {
 struct PipelineTotals {
   double readerBusy = 0, writerBusy = 0;   // the three busy times overlap
   uint64_t bases = 0, batches = 0;
+  uint64_t strandSums[2] = {0, 0};         // --auto-strand: reads taken forward, reverse
   uint64_t solSums[4] = {0, 0, 0, 0};      // --solidity: the sums of four columns of <o>.solidity.tsv (Chunk::solSums)
   uint64_t pieceSums[4] = {0, 0, 0, 0};    // --trim / --split: trimmed reads, their bases, split pieces, their bases
   uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // --corr-edits: Chunk::editSums
@@ -594,8 +626,9 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf;
     double busy = 0;
+    uint64_t strandSums[2] = {0, 0};
     uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
   };
   bool fail(std::string msg);
@@ -665,6 +698,11 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     if (!wr.ef) return fail("cannot write " + files_.edits);
     wr.ef << kEditsHeader;
   }
+  if (o_.autoStrand) {
+    wr.wf.open(files_.strand, std::ios_base::trunc);
+    if (!wr.wf) return fail("cannot write " + files_.strand);
+    wr.wf << kStrandHeader;
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -687,6 +725,8 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.tf.is_open()) wr.tf.close();
   if (wr.pf.is_open()) wr.pf.close();
   if (wr.ef.is_open()) wr.ef.close();
+  if (wr.wf.is_open()) wr.wf.close();
+  for (int i = 0; i < 2; ++i) tot.strandSums[i] = wr.strandSums[i];
   for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; }
   for (int i = 0; i < 6; ++i) tot.editSums[i] = wr.editSums[i];
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
@@ -750,6 +790,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     if (talc_ctx_create(table_, &o_.p, device, &made) != TALC_OK) { fail(talc_last_error()); return; }
     ctx.reset(made);
     if ((o_.corrMap || o_.softMask || o_.trim || o_.split || o_.corrEdits) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
+    if (o_.autoStrand && talc_ctx_set_auto_strand(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -810,6 +851,11 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
   const int frc = o_.softMask ? talc_batch_fetch_corrected_masked(ctx, b.get(), outb.p, total, oo.data(), c.status.data())
                               : talc_batch_fetch_corrected(ctx, b.get(), outb.p, total, oo.data(), c.status.data());
   if (frc != TALC_OK) return fail(talc_last_error());
+  if (o_.autoStrand) {   // the vote ran before the batch was encoded: the rows come beside the records
+    c.strand.resize(n);
+    if (talc_batch_fetch_strand(ctx, b.get(), c.strand.data()) != TALC_OK) return fail(talc_last_error());
+    formatStrand(c);
+  }
   if (o_.corrMap) {   // fetched here, beside the records; the writer appends the lines in batch order
     std::vector<talc_segment> segs(std::max<uint64_t>(talc_batch_num_segments(b.get()), 1));
     std::vector<uint64_t> so(n + 1);
@@ -874,6 +920,8 @@ void Pipeline::writerMain(WriterSide& w) {
     for (int i = 0; i < 4; ++i) w.pieceSums[i] += c->pieceSums[i];
     if (w.ef.is_open()) w.ef.write(c->editText.data(), (std::streamsize)c->editText.size());
     for (int i = 0; i < 6; ++i) w.editSums[i] += c->editSums[i];
+    if (w.wf.is_open()) w.wf.write(c->strandText.data(), (std::streamsize)c->strandText.size());
+    for (int i = 0; i < 2; ++i) w.strandSums[i] += c->strandSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -1074,6 +1122,9 @@ int main(int argc, const char** argv) {
     std::cout << "[TALC]: edits: " << y[0] << " matches, " << y[1] << " mismatches, " << y[2] << " insertions, " << y[3] << " deletions in " << y[4]
               << " corrected reads (" << y[5] << " segments not aligned)" << std::endl;
   }
+  if (o.autoStrand)
+    std::cout << "[TALC]: strand: " << totals.strandSums[0] << " forward, " << totals.strandSums[1] << " reverse of " << totals.strandSums[0] + totals.strandSums[1]
+              << " reads" << std::endl;
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   report(t, totals, scan, o.batchReads, ndev, pipeline.workers());
   return 0;

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "talc_batch_pieces", "talc_batch_num_pieces", "talc_batch_pieces_bytes", "talc_batch_fetch_pieces", "talc_ctx_get_pieces_timing",
     "talc_batch_edits", "talc_batch_num_edit_ops", "talc_batch_fetch_edits", "talc_ctx_get_edits_timing", "talc_test_edit_script",
     "talc_test_batch_edits", "talc_test_parse_text",
+    "talc_ctx_set_auto_strand", "talc_batch_strand", "talc_batch_fetch_strand", "talc_ctx_get_strand_timing",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -56,6 +57,9 @@ PIECE_DTYPE = np.dtype([("read", "<u4"), ("out_start", "<u4"), ("out_len", "<u4"
 EDIT_ROW_FIELDS = ("n_match", "n_mismatch", "n_ins", "n_del", "n_ops", "n_unaligned")
 EDIT_ROW_DTYPE = np.dtype([(f, "<u4") for f in EDIT_ROW_FIELDS])
 EDIT_I, EDIT_D, EDIT_EQ, EDIT_X = 1, 2, 7, 8
+# talc_strand (docs/auto_strand.md)
+STRAND_FIELDS = ("n_kmers", "fwd_solid", "fwd_in", "rc_solid", "rc_in", "reverse")
+STRAND_DTYPE = np.dtype([(f, "<u4") for f in STRAND_FIELDS])
 EDIT_LETTERS = {EDIT_I: "I", EDIT_D: "D", EDIT_EQ: "=", EDIT_X: "X"}
 
 
@@ -215,6 +219,11 @@ def lib():
             L.talc_test_edit_script.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, u64, vp, u64, vp, vp]
         if hasattr(L, "talc_test_parse_text"):  # (likewise: a build from before the parser's test hook)
             L.talc_test_parse_text.argtypes = [C.c_char_p, u32, u32, i32, i32, u64, i32, vp, vp, u64, vp, vp, vp]
+        if hasattr(L, "talc_ctx_set_auto_strand"):   # (likewise: a build from before auto strand)
+            L.talc_ctx_set_auto_strand.argtypes = [vp, i32]
+            L.talc_batch_strand.argtypes = [vp, vp]
+            L.talc_batch_fetch_strand.argtypes = [vp, vp, vp]
+            L.talc_ctx_get_strand_timing.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -465,6 +474,7 @@ class Context:
         h = C.c_void_p()
         _chk(lib().talc_ctx_create(table._h, C.byref(self.params), device, C.byref(h)))
         self._h = h
+        self._auto = False   # auto_strand()
 
     def timing(self):
         t = Timing()
@@ -492,6 +502,18 @@ class Context:
         a, b = C.c_float(), C.c_float()
         _chk(lib().talc_ctx_get_pieces_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def auto_strand(self, on=True):
+        """Later calls of this context take every read in the orientation the short reads support (docs/auto_strand.md;
+        Batch.strand() says which).  TalcError when the context's params have reverse set."""
+        _chk(lib().talc_ctx_set_auto_strand(self._h, 1 if on else 0))
+        self._auto = bool(on)
+
+    def strand_timing(self):
+        """Device time (ms) of the context's last k_strand_vote."""
+        a = C.c_float()
+        _chk(lib().talc_ctx_get_strand_timing(self._h, C.byref(a)))
+        return a.value
 
     def edits_timing(self):
         """(align ms, pack ms) of the context's last Batch.edits(): both runs of k_edit_align, k_edit_count + k_edit_pack."""
@@ -554,6 +576,13 @@ class Batch:
         _chk(lib().talc_batch_create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
         self._h = h
         self._corrected = False   # the batch holds the records of a correction (solidity() then has corrected rows)
+        self._enc_auto = None     # the auto-strand setting the batch's codes were made under
+
+    def _needs_codes(self):
+        """A batch whose codes were made under the other auto-strand setting is encoded again, as if it were new."""
+        if self._enc_auto is not None and self._enc_auto != self.ctx._auto:
+            self._corrected = False
+        self._enc_auto = self.ctx._auto
 
     @property
     def n_kmers(self):
@@ -564,6 +593,7 @@ class Batch:
         return int(lib().talc_batch_num_bases(self._h))
 
     def coverage(self):
+        self._needs_codes()
         _chk(lib().talc_batch_coverage(self.ctx._h, self._h))
 
     def fetch_coverage(self):
@@ -583,6 +613,7 @@ class Batch:
 
     def structure(self):
         """Test hook: encode, coverage and the structure kernel; nothing of the search."""
+        self._needs_codes()
         self._corrected = False
         _chk(lib().talc_batch_structure(self.ctx._h, self._h))
 
@@ -607,6 +638,7 @@ class Batch:
 
     def correct(self):
         """0, or WARN_READ_ERRORS when some reads exhausted the device scratch (status READ_ERROR, passed through)."""
+        self._needs_codes()
         self._corrected = False
         rc = _chk(lib().talc_batch_correct(self.ctx._h, self._h))
         self._corrected = True
@@ -641,11 +673,20 @@ class Batch:
         """The solidity report (docs/solidity.md): (raw, corrected) as SOLIDITY_DTYPE arrays of one row per read — how
         much of the read, and of its record, the short reads support.  corrected is None on a batch that has not been
         corrected."""
+        self._needs_codes()
         _chk(lib().talc_batch_solidity(self.ctx._h, self._h))
         raw = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE)
         cor = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE) if self._corrected else None
         _chk(lib().talc_batch_fetch_solidity(self.ctx._h, self._h, raw.ctypes.data, cor.ctypes.data if self._corrected else None))
         return raw, cor
+
+    def strand(self):
+        """The strand vote (docs/auto_strand.md) as a STRAND_DTYPE array of one row per read: solid and IN k-mers of the
+        read as it came and of its reverse complement, and the orientation chosen.  Runs the vote if the batch has none."""
+        _chk(lib().talc_batch_strand(self.ctx._h, self._h))
+        rows = np.zeros(self.n_reads, dtype=STRAND_DTYPE)
+        _chk(lib().talc_batch_fetch_strand(self.ctx._h, self._h, rows.ctypes.data))
+        return rows
 
     def pieces(self, mode, min_len=0, soft_mask=False):
         """Trimmed (PIECES_TRIM) or split (PIECES_SPLIT) output of the last correction (docs/trim_split.md; needs
