@@ -464,6 +464,38 @@ int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows);
 /* Measurement: device time (ms) of the context's last k_strand_vote. */
 int talc_ctx_get_strand_timing(const talc_ctx* c, float* vote_ms);
 
+/* Per-base support (docs/base_support.md): one byte for every base, how many of the k-mers that hold it the short reads
+ * confirm.  S, n, c[i] and solid[i] as for the solidity report above.  For a base j, 0 <= j < L, with lo = max(0, j - K + 1)
+ * and hi = min(j, n - 1):
+ *   span[j]  = hi - lo + 1, the k-mer positions whose k-mer holds base j (1 .. K); 0 when n = 0;
+ *   cover[j] = #{ i in [lo, hi] : solid[i] }; 0 when n = 0.
+ * With the solidity row of the same S: the sum of cover[j] over j is K * n_solid, and #{ j : cover[j] > 0 } is solid_bases. */
+enum { TALC_SUPPORT_RAW = 0, TALC_SUPPORT_RECORD = 1 };
+typedef struct talc_support_params {
+  uint32_t source;     /* TALC_SUPPORT_RAW | TALC_SUPPORT_RECORD */
+  uint32_t phred;      /* 0: byte = cover[j] (0..K);  1: byte = 33 + qmin + ((qmax - qmin) * cover[j]) / span[j], integer
+                          division; 33 + qmin where span[j] == 0 */
+  uint32_t qmin, qmax; /* phred only: 0 <= qmin <= qmax <= 93, else TALC_ERR_INVALID */
+} talc_support_params;
+/* RAW: S is the read as the correction sees it (Dna5-converted; reverse-complemented under -rev or when auto strand flagged
+ * it), and the bytes are laid out as the input reads were given, with the batch's input offsets.  RECORD: S is the record
+ * talc_batch_fetch_corrected returns in that same orientation (the corrected row of the solidity report: read back to front
+ * and complemented when the read is TALC_READ_CORRECTED without overflow and reverse or its auto-strand flag holds; a record
+ * that was passed through as it stands), and the bytes are laid out as the records, with the records' offsets.  Either way
+ * byte j of read r describes byte j of what the caller holds: where S was obtained by reverse complement it is the value of
+ * S's position L - 1 - j.  May be called on any batch (RECORD: TALC_ERR_STATE before talc_batch_correct); runs k_encode on a
+ * batch never encoded and, with auto strand on, the vote if it has not run.  It writes only its own buffer — nothing a later
+ * talc_batch_correct, _fetch_map, _solidity, _pieces or _edits reads is touched — and a later call replaces the result. */
+int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p);
+/* Bytes of the last talc_batch_support of b (0 when there is none since the last correction). */
+uint64_t talc_batch_support_bytes(const talc_batch* b);
+/* out: the bytes (may be NULL), out_offsets: n_reads + 1 entries (may be NULL) — the numbers talc_batch_fetch_corrected
+ * writes for RECORD, the input offsets for RAW.  TALC_ERR_STATE when talc_batch_support has not run on b since its last
+ * correction; TALC_ERR_CAPACITY, naming the bytes needed, when out_capacity is too small. */
+int talc_batch_fetch_support(talc_ctx* c, talc_batch* b, uint8_t* out, uint64_t out_capacity, uint64_t* out_offsets);
+/* Measurement: device time (ms) of the k_base_support launch of the context's last talc_batch_support. */
+int talc_ctx_get_support_timing(const talc_ctx* c, float* support_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

@@ -26,6 +26,7 @@
 #include "talc_kernels_search.h"
 #include "talc_kernels_solidity.h"
 #include "talc_kernels_strand.h"
+#include "talc_kernels_support.h"
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -124,9 +125,9 @@ struct talc_ctx {
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[26] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
+  hipEvent_t ev[28] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
                             // 14, 15: around k_piece_count; 16, 17: around k_piece_pack; 18 .. 23: the edit scripts (run_edits);
-                            // 24, 25: around k_strand_vote
+                            // 24, 25: around k_strand_vote; 26, 27: around k_base_support
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
@@ -138,6 +139,7 @@ struct talc_ctx {
   float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
   float piece_count_ms = 0, piece_pack_ms = 0;   // the last talc_batch_pieces: k_piece_count, k_piece_pack
   float edit_align_ms = 0, edit_pack_ms = 0;     // the last edit scripts: both k_edit_align runs, k_edit_count + k_edit_pack
+  float support_ms = 0;                          // the last talc_batch_support: k_base_support
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -186,6 +188,9 @@ struct talc_batch {
   uint64_t pieces_cap = 0, piece_bytes_cap = 0;
   // the edit scripts (talc_batch_edits) of the last correction, made since that correction
   bool edited = false;
+  // the per-base support (talc_batch_support) made since the last correction: of the records, or of the reads
+  bool supported = false, supportRecords = false;
+  uint64_t support_cap = 0;
   // auto strand: k_strand_vote has run on d_raw (d_strand, d_strand_flag hold its result: the raw bytes never change, so
   // it runs once per batch); encodedAuto: d_codes were made with the flags, and k_pack, k_pack_map, k_solidity take them too
   bool voted = false, encodedAuto = false;
@@ -194,6 +199,7 @@ struct talc_batch {
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
   CachedBuf<uint8_t> d_strand_flag;   // ... and its choice as one byte per read: what the four kernels that orient a read take
   const uint8_t* rev_flags() const { return encodedAuto ? d_strand_flag.get() : nullptr; }
+  CachedBuf<uint8_t> d_support;       // one byte per base (k_base_support), sized exactly
   EditOut edits;
   CachedBuf<uint8_t> d_piece_bytes;  // the kept pieces' bytes, dense (k_piece_pack), sized exactly
   CachedBuf<uint64_t> d_piece_off;   // one per piece: where its bytes start in d_piece_bytes
@@ -1006,7 +1012,7 @@ static int vote_time(talc_ctx* c) {
 static int prepare_strand(talc_ctx* c, talc_batch* b) {
   if (b->encoded && b->encodedAuto != c->autoStrand) {
     b->encoded = b->covered = b->structured = b->corrected = b->mapped = b->masked = false;
-    b->solidity = b->solidityCorrected = b->pieced = b->edited = false;
+    b->solidity = b->solidityCorrected = b->pieced = b->edited = b->supported = false;
   }
   if (c->autoStrand && !b->voted) return launch_vote(c, b);
   return TALC_OK;
@@ -1419,5 +1425,6 @@ void talc_counter_destroy(talc_counter* c) {
 
 #include "talc_capi_correct.inc"
 #include "talc_capi_edits.inc"
+#include "talc_capi_support.inc"
 
 }  // extern "C"

@@ -316,7 +316,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
   //  would be a mixture of this run's and the last one's)
   b->structured = false; b->corrected = false; b->mapped = false; b->masked = false;
-  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false;
+  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false; b->supported = false;
   const bool map = c->map;
   if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
@@ -351,7 +351,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipSetDevice(c->device));
   int rc;
   b->structured = false; b->corrected = false;
-  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false;
+  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false; b->supported = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
   if ((rc = read_stage_times(c, 3)) || (rc = vote_time(c))) return rc;

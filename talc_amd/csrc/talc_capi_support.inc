@@ -1,0 +1,67 @@
+// talc_capi_support.inc — host side of the per-base support (docs/base_support.md, talc_kernels_support.h); included by
+// talc_capi.hip inside its extern "C" block, after talc_capi_edits.inc.
+
+// k_base_support over the batch's codes (RAW) or its dense records (RECORD), events 26 and 27 around it.  The byte buffer is
+// the batch's, sized exactly; the buffer of an earlier call is kept when it is large enough.
+int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p) {
+  if (!c || !b || b->ctx != c || !p) return fail(TALC_ERR_INVALID, "bad context/batch/params");
+  if (p->source != TALC_SUPPORT_RAW && p->source != TALC_SUPPORT_RECORD)
+    return fail(TALC_ERR_INVALID, "support source %u is neither TALC_SUPPORT_RAW nor TALC_SUPPORT_RECORD", p->source);
+  if (p->phred > 1) return fail(TALC_ERR_INVALID, "phred must be 0 or 1, not %u", p->phred);
+  if (p->phred && (p->qmin > p->qmax || p->qmax > 93))
+    return fail(TALC_ERR_INVALID, "quality range %u .. %u: 0 <= qmin <= qmax <= 93 is required", p->qmin, p->qmax);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  int rc;
+  if ((rc = prepare_strand(c, b))) return rc;   // (a batch encoded under the other setting is no longer corrected either)
+  const bool records = p->source == TALC_SUPPORT_RECORD;
+  if (records && !b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch: it has no records");
+  b->supported = false;
+  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  const std::vector<uint64_t>& off = records ? b->h_dense_off : b->h_offsets;
+  const uint64_t total = off[b->n_reads];
+  if (b->d_support && b->support_cap < total) b->d_support.reset();
+  if (!b->d_support) { b->support_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_support.alloc(c->cache, b->support_cap)); }
+  // (the buffer is an allocation of its own, 256-byte aligned: k_base_support takes a byte's alignment from its offset)
+  HIPCHK(hipEventRecord(c->ev[26], s));
+  if (b->n_reads)
+    hipLaunchKernelGGL(k_base_support, dim3(b->n_reads), dim3(64), 0, s, c->view, records ? b->d_dense.get() : b->d_codes.get(),
+                       records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
+                       c->p.reverse ? 1 : 0, b->rev_flags(), c->p.min_count, b->n_reads, p->phred ? 1 : 0, p->phred ? p->qmin : 0u,
+                       p->phred ? p->qmax - p->qmin : 0u, b->d_support.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev[27], s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventElapsedTime(&c->support_ms, c->ev[26], c->ev[27]));
+  if ((rc = vote_time(c))) return rc;
+  b->supported = true; b->supportRecords = records;
+  return TALC_OK;
+}
+
+// the offsets of the bytes: the records' for RECORD, the input reads' for RAW
+static const std::vector<uint64_t>& support_offsets(const talc_batch* b) { return b->supportRecords ? b->h_dense_off : b->h_offsets; }
+
+uint64_t talc_batch_support_bytes(const talc_batch* b) { return (b && b->supported) ? support_offsets(b)[b->n_reads] : 0; }
+
+int talc_batch_fetch_support(talc_ctx* c, talc_batch* b, uint8_t* out, uint64_t out_capacity, uint64_t* out_offsets) {
+  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (!b->supported) return fail(TALC_ERR_STATE, "talc_batch_support has not run on this batch since its last correction");
+  HIPCHK(hipSetDevice(c->device));
+  const std::vector<uint64_t>& off = support_offsets(b);
+  const uint64_t total = off[b->n_reads];
+  if (out_offsets) memcpy(out_offsets, off.data(), ((size_t)b->n_reads + 1) * 8);
+  if (out) {
+    if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "support buffer too small: need %llu bytes", (unsigned long long)total);
+    if (total) {
+      HIPCHK(hipMemcpyAsync(out, b->d_support.get(), total, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+  }
+  return TALC_OK;
+}
+
+int talc_ctx_get_support_timing(const talc_ctx* c, float* support_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (support_ms) *support_ms = c->support_ms;
+  return TALC_OK;
+}

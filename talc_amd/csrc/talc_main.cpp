@@ -26,6 +26,10 @@
 //   --max-edit-cells N  with --corr-edits: a corrected stretch of more than N cells (raw x corrected length) is not aligned
 //   --auto-strand    every read is corrected in the orientation the short reads support, chosen on the device (docs/
 //                    auto_strand.md); writes <o>.strand.tsv: one line per read, in input order, with the vote and the choice
+//   --fastq         write <o>.fq beside <o>.fa: the same records with a quality for every base, made on the device from the
+//                    short reads' support of the k-mers that hold it (docs/base_support.md); with --trim / --split also
+//                    <o>.trim.fq / <o>.split.fq
+//   --qual-range MIN,MAX  with --fastq: the qualities of a base no solid k-mer holds and of one all of them hold (default 2,40)
 //   -k accepts 18..31 (the reference stops at 30, main.cpp:115-116; 31 still fits 62 bits)
 //   -SR / -j accept a Jellyfish 2 count file (.jf, `jellyfish count` output) as well as the text dump, in either mode
 //   -qm jellyfish2 works (the reference's is dead code): with -jf2 DIR the counts come from `DIR/jellyfish
@@ -110,6 +114,8 @@ struct Options {
   bool corrEdits = false;                   // --corr-edits
   uint64_t maxEditCells = 0;                // --max-edit-cells (0: the library's default)
   bool autoStrand = false;                  // --auto-strand
+  bool fastq = false, haveQualRange = false;   // --fastq, --qual-range
+  uint32_t qmin = 2, qmax = 40;
 };
 
 void usage(FILE* f) {
@@ -152,6 +158,11 @@ void usage(FILE* f) {
           "                              length), default 67108864; beyond 536870912 it acts as that (docs/correction_edits.md)\n"
           "  --auto-strand               correct every read in the orientation the short reads support (not with -rev); write\n"
           "                              <o>.strand.tsv: solid and IN k-mers of the read and of its reverse complement, + or -\n"
+          "  --fastq                     write <o>.fq beside <o>.fa: every record with one quality per base, from the short reads'\n"
+          "                              support of the k-mers that hold the base (docs/base_support.md); with --trim / --split\n"
+          "                              also <o>.trim.fq / <o>.split.fq\n"
+          "  --qual-range MIN,MAX        with --fastq: the quality of a base no solid k-mer holds and of one all of them hold,\n"
+          "                              0 <= MIN <= MAX <= 93, default 2,40\n"
           "  -h, --help / --version\n");
 }
 
@@ -209,6 +220,15 @@ Options parse(int argc, const char** argv) {
     else if (a == "--corr-edits") o.corrEdits = true;
     else if (a == "--max-edit-cells") { double v = num(need(i), "max-edit-cells"); range(v, 1, 9e18, "max-edit-cells"); o.maxEditCells = (uint64_t)v; }
     else if (a == "--auto-strand") o.autoStrand = true;
+    else if (a == "--fastq") o.fastq = true;
+    else if (a == "--qual-range") {
+      const std::string v = need(i);
+      const size_t comma = v.find(',');
+      if (comma == std::string::npos) parse_error("the given value '" + v + "' cannot be cast for qual-range: MIN,MAX is expected");
+      const double lo = num(v.substr(0, comma).c_str(), "qual-range"), hi = num(v.substr(comma + 1).c_str(), "qual-range");
+      if (lo != (double)(long long)lo || hi != (double)(long long)hi || lo < 0 || lo > hi || hi > 93) parse_error("value out of range for qual-range: 0 <= MIN <= MAX <= 93");
+      o.qmin = (uint32_t)lo; o.qmax = (uint32_t)hi; o.haveQualRange = true;
+    }
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -224,6 +244,7 @@ Options parse(int argc, const char** argv) {
   if (o.haveSR && !o.srReads.empty()) parse_error("-SR and --SRReads exclude each other: give the counts or the short reads");
   if (!o.srReads.empty() && o.queryMode == "jellyfish2") parse_error("--SRReads counts the k-mers itself: it does not go with -qm jellyfish2");
   if (!o.srCountsOut.empty() && o.srReads.empty()) parse_error("--SRCountsOut needs --SRReads");
+  if (o.haveQualRange && !o.fastq) parse_error("--qual-range needs --fastq");
   if (o.autoStrand && o.p.reverse) parse_error("--auto-strand chooses every read's orientation: it does not go with -rev");
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
@@ -260,10 +281,11 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits, strand;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
-        trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv") {}
+        trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv"),
+        fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -403,6 +425,7 @@ struct Chunk {
   std::vector<talc_strand> strand;      // --auto-strand: the vote of every read (empty without)
   std::string strandText;               // ... and the lines of <o>.strand.tsv
   uint64_t strandSums[2] = {0, 0};      // reads taken forward, reverse
+  std::string fqText, trimFqText, splitFqText;   // ... and to <o>.fq, <o>.trim.fq, <o>.split.fq (--fastq)
   // the read was corrected as under -rev: the whole file's -rev, or the read's own vote
   bool reversed(const talc_params& p, size_t r) const { return p.reverse || (!strand.empty() && strand[r].reverse); }
 };
@@ -457,6 +480,29 @@ void formatPieces(const Chunk& k, bool split, const char* bytes, const uint64_t*
       for (size_t p = 0; p < L; p += 70) { text.append(bytes + po[i] + p, std::min<size_t>(70, L - p)); text += '\n'; }
       sums[0] += 1; sums[1] += L;
     }
+}
+
+// one FASTQ record: @name, the sequence on one line, +, the qualities
+void appendFastq(std::string& text, const std::string& id, uint64_t piece, const char* seq, const char* qual, size_t L) {
+  text += '@'; text += id;
+  if (piece) { text += '_'; text += std::to_string(piece); }
+  text += '\n';
+  text.append(seq, L); text += "\n+\n";
+  text.append(qual, L); text += '\n';
+}
+
+// the records of <o>.fq for one batch: the records of <o>.fa (recs, oo) with the batch's quality bytes, which lie as the records do
+void formatFastq(Chunk& k, const char* recs, const char* qual, const uint64_t* oo) {
+  for (size_t r = 0; r < k.ids.size(); ++r) appendFastq(k.fqText, k.ids[r], 0, recs + oo[r], qual + oo[r], (size_t)(oo[r + 1] - oo[r]));
+}
+
+// the records of <o>.trim.fq or <o>.split.fq: the pieces as formatPieces names them; a piece's qualities are those of its
+// place in the record (pieces[i].out_start of read r's record, which starts at oo[r])
+void formatPiecesFastq(const Chunk& k, bool split, const char* bytes, const uint64_t* po, const talc_piece* pieces, const uint64_t* rpo, const char* qual,
+                       const uint64_t* oo, std::string& text) {
+  for (size_t r = 0; r < k.ids.size(); ++r)
+    for (uint64_t i = rpo[r]; i < rpo[r + 1]; ++i)
+      appendFastq(text, k.ids[r], split ? i - rpo[r] + 1 : 0, bytes + po[i], qual + oo[r] + pieces[i].out_start, (size_t)(po[i + 1] - po[i]));
 }
 
 // the lines of <o>.solidity.tsv for one batch (k.status filled; oo: the records' offsets): read_name status raw_length
@@ -572,6 +618,10 @@ void passThrough(const Options& o, Chunk& c, const HostBuf& in) {
     formatEdits(o, c, ops.data(), po.data(), rows.data(), oo.data());
   }
   if (o.autoStrand) formatStrand(c);
+  if (o.fastq) {   // (no table: no k-mer is solid, every base has the lowest quality)
+    const std::string qual(all.size(), (char)(33 + o.qmin));
+    formatFastq(c, all.data(), qual.data(), oo.data());
+  }
   formatChunk(o, c, all.data(), oo.data());
 }
 
@@ -583,6 +633,7 @@ struct Scan {   // what the first pass over the read file found
 // what one worker's time went into ([talc-timing]: device_busy_s_sum_over_workers and device_parts_s), and the reads it
 // had to leave uncorrected; one per worker, added up once the workers have ended
 struct WorkerTally {
+  double supportMs = 0;   // --fastq: the device time of k_base_support, summed over the worker's batches
   double busy = 0, ctx = 0, create = 0, correct = 0, fetch = 0, text = 0, waitChunk = 0;
   uint64_t readErrors = 0;
 };
@@ -626,7 +677,7 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf;
     double busy = 0;
     uint64_t strandSums[2] = {0, 0};
     uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
@@ -636,7 +687,7 @@ class Pipeline {
   void workerMain(int device, WorkerTally& t);
   void correctChunks(int device, WorkerTally& t);
   bool correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTally& t);
-  bool fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split);
+  bool fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split, const char* qual, const uint64_t* oo);
   void writerMain(WriterSide& w);   // io.cpp:50-75 + SeqFileOut FASTA writer, io.cpp:105-111 log lines
 
   // immutable once constructed
@@ -693,6 +744,12 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     wr.pf.open(files_.split, std::ios_base::trunc);
     if (!wr.pf) return fail("cannot write " + files_.split);
   }
+  if (o_.fastq) {   // (without a table the piece files exist and stay empty, as <o>.trim.fa and <o>.split.fa do)
+    wr.qf.open(files_.fq, std::ios_base::trunc);
+    if (!wr.qf) return fail("cannot write " + files_.fq);
+    if (o_.trim) { wr.tqf.open(files_.trimFq, std::ios_base::trunc); if (!wr.tqf) return fail("cannot write " + files_.trimFq); }
+    if (o_.split) { wr.pqf.open(files_.splitFq, std::ios_base::trunc); if (!wr.pqf) return fail("cannot write " + files_.splitFq); }
+  }
   if (o_.corrEdits) {
     wr.ef.open(files_.edits, std::ios_base::trunc);
     if (!wr.ef) return fail("cannot write " + files_.edits);
@@ -726,6 +783,9 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.pf.is_open()) wr.pf.close();
   if (wr.ef.is_open()) wr.ef.close();
   if (wr.wf.is_open()) wr.wf.close();
+  if (wr.qf.is_open()) wr.qf.close();
+  if (wr.tqf.is_open()) wr.tqf.close();
+  if (wr.pqf.is_open()) wr.pqf.close();
   for (int i = 0; i < 2; ++i) tot.strandSums[i] = wr.strandSums[i];
   for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; }
   for (int i = 0; i < 6; ++i) tot.editSums[i] = wr.editSums[i];
@@ -734,7 +794,7 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   for (const WorkerTally& t : tally) {
     WorkerTally& s = tot.workers;
     s.busy += t.busy; s.ctx += t.ctx; s.create += t.create; s.correct += t.correct; s.fetch += t.fetch; s.text += t.text; s.waitChunk += t.waitChunk;
-    s.readErrors += t.readErrors;
+    s.readErrors += t.readErrors; s.supportMs += t.supportMs;
   }
   return !q_.failed;
 }
@@ -818,13 +878,16 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
 }
 
 // --trim / --split: the batch's records cut on the device, only the kept bytes fetched, and turned into the file's text
-bool Pipeline::fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split) {
+// (qual: the batch's quality bytes with the records' offsets oo, for the pieces' FASTQ records; null without --fastq)
+bool Pipeline::fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split, const char* qual, const uint64_t* oo) {
   if (talc_batch_pieces(ctx, b, split ? TALC_PIECES_SPLIT : TALC_PIECES_TRIM, o_.minPieceLen, o_.softMask ? 1 : 0) != TALC_OK) return fail(talc_last_error());
   const uint64_t np = talc_batch_num_pieces(b), nb = talc_batch_pieces_bytes(b);
   std::vector<char> bytes(std::max<uint64_t>(nb, 1));
   std::vector<uint64_t> po(np + 1), rpo(c.ids.size() + 1);
-  if (talc_batch_fetch_pieces(ctx, b, bytes.data(), nb, po.data(), nullptr, 0, rpo.data()) != TALC_OK) return fail(talc_last_error());
+  std::vector<talc_piece> pieces(qual ? std::max<uint64_t>(np, 1) : 0);
+  if (talc_batch_fetch_pieces(ctx, b, bytes.data(), nb, po.data(), qual ? pieces.data() : nullptr, qual ? np : 0, rpo.data()) != TALC_OK) return fail(talc_last_error());
   formatPieces(c, split, bytes.data(), po.data(), rpo.data(), split ? c.splitText : c.trimText, c.pieceSums + (split ? 2 : 0));
+  if (qual) formatPiecesFastq(c, split, bytes.data(), po.data(), pieces.data(), rpo.data(), qual, oo, split ? c.splitFqText : c.trimFqText);
   return true;
 }
 
@@ -867,8 +930,20 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
     if (talc_batch_solidity(ctx, b.get()) != TALC_OK || talc_batch_fetch_solidity(ctx, b.get(), raw.data(), cor.data()) != TALC_OK) return fail(talc_last_error());
     formatSolidity(c, raw.data(), cor.data(), oo.data());
   }
-  if (o_.trim && !fetchPieces(ctx, b.get(), c, false)) return false;
-  if (o_.split && !fetchPieces(ctx, b.get(), c, true)) return false;
+  std::vector<char> qual;
+  if (o_.fastq) {   // one more device pass over the records while they are in HBM; one byte per base crosses, beside the records
+    const talc_support_params sp = {TALC_SUPPORT_RECORD, 1u, o_.qmin, o_.qmax};
+    if (talc_batch_support(ctx, b.get(), &sp) != TALC_OK) return fail(talc_last_error());
+    qual.resize(std::max<uint64_t>(talc_batch_support_bytes(b.get()), 1));
+    if (talc_batch_fetch_support(ctx, b.get(), (uint8_t*)qual.data(), qual.size(), nullptr) != TALC_OK) return fail(talc_last_error());
+    float ms = 0;
+    talc_ctx_get_support_timing(ctx, &ms);
+    t.supportMs += ms;
+    formatFastq(c, outb.p, qual.data(), oo.data());
+  }
+  const char* q = o_.fastq ? qual.data() : nullptr;
+  if (o_.trim && !fetchPieces(ctx, b.get(), c, false, q, oo.data())) return false;
+  if (o_.split && !fetchPieces(ctx, b.get(), c, true, q, oo.data())) return false;
   if (o_.corrEdits) {   // aligned on the device while the reads and the records are in HBM; only the ops cross
     if (talc_batch_edits(ctx, b.get(), o_.maxEditCells) != TALC_OK) return fail(talc_last_error());
     const uint64_t nops = talc_batch_num_edit_ops(b.get());
@@ -921,6 +996,9 @@ void Pipeline::writerMain(WriterSide& w) {
     if (w.ef.is_open()) w.ef.write(c->editText.data(), (std::streamsize)c->editText.size());
     for (int i = 0; i < 6; ++i) w.editSums[i] += c->editSums[i];
     if (w.wf.is_open()) w.wf.write(c->strandText.data(), (std::streamsize)c->strandText.size());
+    if (w.qf.is_open()) w.qf.write(c->fqText.data(), (std::streamsize)c->fqText.size());
+    if (w.tqf.is_open()) w.tqf.write(c->trimFqText.data(), (std::streamsize)c->trimFqText.size());
+    if (w.pqf.is_open()) w.pqf.write(c->splitFqText.data(), (std::streamsize)c->splitFqText.size());
     for (int i = 0; i < 2; ++i) w.strandSums[i] += c->strandSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
@@ -1126,6 +1204,8 @@ int main(int argc, const char** argv) {
     std::cout << "[TALC]: strand: " << totals.strandSums[0] << " forward, " << totals.strandSums[1] << " reverse of " << totals.strandSums[0] + totals.strandSums[1]
               << " reads" << std::endl;
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
+  if (sw.timing && o.fastq && ndev)
+    fprintf(stderr, "[talc-lib] base support: %llu batches, k_base_support %.3f ms\n", (unsigned long long)totals.batches, totals.workers.supportMs);
   report(t, totals, scan, o.batchReads, ndev, pipeline.workers());
   return 0;
 }

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "talc_batch_edits", "talc_batch_num_edit_ops", "talc_batch_fetch_edits", "talc_ctx_get_edits_timing", "talc_test_edit_script",
     "talc_test_batch_edits", "talc_test_parse_text",
     "talc_ctx_set_auto_strand", "talc_batch_strand", "talc_batch_fetch_strand", "talc_ctx_get_strand_timing",
+    "talc_batch_support", "talc_batch_support_bytes", "talc_batch_fetch_support", "talc_ctx_get_support_timing",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -60,6 +61,8 @@ EDIT_I, EDIT_D, EDIT_EQ, EDIT_X = 1, 2, 7, 8
 # talc_strand (docs/auto_strand.md)
 STRAND_FIELDS = ("n_kmers", "fwd_solid", "fwd_in", "rc_solid", "rc_in", "reverse")
 STRAND_DTYPE = np.dtype([(f, "<u4") for f in STRAND_FIELDS])
+# talc_support_params (docs/base_support.md)
+SUPPORT_RAW, SUPPORT_RECORD = 0, 1
 EDIT_LETTERS = {EDIT_I: "I", EDIT_D: "D", EDIT_EQ: "=", EDIT_X: "X"}
 
 
@@ -70,6 +73,10 @@ def cigar_text(ops):
 
 class TalcError(RuntimeError):
     pass
+
+
+class SupportParams(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("phred", C.c_uint32), ("qmin", C.c_uint32), ("qmax", C.c_uint32)]
 
 
 class Params(C.Structure):
@@ -224,6 +231,12 @@ def lib():
             L.talc_batch_strand.argtypes = [vp, vp]
             L.talc_batch_fetch_strand.argtypes = [vp, vp, vp]
             L.talc_ctx_get_strand_timing.argtypes = [vp, vp]
+        if hasattr(L, "talc_batch_support"):
+            L.talc_batch_support.argtypes = [vp, vp, C.POINTER(SupportParams)]
+            L.talc_batch_support_bytes.restype = u64
+            L.talc_batch_support_bytes.argtypes = [vp]
+            L.talc_batch_fetch_support.argtypes = [vp, vp, vp, u64, vp]
+            L.talc_ctx_get_support_timing.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -515,6 +528,12 @@ class Context:
         _chk(lib().talc_ctx_get_strand_timing(self._h, C.byref(a)))
         return a.value
 
+    def support_timing(self):
+        """Device time (ms) of the k_base_support launch of the context's last Batch.support()."""
+        a = C.c_float()
+        _chk(lib().talc_ctx_get_support_timing(self._h, C.byref(a)))
+        return a.value
+
     def edits_timing(self):
         """(align ms, pack ms) of the context's last Batch.edits(): both runs of k_edit_align, k_edit_count + k_edit_pack."""
         a, b = C.c_float(), C.c_float()
@@ -679,6 +698,28 @@ class Batch:
         cor = np.zeros(self.n_reads, dtype=SOLIDITY_DTYPE) if self._corrected else None
         _chk(lib().talc_batch_fetch_solidity(self.ctx._h, self._h, raw.ctypes.data, cor.ctypes.data if self._corrected else None))
         return raw, cor
+
+    def support(self, source="record", phred=None):
+        """Per-base support (docs/base_support.md): (bytes uint8, offsets u64[n_reads + 1]), one byte per base — of the
+        records of the last correction (source="record", laid out as fetch_corrected's) or of the reads as they were
+        given (source="raw").  The byte is cover, the number of solid k-mers that hold the base (0 .. K); with
+        phred=(qmin, qmax) it is the quality character 33 + qmin + (qmax - qmin) * cover // span."""
+        if source not in ("raw", "record"):
+            raise ValueError("source must be 'raw' or 'record'")
+        self._needs_codes()
+        p = SupportParams(SUPPORT_RECORD if source == "record" else SUPPORT_RAW, 0, 0, 0)
+        if phred is not None:
+            lo, hi = phred
+            if lo < 0 or hi < 0:
+                raise ValueError("qualities are not negative")
+            p.phred, p.qmin, p.qmax = 1, int(lo), int(hi)
+        L = lib()
+        _chk(L.talc_batch_support(self.ctx._h, self._h, C.byref(p)))
+        total = int(L.talc_batch_support_bytes(self._h))
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        oo = np.empty(self.n_reads + 1, dtype=np.uint64)
+        _chk(L.talc_batch_fetch_support(self.ctx._h, self._h, out.ctypes.data, total, oo.ctypes.data))
+        return out[:total], oo
 
     def strand(self):
         """The strand vote (docs/auto_strand.md) as a STRAND_DTYPE array of one row per read: solid and IN k-mers of the
