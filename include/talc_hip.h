@@ -431,6 +431,34 @@ int talc_test_batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells, uint64
 int talc_test_parse_text(const char* path, uint32_t k, uint32_t min_count, int where, int device, uint64_t chunk_bytes,
                          int reader_threads, uint64_t* kmers_out, uint32_t* counts_out, uint64_t capacity,
                          uint64_t* n_lines_out, uint64_t* kept_out, uint64_t* flags_out);
+/* Test hooks: poisoned allocations and red zones.  No result may depend on what device memory held before, and no kernel
+ * may write outside its buffers; sanitizers cannot say so for device code, these hooks can.  talc_test_set_poison sets a
+ * process-wide setting for the allocations made from then on, in every thread: byte = -1 switches it off, 0 .. 255 is the
+ * poison; guard_bytes (a multiple of 256, at most 1 MiB) is the size of the red zones.  While it is on, every device buffer
+ * the library hands out — a fresh one or one from a context's cache — is filled with byte over its whole capacity before
+ * it is used, and has guard_bytes of ~byte in front of it and behind it; the search scratch, the edge boxes and a retry
+ * stage are poisoned again before every k_search launch.  When a buffer is given back (to the cache, and again to the
+ * runtime) both red zones are read back and compared; a mismatch is counted, nothing aborts.  A buffer made under one
+ * setting may be given back under another.  Off, the hooks cost one relaxed load per allocation.  What they cannot see: a
+ * read past a red zone, and a stray write that lands inside the same buffer (one wave's scratch slot spilling into the
+ * next one's).  TALC_ERR_INVALID for a byte or a guard size outside these ranges. */
+int talc_test_set_poison(int byte, uint32_t guard_bytes);
+/* The setting as it is now: *byte = -1 when off.  Either pointer may be NULL. */
+int talc_test_get_poison(int* byte, uint32_t* guard_bytes);
+/* out = {buffers checked, violations, bytes asked for of the first offender, its side << 32 | the offset of the first
+ * changed byte inside that red zone}; side 0 is the zone in front of the buffer, 1 the one behind it.  Process-wide, since
+ * the library was loaded. */
+int talc_test_guard_report(uint64_t out[4]);
+/* How many requests the contexts' caches have served with a buffer used before, while the setting was on. */
+uint64_t talc_test_cache_reuses(void);
+/* Proves that the hooks do something; needs the setting on with red zones (TALC_ERR_STATE otherwise) and a GPU.  Makes one
+ * buffer of 1000 bytes of its own and one cached buffer of 1000 bytes served from a used buffer of 2000, reads them back,
+ * writes one byte just behind the first and one just in front of the second (both land in the red zones, the library's
+ * own memory) and gives both back.  out = {fills: bit 0 the first buffer's bytes are the poison, bit 1 its red zones are
+ * ~poison, bits 2 and 3 the same for the cached buffer, its slack included: 15 when all is as specified; the violations
+ * the two writes caused: 2; where the first buffer's was found, where the second's was: side << 32 | offset}.  Its
+ * checks do not enter talc_test_guard_report. */
+int talc_test_guard_selftest(uint64_t out[4]);
 
 /* Auto strand (docs/auto_strand.md): the k-mer table is directional and a long cDNA read arrives in either orientation; -rev
  * (talc_params.reverse) turns the whole file.  With auto strand every read is corrected in the orientation the short reads

@@ -11,6 +11,7 @@
 #include <fstream>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -274,6 +275,79 @@ void* talc_pinned_alloc(uint64_t bytes) {
   return p.release();
 }
 void talc_pinned_free(void* p) { PinnedBuf gone(p); }
+
+// ---- Test hooks: poisoned allocations and red zones (talc_devmem.h: memcheck)
+int talc_test_set_poison(int byte, uint32_t guard_bytes) {
+  if (byte < -1 || byte > 255) return fail(TALC_ERR_INVALID, "the poison byte is -1 (off) or 0 .. 255, %d given", byte);
+  if (guard_bytes % 256 || guard_bytes > (1u << 20)) return fail(TALC_ERR_INVALID, "red zones are a multiple of 256 bytes, at most 1 MiB: %u given", guard_bytes);
+  memcheck::set(byte, byte < 0 ? 0 : guard_bytes);
+  return TALC_OK;
+}
+int talc_test_get_poison(int* byte, uint32_t* guard_bytes) {
+  const memcheck::Setting s = memcheck::setting();
+  if (byte) *byte = s.on ? (int)s.byte : -1;
+  if (guard_bytes) *guard_bytes = s.on ? s.guard : 0;
+  return TALC_OK;
+}
+int talc_test_guard_report(uint64_t out[4]) {
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(memcheck::lock());
+  const memcheck::Tally& t = memcheck::global_tally();
+  out[0] = t.checked; out[1] = t.violations; out[2] = t.firstBytes; out[3] = t.firstWhere;
+  return TALC_OK;
+}
+uint64_t talc_test_cache_reuses(void) {
+  std::lock_guard<std::mutex> lk(memcheck::lock());
+  return memcheck::global_tally().reused;
+}
+// the checks of a scope go to a tally of its own
+struct TallyScope {
+  memcheck::Tally* before;
+  explicit TallyScope(memcheck::Tally* t) : before(memcheck::tally_override()) { memcheck::tally_override() = t; }
+  ~TallyScope() { memcheck::tally_override() = before; }
+};
+int talc_test_guard_selftest(uint64_t out[4]) {
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  const memcheck::Setting s = memcheck::setting();
+  if (!s.on || !s.guard) return fail(TALC_ERR_STATE, "the self test needs a poison byte and red zones (talc_test_set_poison)");
+  const uint8_t poison = s.byte, red = (uint8_t)~s.byte;
+  const uint64_t n = 1000, G = s.guard;
+  auto all = [](const uint8_t* p, uint64_t len, uint8_t v) { for (uint64_t i = 0; i < len; ++i) if (p[i] != v) return false; return true; };
+  uint64_t fills = 0;
+  memcheck::Tally ofBuf, ofCached, rest;
+  std::vector<uint8_t> h(2 * n + 2 * G);
+  {   // a DevBuf of n bytes; one byte just past its end
+    TallyScope scope(&ofBuf);
+    DevBuf<uint8_t> d;
+    HIPCHK(d.alloc(n));
+    HIPCHK(hipMemcpy(h.data(), d.get() - G, n + 2 * G, hipMemcpyDeviceToHost));
+    fills |= all(h.data() + G, n, poison) ? 1 : 0;
+    fills |= all(h.data(), G, red) && all(h.data() + G + n, G, red) ? 2 : 0;
+    HIPCHK(hipMemcpy(d.get() + n, &poison, 1, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  {   // a cached buffer of n bytes, taken from the pool (2 n bytes, overwritten before it went there); one byte just before its start
+    TallyScope scope(&rest);
+    DevCache cache;
+    void *big = nullptr, *p = nullptr;
+    HIPCHK(cache.alloc(&big, 2 * n));
+    HIPCHK(hipMemset(big, red, 2 * n));
+    HIPCHK(hipDeviceSynchronize());
+    cache.release(big);
+    HIPCHK(cache.alloc(&p, n));
+    if (p == big && rest.reused == 1) {
+      HIPCHK(hipMemcpy(h.data(), (uint8_t*)p - G, 2 * n + 2 * G, hipMemcpyDeviceToHost));
+      fills |= all(h.data() + G, 2 * n, poison) ? 4 : 0;   // (the slack behind the n bytes too)
+      fills |= all(h.data(), G, red) && all(h.data() + G + 2 * n, G, red) ? 8 : 0;
+    }
+    HIPCHK(hipMemcpy((uint8_t*)p - 1, &poison, 1, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    TallyScope mine(&ofCached);
+    cache.release(p);
+  }
+  out[0] = fills; out[1] = ofBuf.violations + ofCached.violations; out[2] = ofBuf.firstWhere; out[3] = ofCached.firstWhere;
+  return TALC_OK;
+}
 
 static int check_params(const talc_params* p) {
   if (!p) return fail(TALC_ERR_INVALID, "null params");

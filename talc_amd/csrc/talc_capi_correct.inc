@@ -180,6 +180,9 @@ static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint
                          uint32_t traceRead, bool edgeTasks) {
   hipStream_t s = c->stream;
   HIPCHK(hipMemsetAsync(c->d_queue.get(), 0, kQueueWords * sizeof(uint32_t), s));
+  // test hook (talc_test_set_poison): the scratch, the boxes and a retry stage outlive a launch; every launch finds them poisoned
+  const memcheck::Setting poison = memcheck::setting();
+  if (poison.on && st.scratch_bytes) HIPCHK(hipMemsetAsync(st.scratch.get(), poison.byte, st.scratch_bytes, s));
   EdgeTaskArgs ea = {};
   ea.test = c->sw.edgeLane ? 0u : kTestNoEdgeLane;
   if (edgeTasks && st.boxes) {   // the claim counters sit behind the boxes
@@ -189,6 +192,7 @@ static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint
     ea.minWeak = c->sw.edgeTaskMin; ea.heavy = c->sw.edgeTaskHeavy; ea.heavyRounds = c->sw.edgeTaskRounds;
     ea.lingerMod = c->sw.edgeLingerMod; ea.test |= c->sw.edgeRedo ? kTestEdgeRedo : 0u;
     ea.autoSwitch = c->sw.edgeTasks > 0 ? nullptr : batch_stats(c) + kStatBranching;   // (switched on: whatever the batch looks like)
+    if (poison.on) HIPCHK(hipMemsetAsync(ea.boxes, poison.byte, (uint64_t)st.n_slots * edge_box_bytes(st.box_seq_cap), s));   // (not the claim counters)
     HIPCHK(hipMemsetAsync(ea.avail, 0, (uint64_t)st.n_slots * 4, s));
   }
   hipLaunchKernelGGL(k_search, dim3(st.n_slots), dim3(64), 0, s, c->dp, c->view, st.caps, b->d_codes.get(), b->d_offsets.get(),

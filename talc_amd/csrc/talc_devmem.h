@@ -5,8 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <map>
+#include <mutex>
 #include <utility>
 #include <vector>
 
@@ -14,6 +16,121 @@ namespace talc {
 
 // the runtime's own start-up, as the call that does nothing else
 inline hipError_t hip_runtime_start() { return hipFree(nullptr); }
+
+// Test hook (talc_test_set_poison, include/talc_hip.h): poisoned allocations and red zones.  While the setting is on, every
+// buffer the two owners below hand out is filled with `byte` over its whole capacity (a pooled buffer's slack included)
+// before its pointer is returned, and sits between two red zones of `guard` bytes of ~byte that are read back and compared
+// when the buffer is given back.  A buffer remembers the guard and the fill it was made with, so one made under one setting
+// can be released under another.  With the setting off an allocation costs one relaxed load more than without the hook.
+// What this cannot see: a read past a red zone, and a stray write that lands inside the same buffer (one wave's scratch
+// slot spilling into its neighbour's).
+namespace memcheck {
+
+struct Setting { bool on; uint8_t byte; uint32_t guard; };
+inline std::atomic<uint64_t>& setting_word() { static std::atomic<uint64_t> w{0}; return w; }   // 0: off; 1 << 40 | byte << 32 | guard
+inline Setting setting() {
+  const uint64_t w = setting_word().load(std::memory_order_relaxed);
+  return Setting{w != 0, (uint8_t)(w >> 32), (uint32_t)w};
+}
+inline void set(int byte, uint32_t guard) { setting_word().store(byte < 0 ? 0 : (1ull << 40 | (uint64_t)(byte & 0xFF) << 32 | guard)); }
+
+// what the checks have seen: process-wide, or the self test's own while it runs (tally_override)
+struct Tally {
+  uint64_t checked = 0, violations = 0;
+  uint64_t firstBytes = 0, firstWhere = 0;   // the first offender: bytes asked for; side << 32 | offset of the first changed byte (side 0: before the buffer, 1: behind it)
+  uint64_t reused = 0;                       // DevCache::alloc calls served from the pool
+};
+inline std::mutex& lock() { static std::mutex m; return m; }
+inline Tally& global_tally() { static Tally t; return t; }
+inline Tally*& tally_override() { static thread_local Tally* t = nullptr; return t; }
+inline void count_reuse() {
+  std::lock_guard<std::mutex> g(lock());
+  ++(tally_override() ? *tally_override() : global_tally()).reused;
+}
+
+// one guarded buffer: the caller's pointer is base + guard
+struct Guard { uint32_t guard = 0; uint8_t fill = 0; uint64_t asked = 0; };
+
+// `bytes` of device memory, poisoned and between red zones when the setting is on (g says what was made)
+inline hipError_t alloc(void** out, uint64_t bytes, Guard& g) {
+  const Setting s = setting();
+  g = Guard();
+  if (!s.on) return hipMalloc(out, bytes);
+  char* base = nullptr;
+  hipError_t e = hipMalloc((void**)&base, bytes + 2ull * s.guard);
+  if (e != hipSuccess) return e;
+  g.guard = s.guard; g.fill = (uint8_t)~s.byte; g.asked = bytes;
+  if (s.guard) {
+    if (e == hipSuccess) e = hipMemset(base, g.fill, s.guard);
+    if (e == hipSuccess) e = hipMemset(base + s.guard + bytes, g.fill, s.guard);
+  }
+  if (e == hipSuccess) e = hipMemset(base + s.guard, s.byte, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // (the null stream is not ordered with the contexts' non-blocking streams)
+  if (e != hipSuccess) { (void)hipFree(base); return e; }
+  *out = base + s.guard;
+  return hipSuccess;
+}
+// a buffer that is handed out again (DevCache's pool): poisoned over its whole capacity when the setting is on
+inline hipError_t repoison(void* p, uint64_t capacity) {
+  const Setting s = setting();
+  if (!s.on) return hipSuccess;
+  hipError_t e = hipMemset(p, s.byte, capacity);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+// both red zones of a buffer of `capacity` bytes against their fill; a mismatch is counted, the first one kept
+inline void check(const void* p, uint64_t capacity, const Guard& g) {
+  if (!g.guard) return;
+  std::vector<uint8_t> h(2ull * g.guard);
+  const char* base = (const char*)p - g.guard;
+  bool read = hipDeviceSynchronize() == hipSuccess && hipMemcpy(h.data(), base, g.guard, hipMemcpyDeviceToHost) == hipSuccess &&
+              hipMemcpy(h.data() + g.guard, (const char*)p + capacity, g.guard, hipMemcpyDeviceToHost) == hipSuccess;
+  if (!read) (void)hipGetLastError();
+  std::lock_guard<std::mutex> lk(lock());
+  Tally& t = tally_override() ? *tally_override() : global_tally();
+  ++t.checked;
+  for (uint64_t side = 0; side < 2; ++side)
+    for (uint32_t i = 0; i < g.guard; ++i)
+      if (!read || h[side * g.guard + i] != g.fill) {
+        if (!t.violations) { t.firstBytes = g.asked; t.firstWhere = side << 32 | i; }
+        ++t.violations;
+        break;
+      }
+}
+inline void free_checked(void* p, uint64_t capacity, const Guard& g) {
+  check(p, capacity, g);
+  (void)hipFree((char*)p - g.guard);
+}
+
+// the guarded buffers that DevBuf owns, by the caller's pointer (DevBuf::release() hands a pointer to another DevBuf: the
+// record stays with the pointer); n_registered spares the lock while nothing is guarded
+struct Registered { uint64_t bytes; Guard g; };
+inline std::map<void*, Registered>& registry() { static std::map<void*, Registered> r; return r; }
+inline std::atomic<uint64_t>& n_registered() { static std::atomic<uint64_t> n{0}; return n; }
+inline hipError_t alloc_registered(void** out, uint64_t bytes) {
+  Guard g;
+  const hipError_t e = alloc(out, bytes, g);
+  if (e == hipSuccess && g.guard) {
+    std::lock_guard<std::mutex> lk(lock());
+    registry()[*out] = Registered{bytes, g};
+    n_registered().fetch_add(1);
+  }
+  return e;
+}
+inline void free_registered(void* p) {
+  if (n_registered().load(std::memory_order_relaxed)) {
+    Registered r{0, Guard()};
+    {
+      std::lock_guard<std::mutex> lk(lock());
+      auto it = registry().find(p);
+      if (it != registry().end()) { r = it->second; registry().erase(it); n_registered().fetch_sub(1); }
+    }
+    if (r.g.guard) { free_checked(p, r.bytes, r.g); return; }
+  }
+  (void)hipFree(p);
+}
+
+}  // namespace memcheck
 
 // n elements of hipMalloc memory; move-only.  Which device is current is the caller's business, as with the runtime itself.
 template <typename T>
@@ -28,13 +145,13 @@ class DevBuf {
   // (what was held goes first: the old and the new buffer never exist side by side)
   hipError_t alloc(uint64_t n) {
     reset();
-    const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+    const hipError_t e = memcheck::alloc_registered((void**)&p_, n * sizeof(T));
     if (e != hipSuccess) p_ = nullptr;
     return e;
   }
   T* get() const { return p_; }
   explicit operator bool() const { return p_ != nullptr; }
-  void reset() { if (p_) { (void)hipFree(p_); p_ = nullptr; } }   // free now
+  void reset() { if (p_) { memcheck::free_registered(p_); p_ = nullptr; } }   // free now
   T* release() { T* p = p_; p_ = nullptr; return p; }            // hand over to a longer-lived owner
 };
 
@@ -62,8 +179,9 @@ class PinnedBuf {
 // device buffers of finished batches, kept for the next batch of their context (a streaming run creates and destroys
 // a batch per chunk of reads: ~20 hipMalloc / hipFree pairs each time otherwise)
 struct DevCache {
-  std::vector<std::pair<uint64_t, void*>> pool;   // (bytes, pointer), free
-  std::map<void*, uint64_t> live;                 // pointer -> bytes, handed out
+  struct Buf { uint64_t bytes; void* p; memcheck::Guard g; };
+  std::vector<Buf> pool;          // free
+  std::map<void*, Buf> live;      // by pointer, handed out
   uint64_t pool_bytes = 0;        // bytes cached (free)
   uint64_t live_bytes = 0;        // bytes handed out
   uint64_t peak_live_bytes = 0;   // the largest footprint the batches of this context have had together
@@ -72,43 +190,56 @@ struct DevCache {
   DevCache(const DevCache&) = delete;
   DevCache& operator=(const DevCache&) = delete;
   // (what is still handed out goes too: batches that outlived their context lose their memory with it)
-  ~DevCache() { trim(0); for (auto& e : live) (void)hipFree(e.first); }
+  ~DevCache() { trim(0); for (auto& e : live) memcheck::free_checked(e.first, e.second.bytes, e.second.g); }
 
+  void drop_oldest() {
+    pool_bytes -= pool.front().bytes;
+    memcheck::free_checked(pool.front().p, pool.front().bytes, pool.front().g);
+    pool.erase(pool.begin());
+  }
   // drop cached buffers, oldest first, until the cache holds at most `keep_bytes`
   void trim(uint64_t keep_bytes) {
-    while (!pool.empty() && pool_bytes > keep_bytes) {
-      pool_bytes -= pool.front().first;
-      (void)hipFree(pool.front().second);
-      pool.erase(pool.begin());
-    }
+    while (!pool.empty() && pool_bytes > keep_bytes) drop_oldest();
+  }
+  void hand_out(void** out, const Buf& b) {
+    *out = b.p;
+    live[b.p] = b;
+    live_bytes += b.bytes;
+    peak_live_bytes = std::max(peak_live_bytes, live_bytes);
   }
 
   // a device buffer of at least `bytes` from the cache (smallest cached one that fits and is not more than twice as
-  // large), or a fresh one
+  // large), or a fresh one.  (Test hook: only a cached buffer with the red zones of the current setting fits, and it is
+  // poisoned again, slack included.)
   hipError_t alloc(void** out, uint64_t bytes) {
     bytes = std::max<uint64_t>(bytes, 256);
+    const memcheck::Setting ms = memcheck::setting();
+    const uint32_t guard = ms.on ? ms.guard : 0;
     int best = -1;
     for (int i = 0; i < (int)pool.size(); ++i)
-      if (pool[i].first >= bytes && pool[i].first <= 2 * bytes + 4096 && (best < 0 || pool[i].first < pool[best].first)) best = i;
+      if (pool[i].bytes >= bytes && pool[i].bytes <= 2 * bytes + 4096 && pool[i].g.guard == guard && (best < 0 || pool[i].bytes < pool[best].bytes)) best = i;
     if (best >= 0) {
-      *out = pool[best].second;
-      live[*out] = pool[best].first;
-      live_bytes += pool[best].first;
-      peak_live_bytes = std::max(peak_live_bytes, live_bytes);
-      pool_bytes -= pool[best].first;
+      Buf b = pool[best];
+      if (ms.on) {
+        const hipError_t e = memcheck::repoison(b.p, b.bytes);
+        if (e != hipSuccess) { *out = nullptr; return e; }
+        b.g.asked = bytes;
+        memcheck::count_reuse();
+      }
+      pool_bytes -= b.bytes;
       pool.erase(pool.begin() + best);
+      hand_out(out, b);
       return hipSuccess;
     }
-    if (hipMalloc(out, bytes) != hipSuccess) {
+    memcheck::Guard g;
+    if (memcheck::alloc(out, bytes, g) != hipSuccess) {
       // out of memory: drop the cache and try once more
       (void)hipGetLastError();
       trim(0);
-      const hipError_t e = hipMalloc(out, bytes);
+      const hipError_t e = memcheck::alloc(out, bytes, g);
       if (e != hipSuccess) { *out = nullptr; return e; }   // (nothing is handed out)
     }
-    live[*out] = bytes;
-    live_bytes += bytes;
-    peak_live_bytes = std::max(peak_live_bytes, live_bytes);
+    hand_out(out, Buf{bytes, *out, g});
     return hipSuccess;
   }
 
@@ -116,20 +247,17 @@ struct DevCache {
     if (!p) return;
     auto it = live.find(p);
     if (it == live.end()) { (void)hipFree(p); return; }
-    const uint64_t bytes = it->second;
+    const Buf b = it->second;
     live.erase(it);
-    live_bytes -= bytes;
-    pool.push_back({bytes, p});
-    pool_bytes += bytes;
+    live_bytes -= b.bytes;
+    memcheck::check(b.p, b.bytes, b.g);
+    pool.push_back(b);
+    pool_bytes += b.bytes;
     // a bounded cache, by count and by bytes: what one batch hands back is what the next one of the same shape asks for, so
     // cache + live buffers never need to exceed the largest footprint the batches of this context have had (everybody
     // else who sizes something from hipMemGetInfo — the search scratch, the retry stage, another context on the same GPU,
     // the walk-table decision of an upload — sees cached bytes as used)
-    while (pool.size() > 64) {
-      pool_bytes -= pool.front().first;
-      (void)hipFree(pool.front().second);
-      pool.erase(pool.begin());
-    }
+    while (pool.size() > 64) drop_oldest();
     if (pool_bytes + live_bytes > peak_live_bytes)
       trim(peak_live_bytes > live_bytes ? peak_live_bytes - live_bytes : 0);
   }

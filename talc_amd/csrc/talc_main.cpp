@@ -1128,7 +1128,7 @@ void report(const Clock::time_point t[5], const PipelineTotals& p, const Scan& s
 
 }  // namespace
 
-int main(int argc, const char** argv) {
+static int run(int argc, const char** argv) {
   std::cout << "******************************************************\n"
             << "* TALC : Transcriptome-Aware Long Read Correction    *\n"
             << "*----------------------------------------------------*\n"
@@ -1137,7 +1137,8 @@ int main(int argc, const char** argv) {
             << "******************************************************" << std::endl;
   std::cout << "[TALC]: Parsing arguments" << std::endl;
   Options o = parse(argc, argv);
-  const talc::Switches sw = talc::read_switches();   // (TALC_TIMING, TALC_FAKE_GPUS)
+  const talc::Switches sw = talc::read_switches();   // (TALC_TIMING, TALC_FAKE_GPUS, TALC_TEST_POISON)
+  if (sw.poisonByte >= 0 && talc_test_set_poison(sw.poisonByte, sw.poisonGuard) != TALC_OK) { std::cerr << "talc: " << talc_last_error() << "\n"; return 2; }
   const Files files(o.outPrefix);
   outputConfig(o, files.stats);          // Settings.cpp:122
   setBasicReadStatsHeader(files.stats);  // main.cpp:204
@@ -1208,4 +1209,19 @@ int main(int argc, const char** argv) {
     fprintf(stderr, "[talc-lib] base support: %llu batches, k_base_support %.3f ms\n", (unsigned long long)totals.batches, totals.workers.supportMs);
   report(t, totals, scan, o.batchReads, ndev, pipeline.workers());
   return 0;
+}
+
+// (the table and the contexts are gone when run() has returned: their buffers' red zones have been checked)
+int main(int argc, const char** argv) {
+  const int ec = run(argc, argv);
+  int byte = -1;
+  uint32_t guard = 0;
+  talc_test_get_poison(&byte, &guard);
+  if (byte < 0) return ec;
+  uint64_t r[4] = {0, 0, 0, 0};
+  talc_test_guard_report(r);
+  fprintf(stderr, "[talc-poison] byte %d, red zones of %u bytes: %llu buffers checked, %llu violations", byte, guard, (unsigned long long)r[0], (unsigned long long)r[1]);
+  if (r[1]) fprintf(stderr, "; the first at a buffer of %llu bytes, %s it, byte %llu of the red zone", (unsigned long long)r[2], (r[3] >> 32) ? "behind" : "in front of", (unsigned long long)(r[3] & 0xFFFFFFFFull));
+  fprintf(stderr, "\n");
+  return r[1] ? 3 : ec;
 }

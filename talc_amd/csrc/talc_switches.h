@@ -27,6 +27,8 @@ struct Switches {
   bool edgeLane = true;         // TALC_TEST_EDGE_LANE=0: an edge search never enters the fused walk-and-score lane
   bool traceSteps = false;      // TALC_TRACE_STEPS: talc_batch_trace_read records every step
   uint32_t fakeGpus = 0;        // TALC_FAKE_GPUS (the CLI): the sharder runs as on a node with this many GPUs (0: the real count)
+  int poisonByte = -1;          // TALC_TEST_POISON=<byte>[,<guard>] (the CLI): talc_test_set_poison at startup, the guard report at exit
+  uint32_t poisonGuard = 256;
   std::string profReads;        // TALC_PROF_READS (the profile build): a file of one row per read
   bool profPrint = false, profSlow = false;   // TALC_PROF_PRINT, TALC_PROF_SLOW (the profile build): its reports on stderr
 };
@@ -54,6 +56,14 @@ inline Switches read_switches() {
   s.edgeLane = num("TALC_TEST_EDGE_LANE", 1) != 0;
   s.traceSteps = num("TALC_TRACE_STEPS", 0) != 0;
   s.fakeGpus = clamped("TALC_FAKE_GPUS", 0, 0, 1L << 20);
+  if (const char* e = std::getenv("TALC_TEST_POISON")) {
+    char* end = nullptr;
+    const long b = std::strtol(e, &end, 10);
+    if (end != e && b >= 0 && b <= 255) {
+      s.poisonByte = (int)b;
+      if (*end == ',') { const unsigned long g = std::strtoul(end + 1, nullptr, 10); if (g % 256 == 0 && g <= (1ul << 20)) s.poisonGuard = (uint32_t)g; }
+    }
+  }
   if (const char* e = std::getenv("TALC_PROF_READS")) s.profReads = e;
   s.profPrint = given("TALC_PROF_PRINT");
   s.profSlow = given("TALC_PROF_SLOW");

@@ -3,6 +3,7 @@
 There is no CPU fallback: every compute entry point needs a MI355X and fails loudly
 (TalcError) without one.  Loading the library and resolving its symbols works on any host.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -42,6 +43,7 @@ ABI_SYMBOLS = [
     "talc_test_batch_edits", "talc_test_parse_text",
     "talc_ctx_set_auto_strand", "talc_batch_strand", "talc_batch_fetch_strand", "talc_ctx_get_strand_timing",
     "talc_batch_support", "talc_batch_support_bytes", "talc_batch_fetch_support", "talc_ctx_get_support_timing",
+    "talc_test_set_poison", "talc_test_get_poison", "talc_test_guard_report", "talc_test_cache_reuses", "talc_test_guard_selftest",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -237,6 +239,13 @@ def lib():
             L.talc_batch_support_bytes.argtypes = [vp]
             L.talc_batch_fetch_support.argtypes = [vp, vp, vp, u64, vp]
             L.talc_ctx_get_support_timing.argtypes = [vp, vp]
+        if hasattr(L, "talc_test_set_poison"):
+            L.talc_test_set_poison.argtypes = [i32, u32]
+            L.talc_test_get_poison.argtypes = [vp, vp]
+            L.talc_test_guard_report.argtypes = [vp]
+            L.talc_test_cache_reuses.restype = u64
+            L.talc_test_cache_reuses.argtypes = []
+            L.talc_test_guard_selftest.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -263,6 +272,44 @@ def default_params(**kw):
 
 def device_count():
     return int(lib().talc_device_count())
+
+
+def poison_setting():
+    """Test hook: (byte, guard bytes) of the poison setting as it is now; byte is -1 when it is off."""
+    b, g = C.c_int(), C.c_uint32()
+    _chk(lib().talc_test_get_poison(C.byref(b), C.byref(g)))
+    return b.value, g.value
+
+
+@contextlib.contextmanager
+def poisoned(byte, guard=256):
+    """Test hook: inside the block every device buffer the library hands out is filled with `byte` (0 .. 255) and sits between
+    red zones of `guard` bytes (a multiple of 256) that are checked when it is given back (guard_report()).  Process-wide;
+    always switched off again."""
+    _chk(lib().talc_test_set_poison(int(byte), int(guard)))
+    try:
+        yield
+    finally:
+        _chk(lib().talc_test_set_poison(-1, 0))
+
+
+def guard_report():
+    """Test hook: what the red-zone checks have seen since the library was loaded: dict of checked, violations, first_bytes,
+    first_side (0 in front of the buffer, 1 behind it), first_offset, and reused (requests a context's cache served with a
+    buffer used before, while the setting was on)."""
+    r = np.zeros(4, dtype=np.uint64)
+    _chk(lib().talc_test_guard_report(r.ctypes.data))
+    return dict(checked=int(r[0]), violations=int(r[1]), first_bytes=int(r[2]), first_side=int(r[3]) >> 32,
+                first_offset=int(r[3]) & 0xFFFFFFFF, reused=int(lib().talc_test_cache_reuses()))
+
+
+def guard_selftest():
+    """Test hook (needs a GPU, inside poisoned()): dict of fills (15: every byte read back as specified), violations (2) and
+    the (side, offset) of the two it caused: behind the first buffer, in front of the second."""
+    r = np.zeros(4, dtype=np.uint64)
+    _chk(lib().talc_test_guard_selftest(r.ctypes.data))
+    where = [(int(x) >> 32, int(x) & 0xFFFFFFFF) for x in r[2:]]
+    return dict(fills=int(r[0]), violations=int(r[1]), behind=where[0], in_front=where[1])
 
 
 def parse_text_hook(path, k, min_count=2, where=1, device=0, chunk_bytes=32 << 20, reader_threads=8, arrays=True):

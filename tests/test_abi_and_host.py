@@ -55,6 +55,38 @@ def test_device_memory_has_one_owner_and_one_way_to_fail():
             assert idiom not in text[f], (f, idiom)
 
 
+def test_poison_hooks_are_exported_and_take_only_what_the_header_allows():
+    L = T.lib()
+    for sym in ("talc_test_set_poison", "talc_test_get_poison", "talc_test_guard_report", "talc_test_cache_reuses", "talc_test_guard_selftest"):
+        assert hasattr(L, sym) and sym in T.ABI_SYMBOLS, sym
+    assert T.poison_setting() == (-1, 0)
+    for byte, guard in ((-2, 0), (256, 256), (0, 100), (0, 255), (0, (1 << 20) + 256)):
+        assert L.talc_test_set_poison(byte, guard) == -1 and T.poison_setting() == (-1, 0), (byte, guard)      # TALC_ERR_INVALID
+    before = T.guard_report()
+    try:
+        assert L.talc_test_set_poison(0xA5, 512) == 0 and T.poison_setting() == (0xA5, 512)
+        assert L.talc_test_set_poison(0, 0) == 0 and T.poison_setting() == (0, 0)                              # poison without red zones
+    finally:
+        assert L.talc_test_set_poison(-1, 4096) == 0
+    assert T.poison_setting() == (-1, 0) and T.guard_report() == before
+
+
+def test_poisoned_switches_off_again_when_its_body_raises():
+    assert T.poison_setting() == (-1, 0)
+    with pytest.raises(ZeroDivisionError):
+        with T.poisoned(0xFF):
+            assert T.poison_setting() == (0xFF, 256)
+            1 // 0
+    assert T.poison_setting() == (-1, 0)
+    with T.poisoned(0x35, guard=1024):
+        assert T.poison_setting() == (0x35, 1024)
+    assert T.poison_setting() == (-1, 0)
+    with pytest.raises(T.TalcError):                     # a setting the library refuses switches nothing on
+        with T.poisoned(300):
+            pass
+    assert T.poison_setting() == (-1, 0)
+
+
 def test_params_default_match_reference_defaults():
     p = T.default_params()
     q = O.params()

@@ -13,6 +13,7 @@ import parity_util as PU
 import solidity_ref as S
 import strand_ref as R
 import test_gpu_solidity as G
+from memcheck_util import everything   # (every output of a corrected batch, per read; shared with test_gpu_poison.py)
 from talc_amd import build as B
 from talc_amd import lib as T
 from talc_amd.synth import Synth
@@ -246,39 +247,6 @@ def test_rc_probes_follow_a_chain_across_the_end_of_the_table():
 
 
 # ---------------------------------------------------------------- 2. equivalence with the two fixed contexts
-def everything(ctx, reads):
-    """Everything a corrected batch gives, per read: a list of tuples of bytes and integers."""
-    ctx.record_map(True)
-    b = ctx.batch(*G.pack_reads(reads))
-    try:
-        rc = b.correct()
-        t = ctx.timing()
-        work = (rc, t.n_trail_steps, t.n_dp_cells, t.n_kmers, t.n_bases, t.n_retried, t.n_failed)
-        out, oo, st = b.fetch_corrected()
-        msk = b.fetch_corrected(soft_mask=True)[0]
-        out, msk = bytes(out), bytes(msk)
-        segs, so = b.fetch_map()
-        raw, cor = b.solidity()
-        pieces = []
-        for mode, mask in ((T.PIECES_TRIM, True), (T.PIECES_TRIM, False), (T.PIECES_SPLIT, False)):
-            pb, po, pc, rpo = b.pieces(mode, 0, mask)
-            pieces.append((bytes(pb), po, pc, rpo))
-        ops, eo, erows = b.edits()
-        stats = b.fetch_read_stats()
-        per = []
-        for r in range(len(reads)):
-            rec = (out[int(oo[r]):int(oo[r + 1])], int(st[r]), msk[int(oo[r]):int(oo[r + 1])], segs[int(so[r]):int(so[r + 1])].tobytes(),
-                   raw[r].tolist(), cor[r].tolist(), ops[int(eo[r]):int(eo[r + 1])].tobytes(), erows[r].tolist(), stats[r].tolist())
-            for pb, po, pc, rpo in pieces:
-                a, e = int(rpo[r]), int(rpo[r + 1])
-                rec += (tuple(pb[int(po[i]):int(po[i + 1])] for i in range(a, e)), pc[a:e].tobytes())
-            per.append(rec)
-        return per, work, b.strand() if ctx._auto else None
-    finally:
-        b.close()
-        ctx.record_map(False)
-
-
 _three = {}
 
 
