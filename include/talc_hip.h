@@ -99,7 +99,7 @@ void talc_pinned_free(void* p);
 /* ---------------------------------------------------------------- (1) table surface ------
  * Replaces  colouredDBG buildCDBG(int, string& dump, string& junctionDump)   Jellyfish.cpp:236-295
  *           void decolourRepeatsFromDBG(colouredDBG&, K)                     utils.cpp:658-669
- * k-mers are directional (non-canonical, main.cpp:89).  Packed k-mers are 2 bits per base
+ * k-mers are directional (non-canonical, main.cpp:89) unless a table is built on both strands, (1c).  Packed k-mers are 2 bits per base
  * (A=0,C=1,G=2,T=3), first base in the most significant position of the 2K-bit value. */
 
 /* Parse a `jellyfish dump -c` text file ("KMER count" per line, whitespace separated,
@@ -211,6 +211,33 @@ int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uin
  * afterwards: only talc_counter_destroy may follow. */
 int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]);
 void talc_counter_destroy(talc_counter* c);
+
+/* ---------------------------------------------------------------- (1c) both strands ------
+ * For short reads that are not forward-stranded, and for `jellyfish count -C` counts (docs/both_strands.md).  rc(x) is
+ * the reverse complement of a packed k-mer, canon(x) = min(x, rc(x)) as unsigned integers (A<C<G<T, Jellyfish's -C).
+ * The folded count C(y) of a canonical k-mer y is the sum of the counts of every observation whose canonical form is y:
+ * a window of a read counts once (a palindromic window too), a counted k-mer `x c` adds c to C(canon(x)), lines of the
+ * same k-mer ADD UP (the one deliberate difference from the directional route's first-line-wins), a count of 0 adds
+ * nothing.  The table stores, for every y with C(y) >= min_count, y and rc(y) with count C(y) (a palindrome once): an
+ * ordinary talc_table, as talc_table_from_arrays_device makes from those entries.  The fold runs on the GPU; there is no
+ * host fold: without a GPU these calls fail with TALC_ERR_DEVICE, like the counter. */
+/* before the first add / add_counts; TALC_ERR_STATE afterwards or on a spent counter.  A both-strands counter keys every
+ * window by canon(x): talc_counter_fetch returns canonical k-mers, talc_counter_stats {windows + entries added, distinct
+ * canonical k-mers, canonical k-mers with C >= min_count}, talc_counter_build_table stores both strands of the latter
+ * (stats = {distinct canonical k-mers, k-mers stored in the table, malformed junction lines}). */
+int talc_counter_set_both_strands(talc_counter* c, int on);
+/* counted k-mers (host arrays) into the counter: a directional counter adds counts[i] to kmers[i], a both-strands counter to
+ * canon(kmers[i]); may be mixed with talc_counter_add; a k-mer wider than 2K bits is TALC_ERR_INVALID.  An entry with
+ * count 0 adds nothing and is not among the "entries added" of talc_counter_stats.  Returns when the entries are in. */
+int talc_counter_add_counts(talc_counter* c, const uint64_t* kmers, const uint32_t* counts, uint64_t n);
+/* talc_table_build_device / talc_table_from_arrays_device on both strands: a both-strands counter fed by
+ * talc_counter_add_counts, then its table.  MIN_COUNT applies to the folded sum.  The text dump is parsed on the device
+ * when talc_table_build_device would parse it there, else by the host's tokeniser or the .jf reader.  stats (may be
+ * NULL) = {lines read, k-mers stored in the table, malformed lines}. */
+int talc_table_build_device_both_strands(const char* dump_path, const char* junction_path, const talc_params* p,
+                                         int device, talc_table** out, int64_t stats[3]);
+int talc_table_from_arrays_device_both_strands(const uint64_t* kmers, const uint32_t* counts, uint64_t n,
+                                               const talc_params* p, int device, talc_table** out);
 
 /* ---------------------------------------------------------------- (2) per-read surface ---
  * Replaces, for a whole batch, the loop body of main.cpp:247-308:

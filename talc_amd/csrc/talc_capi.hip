@@ -1219,7 +1219,9 @@ int talc_batch_fetch_coverage_degrees(talc_ctx* c, talc_batch* b, uint8_t* degre
 // caller's records into one of two page-locked staging buffers (one separator byte after each record), queues the copy
 // to the device and the count kernel, and returns.  The hash grows before a batch whose windows could push it past load
 // 0.7: the host keeps an upper bound of the distinct k-mers (the exact number at the last synchronisation plus every
-// window queued since) and reads the exact number back only when that bound says the batch might not fit.
+// window queued since) and reads the exact number back only when that bound says the batch might not fit.  A both-strands
+// counter (docs/both_strands.md) keys everything by the canonical k-mer and expands the kept ones to both strands when
+// the table is built.
 struct talc_counter {
   talc_params p;
   int device = 0;
@@ -1240,6 +1242,9 @@ struct talc_counter {
   uint64_t winsSince = 0;       // windows (upper bound) queued since then
   uint64_t winsTotal = 0;       // windows (upper bound) over every batch: counts cannot pass it
   bool spent = false;
+  bool bothStrands = false;     // keys are canon(x); the table gets y and rc(y) (talc_counter_set_both_strands)
+  bool started = false;         // something has been added: the mode is fixed
+  bool countsAdded = false;     // talc_counter_add_counts was used: a count no longer stays below the windows counted
   // TALC_TIMING
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
   uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
@@ -1265,12 +1270,15 @@ static int counter_sync(talc_counter* c, unsigned long long st[2]) {
   return TALC_OK;
 }
 
-// slots with count >= thr: how many (outK == nullptr) or the arrays themselves (device pointers of outCap entries)
-static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32_t* outC, uint64_t outCap, uint64_t* n) {
+// slots with count >= thr: how many (outK == nullptr) or the arrays themselves (device pointers of outCap entries);
+// expand: both strands of every kept (canonical) k-mer, *n = 2 * kept - palindromes
+static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32_t* outC, uint64_t outCap, uint64_t* n, bool expand = false) {
   HIPCHK(hipMemsetAsync(c->dStats.get() + 2, 0, 8, c->stream));
-  if (c->cap)
-    hipLaunchKernelGGL(k_count_compact, dim3((unsigned)((c->cap + 4 * 64 * kCompactRows - 1) / (4 * 64 * kCompactRows))), dim3(256), 0,
-                       c->stream, c->tab.get(), c->cap, thr, outK, outC, outCap, c->dStats.get() + 2);
+  const dim3 grid((unsigned)((c->cap + 4 * 64 * kCompactRows - 1) / (4 * 64 * kCompactRows)));
+  if (c->cap && expand)
+    hipLaunchKernelGGL(k_count_compact<true>, grid, dim3(256), 0, c->stream, c->tab.get(), c->cap, thr, c->p.k, outK, outC, outCap, c->dStats.get() + 2);
+  else if (c->cap)
+    hipLaunchKernelGGL(k_count_compact<false>, grid, dim3(256), 0, c->stream, c->tab.get(), c->cap, thr, c->p.k, outK, outC, outCap, c->dStats.get() + 2);
   HIPCHK(hipGetLastError());
   unsigned long long v = 0;
   HIPCHK(hipMemcpyAsync(&v, c->dStats.get() + 2, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1340,6 +1348,7 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   if (!c || (n_reads && (!bases || !offsets))) return fail(TALC_ERR_INVALID, "null argument");
   if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
   if (!n_reads) return TALC_OK;
+  c->started = true;
   const uint32_t K = c->p.k;
   const uint64_t o0 = offsets[0];
   uint64_t wins = 0;
@@ -1394,7 +1403,7 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   HIPCHK(hipEventRecord(c->stageEv[b], c->stream));
   c->stageBusy[b] = true;
   c->winsTotal += wins;
-  const bool checked = c->winsTotal >= 0xFFFFFFFFull;   // below that no count can reach 2^32
+  const bool checked = c->countsAdded || c->winsTotal >= 0xFFFFFFFFull;   // below that no count can reach 2^32
   const uint64_t nblk = (nbytes + kCountTile - 1) / kCountTile;
   if (nblk >= (1ull << 31)) return fail(TALC_ERR_INVALID, "batch of %llu bytes is too large", (unsigned long long)nbytes);
   std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
@@ -1403,18 +1412,66 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
     else { if (ev.first) hipEventDestroy(ev.first); ev = {nullptr, nullptr}; }
   }
   if (ev.second) HIPCHK(hipEventRecord(ev.first, c->stream));
-  if (checked)
-    hipLaunchKernelGGL(k_count_batch<true>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText.get(), nbytes, K, c->tab.get(),
-                       c->cap - 1, c->dStats.get(), c->dOverflow.get());
-  else
-    hipLaunchKernelGGL(k_count_batch<false>, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText.get(), nbytes, K, c->tab.get(),
-                       c->cap - 1, c->dStats.get(), c->dOverflow.get());
+  auto* const kernel = c->bothStrands ? (checked ? k_count_batch<true, true> : k_count_batch<false, true>)
+                                      : (checked ? k_count_batch<true, false> : k_count_batch<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, c->dText.get(), nbytes, K, c->tab.get(), c->cap - 1,
+                     c->dStats.get(), c->dOverflow.get());
   HIPCHK(hipGetLastError());
   if (ev.second) HIPCHK(hipEventRecord(ev.second, c->stream));
   c->winsSince += wins;
   ++c->nBatches;
   c->nBytes += nbytes;
   return TALC_OK;
+}
+
+int talc_counter_set_both_strands(talc_counter* c, int on) {
+  if (!c) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (c->started) return fail(TALC_ERR_STATE, "the counter already holds k-mers: the strand mode is chosen before the first add");
+  c->bothStrands = on != 0;
+  return TALC_OK;
+}
+
+// n counted k-mers as device arrays into the hash (k_count_add_counts); the arrays may be freed on return.  Growth as for
+// a batch of n windows: every entry may be a new key.
+static int counter_add_counts_device(talc_counter* c, const uint64_t* dK, const uint32_t* dC, uint64_t n) {
+  if (!n) return TALC_OK;
+  c->started = true;
+  c->countsAdded = true;
+  HIPCHK(hipSetDevice(c->device));
+  if ((double)(c->distinctKnown + c->winsSince + n) > 0.7 * (double)c->cap) {
+    unsigned long long st[2];
+    int rc = counter_sync(c, st);
+    if (rc) return rc;
+    if ((double)(c->distinctKnown + n) > 0.7 * (double)c->cap && (rc = counter_grow(c, c->distinctKnown + n))) return rc;
+  }
+  const uint64_t nblk = (n + kCountThreads - 1) / kCountThreads;
+  if (nblk >= (1ull << 31)) return fail(TALC_ERR_INVALID, "%llu counted k-mers are too many for one call", (unsigned long long)n);
+  auto* const kernel = c->bothStrands ? k_count_add_counts<true> : k_count_add_counts<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(kCountThreads), 0, c->stream, dK, dC, n, c->p.k, c->tab.get(), c->cap - 1, c->dStats.get(),
+                     c->dOverflow.get());
+  HIPCHK(hipGetLastError());
+  c->winsSince += n;
+  HIPCHK(hipStreamSynchronize(c->stream));   // (the caller's arrays are read until here)
+  return TALC_OK;
+}
+
+int talc_counter_add_counts(talc_counter* c, const uint64_t* kmers, const uint32_t* counts, uint64_t n) {
+  if (!c || (n && (!kmers || !counts))) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (!n) return TALC_OK;
+  const uint64_t wide = ~((1ULL << (2 * c->p.k)) - 1);
+  uint64_t nWide = 0;
+#pragma omp parallel for reduction(+ : nWide) if (n > 1000000)
+  for (long i = 0; i < (long)n; ++i) nWide += (kmers[i] & wide) ? 1 : 0;
+  if (nWide) return fail(TALC_ERR_INVALID, "%llu of the counted k-mers are wider than 2 K = %u bits", (unsigned long long)nWide, 2 * c->p.k);
+  HIPCHK(hipSetDevice(c->device));
+  DevBuf<uint64_t> dK;
+  DevBuf<uint32_t> dC;
+  if (dK.alloc(n) != hipSuccess || dC.alloc(n) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu counted k-mers on the device", (unsigned long long)n); }
+  HIPCHK(hipMemcpy(dK.get(), kmers, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dC.get(), counts, n * 4, hipMemcpyHostToDevice));
+  return counter_add_counts_device(c, dK.get(), dC.get(), n);
 }
 
 int talc_counter_stats(talc_counter* c, uint64_t stats[3]) {
@@ -1452,22 +1509,26 @@ int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uin
   return TALC_OK;
 }
 
-int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]) {
-  if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
-  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+// The counter's table.  lines: the build-from-a-file callers' {lines read, -, malformed lines} (nullptr: the distinct
+// k-mers are the "lines read"); finish false: no colouring, no de-colouring (the from_arrays builders).
+static int counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3], const DumpStats* lines, bool finish) {
   Stopwatch watch;
   unsigned long long st[2];
   int rc = counter_sync(c, st);
   if (rc) return rc;
   const double tWait = watch.lap();
-  uint64_t kept = 0;
-  if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept))) return rc;
-  if (kept >= 0xFFFFFFFEull) return fail(TALC_ERR_INVALID, "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
+  uint64_t kept = 0;   // entries for the builder: both strands of every kept k-mer of a both-strands counter
+  const bool expand = c->bothStrands;
+  if ((rc = counter_compact(c, c->p.min_count, nullptr, nullptr, 0, &kept, expand))) return rc;
+  if (kept >= 0xFFFFFFFEull)
+    return fail(TALC_ERR_INVALID, expand ? "%llu k-mers (both strands of those that reach MIN_COUNT) are too many: the device builder takes fewer than 2^32-2"
+                                         : "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
   DevBuf<uint64_t> dK;
   DevBuf<uint32_t> dC;
   if (dK.alloc(std::max<uint64_t>(kept, 1)) != hipSuccess || dC.alloc(std::max<uint64_t>(kept, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the %llu kept k-mers", (unsigned long long)kept); }
   uint64_t got = 0;
-  if ((rc = counter_compact(c, c->p.min_count, dK.get(), dC.get(), kept, &got))) return rc;
+  if ((rc = counter_compact(c, c->p.min_count, dK.get(), dC.get(), kept, &got, expand))) return rc;
+  if (got != kept) return fail(TALC_ERR_STATE, "the counter changed between two compactions (%llu, %llu)", (unsigned long long)kept, (unsigned long long)got);
   // the hash goes before the builder allocates its buckets; the counter is spent from here on
   c->tab.reset(); c->cap = 0;
   c->dText.reset(); c->dTextCap = 0;
@@ -1485,9 +1546,80 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
   TablePtr t;
   if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, t, 0.0, 0.0, c->sw))) return rc;
   DumpStats ds;
-  ds.nread = (int64_t)st[1];
+  ds.nread = lines ? lines->nread : (int64_t)st[1];
   ds.nkept = (int64_t)kept;
-  return table_finish(std::move(t), junction_path, &c->p, ds, out, stats);
+  ds.nbad = lines ? lines->nbad : 0;
+  if (finish) return table_finish(std::move(t), junction_path, &c->p, ds, out, stats);
+  if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
+  *out = t.release();
+  return TALC_OK;
+}
+
+int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]) {
+  if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  return counter_build_table(c, junction_path, out, stats, nullptr, true);
+}
+
+// ------------------------------------------------------------------ both strands from counted k-mers (docs/both_strands.md)
+// A both-strands counter fed by add_counts, then its table: the fold is a sum per canonical k-mer on the device, MIN_COUNT
+// applies to the sum.  There is no host fold.
+struct CounterOwner { talc_counter* c = nullptr; ~CounterOwner() { talc_counter_destroy(c); } };
+
+int talc_table_from_arrays_device_both_strands(const uint64_t* kmers, const uint32_t* counts, uint64_t n, const talc_params* p, int device,
+                                               talc_table** out) {
+  if (!out || (n && (!kmers || !counts))) return fail(TALC_ERR_INVALID, "null argument");
+  CounterOwner own;
+  int rc;
+  if ((rc = talc_counter_create(p, device, 0, &own.c))) return rc;
+  own.c->bothStrands = true;
+  if ((rc = talc_counter_add_counts(own.c, kmers, counts, n))) return rc;
+  return counter_build_table(own.c, nullptr, out, nullptr, nullptr, false);
+}
+
+int talc_table_build_device_both_strands(const char* dump_path, const char* junction_path, const talc_params* p, int device, talc_table** out,
+                                         int64_t stats[3]) {
+  if (!dump_path || !out) return fail(TALC_ERR_INVALID, "null argument");
+  CounterOwner own;
+  int rc;
+  if ((rc = talc_counter_create(p, device, 0, &own.c))) return rc;
+  own.c->bothStrands = true;
+  const Switches sw = own.c->sw;
+  Stopwatch watch;
+  DumpStats ds;
+  struct stat sb;
+  if (stat(dump_path, &sb) != 0) return fail(TALC_ERR_IO, "cannot open %s", dump_path);
+  const uint64_t size = (uint64_t)sb.st_size;
+  bool onDevice = false;
+  if (size >= (8u << 20) && !sw.hostParse) {   // the text parsed on the device, as table_from_text_on_device takes it
+    char head[64] = {0};
+    FILE* f = fopen(dump_path, "rb");
+    if (!f) return fail(TALC_ERR_IO, "cannot open %s", dump_path);
+    const size_t got = fread(head, 1, sizeof head, f);
+    fclose(f);
+    DevBuf<uint8_t> dText;
+    ParsedText parsed;
+    int T = 0;
+    if (!jfLooksLike(head, got) && text_to_device(dump_path, size, kDumpChunkBytes, kDumpReaders, device, dText, &T) == 0 &&
+        parse_device_text(dText.get(), size, p->k, p->min_count, parsed) == 0 && parsed.stats.flags == 0) {
+      dText.reset();
+      if ((rc = counter_add_counts_device(own.c, parsed.kmers.get(), parsed.counts.get(), parsed.nlines))) return rc;
+      ds.nread = (int64_t)parsed.nlines;
+      onDevice = true;
+    }
+  }
+  if (!onDevice) {   // the host's tokeniser or the .jf reader, every line whatever its count
+    std::vector<uint64_t> kmers;
+    std::vector<uint32_t> counts;
+    std::string why;
+    if (!parseDumpFile(dump_path, p->k, p->min_count, false, kmers, &counts, nullptr, ds, &why))
+      return why.empty() ? fail(TALC_ERR_IO, "cannot open %s", dump_path) : fail(TALC_ERR_INVALID, "%s", why.c_str());
+    if ((rc = talc_counter_add_counts(own.c, kmers.data(), counts.data(), kmers.size()))) return rc;
+  }
+  if (sw.timing)
+    fprintf(stderr, "[talc-lib] both strands: %llu lines of %s folded on the device in %.3f s (text parsed on the %s)\n", (unsigned long long)ds.nread,
+            dump_path, watch.seconds(), onDevice ? "device" : "host");
+  return counter_build_table(own.c, junction_path, out, stats, &ds, true);
 }
 
 void talc_counter_destroy(talc_counter* c) {

@@ -38,6 +38,9 @@
 //   --SRReads FILE   (repeatable, instead of -SR) short reads, FASTA or FASTQ: their k-mers are counted on the GPU
 //                    (talc_counter_*, docs/kmer_counting.md) in place of `jellyfish count` + `dump -c` (README.md:37-49)
 //   --SRCountsOut F  with --SRReads: the kept k-mers as `jellyfish dump -c` text, for a later -SR F
+//   --both-strands   the k-mer table holds the short reads' support on either strand (docs/both_strands.md): --SRReads
+//                    counts canonical k-mers, -SR folds the counts (a `jellyfish count -C` dump, or a directional one) over
+//                    reverse complements on the GPU, and every kept k-mer is stored with its reverse complement
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -114,6 +117,7 @@ struct Options {
   bool corrEdits = false;                   // --corr-edits
   uint64_t maxEditCells = 0;                // --max-edit-cells (0: the library's default)
   bool autoStrand = false;                  // --auto-strand
+  bool bothStrands = false;                 // --both-strands
   bool fastq = false, haveQualRange = false;   // --fastq, --qual-range
   uint32_t qmin = 2, qmax = 40;
 };
@@ -129,6 +133,10 @@ void usage(FILE* f) {
           "  --SRReads TEXT              short reads (FASTA or FASTQ; repeat for several files): their k-mers are counted on\n"
           "                              the GPU instead of read from -SR (every window of K ACGT bases of a record, directional)\n"
           "  --SRCountsOut TEXT          with --SRReads: write the kept k-mers as `jellyfish dump -c` text (usable as -SR)\n"
+          "  --both-strands              take the k-mers on both strands (unstranded short reads, `jellyfish count -C` counts):\n"
+          "                              counts are summed over a k-mer and its reverse complement on the GPU, MIN_COUNT applies\n"
+          "                              to the sum and both are stored; --SRCountsOut then writes the canonical k-mers (not with\n"
+          "                              --auto-strand; docs/both_strands.md)\n"
           "  -j, --junctions TEXT        k-mers flanking junctions and their counts\n"
           "  -jf2, --pathToJF2 TEXT      directory of the jellyfish program: -qm jellyfish2 then reads the .jf through\n"
           "                              `jellyfish dump` (without it: the native .jf reader)\n"
@@ -220,6 +228,7 @@ Options parse(int argc, const char** argv) {
     else if (a == "--corr-edits") o.corrEdits = true;
     else if (a == "--max-edit-cells") { double v = num(need(i), "max-edit-cells"); range(v, 1, 9e18, "max-edit-cells"); o.maxEditCells = (uint64_t)v; }
     else if (a == "--auto-strand") o.autoStrand = true;
+    else if (a == "--both-strands") o.bothStrands = true;
     else if (a == "--fastq") o.fastq = true;
     else if (a == "--qual-range") {
       const std::string v = need(i);
@@ -246,6 +255,8 @@ Options parse(int argc, const char** argv) {
   if (!o.srCountsOut.empty() && o.srReads.empty()) parse_error("--SRCountsOut needs --SRReads");
   if (o.haveQualRange && !o.fastq) parse_error("--qual-range needs --fastq");
   if (o.autoStrand && o.p.reverse) parse_error("--auto-strand chooses every read's orientation: it does not go with -rev");
+  if (o.bothStrands && o.autoStrand)
+    parse_error("--both-strands makes the k-mer table symmetric, so every vote of --auto-strand is a tie: they do not go together");
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
 }
@@ -261,7 +272,9 @@ void outputConfig(const Options& o, const std::string& statFile) {
     << "****************************" << "\n"
     << "KmerSize=" << o.p.k << "\n"
     << "Junction mode activated? " << (o.useJ ? 1 : 0) << "\n"
-    << "queryMode=" << o.queryMode << "\n"
+    << "queryMode=" << o.queryMode << "\n";
+  if (o.bothStrands) f << "Both strands? 1" << "\n";
+  f
     << "****************************" << "\n"
     << "MIN_INNER_SCORE=" << o.p.min_inner_score << "\n"
     << "MIN_BORDER_SCORE=" << o.p.min_border_score << "\n"
@@ -334,6 +347,7 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
   talc_counter* ctr = nullptr;
   if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) return libError();
   struct Guard { talc_counter*& c; ~Guard() { talc_counter_destroy(c); } } guard{ctr};
+  if (o.bothStrands && talc_counter_set_both_strands(ctr, 1) != TALC_OK) return libError();
   const size_t kBatchBytes = 64u << 20;
   std::string buf;
   std::vector<uint64_t> offs{0};
@@ -377,7 +391,7 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
   nBytes += buf.size();
   if (!flush()) return libError();
   const auto t1 = Clock::now();
-  if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers
+  if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers (--both-strands: of the canonical ones, as after count -C)
     uint64_t n = 0;
     if (talc_counter_fetch(ctr, o.p.min_count, nullptr, nullptr, 0, &n) != TALC_OK) return libError();
     std::vector<uint64_t> km(std::max<uint64_t>(n, 1));
@@ -1042,7 +1056,8 @@ int prepareCounts(Options& o, TmpDumps& tmp, bool& haveTable) {
     const std::string sr = o.outPrefix + ".SRCounts.dump.tmp", jn = o.outPrefix + ".junctions.dump.tmp";
     std::cout << "[TALC]: jellyfish2 mode: " << o.jf2 << "/jellyfish dump of " << o.dump << std::endl;
     tmp.files.push_back(sr);
-    bool ok = jellyfishDump(o.jf2, o.dump, o.p.min_count, sr, why);
+    // (--both-strands: MIN_COUNT applies to the folded sum, so the tool must not drop a line)
+    bool ok = jellyfishDump(o.jf2, o.dump, o.bothStrands ? 1 : o.p.min_count, sr, why);
     if (ok && o.useJ) { tmp.files.push_back(jn); ok = jellyfishDump(o.jf2, o.jdump, 0, jn, why); }
     if (!ok) { std::cerr << "talc: " << why << "\n"; return 2; }
     o.dump = sr;
@@ -1069,9 +1084,12 @@ int buildTable(const Options& o, const talc::Switches& sw, TablePtr& table, uint
     else std::cout << "[TALC]: Building the SR-dBG from count file: " << o.dump << std::endl;
     // the insert loop of buildCDBG runs on the first GPU when there is one (same table, ~10x faster on a 50 M dump)
     talc_table* built = nullptr;
-    rc = (talc_device_count() > 0)
-             ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &built, st)
-             : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &built, st);
+    if (o.bothStrands)   // folded on the GPU; there is no host fold
+      rc = talc_table_build_device_both_strands(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &built, st);
+    else
+      rc = (talc_device_count() > 0)
+               ? talc_table_build_device(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, 0, &built, st)
+               : talc_table_build(o.dump.c_str(), o.useJ ? o.jdump.c_str() : nullptr, &o.p, &built, st);
     table.reset(built);
   }
   if (rc != TALC_OK) {
@@ -1129,11 +1147,13 @@ void report(const Clock::time_point t[5], const PipelineTotals& p, const Scan& s
 }  // namespace
 
 static int run(int argc, const char** argv) {
+  bool bothStrands = false;   // (the banner comes before the arguments are parsed)
+  for (int i = 1; i < argc; ++i) bothStrands |= std::string(argv[i]) == "--both-strands";
   std::cout << "******************************************************\n"
             << "* TALC : Transcriptome-Aware Long Read Correction    *\n"
             << "*----------------------------------------------------*\n"
             << "*                                                    *\n"
-            << "* Kmers are assumed directional                      *\n"
+            << (bothStrands ? "* Kmers are taken on both strands                    *\n" : "* Kmers are assumed directional                      *\n")
             << "******************************************************" << std::endl;
   std::cout << "[TALC]: Parsing arguments" << std::endl;
   Options o = parse(argc, argv);

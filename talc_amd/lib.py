@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "talc_table_fetch_walk", "talc_batch_fetch_coverage_degrees", "talc_batch_structure", "talc_batch_fetch_structure",
     "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
     "talc_counter_destroy",
+    "talc_counter_set_both_strands", "talc_counter_add_counts", "talc_table_build_device_both_strands",
+    "talc_table_from_arrays_device_both_strands",
     "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
     "talc_ctx_get_map_timing",
     "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
@@ -198,6 +200,11 @@ def lib():
         L.talc_counter_fetch.argtypes = [vp, u32, vp, vp, u64, vp]
         L.talc_counter_build_table.argtypes = [vp, C.c_char_p, C.POINTER(vp), vp]
         L.talc_counter_destroy.argtypes = [vp]
+        if hasattr(L, "talc_counter_set_both_strands"):   # (a build from before both strands loads; asking it for them raises)
+            L.talc_counter_set_both_strands.argtypes = [vp, i32]
+            L.talc_counter_add_counts.argtypes = [vp, vp, vp, u64]
+            L.talc_table_build_device_both_strands.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), i32, C.POINTER(vp), vp]
+            L.talc_table_from_arrays_device_both_strands.argtypes = [vp, vp, u64, C.POINTER(Params), i32, C.POINTER(vp)]
         # (a build from before the correction map, selected with TALC_LIB for an A/B, loads; asking it for a map raises)
         if hasattr(L, "talc_ctx_set_map"):
             L.talc_ctx_set_map.argtypes = [vp, i32]
@@ -365,12 +372,19 @@ class Table:
         self.params = params
 
     @classmethod
-    def from_arrays(cls, kmers, counts, params, device=None):
-        """device=None: host builder; device=d: insertion on GPU d (same content)."""
+    def from_arrays(cls, kmers, counts, params, device=None, both_strands=False):
+        """device=None: host builder; device=d: insertion on GPU d (same content).  both_strands (docs/both_strands.md,
+        device only): the counts are summed over every k-mer and its reverse complement on the GPU, the filter applies
+        to the sum and both are stored."""
         kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
         h = C.c_void_p()
-        if device is None:
+        if both_strands:
+            if device is None:
+                raise TalcError("a table on both strands is folded on the GPU: give a device (there is no host fold)")
+            _chk(lib().talc_table_from_arrays_device_both_strands(kmers.ctypes.data, counts.ctypes.data, len(kmers), C.byref(params),
+                                                                  int(device), C.byref(h)))
+        elif device is None:
             _chk(lib().talc_table_from_arrays(kmers.ctypes.data, counts.ctypes.data, len(kmers), C.byref(params), C.byref(h)))
         else:
             _chk(lib().talc_table_from_arrays_device(kmers.ctypes.data, counts.ctypes.data, len(kmers), C.byref(params),
@@ -378,10 +392,16 @@ class Table:
         return cls(h, params)
 
     @classmethod
-    def from_files(cls, dump, junctions, params, device=None):
+    def from_files(cls, dump, junctions, params, device=None, both_strands=False):
+        """both_strands (device only): the dump's counts folded over reverse complements on the GPU, as from_arrays."""
         h = C.c_void_p()
         st = np.zeros(3, dtype=np.int64)
-        if device is None:
+        if both_strands:
+            if device is None:
+                raise TalcError("a table on both strands is folded on the GPU: give a device (there is no host fold)")
+            _chk(lib().talc_table_build_device_both_strands(dump.encode(), junctions.encode() if junctions else None, C.byref(params),
+                                                            int(device), C.byref(h), st.ctypes.data))
+        elif device is None:
             _chk(lib().talc_table_build(dump.encode(), junctions.encode() if junctions else None, C.byref(params), C.byref(h), st.ctypes.data))
         else:
             _chk(lib().talc_table_build_device(dump.encode(), junctions.encode() if junctions else None, C.byref(params),
@@ -473,14 +493,32 @@ class Table:
 
 class KmerCounter:
     """Short-read k-mer counter on GPU `device` (replaces `jellyfish count -m K` + `dump -c`; docs/kmer_counting.md):
-    every window of K bases of ACGTacgt inside one record counts once, directional, 2 bits per base."""
+    every window of K bases of ACGTacgt inside one record counts once, directional, 2 bits per base.  both_strands
+    (docs/both_strands.md): every observation counts for the canonical k-mer min(x, rc(x)); fetch returns canonical k-mers
+    and build_table stores each kept one with its reverse complement."""
 
-    def __init__(self, params, device=0, expected_distinct=0):
+    def __init__(self, params, device=0, expected_distinct=0, both_strands=False):
         self.params = params
         self.device = int(device)
+        self.both_strands = bool(both_strands)
         h = C.c_void_p()
         _chk(lib().talc_counter_create(C.byref(params), self.device, int(expected_distinct), C.byref(h)))
         self._h = h
+        if self.both_strands:
+            self.set_both_strands(True)
+
+    def set_both_strands(self, on=True):
+        """Before the first add / add_counts only (TalcError afterwards)."""
+        _chk(lib().talc_counter_set_both_strands(self._h, 1 if on else 0))
+        self.both_strands = bool(on)
+
+    def add_counts(self, kmers, counts):
+        """Counted k-mers (packed u64, u32): counts[i] is added to kmers[i], or to its canonical form on a both-strands counter."""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if len(kmers) != len(counts):
+            raise ValueError("kmers and counts differ in length")
+        _chk(lib().talc_counter_add_counts(self._h, kmers.ctypes.data, counts.ctypes.data, len(kmers)))
 
     def add(self, bases, offsets):
         """Queue a batch of records (bases: uint8 / bytes concatenated, offsets: u64[n+1]); the arrays may be reused at once."""

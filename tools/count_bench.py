@@ -10,6 +10,7 @@ Kernel times of a separate `rocprofv3 --kernel-trace --stats -- python tools/cou
 figures to quote for the kernels themselves.
 
   python tools/count_bench.py [--reads 40000000] [--file-reads 4000000] [--long-reads 20000] [--leg all|memory|file]
+                              [--both-strands]
 """
 import argparse
 import json
@@ -29,7 +30,7 @@ def memory_leg(a):
     from talc_amd.synth import Synth
     S = Synth(target_kmers=a.target_kmers, k=a.k, seed=a.seed)
     p = T.default_params(k=a.k)
-    c = T.KmerCounter(p, 0)
+    c = T.KmerCounter(p, 0, both_strands=a.both_strands)
     add_s, nbytes = 0.0, 0
     for first in range(0, a.reads, a.batch):
         n = min(a.batch, a.reads - first)
@@ -45,7 +46,7 @@ def memory_leg(a):
     t = c.build_table()
     build_s = time.perf_counter() - t0
     c.close()
-    out = {"reads": a.reads, "bytes": nbytes, "windows": windows, "distinct": distinct, "kept": kept, "table_size": len(t),
+    out = {"both_strands": a.both_strands, "reads": a.reads, "bytes": nbytes, "windows": windows, "distinct": distinct, "kept": kept, "table_size": len(t),
            "add_s": round(add_s, 4), "final_wait_s": round(wait_s, 4), "table_build_s": round(build_s, 4),
            "windows_per_s_whole": windows / max(add_s + wait_s, 1e-9)}
     t.close()
@@ -56,15 +57,17 @@ def run_memory_child(a):
     env = dict(os.environ, TALC_TIMING="1")
     cmd = [sys.executable, os.path.abspath(__file__), "--leg", "memory-child", "--reads", str(a.reads), "--batch", str(a.batch),
            "--target-kmers", str(a.target_kmers), "--k", str(a.k), "--length", str(a.length), "--sub-rate", str(a.sub_rate),
-           "--seed", str(a.seed)]
+           "--seed", str(a.seed)] + (["--both-strands"] if a.both_strands else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=1800)
     if r.returncode != 0:
         raise SystemExit("memory leg failed (%d): %s" % (r.returncode, r.stderr.decode()[-2000:]))
     res = json.loads(r.stdout.decode().split("MEMORY_LEG ", 1)[1].splitlines()[0])
-    m = re.search(r"count kernels ([0-9.]+) ms \(([0-9.]+) ms per batch\), (\d+) grows ([0-9.]+) s", r.stderr.decode())
+    m = re.search(r"count kernels ([0-9.]+) ms \(([0-9.]+) ms per batch\), (\d+) grows ([0-9.]+) s, "
+                  r"last batch wait [0-9.]+ s, compaction ([0-9.]+) s", r.stderr.decode())
     if m:
         kms = float(m.group(1))
         res.update(kernel_ms=kms, kernel_ms_per_batch=float(m.group(2)), grows=int(m.group(3)), grow_s=float(m.group(4)),
+                   compaction_s=float(m.group(5)),
                    windows_per_s_kernel=res["windows"] / (kms / 1e3) if kms > 0 else None,
                    # one add per window at most (runs of one k-mer in a lane share one) plus one CAS per distinct k-mer
                    atomics_per_s_kernel_upper=(res["windows"] + res["distinct"]) / (kms / 1e3) if kms > 0 else None)
@@ -119,6 +122,8 @@ def main():
     ap.add_argument("--file-reads", type=int, default=4_000_000)
     ap.add_argument("--long-reads", type=int, default=20_000)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--both-strands", action="store_true",
+                    help="the memory leg with the canonical kernel and the expanding compaction (docs/both_strands.md)")
     a = ap.parse_args()
     if a.leg == "memory-child":
         memory_leg(a)
