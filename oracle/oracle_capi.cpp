@@ -1,4 +1,4 @@
-// oracle_capi.cpp — CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).  parity unpinned.
+// oracle_capi.cpp — CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).
 // Plain C entry points over talc_oracle.{hpp,cpp} so tests/ and bench.py's cpu_baseline leg can
 // drive the oracle through ctypes.  Nothing in talc_amd/ links or loads this library.
 #include <omp.h>
@@ -257,8 +257,9 @@ int64_t orc_trace_read(void* t, const orc_params* p, const char* bases, uint64_t
   return (int64_t)s.size() + 1;
 }
 
-void orc_ub_counters(int64_t* out3) {
-  out3[0] = ubCounters().infixClamped; out3[1] = ubCounters().seedTooShort; out3[2] = ubCounters().gardeningOOB;
+void orc_ub_counters(int64_t* out4) {
+  out4[0] = ubCounters().infixClamped; out4[1] = ubCounters().seedTooShort; out4[2] = ubCounters().gardeningOOB;
+  out4[3] = ubCounters().scoreBridgesCalls;
 }
 
 // ---------------------------------------------------------------- primitives (for KATs and device unit tests)

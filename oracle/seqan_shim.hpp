@@ -5,7 +5,9 @@
 // README.md:26, Makefile:3) is absent from /root/reference and from this image,
 // so these follow its published algorithms (include/seqan/align/*,
 // include/seqan/seeds/seeds_extension.h) as recalled in SURVEY.md Appendix A.
-// parity unpinned: pinned only by hand-derived KATs (tests/test_oracle_primitives.py).
+// Pinned only by hand-derived KATs (tests/test_oracle_primitives.py): this is the part of the
+// oracle that the reference pin (docs/reference_pin.md) does not reach, because the reference
+// binaries of oracle/_ref/ call these same functions through oracle/seqan_compat/.
 //
 // Call sites restated:
 //   globalAlignment(score-only)  Trail.cpp:166,171,422  Trajectory.cpp:413

@@ -1,8 +1,12 @@
 // talc_oracle.cpp — CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).  See talc_oracle.hpp.
-// parity unpinned (no reference golden vectors exist; SeqAn2 absent) — SURVEY.md §8c.
+// Held to the reference's own sources by tests/test_reference_pin.py (docs/reference_pin.md).
 //
 // Deliberate, documented interpretation choices where the reference is undefined:
 //  * Explorer.cpp:705 `for(unsigned int(j); j<...` has no initialiser -> j starts at 0.
+//    The reference as its own build line compiles it (g++ 11.4 -O3) does the same: the loop
+//    counter is cleared right before the loop (xor %edx,%edx in scoreBridges), and that binary
+//    writes the files of the one built with -ftrivial-auto-var-init=zero on every run of the
+//    pin, 292 reads of which enter scoreBridges.
 //  * std::pow(x,2) (Explorer.cpp:1195-1196,1213-1214) is evaluated as x*x: g++ folds
 //    pow(x,2.0) to a multiplication at every optimisation level the reference uses (-O3).
 //  * abs(double) in Explorer.cpp:1247 resolves to the floating-point overload.
@@ -914,6 +918,8 @@ double computePercentID(const TSeq& seq1, const TSeq& seq2) {  // :505-528
 // ---------------------------------------------------------------- scoring / gardening (Explorer.cpp:689-865)
 void scoreBridges(const Params& P, std::vector<Trail>& newCompetingPaths, unsigned int stepCounter,
                   const TSeq& reference, Direction direction) {
+#pragma omp atomic
+  g_ub.scoreBridgesCalls++;
   TSeq truncatedReference;
   int bound = 0;
   if (direction == RIGHT) {

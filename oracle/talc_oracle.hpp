@@ -5,14 +5,17 @@
 // specification.  Every function cites the reference file:line it follows
 // (paths relative to /root/reference/src).
 //
-// PARITY STATUS: *parity unpinned*.  The reference ships no tests, golden
-// vectors or fixtures and cannot be compiled in this image
-// because every translation unit needs SeqAn2, which is not vendored
-// (Makefile:3, README.md:26).  The SeqAn2 primitives used on the path
-// (score-only global/local alignment, gapped X-drop seed extension, Horspool
-// find, Dna5 conversion, FASTA I/O) are restated from their published
-// behaviour in seqan_shim.hpp and pinned only by hand-derived known-answer
-// tests (tests/test_oracle_primitives.py).
+// PARITY STATUS: pinned to the reference's own sources (docs/reference_pin.md).
+// The reference ships no tests, golden vectors or fixtures and
+// needs SeqAn2, which is not vendored (Makefile:3, README.md:26); its nine
+// translation units are compiled unmodified against oracle/seqan_compat/ into
+// oracle/_ref/, and tests/test_reference_pin.py holds this restatement to them.
+// Not reached by that pin: the SeqAn2 primitives used on the path (score-only
+// global/local alignment, gapped X-drop seed extension, Horspool find), which
+// are restated from their published behaviour in seqan_shim.hpp, called by both
+// sides, and pinned only by hand-derived known-answer tests
+// (tests/test_oracle_primitives.py); and Dna5 conversion, FASTA I/O and the
+// argument parser, where the compat headers take this restatement's position.
 //
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
 // use anything in this directory.  The product (talc_amd/) never includes,
@@ -371,6 +374,7 @@ struct UBCounters {
   long infixClamped = 0;      // infix/prefix/suffix with out-of-range or inverted bounds
   long seedTooShort = 0;      // getSeedAndExtension on a sequence shorter than the seed
   long gardeningOOB = 0;      // Explorer.cpp:852 out-of-range read (guarded)
+  long scoreBridgesCalls = 0; // calls of scoreBridges, whose loop index the reference leaves uninitialised (Explorer.cpp:705)
 };
 UBCounters& ubCounters();
 

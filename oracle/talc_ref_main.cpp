@@ -1,4 +1,5 @@
-// talc_ref_main.cpp — CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).  parity unpinned.
+// talc_ref_main.cpp — CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).
+// Held to the reference's own driver, built into oracle/_ref/, by tests/test_reference_pin.py (docs/reference_pin.md).
 // Restatement of the reference's driver: main.cpp:83-325 + Settings.cpp:74-185 (option table,
 // output files, per-read OpenMP loop).  stdout banners are reduced; the four output files
 // (<o>.fa, <o>.log, <o>.config.txt, <o>.stats_basics.txt) follow the reference text exactly.

@@ -131,12 +131,38 @@ def build_oracle():
     _run(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
 
 
+REFERENCE_SRC = os.environ.get("TALC_REFERENCE_SRC", "/root/reference")
+REF_OUT = os.path.join(ROOT, "oracle", "_ref")
+
+
+def build_reference(force=False):
+    """The reference's own nine translation units, compiled in place against oracle/seqan_compat into oracle/_ref/
+    (docs/reference_pin.md): talc_gxx by the reference Makefile's line, talc_zero with clang++ and
+    -ftrivial-auto-var-init=zero.  Where the reference sources are absent (the GPU box) nothing is done and
+    oracle/_ref/ is left as it is."""
+    srcdir = os.path.join(REFERENCE_SRC, "src")
+    if not os.path.isdir(srcdir):
+        return []
+    compat = os.path.join(ROOT, "oracle", "seqan_compat", "seqan")
+    deps = [os.path.join(srcdir, f) for f in os.listdir(srcdir) if f.endswith((".cpp", ".hpp")) and not f.startswith("Path.")]
+    deps += [os.path.join(compat, f) for f in os.listdir(compat)]
+    deps += [os.path.join(ROOT, "oracle", "seqan_shim.hpp"), os.path.join(ROOT, "oracle", "Makefile")]
+    out = []
+    for name in ("talc_gxx", "talc_zero"):
+        tgt = os.path.join(REF_OUT, name)
+        cmd = ["make", "-s", "-j16", "-C", os.path.join(ROOT, "oracle"), "TALC_REFERENCE_SRC=" + REFERENCE_SRC, "_ref/" + name]
+        _build_if_stale(tgt, deps, cmd + (["-B"] if force else []), force)
+        out.append(tgt)
+    return out
+
+
 def build_all(force=False):
     build_synth(force)
     build_pure(force)
     build_hip(force)
     build_cli(force)
     build_oracle()
+    build_reference(force)
 
 
 def build_hip_variants():

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Generates the golden fixtures in this directory FROM THE ORACLE (the reference ships no
-golden vectors — SURVEY.md §4 — and cannot be built here — §8c — so these pin the oracle's
-behaviour, "parity unpinned" with respect to a real TALC binary).
+"""Generates the golden fixtures in this directory FROM THE ORACLE: the wider, oracle-made set.
+The pin to the reference itself is tests/golden/ref/*.json.gz, recorded by make_ref_golden.py from
+the reference's own sources built into oracle/_ref/ (docs/reference_pin.md); those mirror g1-g5 and
+g7-g10 of this set.  What only this set covers is what the reference's command line cannot express:
+K = 31 (g6) and MAX_NB_BRANCHES 4 (g10).
 
 Each fixture is data only: the synthetic-input recipe (generator seed + sha256 of the k-mer
 dump arrays it must reproduce), the reads as text, the parameters, and the expected outputs

@@ -1,7 +1,7 @@
 """ctypes binding of oracle/_build/liboracle.so — TEST INFRASTRUCTURE ONLY.
 
-The oracle is the CPU restatement of the reference algorithm (oracle/talc_oracle.cpp, parity
-unpinned).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
+The oracle is the CPU restatement of the reference algorithm (oracle/talc_oracle.cpp, held to
+the reference's own sources by tests/test_reference_pin.py).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
 import ctypes as C
 import os
@@ -217,6 +217,6 @@ class OracleTable:
 
 
 def ub_counters():
-    a = np.zeros(3, dtype=np.int64)
+    a = np.zeros(4, dtype=np.int64)
     lib().orc_ub_counters(a.ctypes.data)
-    return dict(infixClamped=int(a[0]), seedTooShort=int(a[1]), gardeningOOB=int(a[2]))
+    return dict(infixClamped=int(a[0]), seedTooShort=int(a[1]), gardeningOOB=int(a[2]), scoreBridgesCalls=int(a[3]))
