@@ -293,6 +293,12 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b);
 int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint32_t* n_regions, double* lambda,
                                uint32_t* in_span, uint64_t* region_offsets, uint32_t* regions, uint32_t* region_hits,
                                uint64_t region_capacity, uint32_t* head_counts);
+/* Test hook.  On a batch talc_batch_structure has run on: orders the work queue as talc_batch_correct does before its
+ * search and returns it — order[n_reads], read numbers, heaviest bucket first — with bucket[r], the bucket of read r as
+ * the host computes it from the read's state and the gap scale the device derived for the batch (the same function the
+ * kernels use), and that scale itself (in 1/256) in bucket[n_reads]: bucket has room for n_reads + 1 words.
+ * bucket[order[i]] never decreases with i; the order inside a bucket is arbitrary. */
+int talc_batch_order(talc_ctx* c, talc_batch* b, uint32_t* order, uint32_t* bucket);
 /* Total corrected size (bytes) so the caller can allocate; valid after talc_batch_correct. */
 uint64_t talc_batch_corrected_bytes(const talc_batch* b);
 /* out: corrected (or passed-through) sequences as upper-case ACGTN text, concatenated in input

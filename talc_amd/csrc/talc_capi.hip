@@ -147,6 +147,8 @@ struct talc_ctx {
   DevBuf<uint64_t> d_counters;   // kCounterWords: trail steps, dp cells, the profile build's counters and wave log
   DevBuf<uint32_t> d_thr;        // the count model's thresholds by count (DevParams.thr)
   DevCache cache;       // the device buffers of this context's batches
+  HostPool host_pool;   // the page-locked host arrays of its finished batches, for the next batch (talc_devmem.h)
+  HostArr<uint64_t> h_land;   // page-locked: kTotWords of the offset kernels' totals, then the counters below the wave log
   ~talc_ctx() {
     (void)hipSetDevice(device);
     for (auto& e : ev) if (e) hipEventDestroy(e);
@@ -174,12 +176,13 @@ struct talc_batch {
   uint64_t out_capacity = 0;
   bool encoded = false, covered = false, corrected = false;
   bool structured = false;   // talc_batch_structure has run and no search has touched the region lists since
-  std::vector<ReadState> h_state;
-  std::vector<uint64_t> h_dense_off;
+  // what comes back from the device with every correction: page-locked, from the context's pool and back to it
+  HostArr<ReadState> h_state;
+  HostArr<uint64_t> h_dense_off;
   uint64_t dense_cap = 0;
   // the correction map of the last correction, when the context kept one (talc_ctx_set_map)
   bool mapped = false, masked = false;   // d_segs holds that correction's map; d_masked its records, RAW stretches in lower case
-  std::vector<uint64_t> h_seg_off;
+  HostArr<uint64_t> h_seg_off;
   uint64_t segs_cap = 0, masked_cap = 0;
   // the solidity report (talc_batch_solidity): rows of the reads, and of the records of the correction before it
   bool solidity = false, solidityCorrected = false;
@@ -213,6 +216,7 @@ struct talc_batch {
   CachedBuf<uint64_t> d_seg_off;
   CachedBuf<uint32_t> d_mapedge;     // 2 x u32 per read: what k_search made of its head and its tail (leave_outcome)
   CachedBuf<uint32_t> d_headcov;     // 16 x u32 per read: dense counts of its first positions (k_structure -> k_search)
+  CachedBuf<EmitSum> d_emit;         // the offset kernels' block sums, then their totals record (k_emit_sums, k_emit_offsets)
   CachedBuf<uint64_t> d_dense_off;
   CachedBuf<uint8_t> d_dense;
   CachedBuf<uint64_t> d_outoff;      // per-read offset into d_out
@@ -940,6 +944,7 @@ int talc_ctx_create(talc_table* t, const talc_params* p, int device, talc_ctx** 
   HIPCHK(c->d_queue.alloc(kQueueWords));
   HIPCHK(c->d_hist.alloc(kHistWords));
   HIPCHK(c->d_counters.alloc(kCounterWords));
+  if (!c->h_land.resize(kTotWords + kCntWaveLog)) return fail(TALC_ERR_NOMEM, "cannot allocate the context's host landing area");
   {   // isExpectedbyMyModel as two thresholds per count (Explorer.cpp:1185-1201), from the formula itself, for this ALPHA
     const uint32_t n = 4096;
     HIPCHK(c->d_thr.alloc(2ull * n));
@@ -1008,6 +1013,7 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   HIPCHK(hipSetDevice(c->device));
   auto b = std::make_unique<talc_batch>();
   b->ctx = c; b->n_reads = n_reads;
+  b->h_state.use_pool(&c->host_pool); b->h_dense_off.use_pool(&c->host_pool); b->h_seg_off.use_pool(&c->host_pool);
   b->h_offsets.assign(offsets, offsets + n_reads + 1);
   if (b->h_offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
   b->n_bases = b->h_offsets[n_reads];
@@ -1134,7 +1140,9 @@ static int launch_coverage(talc_ctx* c, talc_batch* b) {
 static int32_t read_status(const ReadState& st) { return st.overflow ? TALC_READ_ERROR : st.status; }
 
 // the stage times into c->timing, from the events around the stages.  `last`: the last event recorded and waited for —
-// 2 (coverage), 3 (structure) or 7 (the whole correction; between events 4 and 5 the host looks at the first pass)
+// 2 (coverage), 3 (structure) or 7 (the whole correction).  search_ms ends with the first k_search (event 4); retry_ms spans
+// the retry passes (events 5, 6: next to nothing when no read overflowed); emit_ms (events 6, 7) spans the offset kernels,
+// the host's wait for their totals and k_pack
 static int read_stage_times(talc_ctx* c, int last) {
   talc_timing& t = c->timing;
   HIPCHK(hipEventElapsedTime(&t.encode_ms, c->ev[0], c->ev[1]));

@@ -124,7 +124,7 @@ static uint32_t* batch_stats(talc_ctx* c) { return c->d_hist.get() + kBatchStats
 
 // the reads' states as the device has them now, into b->h_state (waits for the stream)
 static int fetch_states(talc_ctx* c, talc_batch* b) {
-  b->h_state.resize(b->n_reads);
+  if (!b->h_state.resize(b->n_reads)) return fail(TALC_ERR_NOMEM, "cannot allocate the host copy of %u read states", b->n_reads);
   if (b->n_reads) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), b->n_reads * sizeof(ReadState), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return TALC_OK;
@@ -164,11 +164,11 @@ static int order_queue(talc_ctx* c, talc_batch* b) {
   hipStream_t s = c->stream;
   uint32_t* const hist = c->d_hist.get();
   HIPCHK(hipMemsetAsync(hist, 0, kOrderBuckets * sizeof(uint32_t), s));
-  const unsigned nb = (b->n_reads + 255) / 256;
+  const unsigned nb = (b->n_reads + kOrderBlock - 1) / kOrderBlock;
   hipLaunchKernelGGL(k_order_scale, dim3(1), dim3(64), 0, s, batch_stats(c));
-  hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, hist, batch_stats(c));
+  hipLaunchKernelGGL(k_order_hist, dim3(nb), dim3(kOrderBlock), 0, s, b->d_state.get(), b->n_reads, hist, batch_stats(c));
   hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(kOrderBuckets), 0, s, hist);
-  hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(256), 0, s, b->d_state.get(), b->n_reads, hist, b->d_order.get(), batch_stats(c));
+  hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(kOrderBlock), 0, s, b->d_state.get(), b->n_reads, hist, b->d_order.get(), batch_stats(c));
   HIPCHK(hipGetLastError());
   return TALC_OK;
 }
@@ -203,7 +203,7 @@ static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint
   return TALC_OK;
 }
 
-// the first pass: every read, in queue order, through the context's stage (event 4 after it); leaves the states in b->h_state
+// the first pass: every read, in queue order, through the context's stage (event 4 after it); the states stay on the device
 static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
   int rc;
@@ -216,10 +216,31 @@ static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uin
     if ((rc = launch_search(c, b, c->stage, b->d_order.get(), b->n_reads, tb, traceRead, true))) return rc;
   }
   HIPCHK(hipEventRecord(c->ev[4], s));
-  return fetch_states(c, b);
+  return TALC_OK;
 }
 
-// retry passes for the reads whose scratch overflowed (events 5 and 6 around them): buffers sized from the batch's longest
+// The offsets of the dense output from the states as the device has them now: b->d_dense_off[0 .. n] and, with the map on,
+// b->d_seg_off[0 .. n] (k_emit_sums, k_emit_offsets), and the totals record, which the host waits for: `totals`
+// (kTotWords words: reads with overflow set, record bytes, segments) points into the context's page-locked landing area
+static int emit_offsets(talc_ctx* c, talc_batch* b, bool map, const uint64_t** totals) {
+  hipStream_t s = c->stream;
+  const uint32_t n = b->n_reads, nb = emit_blocks(n);
+  if (!b->d_emit) HIPCHK(b->d_emit.alloc(c->cache, nb + 1));
+  if (!b->d_dense_off) HIPCHK(b->d_dense_off.alloc(c->cache, n + 1));
+  if (map && !b->d_seg_off) HIPCHK(b->d_seg_off.alloc(c->cache, n + 1));
+  EmitSum* const sums = b->d_emit.get();
+  hipLaunchKernelGGL(k_emit_sums, dim3(nb), dim3(kEmitThreads), 0, s, b->d_state.get(), n, sums);
+  hipLaunchKernelGGL(k_emit_offsets, dim3(nb), dim3(kEmitThreads), 0, s, b->d_state.get(), n, sums, b->d_dense_off.get(),
+                     map ? b->d_seg_off.get() : nullptr, (unsigned long long*)(sums + nb));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c->h_land.data(), sums + nb, kTotWords * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *totals = c->h_land.data();
+  return TALC_OK;
+}
+
+// retry passes for the reads whose scratch overflowed (events 5 and 6 around them; b->h_state holds the states of the
+// first pass, fetch_states): buffers sized from the batch's longest
 // read (a path can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
 static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
@@ -255,21 +276,12 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
   return TALC_OK;
 }
 
-// dense packing: the records' offsets from the states' outLen (host), then k_pack into b->d_dense (event 7 after it)
-static int pack_dense(talc_ctx* c, talc_batch* b) {
+// dense packing: k_pack into b->d_dense, `total` bytes at the offsets emit_offsets left (event 7 after it)
+static int pack_dense(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
-  b->h_dense_off.resize(b->n_reads + 1);
-  uint64_t pos = 0;
-  for (uint32_t r = 0; r < b->n_reads; ++r) {
-    b->h_dense_off[r] = pos;
-    pos += b->h_state[r].outLen;
-  }
-  b->h_dense_off[b->n_reads] = pos;
   // the record buffer of an earlier pass over this batch is kept when it is large enough
-  if (b->d_dense && b->dense_cap < pos) b->d_dense.reset();
-  if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(pos, 1); HIPCHK(b->d_dense.alloc(c->cache, b->dense_cap)); }
-  if (!b->d_dense_off) HIPCHK(b->d_dense_off.alloc(c->cache, b->n_reads + 1));
-  HIPCHK(hipMemcpyAsync(b->d_dense_off.get(), b->h_dense_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  if (b->d_dense && b->dense_cap < total) b->d_dense.reset();
+  if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_dense.alloc(c->cache, b->dense_cap)); }
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
                        b->n_reads, c->p.reverse ? 1 : 0, b->rev_flags());
@@ -278,21 +290,12 @@ static int pack_dense(talc_ctx* c, talc_batch* b) {
   return TALC_OK;
 }
 
-// the correction map (talc_ctx_set_map): the reads' segment counts from the states (host: 2 R + 1 for a read k_search
-// reassembled, 1 for every other), then k_pack_map into b->d_segs (event 8 after it)
-static int pack_map(talc_ctx* c, talc_batch* b) {
+// the correction map (talc_ctx_set_map): k_pack_map into b->d_segs, `total` segments (2 R + 1 for a read k_search
+// reassembled, 1 for every other) at the offsets emit_offsets left (event 8 after it)
+static int pack_map(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
-  b->h_seg_off.resize(b->n_reads + 1);
-  uint64_t n = 0;
-  for (uint32_t r = 0; r < b->n_reads; ++r) {
-    b->h_seg_off[r] = n;
-    n += map_has_outcome(b->h_state[r]) ? 2ull * b->h_state[r].nRegions + 1 : 1;
-  }
-  b->h_seg_off[b->n_reads] = n;
-  if (b->d_segs && b->segs_cap < n) b->d_segs.reset();
-  if (!b->d_segs) { b->segs_cap = std::max<uint64_t>(n, 1); HIPCHK(b->d_segs.alloc(c->cache, b->segs_cap)); }
-  if (!b->d_seg_off) HIPCHK(b->d_seg_off.alloc(c->cache, b->n_reads + 1));
-  HIPCHK(hipMemcpyAsync(b->d_seg_off.get(), b->h_seg_off.data(), (b->n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  if (b->d_segs && b->segs_cap < total) b->d_segs.reset();
+  if (!b->d_segs) { b->segs_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_segs.alloc(c->cache, b->segs_cap)); }
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack_map, dim3(b->n_reads), dim3(64), 0, s, b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_mapedge.get(),
                        b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0,
@@ -302,15 +305,28 @@ static int pack_map(talc_ctx* c, talc_batch* b) {
   return TALC_OK;
 }
 
-// waits for the stream; the stage times and the batch's counts into c->timing, the device counters below the wave log into `counters`
-static int read_timing(talc_ctx* c, talc_batch* b, uint64_t* counters) {
+// The one copy back and the one wait at the end: the states, the offsets and the device counters below the wave log into
+// page-locked host memory; then the stage times and the batch's counts into c->timing (`counters`: into the landing area)
+static int read_timing(talc_ctx* c, talc_batch* b, bool map, uint32_t n_failed, const uint64_t** counters) {
+  hipStream_t s = c->stream;
+  const uint32_t n = b->n_reads;
   int rc;
-  HIPCHK(hipMemcpyAsync(counters, c->d_counters.get(), kCntWaveLog * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!b->h_state.resize(n) || !b->h_dense_off.resize(n + 1) || (map && !b->h_seg_off.resize(n + 1)))
+    return fail(TALC_ERR_NOMEM, "cannot allocate the host copies of %u reads' states and offsets", n);
+  uint64_t* const land = c->h_land.data() + kTotWords;
+  if (n) HIPCHK(hipMemcpyAsync(b->h_state.data(), b->d_state.get(), (size_t)n * sizeof(ReadState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(b->h_dense_off.data(), b->d_dense_off.get(), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (map) HIPCHK(hipMemcpyAsync(b->h_seg_off.data(), b->d_seg_off.get(), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(land, c->d_counters.get(), kCntWaveLog * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   if ((rc = read_stage_times(c, 7))) return rc;
-  c->timing.n_trail_steps = counters[kCntSteps];
-  c->timing.n_dp_cells = counters[kCntCells];
-  for (const ReadState& st : b->h_state) c->timing.n_failed += st.overflow ? 1 : 0;
+  c->timing.n_trail_steps = land[kCntSteps];
+  c->timing.n_dp_cells = land[kCntCells];
+  c->timing.n_failed = n_failed;
+  if (c->sw.timing)   // (TALC_TIMING: whether this batch's copies were DMA transfers, or page-locking failed and they were staged)
+    fprintf(stderr, "[talc-lib] correction: host arrays page-locked: states %d, offsets %d, landing area %d\n", b->h_state.pinned() ? 1 : 0,
+            b->h_dense_off.pinned() ? 1 : 0, c->h_land.pinned() ? 1 : 0);
+  *counters = land;
   return TALC_OK;
 }
 
@@ -324,14 +340,23 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   const bool map = c->map;
   if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
-  uint64_t counters[kCntWaveLog] = {0};
+  const uint64_t* counters = nullptr;
+  const uint64_t* tot = nullptr;
   if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
   if ((rc = order_queue(c, b))) return rc;
   if ((rc = search_first_pass(c, b, tb, traceRead))) return rc;
-  if ((rc = search_retry_passes(c, b, tb, traceRead))) return rc;
-  if ((rc = pack_dense(c, b))) return rc;
-  if (map && (rc = pack_map(c, b))) return rc;
-  if ((rc = read_timing(c, b, counters)) || (rc = vote_time(c))) return rc;
+  HIPCHK(hipEventRecord(c->ev[5], c->stream));   // (no read overflowed: there is no retry pass between these two)
+  HIPCHK(hipEventRecord(c->ev[6], c->stream));
+  if ((rc = emit_offsets(c, b, map, &tot))) return rc;
+  if (tot[kTotOverflow]) {   // some read's scratch ran out: the states to the host, the retry passes, the offsets again
+    if ((rc = fetch_states(c, b))) return rc;
+    if ((rc = search_retry_passes(c, b, tb, traceRead))) return rc;
+    if ((rc = emit_offsets(c, b, map, &tot))) return rc;
+  }
+  const uint32_t n_failed = (uint32_t)tot[kTotOverflow];
+  if ((rc = pack_dense(c, b, tot[kTotBytes]))) return rc;
+  if (map && (rc = pack_map(c, b, tot[kTotSegs]))) return rc;
+  if ((rc = read_timing(c, b, map, n_failed, &counters)) || (rc = vote_time(c))) return rc;
   if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[7], c->ev[8]));
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
@@ -360,6 +385,24 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   if ((rc = fetch_states(c, b))) return rc;
   if ((rc = read_stage_times(c, 3)) || (rc = vote_time(c))) return rc;
   b->structured = true;
+  return TALC_OK;
+}
+
+// Test hook: the work queue of a batch talc_batch_structure has run on (see include/talc_hip.h)
+int talc_batch_order(talc_ctx* c, talc_batch* b, uint32_t* order, uint32_t* bucket) {
+  if (!c || !b || b->ctx != c || !order || !bucket) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
+  if (!b->structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = order_queue(c, b))) return rc;
+  uint32_t scale = 256u;
+  if (b->n_reads) {   // (an empty batch has no queue, and nothing has set the scale)
+    HIPCHK(hipMemcpyAsync(order, b->d_order.get(), (size_t)b->n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&scale, batch_stats(c) + kStatGapScale, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (uint32_t r = 0; r < b->n_reads; ++r) bucket[r] = order_bucket(b->h_state[r], scale);
+  bucket[b->n_reads] = scale;
   return TALC_OK;
 }
 

@@ -18,7 +18,7 @@ int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p)
   if (records && !b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch: it has no records");
   b->supported = false;
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
-  const std::vector<uint64_t>& off = records ? b->h_dense_off : b->h_offsets;
+  const uint64_t* const off = records ? b->h_dense_off.data() : b->h_offsets.data();
   const uint64_t total = off[b->n_reads];
   if (b->d_support && b->support_cap < total) b->d_support.reset();
   if (!b->d_support) { b->support_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_support.alloc(c->cache, b->support_cap)); }
@@ -39,7 +39,7 @@ int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p)
 }
 
 // the offsets of the bytes: the records' for RECORD, the input reads' for RAW
-static const std::vector<uint64_t>& support_offsets(const talc_batch* b) { return b->supportRecords ? b->h_dense_off : b->h_offsets; }
+static const uint64_t* support_offsets(const talc_batch* b) { return b->supportRecords ? b->h_dense_off.data() : b->h_offsets.data(); }
 
 uint64_t talc_batch_support_bytes(const talc_batch* b) { return (b && b->supported) ? support_offsets(b)[b->n_reads] : 0; }
 
@@ -47,9 +47,9 @@ int talc_batch_fetch_support(talc_ctx* c, talc_batch* b, uint8_t* out, uint64_t 
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   if (!b->supported) return fail(TALC_ERR_STATE, "talc_batch_support has not run on this batch since its last correction");
   HIPCHK(hipSetDevice(c->device));
-  const std::vector<uint64_t>& off = support_offsets(b);
+  const uint64_t* const off = support_offsets(b);
   const uint64_t total = off[b->n_reads];
-  if (out_offsets) memcpy(out_offsets, off.data(), ((size_t)b->n_reads + 1) * 8);
+  if (out_offsets) memcpy(out_offsets, off, ((size_t)b->n_reads + 1) * 8);
   if (out) {
     if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "support buffer too small: need %llu bytes", (unsigned long long)total);
     if (total) {

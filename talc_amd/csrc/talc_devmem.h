@@ -7,6 +7,8 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -174,6 +176,86 @@ class PinnedBuf {
   char* get() const { return p_; }
   void reset() { if (p_) { (void)hipHostFree(p_); p_ = nullptr; } }
   char* release() { char* p = p_; p_ = nullptr; return p; }
+};
+
+// Host arrays that device-to-host copies land in (a batch's states and offsets).  Page-locked, so that the copy is one DMA
+// transfer the stream does not stage; where page-locked memory cannot be had the block is pageable and everything still
+// works (as talc_cli_io.h's growable buffer does).  Page-locking is slow and a streaming run makes a batch per chunk of
+// reads: a batch's blocks go back to its context's HostPool, the next batch takes them, the context frees them.
+struct HostBlock { void* p = nullptr; uint64_t bytes = 0; bool pinned = false; };
+inline HostBlock host_block_alloc(uint64_t bytes) {
+  HostBlock b;
+  bytes = std::max<uint64_t>(bytes, 64);
+  if (hipHostMalloc(&b.p, bytes, hipHostMallocDefault) == hipSuccess) { b.bytes = bytes; b.pinned = true; return b; }
+  (void)hipGetLastError();
+  b.p = malloc(bytes);
+  b.bytes = b.p ? bytes : 0;
+  return b;
+}
+inline void host_block_free(HostBlock& b) {
+  if (b.p) { if (b.pinned) (void)hipHostFree(b.p); else free(b.p); }
+  b = HostBlock();
+}
+struct HostPool {
+  std::vector<HostBlock> free_;   // oldest first
+  HostPool() = default;
+  HostPool(const HostPool&) = delete;
+  HostPool& operator=(const HostPool&) = delete;
+  ~HostPool() { for (auto& b : free_) host_block_free(b); }
+  // the smallest kept block that holds `bytes` and is not more than twice as large, or a fresh one (p == nullptr: no memory)
+  HostBlock take(uint64_t bytes) {
+    int best = -1;
+    for (int i = 0; i < (int)free_.size(); ++i)
+      if (free_[i].bytes >= bytes && free_[i].bytes <= 2 * bytes + 4096 && (best < 0 || free_[i].bytes < free_[best].bytes)) best = i;
+    if (best < 0) return host_block_alloc(bytes);
+    const HostBlock b = free_[best];
+    free_.erase(free_.begin() + best);
+    return b;
+  }
+  void give(HostBlock b) {
+    if (!b.p) return;
+    free_.push_back(b);
+    while (free_.size() > 16) { host_block_free(free_.front()); free_.erase(free_.begin()); }
+  }
+};
+// n elements of a trivially copyable T in one HostBlock: the few operations of std::vector that the library uses.
+// resize() keeps what the array held and leaves new elements as they are: every user fills them.
+template <typename T>
+class HostArr {
+  HostBlock blk_;
+  uint64_t n_ = 0;
+  HostPool* pool_ = nullptr;
+
+ public:
+  HostArr() = default;
+  HostArr(const HostArr&) = delete;
+  HostArr& operator=(const HostArr&) = delete;
+  ~HostArr() { drop(); }
+  void use_pool(HostPool* pool) { pool_ = pool; }
+  void drop() { if (pool_) pool_->give(blk_); else host_block_free(blk_); blk_ = HostBlock(); n_ = 0; }
+  bool resize(uint64_t n) {   // false: no memory (the array is as it was)
+    if (n * sizeof(T) > blk_.bytes) {
+      HostBlock nb = pool_ ? pool_->take(n * sizeof(T)) : host_block_alloc(n * sizeof(T));
+      if (!nb.p) return false;
+      if (n_) memcpy(nb.p, blk_.p, n_ * sizeof(T));
+      const uint64_t keep = n_;
+      drop();
+      blk_ = nb; n_ = keep;
+    }
+    n_ = n;
+    return true;
+  }
+  bool pinned() const { return blk_.pinned; }
+  T* data() { return (T*)blk_.p; }
+  const T* data() const { return (const T*)blk_.p; }
+  uint64_t size() const { return n_; }
+  bool empty() const { return n_ == 0; }
+  T& operator[](uint64_t i) { return data()[i]; }
+  const T& operator[](uint64_t i) const { return data()[i]; }
+  T* begin() { return data(); }
+  T* end() { return data() + n_; }
+  const T* begin() const { return data(); }
+  const T* end() const { return data() + n_; }
 };
 
 // device buffers of finished batches, kept for the next batch of their context (a streaming run creates and destroys

@@ -4233,13 +4233,9 @@ k_search(DevParams P, TableView T, SearchCaps C, const uint8_t* __restrict__ cod
 // cost the same, and the edges are the part of a read other waves can take over (edge tasks): the reads with long inner
 // gaps have to start first there.  k_order_scale: 1 up to a fork share of 1.2 %, + 1 per further 1 %, at most 3.
 static_assert(kOrderBuckets == 32 * 32, "the key of order_bucket: five bits of exponent, five of mantissa");
-TALC_D uint32_t order_bucket(const ReadState& st, uint32_t gapScale) {
+__host__ __device__ inline uint32_t order_bucket(const ReadState& st, uint32_t gapScale) {
   if (st.status != TALC_READ_CORRECTED || st.overflow) return kOrderBuckets - 1;   // passed through: last
-  const unsigned long long key = (unsigned long long)st.costEst + (((unsigned long long)st.costGap * (gapScale - 256u)) >> 8);
-  const uint32_t c = (uint32_t)min(key, 0xFFFFFFFFull) | 1u;
-  const int e = 31 - __builtin_clz(c);                               // 0..31
-  const uint32_t m = (e >= 5) ? ((c >> (e - 5)) & 31u) : ((c << (5 - e)) & 31u);
-  return kOrderBuckets - 2 - min(kOrderBuckets - 2, (uint32_t)e * 32u + m);                  // heavy first
+  return order_key_bucket(st.costEst, st.costGap, gapScale, kOrderBuckets);        // heavy first (talc_pure.h)
 }
 __global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batchStats) {   // sets the gap scale and whether the graph branches
   const int l = lane_id();
@@ -4251,9 +4247,18 @@ __global__ void __launch_bounds__(64) k_order_scale(uint32_t* __restrict__ batch
   }
   if (l == 0) { batchStats[kStatGapScale] = scale; batchStats[kStatBranching] = scale > 256u ? 1u : 0u; }   // (the edge tasks' switch)
 }
-__global__ void k_order_hist(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ hist, const uint32_t* __restrict__ batchStats) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) atomicAdd(&hist[order_bucket(state[r], batchStats[kStatGapScale])], 1u);
+// A batch's reads land in a few dozen of the buckets: one global atomic per read would queue up on a handful of addresses.
+// A block of kOrderBlock reads counts in LDS and goes to the global words once per bucket it has met.
+static const uint32_t kOrderBlock = kOrderBuckets;   // (thread t of a block also owns bucket t of the block's LDS copy)
+__global__ void __launch_bounds__(kOrderBlock)
+k_order_hist(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ hist, const uint32_t* __restrict__ batchStats) {
+  __shared__ uint32_t cnt[kOrderBuckets];
+  const uint32_t t = threadIdx.x, r = blockIdx.x * kOrderBlock + t;
+  cnt[t] = 0u;
+  __syncthreads();
+  if (r < n) atomicAdd(&cnt[order_bucket(state[r], batchStats[kStatGapScale])], 1u);
+  __syncthreads();
+  if (cnt[t]) atomicAdd(&hist[t], cnt[t]);
 }
 __global__ void __launch_bounds__(kOrderBuckets) k_order_scan(uint32_t* __restrict__ hist) {   // hist[b] := first position of bucket b
   __shared__ uint32_t s[kOrderBuckets];
@@ -4269,10 +4274,105 @@ __global__ void __launch_bounds__(kOrderBuckets) k_order_scan(uint32_t* __restri
   }
   hist[t] = s[t] - v;
 }
-__global__ void k_order_scatter(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
-                                const uint32_t* __restrict__ batchStats) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n) order[atomicAdd(&cursor[order_bucket(state[r], batchStats[kStatGapScale])], 1u)] = r;
+// a read's place: its rank among the block's reads of its bucket (LDS), behind the range the block reserves in the
+// bucket with one global atomic.  The ranges of a bucket add up to k_order_hist's count of it: every place is below n.
+__global__ void __launch_bounds__(kOrderBlock)
+k_order_scatter(const ReadState* __restrict__ state, uint32_t n, uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
+                const uint32_t* __restrict__ batchStats) {
+  __shared__ uint32_t cnt[kOrderBuckets];
+  const uint32_t t = threadIdx.x, r = blockIdx.x * kOrderBlock + t;
+  cnt[t] = 0u;
+  __syncthreads();
+  uint32_t b = 0u, rank = 0u;
+  if (r < n) { b = order_bucket(state[r], batchStats[kStatGapScale]); rank = atomicAdd(&cnt[b], 1u); }
+  __syncthreads();
+  if (cnt[t]) cnt[t] = atomicAdd(&cursor[t], cnt[t]);   // (now the block's first place in bucket t)
+  __syncthreads();
+  if (r < n) {
+    const uint32_t at = cnt[b] + rank;
+    if (at < n) order[at] = r;   // (never false here; it keeps a build whose buckets are altered on purpose, a mutation, in bounds)
+  }
+}
+
+// a read that k_search reassembled: its map is 2 R + 1 segments (k_pack_map), every other read's one
+__host__ __device__ inline bool map_has_outcome(const ReadState& st) { return st.status == TALC_READ_CORRECTED && st.overflow == 0 && st.nRegions > 0; }
+
+// ==================================================================== offsets of the dense output (k_emit_sums, k_emit_offsets)
+// What the host needs before it can size the record buffer and the map, and what k_pack / k_pack_map need to place a read:
+// the running sums of the records' lengths (denseOff[0 .. n]) and, with the map on, of the reads' segment counts
+// (segOff[0 .. n]; null without), and the totals record {reads with overflow set, record bytes, segments}.  A block takes
+// kEmitReads consecutive reads, kEmitPer per thread: k_emit_sums leaves every block's three sums, k_emit_offsets adds the
+// sums of the blocks before its own (n / kEmitReads records at most: 977 for a million reads) and scans its reads.
+static const uint32_t kEmitThreads = 256, kEmitPer = 4, kEmitReads = kEmitThreads * kEmitPer;
+static const uint32_t kTotOverflow = 0, kTotBytes = 1, kTotSegs = 2, kTotWords = 3;   // (the totals record, uint64 words)
+struct EmitSum { unsigned long long bytes, segs, ovf; };
+__host__ __device__ inline uint32_t emit_blocks(uint32_t n) { return n ? (n + kEmitReads - 1) / kEmitReads : 1u; }
+TALC_D EmitSum emit_read(const ReadState& st) {
+  return EmitSum{st.outLen, map_has_outcome(st) ? 2ull * st.nRegions + 1ull : 1ull, st.overflow ? 1ull : 0ull};
+}
+// the block's sum of v: in every thread (LDS: one word per wave)
+TALC_D unsigned long long emit_block_sum(unsigned long long v, unsigned long long* waveSums) {
+  const uint32_t w = threadIdx.x >> 6;
+  const unsigned long long ws = wave_sum_u64(v);
+  __syncthreads();                               // (waveSums may still be read from the call before)
+  if ((threadIdx.x & 63u) == 0u) waveSums[w] = ws;
+  __syncthreads();
+  unsigned long long s = 0;
+  for (uint32_t i = 0; i < kEmitThreads / 64; ++i) s += waveSums[i];
+  return s;
+}
+__global__ void __launch_bounds__(kEmitThreads)
+k_emit_sums(const ReadState* __restrict__ state, uint32_t n, EmitSum* __restrict__ blockSums) {
+  __shared__ unsigned long long waveSums[kEmitThreads / 64];
+  EmitSum mine = {0, 0, 0};
+  const uint32_t r0 = blockIdx.x * kEmitReads + threadIdx.x * kEmitPer;
+  for (uint32_t i = 0; i < kEmitPer; ++i)
+    if (r0 + i < n) { const EmitSum e = emit_read(state[r0 + i]); mine.bytes += e.bytes; mine.segs += e.segs; mine.ovf += e.ovf; }
+  const EmitSum tot = {emit_block_sum(mine.bytes, waveSums), emit_block_sum(mine.segs, waveSums), emit_block_sum(mine.ovf, waveSums)};
+  if (threadIdx.x == 0) blockSums[blockIdx.x] = tot;
+}
+// the sum of v over the threads before this one in the block (exclusive), and over the whole block in `total`
+TALC_D unsigned long long emit_block_scan(unsigned long long v, unsigned long long* waveSums, unsigned long long& total) {
+  const uint32_t l = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  unsigned long long incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long t = ((unsigned long long)(uint32_t)__shfl_up((int)(incl >> 32), off, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)incl, off, 64);
+    if (l >= (uint32_t)off) incl += t;
+  }
+  __syncthreads();
+  if (l == 63u) waveSums[w] = incl;
+  __syncthreads();
+  unsigned long long before = 0;
+  total = 0;
+  for (uint32_t i = 0; i < kEmitThreads / 64; ++i) { const unsigned long long s = waveSums[i]; if (i < w) before += s; total += s; }
+  return before + incl - v;
+}
+__global__ void __launch_bounds__(kEmitThreads)
+k_emit_offsets(const ReadState* __restrict__ state, uint32_t n, const EmitSum* __restrict__ blockSums, uint64_t* __restrict__ denseOff,
+               uint64_t* __restrict__ segOff, unsigned long long* __restrict__ totals) {
+  __shared__ unsigned long long waveSums[kEmitThreads / 64];
+  EmitSum carry = {0, 0, 0};   // of the blocks before this one
+  for (uint32_t i = threadIdx.x; i < blockIdx.x; i += kEmitThreads) { const EmitSum e = blockSums[i]; carry.bytes += e.bytes; carry.segs += e.segs; carry.ovf += e.ovf; }
+  carry = EmitSum{emit_block_sum(carry.bytes, waveSums), emit_block_sum(carry.segs, waveSums), emit_block_sum(carry.ovf, waveSums)};
+  EmitSum mine = {0, 0, 0};
+  const uint32_t r0 = blockIdx.x * kEmitReads + threadIdx.x * kEmitPer;
+  for (uint32_t i = 0; i < kEmitPer; ++i)
+    if (r0 + i < n) { const EmitSum e = emit_read(state[r0 + i]); mine.bytes += e.bytes; mine.segs += e.segs; mine.ovf += e.ovf; }
+  EmitSum tot;
+  unsigned long long bytesAt = carry.bytes + emit_block_scan(mine.bytes, waveSums, tot.bytes);
+  unsigned long long segsAt = carry.segs + emit_block_scan(mine.segs, waveSums, tot.segs);
+  tot.ovf = emit_block_sum(mine.ovf, waveSums);
+  for (uint32_t i = 0; i < kEmitPer && r0 + i < n; ++i) {
+    const EmitSum e = emit_read(state[r0 + i]);
+    denseOff[r0 + i] = bytesAt; if (segOff) segOff[r0 + i] = segsAt;
+    bytesAt += e.bytes; segsAt += e.segs;
+  }
+  if (blockIdx.x + 1 == gridDim.x && threadIdx.x == 0) {   // (the last block: its carry and its own sums are the batch's)
+    denseOff[n] = carry.bytes + tot.bytes;
+    if (segOff) segOff[n] = carry.segs + tot.segs;
+    totals[kTotOverflow] = carry.ovf + tot.ovf; totals[kTotBytes] = carry.bytes + tot.bytes; totals[kTotSegs] = carry.segs + tot.segs;
+  }
 }
 
 // ==================================================================== the count model's thresholds (DevParams.thr)
@@ -4293,11 +4393,28 @@ __global__ void k_build_thresholds(double ALPHA, uint32_t n, uint32_t* __restric
 }
 
 // ==================================================================== k_pack
-// dense output: codes -> ASCII, with the reverse complement of main.cpp:286 for corrected reads
-// under -rev.  One block per (read, 4096-base chunk) of the OUTPUT.  rev_flags: as k_encode's.
-__global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __restrict__ outoff, const ReadState* __restrict__ state,
-                       const uint64_t* __restrict__ dense_off, uint8_t* __restrict__ dense, uint32_t n_reads, int reverse,
-                       const uint8_t* __restrict__ rev_flags) {
+// dense output: codes -> ASCII, with the reverse complement of main.cpp:286 for corrected reads under -rev.  One block per
+// read.  rev_flags: as k_encode's.  The record is written in aligned 4-byte words, each put together from the two aligned
+// words of the read's codes that hold its four bytes (read back to front and byte-swapped when the record is the reverse
+// complement) and converted as a word; the bytes before the record's first aligned word and its last few go one by one,
+// as in block_copy_bytes (talc_kernels_pieces.h).  Every word read holds at least one of the read's codes.
+// four codes to four letters: v_perm_b32 looks each byte up among the eight bytes of {N N N N, table}; codes 4 .. 7 give N
+// as code_to_ascii does, and a word with a byte of 8 or more (no kernel writes one) goes through code_to_ascii itself
+TALC_D uint32_t codes4_to_ascii(uint32_t w, bool complement) {
+  if (w & 0xF8F8F8F8u) {
+    uint32_t o = 0;
+    for (int i = 0; i < 4; ++i) {
+      const uint8_t c = (uint8_t)(w >> (8 * i));
+      o |= (uint32_t)(uint8_t)code_to_ascii(complement ? complement_code(c) : c) << (8 * i);
+    }
+    return o;
+  }
+  return __builtin_amdgcn_perm(0x4E4E4E4Eu, complement ? 0x41434754u : 0x54474341u, w);   // "TGCA" / "ACGT", low byte first
+}
+__global__ void __launch_bounds__(256)
+k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __restrict__ outoff, const ReadState* __restrict__ state,
+       const uint64_t* __restrict__ dense_off, uint8_t* __restrict__ dense, uint32_t n_reads, int reverse,
+       const uint8_t* __restrict__ rev_flags) {
   const uint32_t r = blockIdx.x;
   if (r >= n_reads) return;
   if (rev_flags) reverse |= rev_flags[r];
@@ -4305,9 +4422,32 @@ __global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __res
   const uint32_t len = state[r].outLen;
   uint8_t* dst = dense + dense_off[r];
   const bool rc = reverse && state[r].status == TALC_READ_CORRECTED && state[r].overflow == 0;
-  for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) {
-    if (rc) dst[i] = (uint8_t)code_to_ascii(complement_code(src[len - 1 - i]));
-    else dst[i] = (uint8_t)code_to_ascii(src[i]);
+  const uint32_t t = threadIdx.x, T = blockDim.x;
+  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u));
+  const uint32_t nw = (len - head) / 4u;                       // whole words of the record
+  uint32_t* const dw = (uint32_t*)(dst + head);
+  if (!rc) {
+    const uint32_t sh = (uint32_t)(((uintptr_t)src + head) & 3u);           // of every word's source
+    const uint32_t* const sw = (const uint32_t*)(src + head - sh);
+    for (uint32_t w = t; w < nw; w += T) {
+      const uint32_t lo = sw[w], hi = sh ? sw[w + 1] : 0u;
+      dw[w] = codes4_to_ascii((uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * sh)), false);
+    }
+  } else if (nw) {
+    // word w of the record = the codes at len - head - 4 w - 4 .. + 3, last first
+    const uint8_t* const top = src + (len - head - 4u);                     // the source of word 0
+    const uint32_t sh = (uint32_t)((uintptr_t)top & 3u);
+    const uint32_t* const sw = (const uint32_t*)(top - sh);
+    for (uint32_t w = t; w < nw; w += T) {
+      const uint32_t* const at = sw - w;
+      const uint32_t lo = at[0], hi = sh ? at[1] : 0u;
+      dw[w] = codes4_to_ascii(__builtin_bswap32((uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * sh))), true);
+    }
+  }
+  const uint32_t done = head + 4u * nw;
+  for (uint32_t i = t; i < head + (len - done); i += T) {
+    const uint32_t at = i < head ? i : done + (i - head);
+    dst[at] = rc ? (uint8_t)code_to_ascii(complement_code(src[len - 1 - at])) : (uint8_t)code_to_ascii(src[at]);
   }
 }
 
@@ -4319,7 +4459,6 @@ __global__ void k_pack(const uint8_t* __restrict__ outAll, const uint64_t* __res
 // read are flipped (order, raw_start, out_start).  Every other read is one RAW segment over the whole record.
 struct MapSeg { uint32_t kind, rawStart, rawLen, outStart, outLen; };
 enum : uint32_t { SEG_SOLID = 0, SEG_CORRECTED = 1, SEG_RAW = 2 };
-__host__ __device__ inline bool map_has_outcome(const ReadState& st) { return st.status == TALC_READ_CORRECTED && st.overflow == 0 && st.nRegions > 0; }
 __global__ void __launch_bounds__(64)
 k_pack_map(const ReadState* __restrict__ state, const uint32_t* __restrict__ regions, const uint64_t* __restrict__ regoff,
            const uint32_t* __restrict__ mapEdge, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ segOff,

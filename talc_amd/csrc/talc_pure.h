@@ -325,4 +325,18 @@ struct LessAnchor {
   }
 };
 
+// The bucket of the work-queue order (talc_kernels_search.h: order_bucket) of a read that is to be searched, from its
+// cost estimate: key = costEst + costGap x (gapScale - 256) / 256, clamped to 32 bits; the bucket is five bits of the
+// key's exponent and its five mantissa bits below the leading one, counted down from nBuckets - 2 (heavy first; the last
+// bucket is for the reads that are passed through).  A scale below 256 counts as 256.
+TALC_HD uint32_t order_key_bucket(uint32_t costEst, uint32_t costGap, uint32_t gapScale, uint32_t nBuckets) {
+  const uint32_t extra = gapScale > 256u ? gapScale - 256u : 0u;
+  const unsigned long long key = (unsigned long long)costEst + (((unsigned long long)costGap * extra) >> 8);
+  const uint32_t c = (uint32_t)(key < 0xFFFFFFFFull ? key : 0xFFFFFFFFull) | 1u;
+  const int e = 31 - __builtin_clz(c);                               // 0..31
+  const uint32_t m = (e >= 5) ? ((c >> (e - 5)) & 31u) : ((c << (5 - e)) & 31u);
+  const uint32_t k = (uint32_t)e * 32u + m;
+  return nBuckets - 2 - (k < nBuckets - 2 ? k : nBuckets - 2);
+}
+
 }  // namespace talc

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "talc_batch_copy_corrected_device", "talc_correct_batch",
     "talc_ctx_get_timing", "talc_batch_trace_read", "talc_test_dp",
     "talc_table_fetch_walk", "talc_batch_fetch_coverage_degrees", "talc_batch_structure", "talc_batch_fetch_structure",
+    "talc_batch_order",
     "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
     "talc_counter_destroy",
     "talc_counter_set_both_strands", "talc_counter_add_counts", "talc_table_build_device_both_strands",
@@ -179,6 +180,8 @@ def lib():
         L.talc_batch_fetch_coverage_degrees.argtypes = [vp, vp, vp]
         L.talc_batch_structure.argtypes = [vp, vp]
         L.talc_batch_fetch_structure.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+        if hasattr(L, "talc_batch_order"):   # (a TALC_LIB build from before the hook still loads: A/B against a parent)
+            L.talc_batch_order.argtypes = [vp, vp, vp, vp]
         L.talc_batch_num_kmers.restype = u64
         L.talc_batch_num_kmers.argtypes = [vp]
         L.talc_batch_num_bases.restype = u64
@@ -720,6 +723,14 @@ class Batch:
         self._needs_codes()
         self._corrected = False
         _chk(lib().talc_batch_structure(self.ctx._h, self._h))
+
+    def order(self):
+        """Test hook, after structure(): (order u32[n], bucket u32[n], gap scale) — the work queue, every read's bucket
+        and the batch's gap scale (in 1/256) as the device derived it."""
+        n = self.n_reads
+        order, bucket = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint32)
+        _chk(lib().talc_batch_order(self.ctx._h, self._h, order.ctypes.data, bucket.ctypes.data))
+        return order[:n], bucket[:n], int(bucket[n])
 
     def fetch_structure(self):
         """Test hook, after structure(): dict of status i32[n], n_regions u32[n], lambda f64[n], in_span u32[n],
