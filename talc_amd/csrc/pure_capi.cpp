@@ -17,6 +17,11 @@ extern "C" {
 // the work-queue bucket of a searched read (talc_pure.h: order_key_bucket), 1024 buckets as the kernels use it
 uint32_t talc_pure_order_bucket(uint32_t cost_est, uint32_t cost_gap, uint32_t gap_scale) { return order_key_bucket(cost_est, cost_gap, gap_scale, 1024u); }
 
+// the byte -> Dna5 code select of the k-mer window kernels (talc_common.h), next to the switch it restates
+uint32_t talc_pure_ascii_to_code_select(uint32_t c) { return ascii_to_code_select(c); }
+uint32_t talc_pure_ascii_to_code(uint32_t c) { return ascii_to_code((uint8_t)c); }
+uint32_t talc_pure_complement_code(uint32_t c) { return complement_code((uint8_t)c); }
+
 int pure_is_expected_by_model(double alpha, uint32_t nextc, uint32_t cc, int classe_unexpected) {
   return is_expected_by_model(alpha, nextc, cc, classe_unexpected != 0) ? 1 : 0;
 }

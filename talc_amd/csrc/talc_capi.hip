@@ -120,15 +120,30 @@ struct Stage {
   uint32_t box_seq_cap = 0;
 };
 
+// the context's events, all recorded on its stream
+enum CtxEvent {
+  // the correction's stages, in order (read_stage_times): before k_encode, after it, after k_coverage, after k_structure,
+  // after the first k_search, around the retry passes, after k_pack
+  kEvBegin, kEvEncoded, kEvCovered, kEvStructured, kEvSearched, kEvRetry0, kEvRetry1, kEvEmitted,
+  kEvPackMap,                                  // after k_pack_map
+  kEvMaskCase0, kEvMaskCase1,                  // around k_mask_case
+  kEvSolidity0, kEvSolidity1, kEvSolidity2,    // around the two k_solidity: over the reads, over the records
+  kEvPieceCount0, kEvPieceCount1,              // around k_piece_count
+  kEvPiecePack0, kEvPiecePack1,                // around k_piece_pack
+  // the edit scripts (run_edits): around the first k_edit_align rounds, after k_edit_count, around the second rounds, after k_edit_pack
+  kEvEditAlignA0, kEvEditAlignA1, kEvEditCount, kEvEditAlignB0, kEvEditAlignB1, kEvEditPack,
+  kEvVote0, kEvVote1,                          // around k_strand_vote
+  kEvSupport0, kEvSupport1,                    // around k_base_support
+  kEvCount
+};
+
 struct talc_ctx {
   talc_table* table = nullptr;
   talc_params p;
   DevParams dp;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[28] = {};   // 0 .. 7: the correction's stages (read_stage_times); 8: after k_pack_map; 9, 10: around k_mask_case; 11 .. 13: around the two k_solidity;
-                            // 14, 15: around k_piece_count; 16, 17: around k_piece_pack; 18 .. 23: the edit scripts (run_edits);
-                            // 24, 25: around k_strand_vote; 26, 27: around k_base_support
+  hipEvent_t ev[kEvCount] = {};
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
@@ -1066,16 +1081,16 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
 uint64_t talc_batch_num_kmers(const talc_batch* b) { return b ? b->n_kmers : 0; }
 uint64_t talc_batch_num_bases(const talc_batch* b) { return b ? b->n_bases : 0; }
 
-// ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes, events 24 and 25 around it
+// ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes, kEvVote0 and kEvVote1 around it
 static int launch_vote(talc_ctx* c, talc_batch* b) {
   if (!b->d_strand) HIPCHK(b->d_strand.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
   if (!b->d_strand_flag) HIPCHK(b->d_strand_flag.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
-  HIPCHK(hipEventRecord(c->ev[24], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvVote0], c->stream));
   if (b->n_reads)
     hipLaunchKernelGGL(k_strand_vote, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, b->d_raw.get(), b->d_offsets.get(), c->p.min_count, b->n_reads,
                        b->d_strand.get(), b->d_strand_flag.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[25], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvVote1], c->stream));
   c->votePending = true;
   b->voted = true;
   return TALC_OK;
@@ -1083,7 +1098,7 @@ static int launch_vote(talc_ctx* c, talc_batch* b) {
 // the last vote's device time into c->vote_ms, once the stream has been waited for
 static int vote_time(talc_ctx* c) {
   if (!c->votePending) return TALC_OK;
-  HIPCHK(hipEventElapsedTime(&c->vote_ms, c->ev[24], c->ev[25]));
+  HIPCHK(hipEventElapsedTime(&c->vote_ms, c->ev[kEvVote0], c->ev[kEvVote1]));
   c->votePending = false;
   return TALC_OK;
 }
@@ -1140,18 +1155,18 @@ static int launch_coverage(talc_ctx* c, talc_batch* b) {
 static int32_t read_status(const ReadState& st) { return st.overflow ? TALC_READ_ERROR : st.status; }
 
 // the stage times into c->timing, from the events around the stages.  `last`: the last event recorded and waited for —
-// 2 (coverage), 3 (structure) or 7 (the whole correction).  search_ms ends with the first k_search (event 4); retry_ms spans
-// the retry passes (events 5, 6: next to nothing when no read overflowed); emit_ms (events 6, 7) spans the offset kernels,
-// the host's wait for their totals and k_pack
-static int read_stage_times(talc_ctx* c, int last) {
+// kEvCovered, kEvStructured or kEvEmitted (the whole correction).  search_ms ends with the first k_search; retry_ms spans
+// the retry passes (next to nothing when no read overflowed); emit_ms spans the offset kernels, the host's wait for their
+// totals and k_pack
+static int read_stage_times(talc_ctx* c, CtxEvent last) {
   talc_timing& t = c->timing;
-  HIPCHK(hipEventElapsedTime(&t.encode_ms, c->ev[0], c->ev[1]));
-  HIPCHK(hipEventElapsedTime(&t.coverage_ms, c->ev[1], c->ev[2]));
-  if (last >= 3) HIPCHK(hipEventElapsedTime(&t.structure_ms, c->ev[2], c->ev[3]));
-  if (last >= 7) {
-    HIPCHK(hipEventElapsedTime(&t.search_ms, c->ev[3], c->ev[4]));
-    HIPCHK(hipEventElapsedTime(&t.retry_ms, c->ev[5], c->ev[6]));
-    HIPCHK(hipEventElapsedTime(&t.emit_ms, c->ev[6], c->ev[7]));
+  HIPCHK(hipEventElapsedTime(&t.encode_ms, c->ev[kEvBegin], c->ev[kEvEncoded]));
+  HIPCHK(hipEventElapsedTime(&t.coverage_ms, c->ev[kEvEncoded], c->ev[kEvCovered]));
+  if (last >= kEvStructured) HIPCHK(hipEventElapsedTime(&t.structure_ms, c->ev[kEvCovered], c->ev[kEvStructured]));
+  if (last >= kEvEmitted) {
+    HIPCHK(hipEventElapsedTime(&t.search_ms, c->ev[kEvStructured], c->ev[kEvSearched]));
+    HIPCHK(hipEventElapsedTime(&t.retry_ms, c->ev[kEvRetry0], c->ev[kEvRetry1]));
+    HIPCHK(hipEventElapsedTime(&t.emit_ms, c->ev[kEvRetry1], c->ev[kEvEmitted]));
   }
   return TALC_OK;
 }
@@ -1161,13 +1176,13 @@ int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipSetDevice(c->device));
   int rc;
   if ((rc = prepare_strand(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvBegin], c->stream));
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvEncoded], c->stream));
   if ((rc = launch_coverage(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[2], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvCovered], c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((rc = read_stage_times(c, 2)) || (rc = vote_time(c))) return rc;
+  if ((rc = read_stage_times(c, kEvCovered)) || (rc = vote_time(c))) return rc;
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   return TALC_OK;
 }

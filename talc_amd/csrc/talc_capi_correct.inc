@@ -136,7 +136,7 @@ static TraceBuf trace_buf(const talc_ctx* c, const TraceHost* th) {
   return tb;
 }
 
-// encode -> coverage -> k_structure on the context's stream, events 0 .. 3 around them: what run_pipeline and the test hook
+// encode -> coverage -> k_structure on the context's stream, events kEvBegin .. kEvStructured around them: what run_pipeline and the test hook
 // talc_batch_structure share (the hook stops here, so the region lists are still as k_structure left them)
 static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
@@ -144,17 +144,17 @@ static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   if ((rc = prepare_strand(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[0], s));
+  HIPCHK(hipEventRecord(c->ev[kEvBegin], s));
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[1], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEncoded], s));
   if ((rc = launch_coverage(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[2], s));
+  HIPCHK(hipEventRecord(c->ev[kEvCovered], s));
   HIPCHK(hipMemsetAsync(batch_stats(c), 0, kBatchStatsWords * sizeof(uint32_t), s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_structure, dim3(b->n_reads), dim3(64), 0, s, c->dp, c->view, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
                        b->d_cov.get(), b->d_covw.get(), b->d_nin.get(), b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_headcov.get(), b->n_reads, tb, traceRead, batch_stats(c));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[3], s));
+  HIPCHK(hipEventRecord(c->ev[kEvStructured], s));
   return TALC_OK;
 }
 
@@ -203,7 +203,7 @@ static int launch_search(talc_ctx* c, talc_batch* b, const Stage& st, const uint
   return TALC_OK;
 }
 
-// the first pass: every read, in queue order, through the context's stage (event 4 after it); the states stay on the device
+// the first pass: every read, in queue order, through the context's stage (kEvSearched after it); the states stay on the device
 static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
   hipStream_t s = c->stream;
   int rc;
@@ -215,7 +215,7 @@ static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uin
     ensure_edge_boxes(c, c->stage);
     if ((rc = launch_search(c, b, c->stage, b->d_order.get(), b->n_reads, tb, traceRead, true))) return rc;
   }
-  HIPCHK(hipEventRecord(c->ev[4], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSearched], s));
   return TALC_OK;
 }
 
@@ -239,7 +239,7 @@ static int emit_offsets(talc_ctx* c, talc_batch* b, bool map, const uint64_t** t
   return TALC_OK;
 }
 
-// retry passes for the reads whose scratch overflowed (events 5 and 6 around them; b->h_state holds the states of the
+// retry passes for the reads whose scratch overflowed (kEvRetry0 and kEvRetry1 around them; b->h_state holds the states of the
 // first pass, fetch_states): buffers sized from the batch's longest
 // read (a path can no longer outgrow its buffer), counted capacities x 8, then x 64 for whatever is still left
 static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint32_t traceRead) {
@@ -248,7 +248,7 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
   std::vector<uint32_t> retry;
   for (uint32_t r = 0; r < b->n_reads; ++r) if (b->h_state[r].overflow) retry.push_back(r);
   c->timing.n_retried = (uint32_t)retry.size();
-  HIPCHK(hipEventRecord(c->ev[5], s));
+  HIPCHK(hipEventRecord(c->ev[kEvRetry0], s));
   for (uint32_t scale = 8; scale <= 64 && !retry.empty(); scale *= 8) {
     // The first pass has left a complete, valid batch: a retry stage that does not fit the device is not an error of the
     // batch.  The reads still flagged stay as the first pass left them (passed through, overflow set = TALC_READ_ERROR)
@@ -272,11 +272,11 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
     for (uint32_t r : retry) if (b->h_state[r].overflow) again.push_back(r);
     retry.swap(again);
   }
-  HIPCHK(hipEventRecord(c->ev[6], s));
+  HIPCHK(hipEventRecord(c->ev[kEvRetry1], s));
   return TALC_OK;
 }
 
-// dense packing: k_pack into b->d_dense, `total` bytes at the offsets emit_offsets left (event 7 after it)
+// dense packing: k_pack into b->d_dense, `total` bytes at the offsets emit_offsets left (kEvEmitted after it)
 static int pack_dense(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
   // the record buffer of an earlier pass over this batch is kept when it is large enough
@@ -286,12 +286,12 @@ static int pack_dense(talc_ctx* c, talc_batch* b, uint64_t total) {
     hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
                        b->n_reads, c->p.reverse ? 1 : 0, b->rev_flags());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[7], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEmitted], s));
   return TALC_OK;
 }
 
 // the correction map (talc_ctx_set_map): k_pack_map into b->d_segs, `total` segments (2 R + 1 for a read k_search
-// reassembled, 1 for every other) at the offsets emit_offsets left (event 8 after it)
+// reassembled, 1 for every other) at the offsets emit_offsets left (kEvPackMap after it)
 static int pack_map(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
   if (b->d_segs && b->segs_cap < total) b->d_segs.reset();
@@ -301,7 +301,7 @@ static int pack_map(talc_ctx* c, talc_batch* b, uint64_t total) {
                        b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0,
                        b->rev_flags());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[8], s));
+  HIPCHK(hipEventRecord(c->ev[kEvPackMap], s));
   return TALC_OK;
 }
 
@@ -319,7 +319,7 @@ static int read_timing(talc_ctx* c, talc_batch* b, bool map, uint32_t n_failed, 
   if (map) HIPCHK(hipMemcpyAsync(b->h_seg_off.data(), b->d_seg_off.get(), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(land, c->d_counters.get(), kCntWaveLog * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if ((rc = read_stage_times(c, 7))) return rc;
+  if ((rc = read_stage_times(c, kEvEmitted))) return rc;
   c->timing.n_trail_steps = land[kCntSteps];
   c->timing.n_dp_cells = land[kCntCells];
   c->timing.n_failed = n_failed;
@@ -345,8 +345,8 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   if ((rc = launch_structure(c, b, tb, traceRead))) return rc;
   if ((rc = order_queue(c, b))) return rc;
   if ((rc = search_first_pass(c, b, tb, traceRead))) return rc;
-  HIPCHK(hipEventRecord(c->ev[5], c->stream));   // (no read overflowed: there is no retry pass between these two)
-  HIPCHK(hipEventRecord(c->ev[6], c->stream));
+  HIPCHK(hipEventRecord(c->ev[kEvRetry0], c->stream));   // (no read overflowed: there is no retry pass between these two)
+  HIPCHK(hipEventRecord(c->ev[kEvRetry1], c->stream));
   if ((rc = emit_offsets(c, b, map, &tot))) return rc;
   if (tot[kTotOverflow]) {   // some read's scratch ran out: the states to the host, the retry passes, the offsets again
     if ((rc = fetch_states(c, b))) return rc;
@@ -357,7 +357,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   if ((rc = pack_dense(c, b, tot[kTotBytes]))) return rc;
   if (map && (rc = pack_map(c, b, tot[kTotSegs]))) return rc;
   if ((rc = read_timing(c, b, map, n_failed, &counters)) || (rc = vote_time(c))) return rc;
-  if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[7], c->ev[8]));
+  if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[kEvEmitted], c->ev[kEvPackMap]));
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
 #endif
@@ -383,7 +383,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false; b->supported = false;
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
-  if ((rc = read_stage_times(c, 3)) || (rc = vote_time(c))) return rc;
+  if ((rc = read_stage_times(c, kEvStructured)) || (rc = vote_time(c))) return rc;
   b->structured = true;
   return TALC_OK;
 }
@@ -500,7 +500,7 @@ int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_
   return TALC_OK;
 }
 
-// the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (events 9, 10)
+// the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (kEvMaskCase0, kEvMaskCase1)
 static int mask_dense(talc_ctx* c, talc_batch* b) {
   if (b->masked) return TALC_OK;
   hipStream_t s = c->stream;
@@ -508,13 +508,13 @@ static int mask_dense(talc_ctx* c, talc_batch* b) {
   if (b->d_masked && b->masked_cap < total) b->d_masked.reset();
   if (!b->d_masked) { b->masked_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_masked.alloc(c->cache, b->masked_cap)); }
   if (total) HIPCHK(hipMemcpyAsync(b->d_masked.get(), b->d_dense.get(), total, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[9], s));
+  HIPCHK(hipEventRecord(c->ev[kEvMaskCase0], s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_mask_case, dim3(b->n_reads), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), b->d_dense_off.get(), b->d_masked.get(), b->n_reads);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[10], s));
+  HIPCHK(hipEventRecord(c->ev[kEvMaskCase1], s));
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->mask_case_ms, c->ev[9], c->ev[10]));
+  HIPCHK(hipEventElapsedTime(&c->mask_case_ms, c->ev[kEvMaskCase0], c->ev[kEvMaskCase1]));
   b->masked = true;
   return TALC_OK;
 }
@@ -530,7 +530,7 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
 }
 
 // ---- trimmed and split output (docs/trim_split.md): k_piece_count over the map, the reads' offsets on the host (as
-// pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (events 14 .. 17 around the two kernels)
+// pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (kEvPieceCount0 .. kEvPiecePack1 around the two kernels)
 int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, int soft_mask) {
   if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   if (mode != TALC_PIECES_TRIM && mode != TALC_PIECES_SPLIT) return fail(TALC_ERR_INVALID, "piece mode %d is neither TALC_PIECES_TRIM nor TALC_PIECES_SPLIT", mode);
@@ -543,10 +543,10 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   const bool masked = mode == TALC_PIECES_TRIM && soft_mask;   // (a split piece has no weak byte)
   if (masked && (rc = mask_dense(c, b))) return rc;
   if (!b->d_piece_count) HIPCHK(b->d_piece_count.alloc(c->cache, std::max<uint32_t>(n, 1)));
-  HIPCHK(hipEventRecord(c->ev[14], s));
+  HIPCHK(hipEventRecord(c->ev[kEvPieceCount0], s));
   if (n) hipLaunchKernelGGL(k_piece_count, dim3(n), dim3(64), 0, s, b->d_segs.get(), b->d_seg_off.get(), n, mode, min_len, b->d_piece_count.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[15], s));
+  HIPCHK(hipEventRecord(c->ev[kEvPieceCount1], s));
   std::vector<PieceCount> counts(n);
   if (n) HIPCHK(hipMemcpyAsync(counts.data(), b->d_piece_count.get(), (size_t)n * sizeof(PieceCount), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -568,16 +568,16 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   if (!b->d_read_piece_off) { HIPCHK(b->d_read_piece_off.alloc(c->cache, n + 1)); HIPCHK(b->d_read_byte_off.alloc(c->cache, n + 1)); }
   HIPCHK(hipMemcpyAsync(b->d_read_piece_off.get(), b->h_read_piece_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(b->d_read_byte_off.get(), b->h_read_byte_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[16], s));
+  HIPCHK(hipEventRecord(c->ev[kEvPiecePack0], s));
   if (n && np)
     hipLaunchKernelGGL(k_piece_pack, dim3(n), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), masked ? b->d_masked.get() : b->d_dense.get(),
                        b->d_dense_off.get(), n, mode, min_len, b->d_read_piece_off.get(), b->d_read_byte_off.get(), b->d_pieces.get(),
                        b->d_piece_off.get(), b->d_piece_bytes.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[17], s));
+  HIPCHK(hipEventRecord(c->ev[kEvPiecePack1], s));
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->piece_count_ms, c->ev[14], c->ev[15]));
-  HIPCHK(hipEventElapsedTime(&c->piece_pack_ms, c->ev[16], c->ev[17]));
+  HIPCHK(hipEventElapsedTime(&c->piece_count_ms, c->ev[kEvPieceCount0], c->ev[kEvPieceCount1]));
+  HIPCHK(hipEventElapsedTime(&c->piece_pack_ms, c->ev[kEvPiecePack0], c->ev[kEvPiecePack1]));
   b->pieced = true;
   return TALC_OK;
 }
@@ -627,15 +627,15 @@ int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
   const bool records = b->corrected;
   b->solidity = false; b->solidityCorrected = false;
   if (!b->encoded && (rc = launch_encode(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[11], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSolidity0], s));
   if ((rc = launch_solidity(c, b, false))) return rc;
-  HIPCHK(hipEventRecord(c->ev[12], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSolidity1], s));
   if (records && (rc = launch_solidity(c, b, true))) return rc;
-  HIPCHK(hipEventRecord(c->ev[13], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSolidity2], s));
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->sol_raw_ms, c->ev[11], c->ev[12]));
+  HIPCHK(hipEventElapsedTime(&c->sol_raw_ms, c->ev[kEvSolidity0], c->ev[kEvSolidity1]));
   c->sol_corr_ms = 0;
-  if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[12], c->ev[13]));
+  if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[kEvSolidity1], c->ev[kEvSolidity2]));
   if ((rc = vote_time(c))) return rc;
   b->solidity = true; b->solidityCorrected = records;
   return TALC_OK;

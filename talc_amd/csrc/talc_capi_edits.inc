@@ -17,7 +17,7 @@ struct EditIn {
 };
 // ... and what it leaves: an EditOut (talc_capi.hip)
 
-// events 18 .. 23: around the first k_edit_align rounds, after k_edit_count, around the second rounds, after k_edit_pack.
+// events kEvEditAlignA0 .. kEvEditPack: around the first k_edit_align rounds, after k_edit_count, around the second rounds, after k_edit_pack.
 // scratch_bytes: the budget of the rounds (kEditScratchBytes; the test hook passes a small one to make several rounds).
 // first_distance (may be null): the distance the DP of the first task found, -1 when there was no task.
 static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t scratch_bytes, EditOut& out, int32_t* first_distance) {
@@ -60,12 +60,12 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
     }
     return TALC_OK;
   };
-  HIPCHK(hipEventRecord(c->ev[18], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditAlignA0], s));
   if ((rc = align(0))) return rc;
-  HIPCHK(hipEventRecord(c->ev[19], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditAlignA1], s));
   if (n) hipLaunchKernelGGL(k_edit_count, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_rows.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[20], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditCount], s));
   out.h_rows.assign(n, EditRow{0u, 0u, 0u, 0u, 0u, 0u});
   if (n) HIPCHK(hipMemcpyAsync(out.h_rows.data(), d_rows.get(), (size_t)n * sizeof(EditRow), hipMemcpyDeviceToHost, s));
   if (first_distance) {
@@ -82,16 +82,16 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
   if (!out.d_ops) { out.ops_cap = std::max<uint64_t>(nops, 1); HIPCHK(out.d_ops.alloc(c->cache, out.ops_cap)); }
   HIPCHK(hipMemsetAsync(out.d_ops.get(), 0, std::max<uint64_t>(nops, 1) * sizeof(uint32_t), s));   // the runs are added
   HIPCHK(hipMemcpyAsync(d_op_off.get(), out.h_op_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[21], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditAlignB0], s));
   if ((rc = align(1))) return rc;
-  HIPCHK(hipEventRecord(c->ev[22], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditAlignB1], s));
   if (n) hipLaunchKernelGGL(k_edit_pack, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_op_off.get(), out.d_ops.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[23], s));
+  HIPCHK(hipEventRecord(c->ev[kEvEditPack], s));
   HIPCHK(hipStreamSynchronize(s));
   float a0 = 0, a1 = 0, p0 = 0, p1 = 0;
-  HIPCHK(hipEventElapsedTime(&a0, c->ev[18], c->ev[19])); HIPCHK(hipEventElapsedTime(&p0, c->ev[19], c->ev[20]));
-  HIPCHK(hipEventElapsedTime(&a1, c->ev[21], c->ev[22])); HIPCHK(hipEventElapsedTime(&p1, c->ev[22], c->ev[23]));
+  HIPCHK(hipEventElapsedTime(&a0, c->ev[kEvEditAlignA0], c->ev[kEvEditAlignA1])); HIPCHK(hipEventElapsedTime(&p0, c->ev[kEvEditAlignA1], c->ev[kEvEditCount]));
+  HIPCHK(hipEventElapsedTime(&a1, c->ev[kEvEditAlignB0], c->ev[kEvEditAlignB1])); HIPCHK(hipEventElapsedTime(&p1, c->ev[kEvEditAlignB1], c->ev[kEvEditPack]));
   c->edit_align_ms = a0 + a1; c->edit_pack_ms = p0 + p1;
   return TALC_OK;
 }

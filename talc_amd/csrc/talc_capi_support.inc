@@ -1,7 +1,7 @@
 // talc_capi_support.inc — host side of the per-base support (docs/base_support.md, talc_kernels_support.h); included by
 // talc_capi.hip inside its extern "C" block, after talc_capi_edits.inc.
 
-// k_base_support over the batch's codes (RAW) or its dense records (RECORD), events 26 and 27 around it.  The byte buffer is
+// k_base_support over the batch's codes (RAW) or its dense records (RECORD), kEvSupport0 and kEvSupport1 around it.  The byte buffer is
 // the batch's, sized exactly; the buffer of an earlier call is kept when it is large enough.
 int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p) {
   if (!c || !b || b->ctx != c || !p) return fail(TALC_ERR_INVALID, "bad context/batch/params");
@@ -23,16 +23,16 @@ int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p)
   if (b->d_support && b->support_cap < total) b->d_support.reset();
   if (!b->d_support) { b->support_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_support.alloc(c->cache, b->support_cap)); }
   // (the buffer is an allocation of its own, 256-byte aligned: k_base_support takes a byte's alignment from its offset)
-  HIPCHK(hipEventRecord(c->ev[26], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSupport0], s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_base_support, dim3(b->n_reads), dim3(64), 0, s, c->view, records ? b->d_dense.get() : b->d_codes.get(),
                        records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
                        c->p.reverse ? 1 : 0, b->rev_flags(), c->p.min_count, b->n_reads, p->phred ? 1 : 0, p->phred ? p->qmin : 0u,
                        p->phred ? p->qmax - p->qmin : 0u, b->d_support.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[27], s));
+  HIPCHK(hipEventRecord(c->ev[kEvSupport1], s));
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->support_ms, c->ev[26], c->ev[27]));
+  HIPCHK(hipEventElapsedTime(&c->support_ms, c->ev[kEvSupport0], c->ev[kEvSupport1]));
   if ((rc = vote_time(c))) return rc;
   b->supported = true; b->supportRecords = records;
   return TALC_OK;

@@ -228,6 +228,14 @@ TALC_HD uint8_t ascii_to_code(uint8_t c) {
     default: return 4;
   }
 }
+// ascii_to_code as selects, for code that asks for several bytes at once and must not branch between them (the byte in a
+// register's low 8 bits).  complement_code of what it returns is `code ^ 3` for a code below 4.
+TALC_HD uint32_t ascii_to_code_select(uint32_t c) {
+  const uint32_t up = c & 0xDFu;                    // 'a' -> 'A': no other byte becomes a letter
+  const uint32_t two = (up >> 1) & 3u;              // A, C, G, T -> 0, 1, 3, 2
+  const bool letter = (up == 'A') | (up == 'C') | (up == 'G') | (up == 'T');
+  return letter ? (two ^ (two >> 1)) : 4u;
+}
 TALC_HD uint8_t complement_code(uint8_t c) { return c < 4 ? (uint8_t)(3 - c) : (uint8_t)4; }
 TALC_HD char code_to_ascii(uint8_t c) { return c == 0 ? 'A' : c == 1 ? 'C' : c == 2 ? 'G' : c == 3 ? 'T' : 'N'; }
 

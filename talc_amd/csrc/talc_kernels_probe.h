@@ -225,6 +225,7 @@ k_coverage(TableView T, const uint8_t* __restrict__ codes, const uint64_t* __res
   const bool anyN = s_anyN != 0u;
 
   // the 64 window bits that start with base q (first base most significant), and the N bits [q, q + 64)
+  // (the layout and its guard words are KmerWindow's, talc_kmer_window.h: a change there is a change here)
   auto window = [&](uint32_t q) -> uint64_t {
     const uint32_t w = q >> 5, sh = 2 * (q & 31);
     const uint64_t hi = s_pack[w], lo = s_pack[w + 1];

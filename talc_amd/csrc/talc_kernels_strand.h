@@ -6,16 +6,15 @@
 // before k_encode: the flag decides how k_encode, k_pack, k_pack_map and k_solidity treat the read.
 #pragma once
 #include "talc_kernels_build.h"      // dev_revcomp
-#include "talc_kernels_probe.h"
-#include "talc_kernels_solidity.h"   // HomeBucket, load_home_bucket
+#include "talc_kmer_window.h"
 
 namespace talc {
 
 struct StrandRow { uint32_t nKmers, fwdSolid, fwdIn, rcSolid, rcIn, reverse; };
 
-// The shape of k_solidity: one wave per read, VOTE_TILE positions per pass, the pass's window of VOTE_TILE + K - 1 bases
-// staged in LDS as 2-bit words and an N bitmap straight from the raw bytes (what ascii_to_code does, as selects), a k-mer
-// one funnel shift away; its reverse complement comes from it (dev_revcomp), never from a second window.  A pass:
+// The shape of k_solidity: one wave per read, VOTE_TILE positions per pass, the pass's window staged straight from the raw
+// bytes and the round of count lookups as talc_kmer_window.h has them; a k-mer is one funnel shift away, its reverse
+// complement comes from it (dev_revcomp), never from a second window.  This kernel's own, per pass:
 //   * the hash of every M-mer of the window and of that M-mer's reverse complement go to LDS: the presence filter's block
 //     is chosen by a k-mer's minimizer (talc_common.h), and the M-mers of the reverse complement of a k-mer are the reverse
 //     complements of the k-mer's own, at the same window positions;
@@ -23,21 +22,22 @@ struct StrandRow { uint32_t nKmers, fwdSolid, fwdIn, rcSolid, rcIn, reverse; };
 //     before the first is looked at.  The filter has no false negatives: what it refuses has count 0, exactly;
 //   * the survivors (about 7 % of the forward k-mers of a raw read, next to none in the orientation the short reads do
 //     not have) are probed on a masked branch-free path, one orientation at a time and only when some lane has a
-//     survivor in it: home buckets asked for together, the chains that go on finished by probe_bucket;
+//     survivor in it (probe_round);
 //   * __ballot turns each group of 64 positions into four words — solid and IN, forward and reverse complement —, the
 //     counts are their populations: wave-uniform integer work.
 #define VOTE_UNROLL 4
 #define VOTE_TILE (64 * VOTE_UNROLL)
+static_assert(VOTE_TILE == KWIN_TILE, "a pass is one window");
 #define VOTE_MH (VOTE_TILE + 64)   /* M-mer positions of a window: VOTE_TILE + K - M <= VOTE_TILE + 19 */
 
 __global__ void __launch_bounds__(64)
 k_strand_vote(TableView T, const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offsets, uint32_t min_count, uint32_t n_reads,
               StrandRow* __restrict__ rows, uint8_t* __restrict__ flags) {
-  __shared__ uint64_t s_pack[VOTE_TILE / 32 + 8];    // base i of the window at bits [63 - 2 (i % 32) - 1, 63 - 2 (i % 32)] of word i / 32
-  __shared__ uint64_t s_nmask[VOTE_TILE / 64 + 4];   // bit (i % 64) of word i / 64: base i is N
+  __shared__ uint64_t s_pack[KWIN_PACK_WORDS];
+  __shared__ uint64_t s_nmask[KWIN_N_WORDS];
   __shared__ uint32_t s_mhF[VOTE_MH], s_mhR[VOTE_MH];   // hash of the M-mer that starts at a window position, and of its reverse complement
-  static_assert(sizeof(s_pack) == 64 * 2 && sizeof(s_nmask) == 64, "one 8-base group per lane fills both arrays");
-  static_assert(VOTE_MH + 32 <= 32 * (VOTE_TILE / 32 + 7), "window() reads the word of an M-mer's first base and the one after it");
+  static_assert(VOTE_MH + 32 <= 32 * (KWIN_PACK_WORDS - 1), "window() reads the word of an M-mer's first base and the one after it");
+  const KmerWindow win = {s_pack, s_nmask};
   const uint32_t r = blockIdx.x;
   if (r >= n_reads) return;
   const uint32_t lane = threadIdx.x;
@@ -45,23 +45,7 @@ k_strand_vote(TableView T, const uint8_t* __restrict__ raw, const uint64_t* __re
   const uint64_t rb = offsets[r];
   const uint32_t L = (uint32_t)(offsets[r + 1] - rb);
   const uint32_t n = L >= K ? L - K + 1 : 0;
-  const uint8_t TALC_AS1* src = (const uint8_t TALC_AS1*)(raw + rb);
-  auto code_of = [&](uint32_t c) -> uint32_t {      // ascii_to_code as selects
-    const uint32_t up = c & 0xDFu;                  // 'a' -> 'A': no other byte becomes a letter
-    const uint32_t two = (up >> 1) & 3u;            // A, C, G, T -> 0, 1, 3, 2
-    const bool letter = (up == 'A') | (up == 'C') | (up == 'G') | (up == 'T');
-    return letter ? (two ^ (two >> 1)) : 4u;
-  };
-  auto window = [&](uint32_t q) -> uint64_t {
-    const uint32_t w = q >> 5, sh = 2 * (q & 31);
-    const uint64_t hi = s_pack[w], lo = s_pack[w + 1];
-    return (sh == 0) ? hi : ((hi << sh) | (lo >> (64 - sh)));
-  };
-  auto nbits = [&](uint32_t q) -> uint64_t {
-    const uint32_t nw = q >> 6, nsh = q & 63;
-    const uint64_t nlo = s_nmask[nw], nhi = s_nmask[nw + 1];
-    return (nsh == 0) ? nlo : ((nlo >> nsh) | (nhi << (64 - nsh)));
-  };
+  const SeqView seq = {(const uint8_t TALC_AS1*)(raw + rb), L, true, false};   // raw bytes, as they lie
   const uint32_t kshift = 64 - 2 * K;
   const uint64_t nkmask = (1ULL << K) - 1;          // K <= 31
   const uint64_t cap = T.capacity;                  // >= 64: HostTable::capacity_for never gives less
@@ -74,25 +58,11 @@ k_strand_vote(TableView T, const uint8_t* __restrict__ raw, const uint64_t* __re
   for (uint32_t p0 = 0; p0 < n; p0 += VOTE_TILE) {
     const uint32_t cnt = min((uint32_t)VOTE_TILE, n - p0);
     const uint32_t wlen = cnt + K - 1;              // p0 + wlen <= L
-    {   // stage the window: lane g packs bases 8 g .. 8 g + 7 (zeros beyond the window); the 8 byte loads are asked for
-        // together, at addresses clamped into the window, and masked afterwards
-      uint32_t raw8[8];
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) raw8[j] = src[p0 + min(8 * lane + j, wlen - 1)];
-      uint32_t w = 0, nm = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) {
-        const uint32_t c = (8 * lane + j < wlen) ? code_of(raw8[j]) : 0u;
-        nm |= (c > 3u ? 1u : 0u) << j;
-        w |= (c & 3u) << (14 - 2 * j);
-      }
-      reinterpret_cast<uint16_t*>(s_pack)[lane ^ 3u] = (uint16_t)w;   // group 0 of four = the top 16 bits of its word
-      reinterpret_cast<uint8_t*>(s_nmask)[lane] = (uint8_t)nm;
-    }
+    win.stage(seq, p0, wlen, lane);
     __syncthreads();
     if (filter) {   // (an M-mer that holds an N belongs only to k-mers that are not asked for: its hash is never looked at)
       for (uint32_t q = lane; q < cnt + nwin - 1; q += 64) {
-        const uint64_t mm = window(q) >> (64 - 2 * M);
+        const uint64_t mm = win.window(q) >> (64 - 2 * M);
         s_mhF[q] = mmer_hash((uint32_t)mm);
         s_mhR[q] = mmer_hash((uint32_t)dev_revcomp(mm, M));
       }
@@ -105,8 +75,8 @@ k_strand_vote(TableView T, const uint8_t* __restrict__ raw, const uint64_t* __re
 #pragma unroll
     for (int u = 0; u < VOTE_UNROLL; ++u) {
       const uint32_t q = (uint32_t)u * 64u + lane;
-      ask[u] = q < cnt && (nbits(q) & nkmask) == 0;                   // no N among bases [q, q + K)
-      kmF[u] = window(q) >> kshift;
+      ask[u] = q < cnt && (win.nbits(q) & nkmask) == 0;                  // no N among bases [q, q + K)
+      kmF[u] = win.window(q) >> kshift;
       kmR[u] = dev_revcomp(kmF[u], K);
       fwF[u] = fwR[u] = ~0ULL; fmF[u] = fmR[u] = 1ULL;               // (no filter: every k-mer asked for is probed)
       if (filter && ask[u]) {
@@ -126,37 +96,15 @@ k_strand_vote(TableView T, const uint8_t* __restrict__ raw, const uint64_t* __re
       goR[u] = ask[u] && (fwR[u] & fmR[u]) == fmR[u];
       someF |= goF[u]; someR |= goR[u];
     }
-    // one orientation at a time: the home buckets of the lane's survivors on one branch-free path (a position without
-    // one reads bucket 0 and ignores it), then the chains; the counts end as ballot words
+    // one orientation at a time, the counts end as ballot words
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       if (__ballot(o ? someR : someF) == 0ull) continue;              // (wave-uniform: nothing of this pass survived)
-      uint32_t slot[VOTE_UNROLL];                                     // (capacity < 2^32)
-      HomeBucket bk[VOTE_UNROLL];
-#pragma unroll
-      for (int u = 0; u < VOTE_UNROLL; ++u) {
-        const bool go = o ? goR[u] : goF[u];
-        slot[u] = go ? (uint32_t)dev_home((o ? kmR[u] : kmF[u]) >> 2, cap) : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < VOTE_UNROLL; ++u) bk[u] = load_home_bucket(T.right + slot[u]);
       uint32_t solid = 0, in = 0;
-#pragma unroll
-      for (int u = 0; u < VOTE_UNROLL; ++u) {
-        if ((uint32_t)u * 64u >= cnt) break;                          // (wave-uniform)
-        const bool go = o ? goR[u] : goF[u];
-        const uint64_t km = o ? kmR[u] : kmF[u];
-        const uint64_t key = km >> 2;
-        const int b = (int)(km & 3);
-        const bool match = (bk[u].key & kKeyMask) == key;
-        uint32_t c = (go && match) ? bk[u].count_of(b) : 0u;
-        if (go && !match && bk[u].key != kEmptyKey) {
-          BucketRegs br;
-          if (probe_bucket(T.right, cap, key, br)) c = br.count_of(b);
-        }
-        solid += (uint32_t)__popcll(__ballot(c >= min_count));        // (MIN_COUNT >= 1: an absent k-mer is never solid)
+      probe_round<VOTE_UNROLL>(T.right, cap, o ? kmR : kmF, o ? goR : goF, cnt, [&](int, uint32_t c) {
+        solid += (uint32_t)__popcll(__ballot(c >= min_count));
         in += (uint32_t)__popcll(__ballot(c > min_count));
-      }
+      });
       if (o) { row.rcSolid += solid; row.rcIn += in; }
       else { row.fwdSolid += solid; row.fwdIn += in; }
     }

@@ -15,9 +15,8 @@ namespace talc {
 // and the product below 2^32.  Entry 0 is 0, so a base no k-mer holds gets the lowest quality by the same expression.
 #define SUP_RCP_SHIFT 20
 
-// One wave per sequence, walked in order, SOL_TILE positions per pass: the staging, the probes and the ballots are those of
-// k_solidity (its text is left alone; what it exports — HomeBucket, load_home_bucket, probe_bucket, dev_home, the window
-// layout — is used here).  After the ballots:
+// One wave per sequence, walked in order, SOL_TILE positions per pass: the sequence view, the window and the probe round
+// are talc_kmer_window.h's, the pass and its unroll k_solidity's.  This kernel's own, after the ballots:
 //   * the wave-uniform solid words go to LDS (SUP_WORDS of them); cover[j] is the popcount of the K bits that end at
 //     position j, a field that lies in two adjacent words: a lane reads those two once for its four bases (K + 3 <= 34 bits);
 //   * the output is tiled by absolute address: a lane owns one aligned dword of the output buffer, computes its four bytes
@@ -32,11 +31,11 @@ __global__ void __launch_bounds__(64)
 k_base_support(TableView T, const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ offsets, const ReadState* __restrict__ state,
                int ascii, int reverse, const uint8_t* __restrict__ rev_flags, uint32_t min_count, uint32_t n_reads,
                int phred, uint32_t qmin, uint32_t qrange, uint8_t* __restrict__ out) {
-  __shared__ uint64_t s_pack[SOL_TILE / 32 + 8];    // (k_solidity's window)
-  __shared__ uint64_t s_nmask[SOL_TILE / 64 + 4];
+  __shared__ uint64_t s_pack[KWIN_PACK_WORDS];
+  __shared__ uint64_t s_nmask[KWIN_N_WORDS];
   __shared__ uint64_t s_sol[SUP_WORDS];             // bit (q % 64) of word q / 64: position p0 - 64 + q is solid
   __shared__ uint32_t s_rcp[32];                    // ceil(2^SUP_RCP_SHIFT / d)
-  static_assert(sizeof(s_pack) == 64 * 2 && sizeof(s_nmask) == 64, "one 8-base group per lane fills both arrays");
+  const KmerWindow win = {s_pack, s_nmask};
   const uint32_t r = blockIdx.x;
   if (r >= n_reads) return;
   const uint32_t lane = threadIdx.x;
@@ -48,27 +47,7 @@ k_base_support(TableView T, const uint8_t* __restrict__ seqs, const uint64_t* __
   // a record k_pack reverse complemented is read back to front (k_solidity); the codes are in S's orientation already
   const bool flip = state != nullptr && turned && state[r].status == TALC_READ_CORRECTED && state[r].overflow == 0;
   const bool oflip = state != nullptr ? flip : turned;   // S runs against the bytes the caller holds
-  const uint8_t TALC_AS1* src = (const uint8_t TALC_AS1*)(seqs + rb);
-  auto at_byte = [&](uint32_t i) -> uint32_t { return flip ? L - 1 - i : i; };
-  const uint32_t flipMask = flip ? 3u : 0u;
-  auto code_of = [&](uint32_t c) -> uint32_t {
-    const uint32_t up = c & 0xDFu;
-    const uint32_t two = (up >> 1) & 3u;
-    const bool letter = (up == 'A') | (up == 'C') | (up == 'G') | (up == 'T');
-    const uint32_t a = letter ? (two ^ (two >> 1)) : 4u;
-    const uint32_t code = ascii ? a : c;
-    return code ^ (code < 4u ? flipMask : 0u);
-  };
-  auto window = [&](uint32_t q) -> uint64_t {
-    const uint32_t w = q >> 5, sh = 2 * (q & 31);
-    const uint64_t hi = s_pack[w], lo = s_pack[w + 1];
-    return (sh == 0) ? hi : ((hi << sh) | (lo >> (64 - sh)));
-  };
-  auto nbits = [&](uint32_t q) -> uint64_t {
-    const uint32_t nw = q >> 6, nsh = q & 63;
-    const uint64_t nlo = s_nmask[nw], nhi = s_nmask[nw + 1];
-    return (nsh == 0) ? nlo : ((nlo >> nsh) | (nhi << (64 - nsh)));
-  };
+  const SeqView seq = {(const uint8_t TALC_AS1*)(seqs + rb), L, ascii != 0, flip};
   const uint32_t kshift = 64 - 2 * K;
   const uint64_t nkmask = (1ULL << K) - 1;          // K <= 31
   const uint64_t cap = T.capacity;
@@ -87,48 +66,18 @@ k_base_support(TableView T, const uint8_t* __restrict__ seqs, const uint64_t* __
 #pragma unroll
     for (int u = 0; u < SOL_UNROLL; ++u) sol[u] = 0;
     if (cnt) {             // (wave-uniform)
-      const uint32_t wlen = cnt + K - 1;
-      {
-        uint32_t raw8[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) raw8[j] = src[at_byte(p0 + min(8 * lane + j, wlen - 1))];
-        uint32_t w = 0, nm = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) {
-          const uint32_t c = (8 * lane + j < wlen) ? code_of(raw8[j]) : 0u;
-          nm |= (c > 3u ? 1u : 0u) << j;
-          w |= (c & 3u) << (14 - 2 * j);
-        }
-        reinterpret_cast<uint16_t*>(s_pack)[lane ^ 3u] = (uint16_t)w;
-        reinterpret_cast<uint8_t*>(s_nmask)[lane] = (uint8_t)nm;
-      }
+      win.stage(seq, p0, cnt + K - 1, lane);
       __syncthreads();
       uint64_t kmer[SOL_UNROLL];
-      uint32_t slot[SOL_UNROLL];
-      HomeBucket bk[SOL_UNROLL];
       bool ask[SOL_UNROLL];
 #pragma unroll
       for (int u = 0; u < SOL_UNROLL; ++u) {
         const uint32_t q = (uint32_t)u * 64u + lane;
-        ask[u] = q < cnt && (nbits(q) & nkmask) == 0;
-        kmer[u] = window(q) >> kshift;
-        slot[u] = ask[u] ? (uint32_t)dev_home(kmer[u] >> 2, cap) : 0u;
+        ask[u] = q < cnt && (win.nbits(q) & nkmask) == 0;             // no N among bases [q, q + K)
+        kmer[u] = win.window(q) >> kshift;
       }
-#pragma unroll
-      for (int u = 0; u < SOL_UNROLL; ++u) bk[u] = load_home_bucket(T.right + slot[u]);
-#pragma unroll
-      for (int u = 0; u < SOL_UNROLL; ++u) {
-        if ((uint32_t)u * 64u >= cnt) break;        // (wave-uniform; the words beyond stay 0)
-        const uint64_t key = kmer[u] >> 2;
-        const int b = (int)(kmer[u] & 3);
-        const bool match = (bk[u].key & kKeyMask) == key;
-        uint32_t c = (ask[u] && match) ? bk[u].count_of(b) : 0u;
-        if (ask[u] && !match && bk[u].key != kEmptyKey) {
-          BucketRegs br;
-          if (probe_bucket(T.right, cap, key, br)) c = br.count_of(b);
-        }
-        sol[u] = __ballot(c >= min_count);          // (MIN_COUNT >= 1: a position beyond cnt is never solid)
-      }
+      // (the words of groups without a position stay 0)
+      probe_round<SOL_UNROLL>(T.right, cap, kmer, ask, cnt, [&](int u, uint32_t c) { sol[u] = __ballot(c >= min_count); });
     }
     if (lane == 0) {
       s_sol[0] = prevWord;

@@ -31,6 +31,20 @@ ORC.orc_sort_anchors.argtypes = [C.c_double, C.c_void_p, C.c_void_p, C.c_int]
 ORC.orc_xdrop_right.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
 
 
+def test_byte_to_code_select_is_ascii_to_code():
+    """ascii_to_code_select (talc_common.h: what the k-mer window kernels stage with) for all 256 byte values, and
+    "select, then ^ 3 for a code below 4" against complement_code(ascii_to_code(c))."""
+    for f in (P.talc_pure_ascii_to_code_select, P.talc_pure_ascii_to_code, P.talc_pure_complement_code):
+        f.argtypes, f.restype = [C.c_uint32], C.c_uint32
+    seen = set()
+    for c in range(256):
+        code = P.talc_pure_ascii_to_code_select(c)
+        assert code == P.talc_pure_ascii_to_code(c) == ("ACGT".index(chr(c).upper()) if chr(c).upper() in "ACGT" else 4), c
+        assert (code ^ 3 if code < 4 else code) == P.talc_pure_complement_code(P.talc_pure_ascii_to_code(c)), c
+        seen.add(code)
+    assert seen == {0, 1, 2, 3, 4}
+
+
 def test_count_model_matches_oracle():
     rnd = random.Random(1)
     for alpha in (2.57, 0.67, 1.96, 3.3):
