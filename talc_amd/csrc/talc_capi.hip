@@ -175,8 +175,41 @@ struct talc_ctx {
 struct EditOut {
   std::vector<uint64_t> h_op_off;    // n_reads + 1: the reads' first op
   std::vector<EditRow> h_rows;       // n_reads
-  uint64_t ops_cap = 0;
   CachedBuf<uint32_t> d_ops;         // the ops of all reads, dense, sized exactly
+};
+
+// What a batch holds and what drops it.  A result is valid while its flag is set; "->" reads "is made from", and
+// what drops a result drops everything made from it:
+//   voted                                  from the raw bytes; never dropped
+//   encoded(encodedAuto) -> covered
+//   encoded -> solidity (raw rows), supported (RAW)
+//   encoded -> structured            (test hook; k_search consumes the region lists)
+//   encoded -> corrected(mapped) -> masked, pieced, edited, solidityCorrected, supported (RECORD)
+// A call that makes one result clears that result's flag first and sets it when everything has succeeded.
+struct BatchHolds {
+  bool voted = false;         // d_strand, d_strand_flag: k_strand_vote runs once per batch
+  bool encoded = false;       // d_codes
+  bool encodedAuto = false;   // ... made with the vote's flags: k_pack, k_pack_map, k_solidity and k_base_support then take them too
+  bool covered = false;       // d_cov, d_covw, d_nin
+  bool structured = false;    // the region lists are as k_structure left them: no search has touched them since
+  bool corrected = false;     // the records of the last correction: h_state, h_dense_off, d_dense
+  bool mapped = false;        // ... which kept its map: h_seg_off, d_segs
+  bool masked = false;        // d_masked: those records, RAW stretches in lower case
+  bool pieced = false, edited = false;                // their pieces, their edit scripts
+  bool solidity = false, solidityCorrected = false;   // d_sol_raw, the rows of the reads; d_sol_corr, those of the records
+  bool supported = false, supportRecords = false;     // d_support: of the reads, or of the records
+  // before a correction or talc_batch_structure launches anything: k_search edits the region lists in place, and a run that
+  // fails leaves no records (h_state, h_dense_off and d_dense would be a mixture of this run's and the last one's)
+  void drop_results() { structured = corrected = mapped = masked = solidity = solidityCorrected = pieced = edited = supported = false; }
+  // the codes were made under the other auto-strand setting: the batch is as if it were new, but for the vote
+  void drop_codes() { encoded = covered = false; drop_results(); }
+  bool has_records() const { return corrected; }
+  bool has_map() const { return corrected && mapped; }
+  bool has_mask() const { return has_map() && masked; }
+  bool has_pieces() const { return has_map() && pieced; }
+  bool has_edits() const { return has_map() && edited; }
+  bool has_support() const { return supported; }   // (of the reads: needs no records; of the records: dropped with them)
+  bool has_solidity(bool ofRecords) const { return solidity && (!ofRecords || (corrected && solidityCorrected)); }
 };
 
 struct talc_batch {
@@ -188,36 +221,17 @@ struct talc_batch {
   std::vector<uint32_t> h_tile_read, h_tile_start, h_chunk_read, h_chunk_start;
   std::vector<uint64_t> h_regoff;
   std::vector<uint64_t> h_outoff;
-  uint64_t out_capacity = 0;
-  bool encoded = false, covered = false, corrected = false;
-  bool structured = false;   // talc_batch_structure has run and no search has touched the region lists since
+  BatchHolds holds;
   // what comes back from the device with every correction: page-locked, from the context's pool and back to it
   HostArr<ReadState> h_state;
   HostArr<uint64_t> h_dense_off;
-  uint64_t dense_cap = 0;
-  // the correction map of the last correction, when the context kept one (talc_ctx_set_map)
-  bool mapped = false, masked = false;   // d_segs holds that correction's map; d_masked its records, RAW stretches in lower case
-  HostArr<uint64_t> h_seg_off;
-  uint64_t segs_cap = 0, masked_cap = 0;
-  // the solidity report (talc_batch_solidity): rows of the reads, and of the records of the correction before it
-  bool solidity = false, solidityCorrected = false;
-  // trimmed / split output (talc_batch_pieces): the pieces of the last correction's records, made since that correction
-  bool pieced = false;
-  std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte
-  uint64_t pieces_cap = 0, piece_bytes_cap = 0;
-  // the edit scripts (talc_batch_edits) of the last correction, made since that correction
-  bool edited = false;
-  // the per-base support (talc_batch_support) made since the last correction: of the records, or of the reads
-  bool supported = false, supportRecords = false;
-  uint64_t support_cap = 0;
-  // auto strand: k_strand_vote has run on d_raw (d_strand, d_strand_flag hold its result: the raw bytes never change, so
-  // it runs once per batch); encodedAuto: d_codes were made with the flags, and k_pack, k_pack_map, k_solidity take them too
-  bool voted = false, encodedAuto = false;
+  HostArr<uint64_t> h_seg_off;   // with the correction map
+  std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte (talc_batch_pieces)
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
   CachedBuf<uint8_t> d_strand_flag;   // ... and its choice as one byte per read: what the four kernels that orient a read take
-  const uint8_t* rev_flags() const { return encodedAuto ? d_strand_flag.get() : nullptr; }
+  const uint8_t* rev_flags() const { return holds.encodedAuto ? d_strand_flag.get() : nullptr; }
   CachedBuf<uint8_t> d_support;       // one byte per base (k_base_support), sized exactly
   EditOut edits;
   CachedBuf<uint8_t> d_piece_bytes;  // the kept pieces' bytes, dense (k_piece_pack), sized exactly
@@ -258,6 +272,18 @@ static_assert(sizeof(OutPiece) == sizeof(talc_piece) && sizeof(talc_piece) == 12
 static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) == 24 && sizeof(EditPart) == 32 && sizeof(EditTask) == 16, "k_edit_count writes talc_edit_row records");
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
+
+// What an entry point that takes a context and a batch checks first: they belong together and the `rest` of its arguments is there
+// (`msg`: the call's own wording).  enter() makes the context's device current as well; belong() where a state check comes before that.
+static int belong(const talc_ctx* c, const talc_batch* b, const char* msg, bool rest = true) {
+  if (!c || !b || b->ctx != c || !rest) return fail(TALC_ERR_INVALID, "%s", msg);
+  return TALC_OK;
+}
+static int enter(talc_ctx* c, talc_batch* b, const char* msg, bool rest = true) {
+  if (int rc = belong(c, b, msg, rest)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return TALC_OK;
+}
 
 template <typename T>
 static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
@@ -1050,7 +1076,7 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
     for (uint64_t p = 0; p < L; p += 4096) { b->h_chunk_read.push_back(r); b->h_chunk_start.push_back((uint32_t)p); }
   }
   b->h_koff[n_reads] = ko; b->h_regoff[n_reads] = ro; b->h_outoff[n_reads] = oo;
-  b->n_kmers = ko; b->out_capacity = oo;
+  b->n_kmers = ko;
   hipStream_t s = c->stream;
   int rc;
   HIPCHK(b->d_raw.alloc(c->cache, std::max<uint64_t>(b->n_bases, 1)));
@@ -1083,8 +1109,8 @@ uint64_t talc_batch_num_bases(const talc_batch* b) { return b ? b->n_bases : 0; 
 
 // ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes, kEvVote0 and kEvVote1 around it
 static int launch_vote(talc_ctx* c, talc_batch* b) {
-  if (!b->d_strand) HIPCHK(b->d_strand.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
-  if (!b->d_strand_flag) HIPCHK(b->d_strand_flag.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
+  HIPCHK(b->d_strand.ensure(c->cache, b->n_reads));
+  HIPCHK(b->d_strand_flag.ensure(c->cache, b->n_reads));
   HIPCHK(hipEventRecord(c->ev[kEvVote0], c->stream));
   if (b->n_reads)
     hipLaunchKernelGGL(k_strand_vote, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, b->d_raw.get(), b->d_offsets.get(), c->p.min_count, b->n_reads,
@@ -1092,7 +1118,7 @@ static int launch_vote(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[kEvVote1], c->stream));
   c->votePending = true;
-  b->voted = true;
+  b->holds.voted = true;
   return TALC_OK;
 }
 // the last vote's device time into c->vote_ms, once the stream has been waited for
@@ -1103,38 +1129,34 @@ static int vote_time(talc_ctx* c) {
   return TALC_OK;
 }
 // What every entry point that needs the batch's codes does first: codes made under the other setting are dropped with
-// everything that came of them (the batch is as if it were new), and with auto strand on the vote runs before k_encode
+// everything that came of them, and with auto strand on the vote runs before k_encode
 static int prepare_strand(talc_ctx* c, talc_batch* b) {
-  if (b->encoded && b->encodedAuto != c->autoStrand) {
-    b->encoded = b->covered = b->structured = b->corrected = b->mapped = b->masked = false;
-    b->solidity = b->solidityCorrected = b->pieced = b->edited = b->supported = false;
-  }
-  if (c->autoStrand && !b->voted) return launch_vote(c, b);
+  if (b->holds.encoded && b->holds.encodedAuto != c->autoStrand) b->holds.drop_codes();
+  if (c->autoStrand && !b->holds.voted) return launch_vote(c, b);
   return TALC_OK;
 }
 
 static int launch_encode(talc_ctx* c, talc_batch* b) {
-  b->encodedAuto = c->autoStrand;
+  b->holds.encodedAuto = c->autoStrand;
   if (!b->h_chunk_read.empty())
     hipLaunchKernelGGL(k_encode, dim3((unsigned)b->h_chunk_read.size()), dim3(256), 0, c->stream, b->d_raw.get(), b->d_codes.get(),
                        b->d_offsets.get(), b->d_chunk_read.get(), b->d_chunk_start.get(), c->p.reverse ? 1 : 0, b->rev_flags());
   HIPCHK(hipGetLastError());
-  b->encoded = true;
+  b->holds.encoded = true;
   return TALC_OK;
 }
 
 int talc_batch_strand(talc_ctx* c, talc_batch* b) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  HIPCHK(hipSetDevice(c->device));
   int rc;
-  if (!b->voted && (rc = launch_vote(c, b))) return rc;
+  if ((rc = enter(c, b, "bad context/batch"))) return rc;
+  if (!b->holds.voted && (rc = launch_vote(c, b))) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   return vote_time(c);
 }
 
 int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->voted) return fail(TALC_ERR_STATE, "no strand vote has run on this batch (talc_batch_strand, or auto strand and a call that needs the batch's codes)");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.voted) return fail(TALC_ERR_STATE, "no strand vote has run on this batch (talc_batch_strand, or auto strand and a call that needs the batch's codes)");
   HIPCHK(hipSetDevice(c->device));
   if (rows && b->n_reads) HIPCHK(hipMemcpyAsync(rows, b->d_strand.get(), (size_t)b->n_reads * sizeof(talc_strand), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1147,7 +1169,7 @@ static int launch_coverage(talc_ctx* c, talc_batch* b) {
                        b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(), b->d_tile_read.get(), b->d_tile_start.get(), b->d_cov.get(), b->d_covw.get(), b->d_nin.get(),
                        c->p.min_count);
   HIPCHK(hipGetLastError());
-  b->covered = true;
+  b->holds.covered = true;
   return TALC_OK;
 }
 
@@ -1172,12 +1194,11 @@ static int read_stage_times(talc_ctx* c, CtxEvent last) {
 }
 
 int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  HIPCHK(hipSetDevice(c->device));
   int rc;
+  if ((rc = enter(c, b, "bad context/batch"))) return rc;
   if ((rc = prepare_strand(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvBegin], c->stream));
-  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvEncoded], c->stream));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvCovered], c->stream));
@@ -1218,8 +1239,8 @@ static int expand_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint32_
 
 int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint32_t* jcounts, uint64_t* kmer_offsets,
                               int32_t* n_in_kmers) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
   HIPCHK(hipSetDevice(c->device));
   int rc;
   if ((rc = expand_coverage(c, b, counts, jcounts, nullptr))) return rc;
@@ -1231,8 +1252,8 @@ int talc_batch_fetch_coverage(talc_ctx* c, talc_batch* b, uint32_t* counts, uint
 // Test hook (not part of the reference surface): the degree bits k_coverage leaves beside every hit's colour
 static_assert(kCovDegLShift == kCovDegRShift + 3 && kCovDegKnown == (1u << (kCovDegRShift + 6)), "the degree byte of talc_batch_fetch_coverage_degrees");
 int talc_batch_fetch_coverage_degrees(talc_ctx* c, talc_batch* b, uint8_t* degrees) {
-  if (!c || !b || b->ctx != c || !degrees) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
-  if (!b->covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
+  if (int rc = belong(c, b, "bad context/batch/buffer", degrees)) return rc;
+  if (!b->holds.covered) return fail(TALC_ERR_STATE, "coverage has not been computed for this batch");
   HIPCHK(hipSetDevice(c->device));
   return expand_coverage(c, b, nullptr, nullptr, degrees);
 }

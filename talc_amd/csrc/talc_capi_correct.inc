@@ -145,7 +145,7 @@ static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   if ((rc = prepare_strand(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvBegin], s));
-  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvEncoded], s));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvCovered], s));
@@ -225,9 +225,9 @@ static int search_first_pass(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uin
 static int emit_offsets(talc_ctx* c, talc_batch* b, bool map, const uint64_t** totals) {
   hipStream_t s = c->stream;
   const uint32_t n = b->n_reads, nb = emit_blocks(n);
-  if (!b->d_emit) HIPCHK(b->d_emit.alloc(c->cache, nb + 1));
-  if (!b->d_dense_off) HIPCHK(b->d_dense_off.alloc(c->cache, n + 1));
-  if (map && !b->d_seg_off) HIPCHK(b->d_seg_off.alloc(c->cache, n + 1));
+  HIPCHK(b->d_emit.ensure(c->cache, nb + 1));
+  HIPCHK(b->d_dense_off.ensure(c->cache, n + 1));
+  if (map) HIPCHK(b->d_seg_off.ensure(c->cache, n + 1));
   EmitSum* const sums = b->d_emit.get();
   hipLaunchKernelGGL(k_emit_sums, dim3(nb), dim3(kEmitThreads), 0, s, b->d_state.get(), n, sums);
   hipLaunchKernelGGL(k_emit_offsets, dim3(nb), dim3(kEmitThreads), 0, s, b->d_state.get(), n, sums, b->d_dense_off.get(),
@@ -279,9 +279,7 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
 // dense packing: k_pack into b->d_dense, `total` bytes at the offsets emit_offsets left (kEvEmitted after it)
 static int pack_dense(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
-  // the record buffer of an earlier pass over this batch is kept when it is large enough
-  if (b->d_dense && b->dense_cap < total) b->d_dense.reset();
-  if (!b->d_dense) { b->dense_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_dense.alloc(c->cache, b->dense_cap)); }
+  HIPCHK(b->d_dense.ensure(c->cache, total));   // the record buffer of an earlier pass over this batch is kept when it is large enough
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack, dim3(b->n_reads), dim3(256), 0, s, b->d_out.get(), b->d_outoff.get(), b->d_state.get(), b->d_dense_off.get(), b->d_dense.get(),
                        b->n_reads, c->p.reverse ? 1 : 0, b->rev_flags());
@@ -294,8 +292,7 @@ static int pack_dense(talc_ctx* c, talc_batch* b, uint64_t total) {
 // reassembled, 1 for every other) at the offsets emit_offsets left (kEvPackMap after it)
 static int pack_map(talc_ctx* c, talc_batch* b, uint64_t total) {
   hipStream_t s = c->stream;
-  if (b->d_segs && b->segs_cap < total) b->d_segs.reset();
-  if (!b->d_segs) { b->segs_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_segs.alloc(c->cache, b->segs_cap)); }
+  HIPCHK(b->d_segs.ensure(c->cache, total));
   if (b->n_reads)
     hipLaunchKernelGGL(k_pack_map, dim3(b->n_reads), dim3(64), 0, s, b->d_state.get(), b->d_regions.get(), b->d_regoff.get(), b->d_mapedge.get(),
                        b->d_offsets.get(), b->d_seg_off.get(), b->d_segs.get(), b->n_reads, c->p.k, c->p.reverse ? 1 : 0,
@@ -333,12 +330,9 @@ static int read_timing(talc_ctx* c, talc_batch* b, bool map, uint32_t n_failed, 
 static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t traceRead) {
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  // (k_search edits the region lists in place; a run that fails leaves no records: h_state, h_dense_off and d_dense
-  //  would be a mixture of this run's and the last one's)
-  b->structured = false; b->corrected = false; b->mapped = false; b->masked = false;
-  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false; b->supported = false;
+  b->holds.drop_results();
   const bool map = c->map;
-  if (map && !b->d_mapedge) HIPCHK(b->d_mapedge.alloc(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
+  if (map) HIPCHK(b->d_mapedge.ensure(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);
   const uint64_t* counters = nullptr;
   const uint64_t* tot = nullptr;
@@ -361,7 +355,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
 #endif
-  b->corrected = true; b->mapped = map;
+  b->holds.corrected = true; b->holds.mapped = map;
   if (c->timing.n_failed) {   // the batch is valid: those reads are passed through unchanged with status TALC_READ_ERROR
     fail(TALC_WARN_READ_ERRORS, "%u read(s) exhausted the device scratch even in the retry pass (status TALC_READ_ERROR)", c->timing.n_failed);
     return TALC_WARN_READ_ERRORS;
@@ -370,28 +364,26 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
 }
 
 int talc_batch_correct(talc_ctx* c, talc_batch* b) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
   return run_pipeline(c, b, nullptr, 0xFFFFFFFFu);
 }
 
 // Test hook (not part of the reference surface): the pipeline up to and including k_structure, nothing of the search.
 int talc_batch_structure(talc_ctx* c, talc_batch* b) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  HIPCHK(hipSetDevice(c->device));
   int rc;
-  b->structured = false; b->corrected = false;
-  b->solidity = false; b->solidityCorrected = false; b->pieced = false; b->edited = false; b->supported = false;
+  if ((rc = enter(c, b, "bad context/batch"))) return rc;
+  b->holds.drop_results();
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
   if ((rc = read_stage_times(c, kEvStructured)) || (rc = vote_time(c))) return rc;
-  b->structured = true;
+  b->holds.structured = true;
   return TALC_OK;
 }
 
 // Test hook: the work queue of a batch talc_batch_structure has run on (see include/talc_hip.h)
 int talc_batch_order(talc_ctx* c, talc_batch* b, uint32_t* order, uint32_t* bucket) {
-  if (!c || !b || b->ctx != c || !order || !bucket) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
-  if (!b->structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
+  if (int rc = belong(c, b, "bad context/batch/buffer", order && bucket)) return rc;
+  if (!b->holds.structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
   HIPCHK(hipSetDevice(c->device));
   int rc;
   if ((rc = order_queue(c, b))) return rc;
@@ -410,8 +402,8 @@ int talc_batch_order(talc_ctx* c, talc_batch* b, uint32_t* order, uint32_t* buck
 int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint32_t* n_regions, double* lambda, uint32_t* in_span,
                                uint64_t* region_offsets, uint32_t* regions, uint32_t* region_hits, uint64_t region_capacity,
                                uint32_t* head_counts) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.structured) return fail(TALC_ERR_STATE, "talc_batch_structure has not run on this batch (or a correction has run since)");
   HIPCHK(hipSetDevice(c->device));
   uint64_t total = 0;
   for (uint32_t r = 0; r < b->n_reads; ++r) {
@@ -448,12 +440,12 @@ int talc_batch_fetch_structure(talc_ctx* c, talc_batch* b, int32_t* status, uint
   return TALC_OK;
 }
 
-uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->corrected) ? b->h_dense_off[b->n_reads] : 0; }
+uint64_t talc_batch_corrected_bytes(const talc_batch* b) { return (b && b->holds.has_records()) ? b->h_dense_off[b->n_reads] : 0; }
 
 // the records of a corrected batch into `out` (a host or a device buffer: `kind`; null: offsets and statuses only)
 static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_capacity, uint64_t* out_offsets, int32_t* status,
                          hipMemcpyKind kind, const char* what, bool masked = false) {
-  if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
+  if (!b->holds.has_records()) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t total = b->h_dense_off[b->n_reads];
   if (out_offsets) memcpy(out_offsets, b->h_dense_off.data(), (b->n_reads + 1) * 8);
@@ -471,23 +463,24 @@ static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_cap
 
 int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
                                int32_t* status) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
   return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output");
 }
 
-uint64_t talc_batch_num_segments(const talc_batch* b) { return (b && b->corrected && b->mapped) ? b->h_seg_off[b->n_reads] : 0; }
+uint64_t talc_batch_num_segments(const talc_batch* b) { return (b && b->holds.has_map()) ? b->h_seg_off[b->n_reads] : 0; }
 
-static int need_map(const talc_batch* b) {
-  if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
-  if (!b->mapped) return fail(TALC_ERR_STATE, "the batch's last correction kept no correction map (talc_ctx_set_map)");
+// what every call that reads the map does after its arguments: the batch has one; then the context's device is made current
+static int enter_map(talc_ctx* c, const talc_batch* b) {
+  if (!b->holds.has_records()) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
+  if (!b->holds.has_map()) return fail(TALC_ERR_STATE, "the batch's last correction kept no correction map (talc_ctx_set_map)");
+  HIPCHK(hipSetDevice(c->device));
   return TALC_OK;
 }
 
 int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_t capacity, uint64_t* seg_offsets) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   int rc;
-  if ((rc = need_map(b))) return rc;
-  HIPCHK(hipSetDevice(c->device));
+  if ((rc = belong(c, b, "bad context/batch"))) return rc;
+  if ((rc = enter_map(c, b))) return rc;
   const uint64_t total = b->h_seg_off[b->n_reads];
   if (seg_offsets) memcpy(seg_offsets, b->h_seg_off.data(), (b->n_reads + 1) * 8);
   if (segs) {
@@ -502,11 +495,10 @@ int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_
 
 // the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (kEvMaskCase0, kEvMaskCase1)
 static int mask_dense(talc_ctx* c, talc_batch* b) {
-  if (b->masked) return TALC_OK;
+  if (b->holds.has_mask()) return TALC_OK;
   hipStream_t s = c->stream;
   const uint64_t total = b->h_dense_off[b->n_reads];
-  if (b->d_masked && b->masked_cap < total) b->d_masked.reset();
-  if (!b->d_masked) { b->masked_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_masked.alloc(c->cache, b->masked_cap)); }
+  HIPCHK(b->d_masked.ensure(c->cache, total));
   if (total) HIPCHK(hipMemcpyAsync(b->d_masked.get(), b->d_dense.get(), total, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipEventRecord(c->ev[kEvMaskCase0], s));
   if (b->n_reads)
@@ -515,16 +507,15 @@ static int mask_dense(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipEventRecord(c->ev[kEvMaskCase1], s));
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipEventElapsedTime(&c->mask_case_ms, c->ev[kEvMaskCase0], c->ev[kEvMaskCase1]));
-  b->masked = true;
+  b->holds.masked = true;
   return TALC_OK;
 }
 
 int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
                                       int32_t* status) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   int rc;
-  if ((rc = need_map(b))) return rc;
-  HIPCHK(hipSetDevice(c->device));
+  if ((rc = belong(c, b, "bad context/batch"))) return rc;
+  if ((rc = enter_map(c, b))) return rc;
   if (out && (rc = mask_dense(c, b))) return rc;
   return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output", true);
 }
@@ -532,17 +523,16 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
 // ---- trimmed and split output (docs/trim_split.md): k_piece_count over the map, the reads' offsets on the host (as
 // pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (kEvPieceCount0 .. kEvPiecePack1 around the two kernels)
 int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, int soft_mask) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
   if (mode != TALC_PIECES_TRIM && mode != TALC_PIECES_SPLIT) return fail(TALC_ERR_INVALID, "piece mode %d is neither TALC_PIECES_TRIM nor TALC_PIECES_SPLIT", mode);
   int rc;
-  if ((rc = need_map(b))) return rc;
-  HIPCHK(hipSetDevice(c->device));
+  if ((rc = enter_map(c, b))) return rc;
   hipStream_t s = c->stream;
   const uint32_t n = b->n_reads;
-  b->pieced = false;
+  b->holds.pieced = false;
   const bool masked = mode == TALC_PIECES_TRIM && soft_mask;   // (a split piece has no weak byte)
   if (masked && (rc = mask_dense(c, b))) return rc;
-  if (!b->d_piece_count) HIPCHK(b->d_piece_count.alloc(c->cache, std::max<uint32_t>(n, 1)));
+  HIPCHK(b->d_piece_count.ensure(c->cache, n));
   HIPCHK(hipEventRecord(c->ev[kEvPieceCount0], s));
   if (n) hipLaunchKernelGGL(k_piece_count, dim3(n), dim3(64), 0, s, b->d_segs.get(), b->d_seg_off.get(), n, mode, min_len, b->d_piece_count.get());
   HIPCHK(hipGetLastError());
@@ -558,14 +548,9 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   }
   b->h_read_piece_off[n] = np; b->h_read_byte_off[n] = nb;
   // exactly what the pieces take; the buffers of an earlier call are kept when they are large enough
-  if (b->d_pieces && b->pieces_cap < np) { b->d_pieces.reset(); b->d_piece_off.reset(); }
-  if (!b->d_pieces) {
-    b->pieces_cap = std::max<uint64_t>(np, 1);
-    HIPCHK(b->d_pieces.alloc(c->cache, b->pieces_cap)); HIPCHK(b->d_piece_off.alloc(c->cache, b->pieces_cap));
-  }
-  if (b->d_piece_bytes && b->piece_bytes_cap < nb) b->d_piece_bytes.reset();
-  if (!b->d_piece_bytes) { b->piece_bytes_cap = std::max<uint64_t>(nb, 1); HIPCHK(b->d_piece_bytes.alloc(c->cache, b->piece_bytes_cap)); }
-  if (!b->d_read_piece_off) { HIPCHK(b->d_read_piece_off.alloc(c->cache, n + 1)); HIPCHK(b->d_read_byte_off.alloc(c->cache, n + 1)); }
+  HIPCHK(b->d_pieces.ensure(c->cache, np)); HIPCHK(b->d_piece_off.ensure(c->cache, np));
+  HIPCHK(b->d_piece_bytes.ensure(c->cache, nb));
+  HIPCHK(b->d_read_piece_off.ensure(c->cache, n + 1)); HIPCHK(b->d_read_byte_off.ensure(c->cache, n + 1));
   HIPCHK(hipMemcpyAsync(b->d_read_piece_off.get(), b->h_read_piece_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(b->d_read_byte_off.get(), b->h_read_byte_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipEventRecord(c->ev[kEvPiecePack0], s));
@@ -578,17 +563,17 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipEventElapsedTime(&c->piece_count_ms, c->ev[kEvPieceCount0], c->ev[kEvPieceCount1]));
   HIPCHK(hipEventElapsedTime(&c->piece_pack_ms, c->ev[kEvPiecePack0], c->ev[kEvPiecePack1]));
-  b->pieced = true;
+  b->holds.pieced = true;
   return TALC_OK;
 }
 
-uint64_t talc_batch_num_pieces(const talc_batch* b) { return (b && b->corrected && b->pieced) ? b->h_read_piece_off[b->n_reads] : 0; }
-uint64_t talc_batch_pieces_bytes(const talc_batch* b) { return (b && b->corrected && b->pieced) ? b->h_read_byte_off[b->n_reads] : 0; }
+uint64_t talc_batch_num_pieces(const talc_batch* b) { return (b && b->holds.has_pieces()) ? b->h_read_piece_off[b->n_reads] : 0; }
+uint64_t talc_batch_pieces_bytes(const talc_batch* b) { return (b && b->holds.has_pieces()) ? b->h_read_byte_off[b->n_reads] : 0; }
 
 int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* piece_offsets, talc_piece* pieces,
                             uint64_t piece_capacity, uint64_t* read_piece_offsets) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->corrected || !b->pieced) return fail(TALC_ERR_STATE, "talc_batch_pieces has not run on this batch since its last correction");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.has_pieces()) return fail(TALC_ERR_STATE, "talc_batch_pieces has not run on this batch since its last correction");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t np = b->h_read_piece_off[b->n_reads], nb = b->h_read_byte_off[b->n_reads];
   if (read_piece_offsets) memcpy(read_piece_offsets, b->h_read_piece_off.data(), (b->n_reads + 1) * 8);
@@ -609,7 +594,7 @@ int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_
 // corrected, over the dense records as talc_batch_fetch_corrected returns them (the corrected rows)
 static int launch_solidity(talc_ctx* c, talc_batch* b, bool records) {
   CachedBuf<SolidityRow>& rows = records ? b->d_sol_corr : b->d_sol_raw;
-  if (!rows) HIPCHK(rows.alloc(c->cache, std::max<uint32_t>(b->n_reads, 1)));
+  HIPCHK(rows.ensure(c->cache, b->n_reads));
   if (b->n_reads)
     hipLaunchKernelGGL(k_solidity, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, records ? b->d_dense.get() : b->d_codes.get(),
                        records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
@@ -619,14 +604,13 @@ static int launch_solidity(talc_ctx* c, talc_batch* b, bool records) {
 }
 
 int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
   int rc;
+  if ((rc = enter(c, b, "bad context/batch"))) return rc;
+  hipStream_t s = c->stream;
   if ((rc = prepare_strand(c, b))) return rc;   // (a batch encoded under the other setting is no longer corrected either)
-  const bool records = b->corrected;
-  b->solidity = false; b->solidityCorrected = false;
-  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  const bool records = b->holds.has_records();
+  b->holds.solidity = b->holds.solidityCorrected = false;
+  if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvSolidity0], s));
   if ((rc = launch_solidity(c, b, false))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvSolidity1], s));
@@ -637,14 +621,14 @@ int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
   c->sol_corr_ms = 0;
   if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[kEvSolidity1], c->ev[kEvSolidity2]));
   if ((rc = vote_time(c))) return rc;
-  b->solidity = true; b->solidityCorrected = records;
+  b->holds.solidity = true; b->holds.solidityCorrected = records;
   return TALC_OK;
 }
 
 int talc_batch_fetch_solidity(talc_ctx* c, talc_batch* b, talc_solidity* raw, talc_solidity* corrected) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->solidity) return fail(TALC_ERR_STATE, "talc_batch_solidity has not run on this batch since its last correction");
-  if (corrected && !b->solidityCorrected) return fail(TALC_ERR_STATE, "the batch had not been corrected when talc_batch_solidity ran: it has no corrected rows");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.has_solidity(false)) return fail(TALC_ERR_STATE, "talc_batch_solidity has not run on this batch since its last correction");
+  if (corrected && !b->holds.has_solidity(true)) return fail(TALC_ERR_STATE, "the batch had not been corrected when talc_batch_solidity ran: it has no corrected rows");
   HIPCHK(hipSetDevice(c->device));
   const size_t bytes = (size_t)b->n_reads * sizeof(talc_solidity);
   if (raw && bytes) HIPCHK(hipMemcpyAsync(raw, b->d_sol_raw.get(), bytes, hipMemcpyDeviceToHost, c->stream));
@@ -655,8 +639,8 @@ int talc_batch_fetch_solidity(talc_ctx* c, talc_batch* b, talc_solidity* raw, ta
 
 // Read::outputBasicReadStats (Read.cpp:418-433) for every read of a corrected batch
 int talc_batch_fetch_read_stats(talc_ctx* c, talc_batch* b, int64_t* stats5) {
-  if (!c || !b || b->ctx != c || !stats5) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
-  if (!b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
+  if (int rc = belong(c, b, "bad context/batch/buffer", stats5)) return rc;
+  if (!b->holds.has_records()) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch");
   const uint32_t K = c->p.k;
   for (uint32_t r = 0; r < b->n_reads; ++r) {
     const ReadState& st = b->h_state[r];
@@ -675,7 +659,7 @@ int talc_batch_fetch_read_stats(talc_ctx* c, talc_batch* b, int64_t* stats5) {
 
 int talc_batch_copy_corrected_device(talc_ctx* c, talc_batch* b, void* device_out, uint64_t out_capacity,
                                      uint64_t* out_offsets, int32_t* status) {
-  if (!c || !b || b->ctx != c || !device_out) return fail(TALC_ERR_INVALID, "bad context/batch/buffer");
+  if (int rc = belong(c, b, "bad context/batch/buffer", device_out)) return rc;
   return corrected_out(c, b, device_out, out_capacity, out_offsets, status, hipMemcpyDeviceToDevice, "device");
 }
 
@@ -691,8 +675,7 @@ int talc_correct_batch(talc_ctx* c, const char* bases, const uint64_t* offsets, 
 }
 
 int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, char* buf, uint64_t cap) {
-  if (!c || !b || b->ctx != c || read_index >= b->n_reads) return fail(TALC_ERR_INVALID, "bad context/batch/read index");
-  HIPCHK(hipSetDevice(c->device));
+  if (int rc = enter(c, b, "bad context/batch/read index", b && read_index < b->n_reads)) return rc;
   // a one-read batch from the resident raw bases
   const uint64_t off = b->h_offsets[read_index], len = b->h_offsets[read_index + 1] - off;
   std::vector<char> raw(std::max<uint64_t>(len, 1));
@@ -727,7 +710,7 @@ int64_t talc_batch_trace_read(talc_ctx* c, talc_batch* b, uint32_t read_index, c
     for (uint32_t i = 0; i < e.slen && e.soff + i < npool; ++i) os << code_to_ascii(pool[e.soff + i]);
     os << "\n";
   }
-  if (tbch->corrected) {
+  if (tbch->holds.has_records()) {
     const uint64_t total = tbch->h_dense_off[1];
     std::vector<char> o(std::max<uint64_t>(total, 1));
     if (total) HIPCHK(hipMemcpy(o.data(), tbch->d_dense.get(), total, hipMemcpyDeviceToHost));

@@ -78,8 +78,7 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
   for (uint32_t r = 0; r < n; ++r) { out.h_op_off[r] = nops; nops += out.h_rows[r].nOps; }
   out.h_op_off[n] = nops;
   // exactly what the ops take; the buffer of an earlier call is kept when it is large enough
-  if (out.d_ops && out.ops_cap < nops) out.d_ops.reset();
-  if (!out.d_ops) { out.ops_cap = std::max<uint64_t>(nops, 1); HIPCHK(out.d_ops.alloc(c->cache, out.ops_cap)); }
+  HIPCHK(out.d_ops.ensure(c->cache, nops));
   HIPCHK(hipMemsetAsync(out.d_ops.get(), 0, std::max<uint64_t>(nops, 1) * sizeof(uint32_t), s));   // the runs are added
   HIPCHK(hipMemcpyAsync(d_op_off.get(), out.h_op_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipEventRecord(c->ev[kEvEditAlignB0], s));
@@ -100,14 +99,13 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
 static uint64_t effective_max_cells(uint64_t max_cells) { return max_cells == 0 ? kEditDefaultCells : std::min(max_cells, kEditMaxCells); }
 
 static int batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells, uint64_t scratch_bytes) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
   int rc;
-  if ((rc = need_map(b))) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  b->edited = false;
+  if ((rc = belong(c, b, "bad context/batch"))) return rc;
+  if ((rc = enter_map(c, b))) return rc;
+  b->holds.edited = false;
   const EditIn in = {b->d_segs.get(), b->d_seg_off.get(), b->h_seg_off.data(), b->d_raw.get(), b->d_offsets.get(), b->d_dense.get(), b->d_dense_off.get(), b->n_reads};
   if ((rc = run_edits(c, in, effective_max_cells(max_cells), scratch_bytes, b->edits, nullptr))) return rc;
-  b->edited = true;
+  b->holds.edited = true;
   return TALC_OK;
 }
 
@@ -118,11 +116,11 @@ int talc_test_batch_edits(talc_ctx* c, talc_batch* b, uint64_t max_cells, uint64
   return batch_edits(c, b, max_cells, scratch_bytes);
 }
 
-uint64_t talc_batch_num_edit_ops(const talc_batch* b) { return (b && b->corrected && b->edited) ? b->edits.h_op_off[b->n_reads] : 0; }
+uint64_t talc_batch_num_edit_ops(const talc_batch* b) { return (b && b->holds.has_edits()) ? b->edits.h_op_off[b->n_reads] : 0; }
 
 int talc_batch_fetch_edits(talc_ctx* c, talc_batch* b, uint32_t* ops, uint64_t op_capacity, uint64_t* op_offsets, talc_edit_row* rows) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->corrected || !b->edited) return fail(TALC_ERR_STATE, "talc_batch_edits has not run on this batch since its last correction");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.has_edits()) return fail(TALC_ERR_STATE, "talc_batch_edits has not run on this batch since its last correction");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t nops = b->edits.h_op_off[b->n_reads];
   if (op_offsets) memcpy(op_offsets, b->edits.h_op_off.data(), ((size_t)b->n_reads + 1) * 8);

@@ -4,7 +4,7 @@
 // k_base_support over the batch's codes (RAW) or its dense records (RECORD), kEvSupport0 and kEvSupport1 around it.  The byte buffer is
 // the batch's, sized exactly; the buffer of an earlier call is kept when it is large enough.
 int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p) {
-  if (!c || !b || b->ctx != c || !p) return fail(TALC_ERR_INVALID, "bad context/batch/params");
+  if (int rc = belong(c, b, "bad context/batch/params", p)) return rc;
   if (p->source != TALC_SUPPORT_RAW && p->source != TALC_SUPPORT_RECORD)
     return fail(TALC_ERR_INVALID, "support source %u is neither TALC_SUPPORT_RAW nor TALC_SUPPORT_RECORD", p->source);
   if (p->phred > 1) return fail(TALC_ERR_INVALID, "phred must be 0 or 1, not %u", p->phred);
@@ -15,13 +15,12 @@ int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p)
   int rc;
   if ((rc = prepare_strand(c, b))) return rc;   // (a batch encoded under the other setting is no longer corrected either)
   const bool records = p->source == TALC_SUPPORT_RECORD;
-  if (records && !b->corrected) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch: it has no records");
-  b->supported = false;
-  if (!b->encoded && (rc = launch_encode(c, b))) return rc;
+  if (records && !b->holds.has_records()) return fail(TALC_ERR_STATE, "talc_batch_correct has not run on this batch: it has no records");
+  b->holds.supported = false;
+  if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
   const uint64_t* const off = records ? b->h_dense_off.data() : b->h_offsets.data();
   const uint64_t total = off[b->n_reads];
-  if (b->d_support && b->support_cap < total) b->d_support.reset();
-  if (!b->d_support) { b->support_cap = std::max<uint64_t>(total, 1); HIPCHK(b->d_support.alloc(c->cache, b->support_cap)); }
+  HIPCHK(b->d_support.ensure(c->cache, total));
   // (the buffer is an allocation of its own, 256-byte aligned: k_base_support takes a byte's alignment from its offset)
   HIPCHK(hipEventRecord(c->ev[kEvSupport0], s));
   if (b->n_reads)
@@ -34,18 +33,18 @@ int talc_batch_support(talc_ctx* c, talc_batch* b, const talc_support_params* p)
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipEventElapsedTime(&c->support_ms, c->ev[kEvSupport0], c->ev[kEvSupport1]));
   if ((rc = vote_time(c))) return rc;
-  b->supported = true; b->supportRecords = records;
+  b->holds.supported = true; b->holds.supportRecords = records;
   return TALC_OK;
 }
 
 // the offsets of the bytes: the records' for RECORD, the input reads' for RAW
-static const uint64_t* support_offsets(const talc_batch* b) { return b->supportRecords ? b->h_dense_off.data() : b->h_offsets.data(); }
+static const uint64_t* support_offsets(const talc_batch* b) { return b->holds.supportRecords ? b->h_dense_off.data() : b->h_offsets.data(); }
 
-uint64_t talc_batch_support_bytes(const talc_batch* b) { return (b && b->supported) ? support_offsets(b)[b->n_reads] : 0; }
+uint64_t talc_batch_support_bytes(const talc_batch* b) { return (b && b->holds.has_support()) ? support_offsets(b)[b->n_reads] : 0; }
 
 int talc_batch_fetch_support(talc_ctx* c, talc_batch* b, uint8_t* out, uint64_t out_capacity, uint64_t* out_offsets) {
-  if (!c || !b || b->ctx != c) return fail(TALC_ERR_INVALID, "bad context/batch");
-  if (!b->supported) return fail(TALC_ERR_STATE, "talc_batch_support has not run on this batch since its last correction");
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.has_support()) return fail(TALC_ERR_STATE, "talc_batch_support has not run on this batch since its last correction");
   HIPCHK(hipSetDevice(c->device));
   const uint64_t* const off = support_offsets(b);
   const uint64_t total = off[b->n_reads];

@@ -349,6 +349,7 @@ struct DevCache {
 template <typename T>
 class CachedBuf {
   T* p_ = nullptr;
+  uint64_t n_ = 0;   // the elements the buffer was asked for (the cache rounds up and may have served a larger one); 0 while empty
   DevCache* cache_ = nullptr;
 
  public:
@@ -356,14 +357,19 @@ class CachedBuf {
   CachedBuf(const CachedBuf&) = delete;
   CachedBuf& operator=(const CachedBuf&) = delete;
   ~CachedBuf() { reset(); }
+  // (what was held goes back first: the cache may serve the request from it; a failure leaves the buffer empty)
   hipError_t alloc(DevCache& cache, uint64_t n) {
     reset();
     cache_ = &cache;
-    return cache.alloc((void**)&p_, n * sizeof(T));
+    const hipError_t e = cache.alloc((void**)&p_, n * sizeof(T));
+    if (e == hipSuccess) n_ = n;
+    return e;
   }
+  // the buffer as it is when it was asked for at least n elements, else a new one of exactly max(n, 1)
+  hipError_t ensure(DevCache& cache, uint64_t n) { return p_ && n_ >= n ? hipSuccess : alloc(cache, std::max<uint64_t>(n, 1)); }
   T* get() const { return p_; }
   explicit operator bool() const { return p_ != nullptr; }
-  void reset() { if (p_) { cache_->release(p_); p_ = nullptr; } }
+  void reset() { if (p_) { cache_->release(p_); p_ = nullptr; n_ = 0; } }
 };
 
 }  // namespace talc

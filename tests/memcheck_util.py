@@ -84,6 +84,24 @@ def everything(ctx, reads, order=FORWARD, batch_free=False):
         ctx.record_map(False)
 
 
+# where per_read() puts what, for the tests that look at one field of a read's tuple (batch_free or not)
+F_RECORD, F_STATUS, F_MASKED, F_SEGS, F_SOLIDITY_RAW, F_SOLIDITY_RECORD, F_OPS, F_EDIT_ROW, F_STATS = range(9)
+F_SPLIT_TEXTS = 9 + 2 * 2                            # fetch_all's third pieces call: the texts of the read's SPLIT pieces
+F_SUPPORT = dict(record=-3, raw=-2, phred=-1)        # fetch_all's three support calls come last
+
+
+def _field_layout_holds():
+    """The constants above against per_read itself, on one made-up read."""
+    piece = lambda text: (text, np.array([0, len(text)], np.uint64), np.zeros(1, dtype=[("read", "<u4"), ("out_start", "<u4"), ("out_len", "<u4")]), np.array([0, 1], np.uint64))
+    f = dict(out=b"REC", oo=np.array([0, 3], np.uint64), st=[7], msk=b"msk", segs=np.zeros(1, np.uint32), so=np.array([0, 1], np.uint64),
+             raw=np.array([[1]]), cor=np.array([[2]]), ops=np.zeros(1, np.uint32), eo=np.array([0, 1], np.uint64), erows=np.array([[3]]),
+             stats=np.array([[4]]), pieces=[piece(b"tm"), piece(b"t"), piece(b"split")],
+             support=[(b"rc", np.array([0, 2], np.uint64)), (b"rw", np.array([0, 2], np.uint64)), (b"ph", np.array([0, 2], np.uint64))])
+    t = per_read(f, 1)[0]
+    return (t[F_RECORD], t[F_STATUS], t[F_MASKED], t[F_SOLIDITY_RAW], t[F_SOLIDITY_RECORD], t[F_EDIT_ROW], t[F_STATS], t[F_SPLIT_TEXTS],
+            t[F_SUPPORT["record"]], t[F_SUPPORT["raw"]], t[F_SUPPORT["phred"]]) == (b"REC", 7, b"msk", [1], [2], [3], [4], (b"split",), b"rc", b"rw", b"ph")
+
+
 def first_difference(got, want):
     """(read, fields that differ) of the first read whose tuples differ, or None."""
     for i, (x, y) in enumerate(zip(got, want)):

@@ -1,0 +1,244 @@
+"""What a batch holds and what drops it, across the features and through the C ABI itself: after every step of
+a walk over correct / structure / auto strand, every fetch whose result that step dropped answers TALC_ERR_STATE and every
+count 0, whatever the Python class remembers; and the device buffers a batch keeps or grows from call to call (pieces,
+support, edit scripts, records) give the right bytes between red zones.
+
+Wanted values: memcheck_util.everything() of a fresh batch on a fresh context, plain and auto strand (the per-feature tests
+hold that function's outputs to the oracle and the numpy contracts), and the oracle's own records where the set has them."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import corr_map_ref as M
+import parity_util as PU
+import pieces_ref as P
+import memcheck_util as MU
+from memcheck_util import everything, fetch_all, first_difference, guards_checked, per_read
+from talc_amd import lib as T
+
+pytestmark = pytest.mark.gpu
+
+ERR_STATE = -6
+N_SET = 20
+_in = {}
+
+
+def inputs():
+    """The first 20 reads of the default map set, "", one read of exactly k bases, and two reads of the set reverse
+    complemented (plain, they have no solid k-mer and pass through; auto strand turns and corrects them, so the two
+    orientations' records differ in length).  Computed once, shared, left unchanged."""
+    if not _in:
+        s = M.map_set("default")
+        s.pair.ttab.upload(0)
+        k = int(s.pair.p.k)
+        reads = s.reads[:N_SET] + ["", s.reads[N_SET][:k]] + [M.revcomp(x) for x in s.reads[N_SET:N_SET + 2]]
+        want = {}
+        for auto in (False, True):
+            ctx = T.Context(s.pair.ttab, s.pair.p, 0)
+            ctx.auto_strand(auto)
+            try:
+                want[auto] = everything(ctx, reads)
+            finally:
+                ctx.close()
+        for i in range(N_SET):                        # records and status: the oracle's
+            assert want[False][0][i][MU.F_RECORD].decode() == s.exp[i]["out"] and want[False][0][i][MU.F_STATUS] == s.exp[i]["status"], i
+        ctx = T.Context(s.pair.ttab, s.pair.p, 0)     # the edit scripts with max_cells = 1, of a fresh batch
+        ctx.record_map(True)
+        b = ctx.batch(*PU.pack_reads(reads))
+        try:
+            b.correct()
+            ops, eo, rows = b.edits(max_cells=1)
+            edits1 = (ops.copy(), eo.copy(), rows.copy())
+        finally:
+            b.close()
+            ctx.close()
+        _in.update(s=s, k=k, reads=reads, want=want, edits1=edits1)
+    return _in
+
+
+def record_total(per):
+    return sum(len(t[MU.F_RECORD]) for t in per)
+
+
+def test_the_inputs_do_what_they_are_there_for():
+    s = inputs()
+    assert MU._field_layout_holds()                              # the F_ constants name what per_read puts there
+    reads, plain, auto = s["reads"], s["want"][False][0], s["want"][True][0]
+    assert [len(x) for x in reads].count(0) == 1 and [len(x) for x in reads].count(s["k"]) == 1
+    assert sum(len(t[MU.F_SPLIT_TEXTS]) for t in plain) > len(reads)   # SPLIT, min_len 0: more pieces than reads
+    assert record_total(plain) != sum(len(x) for x in reads)     # the two support sources' totals
+    assert record_total(plain) != record_total(auto)             # the two orientations' record totals
+    assert int(s["want"][True][2]["reverse"].sum()) >= 2 and s["want"][False][2] is None
+
+
+# ---------------------------------------------------------------- 1. the state walk, through T.lib()
+def probe(L, h, n):
+    """({fetch: return code}, {count: value}) of the batch as it stands.  The fetches are asked without buffers (the state
+    check comes before anything is copied, and nothing is made: the masked records are made for a buffer only); the work
+    queue needs its two."""
+    order, bucket = np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint32)
+    codes = dict(
+        corrected=L.talc_batch_fetch_corrected(*h, None, 0, None, None),
+        masked=L.talc_batch_fetch_corrected_masked(*h, None, 0, None, None),
+        map=L.talc_batch_fetch_map(*h, None, 0, None),
+        pieces=L.talc_batch_fetch_pieces(*h, None, 0, None, None, 0, None),
+        edits=L.talc_batch_fetch_edits(*h, None, 0, None, None),
+        support=L.talc_batch_fetch_support(*h, None, 0, None),
+        solidity=L.talc_batch_fetch_solidity(*h, None, None),
+        structure=L.talc_batch_fetch_structure(*h, None, None, None, None, None, None, None, 0, None),
+        order=L.talc_batch_order(*h, order.ctypes.data, bucket.ctypes.data),
+        coverage=L.talc_batch_fetch_coverage(*h, None, None, None, None),
+        strand=L.talc_batch_fetch_strand(*h, None))
+    b = h[1]
+    counts = dict(
+        corrected_bytes=L.talc_batch_corrected_bytes(b), segments=L.talc_batch_num_segments(b), pieces=L.talc_batch_num_pieces(b),
+        pieces_bytes=L.talc_batch_pieces_bytes(b), edit_ops=L.talc_batch_num_edit_ops(b), support_bytes=L.talc_batch_support_bytes(b))
+    return codes, counts
+
+
+def holds(L, h, n, step, fetches=(), counts=()):
+    """The fetches named succeed and the counts named are not 0; every other fetch is TALC_ERR_STATE, every other count 0."""
+    codes, cnt = probe(L, h, n)
+    want = {name: (0 if name in fetches else ERR_STATE) for name in codes}
+    assert codes == want, (step, {x: (codes[x], want[x]) for x in codes if codes[x] != want[x]})
+    for name, v in cnt.items():
+        assert (v != 0) == (name in counts), (step, name, v)
+
+
+EVERY_OUTPUT = ("corrected", "masked", "map", "pieces", "edits", "support", "solidity", "coverage")
+EVERY_COUNT = ("corrected_bytes", "segments", "pieces", "pieces_bytes", "edit_ops", "support_bytes")
+
+
+def make_everything(b):
+    """fetch_all of a batch the walk has corrected through the ABI.  fetch_all goes through the Batch methods; of the class's
+    own memory they use one thing, whether solidity() asks for corrected rows, so that is set to what the library must hold
+    by now.  What the library holds is asked of the library, by probe()."""
+    b._corrected, b._enc_auto = True, b.ctx._auto
+    return per_read(fetch_all(b), b.n_reads)
+
+
+def test_every_step_drops_what_was_made_from_what_it_replaces():
+    s = inputs()
+    reads, n = s["reads"], len(s["reads"])
+    plain, auto, auto_rows = s["want"][False][0], s["want"][True][0], s["want"][True][2]
+    L = T.lib()
+    ctx = T.Context(s["s"].pair.ttab, s["s"].pair.p, 0)
+    ctx.record_map(True)
+    b = ctx.batch(*PU.pack_reads(reads))
+    h = (ctx._h, b._h)
+    raw_support = T.SupportParams(T.SUPPORT_RAW, 0, 0, 0)
+    try:
+        holds(L, h, n, "1: a fresh batch")
+        assert L.talc_batch_correct(*h) == 0
+        holds(L, h, n, "2: corrected, nothing made yet", ("corrected", "masked", "map", "coverage"), ("corrected_bytes", "segments"))
+        d = first_difference(make_everything(b), plain)
+        assert d is None, ("2: every output", d)
+        holds(L, h, n, "2: every output made", EVERY_OUTPUT, EVERY_COUNT)
+
+        assert L.talc_batch_structure(*h) == 0
+        holds(L, h, n, "3: talc_batch_structure", ("structure", "order", "coverage"))
+
+        assert L.talc_batch_correct(*h) == 0
+        holds(L, h, n, "4: corrected again, nothing made yet", ("corrected", "masked", "map", "coverage"), ("corrected_bytes", "segments"))
+        d = first_difference(make_everything(b), plain)
+        assert d is None, ("4: every output", d)
+        assert L.talc_batch_support(*h, C.byref(raw_support)) == 0       # (the last support of the batch is of its codes alone)
+        holds(L, h, n, "4: every output made", EVERY_OUTPUT, EVERY_COUNT)
+
+        ctx.auto_strand(True)
+        assert L.talc_batch_coverage(*h) == 0
+        holds(L, h, n, "5: auto strand on, talc_batch_coverage", ("coverage", "strand"))
+        rows = np.zeros(n, dtype=T.STRAND_DTYPE)
+        assert L.talc_batch_fetch_strand(*h, rows.ctypes.data) == 0 and np.array_equal(rows, auto_rows)
+        assert L.talc_batch_correct(*h) == 0
+        holds(L, h, n, "5: corrected, nothing made yet", ("corrected", "masked", "map", "coverage", "strand"), ("corrected_bytes", "segments"))
+        d = first_difference(make_everything(b), auto)
+        assert d is None, ("5: every output under auto strand", d)
+        holds(L, h, n, "5: every output made", EVERY_OUTPUT + ("strand",), EVERY_COUNT)
+
+        ctx.auto_strand(False)
+        assert L.talc_batch_solidity(*h) == 0
+        holds(L, h, n, "6: auto strand off, talc_batch_solidity", ("solidity", "strand"))
+        raw, cor = np.zeros(n, dtype=T.SOLIDITY_DTYPE), np.zeros(n, dtype=T.SOLIDITY_DTYPE)
+        assert L.talc_batch_fetch_solidity(*h, raw.ctypes.data, None) == 0
+        assert [raw[r].tolist() for r in range(n)] == [t[MU.F_SOLIDITY_RAW] for t in plain]
+        assert L.talc_batch_fetch_solidity(*h, raw.ctypes.data, cor.ctypes.data) == ERR_STATE
+        rows[:] = 0
+        assert L.talc_batch_fetch_strand(*h, rows.ctypes.data) == 0 and np.array_equal(rows, auto_rows)   # the vote is never dropped
+    finally:
+        b.close()
+        ctx.close()
+
+
+# ---------------------------------------------------------------- 2. the buffers a batch keeps or grows
+def same_pieces(got, want, what):
+    for name, g, w in zip(("bytes", "piece offsets", "pieces", "read offsets"), got, want):
+        assert np.array_equal(g, w), (what, name)
+
+
+def per_read_bytes(buf, offs, n):
+    buf = bytes(buf)
+    return [buf[int(offs[r]):int(offs[r + 1])] for r in range(n)]
+
+
+def test_kept_and_grown_buffers_hold_every_result():
+    s = inputs()
+    reads, n = s["reads"], len(s["reads"])
+    plain, auto = s["want"][False][0], s["want"][True][0]
+    bases, offs = PU.pack_reads(reads)
+    with guards_checked():
+        with T.poisoned(0xA5):
+            ctx = T.Context(s["s"].pair.ttab, s["s"].pair.p, 0)
+            b = ctx.batch(bases, offs)
+            try:
+                # records without the map, then with it: the segment buffers' first allocation on a batch that has records
+                assert b.correct() == 0
+                out, oo, st = b.fetch_corrected()
+                assert [(x, int(c)) for x, c in zip(per_read_bytes(out, oo, n), st)] == [(t[MU.F_RECORD], t[MU.F_STATUS]) for t in plain]
+                ctx.record_map(True)
+                assert b.correct() == 0
+                out, oo, st = b.fetch_corrected()
+                segs, so = b.fetch_map()
+                assert [(x, int(c)) for x, c in zip(per_read_bytes(out, oo, n), st)] == [(t[MU.F_RECORD], t[MU.F_STATUS]) for t in plain]
+
+                # pieces: none (buffers of one element), more than reads (they grow), none (the larger ones are kept), more again
+                far = 1 << 20
+                assert far > max(len(t[MU.F_RECORD]) for t in plain)
+                for i, (mode, min_len) in enumerate([(T.PIECES_TRIM, far), (T.PIECES_SPLIT, 0)] * 2):
+                    got = b.pieces(mode, min_len)
+                    assert len(got[2]) == 0 if min_len else len(got[2]) > n, (i, len(got[2]))
+                    same_pieces(got, P.pieces(segs, so, out, oo, mode, min_len), ("pieces", i, mode, min_len))
+
+                # support: the smaller source, the larger, the smaller again
+                totals = dict(raw=int(offs[n]), record=int(oo[n]))
+                assert totals["raw"] != totals["record"]
+                small, large = sorted(totals, key=totals.get)
+                for i, source in enumerate((small, large, small)):
+                    sb, sof = b.support(source)
+                    assert len(sb) == totals[source]
+                    assert per_read_bytes(sb, sof, n) == [t[MU.F_SUPPORT[source]] for t in plain], ("support", i, source)
+
+                # edit scripts: next to no op, the default's, next to none again
+                ops1, eo1, rows1 = s["edits1"]
+                want_default = ([t[MU.F_OPS] for t in plain], [t[MU.F_EDIT_ROW] for t in plain])
+                assert len(ops1) < sum(len(x) for x in want_default[0]) // 4      # fewer ops than the default has: the buffer has to grow
+                for i, cells in enumerate((1, 0, 1)):
+                    ops, eo, rows = b.edits(max_cells=cells)
+                    if cells:
+                        assert np.array_equal(ops, ops1) and np.array_equal(eo, eo1) and np.array_equal(rows, rows1), ("edits", i)
+                    else:
+                        got = ([ops[int(eo[r]):int(eo[r + 1])].tobytes() for r in range(n)], [rows[r].tolist() for r in range(n)])
+                        assert got == want_default, ("edits", i)
+
+                # every output of the plain correction, then of auto strand: the record total differs, d_dense is kept or grown
+                d = first_difference(per_read(fetch_all(b), n), plain)
+                assert d is None, ("plain", d)
+                ctx.auto_strand(True)
+                assert b.correct() == 0
+                assert b.corrected_bytes == record_total(auto) != int(oo[n])
+                d = first_difference(per_read(fetch_all(b), n), auto)
+                assert d is None, ("auto strand", d)
+            finally:
+                b.close()
+                ctx.close()
