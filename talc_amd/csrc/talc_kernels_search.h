@@ -24,8 +24,17 @@
 
 namespace talc {
 
-#define TCAP 288          /* slots per Trail set: <= 4*max_inner_paths children, or kept + MAXB */
-#define NBUF (2 * TCAP)    /* sequence buffers shared by the two Trail sets (9 x 64) */
+// Slots per Trail set.  A step makes at most 4 * max_inner_paths = 240 children.  Gardening keeps more than it is given
+// in its "complex" branch (Explorer.cpp:852 ff.): the MAXB nearest of the candidates that tie for the best score and then
+// all of them again — at most all but one of n candidates tie without one of them being first by distance too, so
+// MAXB + n - 1 <= 64 + 239 = 303 (tests/param_limit_cases.py, bush(): 300).
+#define TCAP 320
+// Sequence buffers shared by the two Trail sets (9 x 64: the pool's bitmap is in words, and a tenth word costs every
+// pool_alloc / pool_free of the search 1.2 % of config 2's step).  The most that are held at once: the candidates of a
+// gardening and fresh copies of what it keeps, 240 + 303; a step's parents and children hold 60 + 240.
+#define NBUF 576
+static_assert(TCAP >= 64 + 4 * 60 - 1 && NBUF % 64 == 0 && NBUF >= 4 * 60 + 64 + 4 * 60 - 1,
+              "TCAP and NBUF cover gardening's kept list at the largest accepted parameters (check_params)");
 #ifndef LDS_DP_CAP
 #define LDS_DP_CAP 320    /* ints per DP array held in LDS; longer problems use the HBM arrays */
 #endif
@@ -3582,8 +3591,12 @@ TALC_D void edge_anchor_search(const AnchorRec* anchors_, int s_) {
   PROF_BEGIN2(); init_first_trail(a, anchors + s, false, PATH_MAXLENGTH); PROF_END2(PF_INITTR);
   int nCur = 1;
   int len = (int)K;
+  // A lone Trail is scored every CHECK_INTERVAL steps only while one Trail is below MAX_NB_OF_BORDER_PATHS (Explorer.cpp:673:
+  // `|| newCompetingPaths.size() >= p_MAX_NB_OF_BORDER_PATHS`); with a limit of 0 or 1 every step is a scoring step, which
+  // the generic step knows and the fast-forward and the edge lane (CHECK_INTERVAL alone) do not.
+  const bool loneRounds = (uint32_t)uni((int)P.MAX_BORDER_PATHS) > 1u;
   while ((int)(nCur > 0) & (int)((uint32_t)nCur <= maxInner) & (int)((uint32_t)uni((int)stepCounter) < PATH_MAXLENGTH) & (int)(uni((int)X.overflow) == 0)) {
-    if (nCur == 1) {
+    if (nCur == 1 && loneRounds) {
       int ff;
       bool leafFell = false;
       // the walk tables, the search's filter in LDS: the edge lane walks and scores until something is not the simple round

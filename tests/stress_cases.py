@@ -1,8 +1,14 @@
 """Seed / parameter sets of the stress comparison (HIP path against the oracle, read by read) beyond the suite's own
 fixtures: branching transcriptomes (1xx, 3xx) and unique-sequence / junction / reverse / parameter variants (2xx).
 `tools/stress_branching.py` runs any of them at any size; `tests/test_gpu_stress.py` draws a bounded sample of them in
-the -m gpu suite (the one parity bug of round 3 passed every fixed fixture and was found by set 103)."""
+the -m gpu suite (the one parity bug of round 3 passed every fixed fixture and was found by set 103).  The 4xx sets are
+parameters at the ends of their ranges: 401-405 the low ends (401 and 403 are in the suite's draw), 406-416 the upper ends (and both ends of max_nb_border_paths)
+of what the C ABI accepts, all of them run by `tests/test_gpu_param_limits.py` on their first 60-200 reads
+(`tests/param_limit_cases.py`; row 412, one border path, found the edge search's lone-Trail rounds scoring too rarely)."""
 import numpy as np
+
+_S301 = dict(target_kmers=350_000, k=21, seed=301, synth_kw=dict(paralog_frac=0.9, paralog_div=0.015))
+_S301_CLEAN = dict(_S301, synth_kw=dict(_S301["synth_kw"], sub_rate=0.01, ins_rate=0.01, del_rate=0.01))
 
 CASES = {
     101: (dict(target_kmers=400_000, k=21, seed=101, synth_kw=dict(paralog_frac=0.6, paralog_div=0.02)), dict()),
@@ -28,6 +34,23 @@ CASES = {
     403: (dict(target_kmers=300_000, k=22, seed=403, synth_kw=dict(paralog_frac=0.4, paralog_div=0.03)), dict(sr_error_rate=1.5, alpha=0.5, min_count=5)),
     404: (dict(target_kmers=300_000, k=30, seed=404), dict(max_start_anchors=1, min_start_anchors=1, max_border_length=50, allowed_failure_rate=0.9, max_nb_border_failures=0)),
     405: (dict(target_kmers=300_000, k=21, seed=405, junctions=True, synth_kw=dict(paralog_frac=0.4, paralog_div=0.05)), dict(max_in_count=40, coloured_count_thr=5, max_nb_border_paths=2, min_inner_score=0.95, min_border_score=0.95)),
+    # ... the upper ends: set 301's generator (the one whose Trail sets grow largest) under the largest values the C ABI
+    # accepts.  tests/param_limit_cases.py names what each row is there for, tests/test_param_limits_reference.py asserts from
+    # the oracle's trace that its first 200 reads get there (Trail sets beyond one wave of 64 in head, inner and tail
+    # searches, gardening of more than 64 candidates with MAXB = 64, 64 start anchors on a side).
+    406: (dict(_S301), dict(max_nb_competing_paths=64, max_nb_inner_paths=60)),
+    407: (dict(_S301), dict(max_nb_competing_paths=63, max_nb_inner_paths=59)),
+    408: (dict(_S301), dict(max_nb_competing_paths=64, max_nb_inner_paths=60, check_interval=1)),
+    409: (dict(_S301), dict(max_nb_competing_paths=64, max_nb_inner_paths=60, check_interval=40, max_nb_border_paths=300)),
+    # (reads with a quarter of the generator's error rates: solid regions of several hundred k-mers, of which 64 and more fork)
+    410: (dict(_S301_CLEAN), dict(max_nb_competing_paths=64, max_nb_inner_paths=60, max_start_anchors=64, min_start_anchors=64)),
+    411: (dict(_S301_CLEAN), dict(max_nb_competing_paths=64, max_nb_inner_paths=60, max_start_anchors=1, min_start_anchors=63)),
+    412: (dict(_S301), dict(max_nb_border_paths=1)),
+    413: (dict(target_kmers=350_000, k=31, seed=413, synth_kw=dict(paralog_frac=0.9, paralog_div=0.015, mixed_lengths=1)), dict(max_nb_competing_paths=64, max_nb_inner_paths=60)),
+    414: (dict(target_kmers=350_000, k=18, seed=414, synth_kw=dict(paralog_frac=0.9, paralog_div=0.015)), dict(max_nb_competing_paths=64, max_nb_inner_paths=60)),
+    415: (dict(_S301), dict(max_nb_competing_paths=64, max_nb_inner_paths=60, reverse=1)),
+    # (no border path at all: like 1, every step of a lone edge Trail is a scoring step, Explorer.cpp:673)
+    416: (dict(_S301), dict(max_nb_border_paths=0)),
 }
 
 

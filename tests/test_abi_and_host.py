@@ -107,6 +107,30 @@ def test_invalid_parameters_are_rejected():
             T.Table.from_arrays(np.zeros(1, np.uint64), np.ones(1, np.uint32), p)
 
 
+@pytest.mark.parametrize("field,top", [("max_nb_competing_paths", 64), ("max_nb_inner_paths", 60), ("max_start_anchors", 64)])
+def test_path_search_parameters_are_accepted_up_to_what_the_scratch_holds(field, top):
+    """The three parameters that size k_search's per-wave scratch (a ballot of 64 lanes, TCAP slots, the aim lists): the
+    largest value is accepted, the one above it and 0 are refused, and the message names the field."""
+    one = (np.zeros(1, np.uint64), np.ones(1, np.uint32))
+    for good in (1, top):
+        T.Table.from_arrays(*one, T.default_params(**{field: good})).close()
+    for bad in (0, top + 1, 0xFFFFFFFF):
+        with pytest.raises(T.TalcError, match=field):
+            T.Table.from_arrays(*one, T.default_params(**{field: bad}))
+
+
+def test_refusals_name_the_field_and_unbounded_parameters_pass():
+    one = (np.zeros(1, np.uint64), np.ones(1, np.uint32))
+    for k in (17, 32):
+        with pytest.raises(T.TalcError, match="k=%d" % k):
+            T.Table.from_arrays(*one, T.default_params(k=k))
+    with pytest.raises(T.TalcError, match="check_interval"):
+        T.Table.from_arrays(*one, T.default_params(check_interval=0))
+    # no upper bound: the border limit and the check interval (tests/param_limit_cases.py runs the search with 300 and 50);
+    # min_start_anchors above max_start_anchors is a legal pair too
+    T.Table.from_arrays(*one, T.default_params(max_nb_border_paths=1 << 30, check_interval=1 << 30, min_start_anchors=63, max_start_anchors=1)).close()
+
+
 @pytest.mark.skipif(PU.T.device_count() > 0, reason="only meaningful on a host without a GPU")
 def test_compute_fails_loudly_without_gpu():
     p = T.default_params()
