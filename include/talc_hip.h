@@ -211,6 +211,30 @@ int talc_counter_fetch(talc_counter* c, uint32_t min_count, uint64_t* kmers, uin
  * afterwards: only talc_counter_destroy may follow. */
 int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_table** out, int64_t stats[3]);
 void talc_counter_destroy(talc_counter* c);
+/* The short-read filter (docs/sr_filter.md): a 3' adapter clip and a quality floor applied to every batch on the device
+ * before it is counted.  Per record S of L bytes: a start p is accepted for an adapter A of m letters when, with
+ * o = min(m, L - p) and mm = the number of i < o where S[p+i] and A[i] differ after upper-casing (a byte of S outside
+ * ACGTacgt always differs), o >= min_overlap and 100 mm <= max_error_pct o.  clip = the smallest accepted p over all
+ * adapters, L without one.  Bytes [clip, L) and every byte j < clip with quality q[j] < 33 + min_qual (Phred+33) are
+ * counted as 'N'; everything else is counted as talc_counter_add counts it.  No adapters and min_qual 0: the filter is off
+ * and talc_counter_add does exactly what it does on a counter whose filter was never set. */
+/* before the first add / add_fastq / add_counts: TALC_ERR_STATE afterwards or on a spent counter.
+ * adapters: NUL-terminated, comma-separated, NULL or "" for none; at most 4, each 1..64 letters of ACGTacgt.
+ * min_qual 0 (off) or 1..93; min_overlap 0 (: 5) .. 64 and not above the shortest adapter; max_error_pct 0..30. */
+int talc_counter_set_filter(talc_counter* c, uint32_t min_qual, const char* adapters,
+                            uint32_t min_overlap /* 0: 5 */, uint32_t max_error_pct);
+/* talc_counter_add with one quality byte per base, same offsets; quals may be NULL (no floor for this batch).
+ * talc_counter_add on a filtered counter acts as this call with quals == NULL.  A filtered counter refuses a record of
+ * 2^32 bytes or more (TALC_ERR_INVALID).  talc_counter_stats()[0] counts the windows after masking. */
+int talc_counter_add_fastq(talc_counter* c, const char* bases, const char* quals,
+                           const uint64_t* offsets, uint32_t n_reads);
+/* {records filtered, records with clip < L, bytes clipped (sum of L - clip), bytes below the floor among [0, clip)}
+ * (waits for the queued batches); all zero while the filter is off */
+int talc_counter_filter_stats(talc_counter* c, uint64_t stats[4]);
+/* test hook: the filter alone on one batch. masked_out: the batch's bytes after the pass, record by
+ * record without separators, n bytes; clip_out[n_reads]. Counts nothing. */
+int talc_test_counter_mask(talc_counter* c, const char* bases, const char* quals, const uint64_t* offsets,
+                           uint32_t n_reads, char* masked_out, uint32_t* clip_out);
 
 /* ---------------------------------------------------------------- (1c) both strands ------
  * For short reads that are not forward-stranded, and for `jellyfish count -C` counts (docs/both_strands.md).  rc(x) is

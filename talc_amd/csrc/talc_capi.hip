@@ -26,6 +26,7 @@
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
 #include "talc_kernels_solidity.h"
+#include "talc_kernels_srfilter.h"
 #include "talc_kernels_strand.h"
 #include "talc_kernels_support.h"
 #include "talc_switches.h"
@@ -1289,6 +1290,18 @@ struct talc_counter {
   bool bothStrands = false;     // keys are canon(x); the table gets y and rc(y) (talc_counter_set_both_strands)
   bool started = false;         // something has been added: the mode is fixed
   bool countsAdded = false;     // talc_counter_add_counts was used: a count no longer stays below the windows counted
+  // the short-read filter (talc_counter_set_filter, docs/sr_filter.md): nothing of it exists while it is off.  Qualities and
+  // offsets are staged like the text: stageQ / stageO[b] travel with stage[b] and share its event.
+  bool filterOn = false;
+  SrFilter filt{0, 0, 0};
+  DevBuf<SrAdapters> dAdapters;            // empty: no adapters
+  DevBuf<unsigned long long> dFiltStats;   // {records, records clipped, bytes clipped, bytes below the floor}
+  DevBuf<uint8_t> dQual;
+  DevBuf<uint64_t> dOffs;
+  uint64_t dQualCap = 0, dOffsCap = 0;
+  PinnedBuf stageQ[2], stageO[2];
+  uint64_t stageQCap[2] = {0, 0}, stageOCap[2] = {0, 0};
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> mev;   // TALC_TIMING: around every k_sr_mask
   // TALC_TIMING
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
   uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
@@ -1297,6 +1310,7 @@ struct talc_counter {
     (void)hipSetDevice(device);
     for (auto& e : stageEv) if (e) hipEventDestroy(e);
     for (auto& ev : kev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    for (auto& ev : mev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     if (stream) hipStreamDestroy(stream);
   }
 };
@@ -1388,42 +1402,58 @@ int talc_counter_create(const talc_params* p, int device, uint64_t expected_dist
   return TALC_OK;
 }
 
-int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets, uint32_t n_reads) {
-  if (!c || (n_reads && (!bases || !offsets))) return fail(TALC_ERR_INVALID, "null argument");
-  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
-  if (!n_reads) return TALC_OK;
-  c->started = true;
+// a batch's records: the offsets must not decrease; *wins = the windows of K bytes the raw lengths hold (an upper bound of
+// what is counted).  The filter keeps a record's length in 32 bits.
+static int counter_check_batch(const talc_counter* c, const uint64_t* offsets, uint32_t n_reads, bool filtered, uint64_t* wins) {
   const uint32_t K = c->p.k;
-  const uint64_t o0 = offsets[0];
-  uint64_t wins = 0;
+  uint64_t w = 0;
   for (uint32_t r = 0; r < n_reads; ++r) {
     if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must not decrease (read %u)", r);
     const uint64_t L = offsets[r + 1] - offsets[r];
-    wins += L >= K ? L - K + 1 : 0;
+    if (filtered && L >= (1ull << 32)) return fail(TALC_ERR_INVALID, "read %u has %llu bytes: the short-read filter takes records below 2^32 bytes", r, (unsigned long long)L);
+    w += L >= K ? L - K + 1 : 0;
   }
-  const uint64_t nbytes = offsets[n_reads] - o0 + n_reads;   // one separator after each record
-  HIPCHK(hipSetDevice(c->device));
-  // growth: the bound first, the exact number only when the bound says the batch might not fit
-  if ((double)(c->distinctKnown + c->winsSince + wins) > 0.7 * (double)c->cap) {
-    unsigned long long st[2];
-    int rc = counter_sync(c, st);
-    if (rc) return rc;
-    if ((double)(c->distinctKnown + wins) > 0.7 * (double)c->cap && (rc = counter_grow(c, c->distinctKnown + wins))) return rc;
+  *wins = w;
+  return TALC_OK;
+}
+
+// a page-locked staging buffer / a device buffer of the counter that holds `need` units (at least `floor` are asked for)
+static int counter_pinned(PinnedBuf& buf, uint64_t& cap, uint64_t need, uint64_t floor) {
+  if (cap >= need) return TALC_OK;
+  buf.reset(); cap = 0;
+  const uint64_t want = std::max<uint64_t>(need, floor);
+  if (buf.alloc(want) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want);
   }
-  // staging buffer: free once the copy that last read it is done
+  cap = want;
+  return TALC_OK;
+}
+extern "C++" template <class T>
+static int counter_devbuf(talc_counter* c, DevBuf<T>& buf, uint64_t& cap, uint64_t need, uint64_t floor) {
+  if (cap >= need) return TALC_OK;
+  HIPCHK(hipStreamSynchronize(c->stream));   // (the previous kernel may still read the old buffer)
+  buf.reset(); cap = 0;
+  const uint64_t want = std::max<uint64_t>(need, floor);
+  if (buf.alloc(want) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes for a batch of the k-mer counter (%llu distinct k-mers so far)",
+                (unsigned long long)(want * sizeof(T)), (unsigned long long)c->distinctKnown);
+  }
+  cap = want;
+  return TALC_OK;
+}
+
+// The batch's bytes into staging buffer *b (one separator after each record) and their copy to the device text queued.
+// The buffer is free once the copies that last read it are done: the caller records stageEv[*b] behind its last copy.
+static int counter_stage_text(talc_counter* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, uint64_t nbytes, int* bOut) {
+  const uint64_t o0 = offsets[0];
   Stopwatch packing;
   const int b = c->next;
   c->next ^= 1;
+  *bOut = b;
   if (c->stageBusy[b]) { HIPCHK(hipEventSynchronize(c->stageEv[b])); c->stageBusy[b] = false; }
-  if (c->stageCap[b] < nbytes) {
-    c->stage[b].reset(); c->stageCap[b] = 0;
-    const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
-    if (c->stage[b].alloc(want) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want);
-    }
-    c->stageCap[b] = want;
-  }
+  if (int rc = counter_pinned(c->stage[b], c->stageCap[b], nbytes, 1u << 20)) return rc;
   char* dst = c->stage[b].get();
 #pragma omp parallel for schedule(static) if (n_reads > 100000)
   for (long r = 0; r < (long)n_reads; ++r) {
@@ -1432,20 +1462,75 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
     dst[at + offsets[r + 1] - offsets[r]] = '\n';
   }
   c->packS += packing.seconds();
-  if (c->dTextCap < nbytes) {   // (the previous kernel may still read the old buffer)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->dText.reset(); c->dTextCap = 0;
-    const uint64_t want = std::max<uint64_t>(nbytes, 1u << 20);
-    if (c->dText.alloc(want) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes for a batch of the k-mer counter (%llu distinct k-mers so far)",
-                  (unsigned long long)want, (unsigned long long)c->distinctKnown);
-    }
-    c->dTextCap = want;
-  }
+  if (int rc = counter_devbuf(c, c->dText, c->dTextCap, nbytes, 1u << 20)) return rc;
   HIPCHK(hipMemcpyAsync(c->dText.get(), dst, nbytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(c->stageEv[b], c->stream));
+  return TALC_OK;
+}
+
+// The filter's part of a batch whose text sits in staging buffer b: the qualities (the text's layout; nullptr: none) and the
+// offsets staged beside it, their copies and k_sr_mask queued behind the text's copy.  Every byte the kernel reads of the
+// quality and offset buffers is written here, for this batch.  dClip: the test hook's clip positions (device), else nullptr.
+static int counter_queue_mask(talc_counter* c, int b, const char* quals, const uint64_t* offsets, uint32_t n_reads, uint64_t nbytes,
+                              bool withStats, uint32_t* dClip) {
+  const uint64_t o0 = offsets[0];
+  Stopwatch packing;
+  const uint64_t noffs = (uint64_t)n_reads + 1;
+  if (int rc = counter_pinned(c->stageO[b], c->stageOCap[b], noffs * 8, 1u << 16)) return rc;
+  memcpy(c->stageO[b].get(), offsets, noffs * 8);
+  if (quals) {
+    if (int rc = counter_pinned(c->stageQ[b], c->stageQCap[b], nbytes, 1u << 20)) return rc;
+    char* dst = c->stageQ[b].get();
+#pragma omp parallel for schedule(static) if (n_reads > 100000)
+    for (long r = 0; r < (long)n_reads; ++r) {
+      const uint64_t at = offsets[r] - o0 + (uint64_t)r;
+      memcpy(dst + at, quals + offsets[r], offsets[r + 1] - offsets[r]);
+      dst[at + offsets[r + 1] - offsets[r]] = '\n';
+    }
+  }
+  c->packS += packing.seconds();
+  if (int rc = counter_devbuf(c, c->dOffs, c->dOffsCap, noffs, 1u << 13)) return rc;
+  HIPCHK(hipMemcpyAsync(c->dOffs.get(), c->stageO[b].get(), noffs * 8, hipMemcpyHostToDevice, c->stream));
+  if (quals) {
+    if (int rc = counter_devbuf(c, c->dQual, c->dQualCap, nbytes, 1u << 20)) return rc;
+    HIPCHK(hipMemcpyAsync(c->dQual.get(), c->stageQ[b].get(), nbytes, hipMemcpyHostToDevice, c->stream));
+  }
+  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  if (c->sw.timing) {
+    if (hipEventCreate(&ev.first) == hipSuccess && hipEventCreate(&ev.second) == hipSuccess) c->mev.push_back(ev);
+    else { if (ev.first) hipEventDestroy(ev.first); ev = {nullptr, nullptr}; }
+  }
+  if (ev.second) HIPCHK(hipEventRecord(ev.first, c->stream));
+  const uint32_t nblk = std::min<uint32_t>((n_reads + kSrWaves - 1) / kSrWaves, kSrMaxBlocks);
+  hipLaunchKernelGGL(k_sr_mask, dim3(nblk), dim3(kSrThreads), 0, c->stream, c->dText.get(), quals ? c->dQual.get() : (const uint8_t*)nullptr,
+                     c->dOffs.get(), n_reads, c->dAdapters.get(), c->filt, withStats ? c->dFiltStats.get() : (unsigned long long*)nullptr, dClip);
+  HIPCHK(hipGetLastError());
+  if (ev.second) HIPCHK(hipEventRecord(ev.second, c->stream));
+  return TALC_OK;
+}
+
+static int counter_add_records(talc_counter* c, const char* bases, const char* quals, const uint64_t* offsets, uint32_t n_reads) {
+  if (!c || (n_reads && (!bases || !offsets))) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (!n_reads) return TALC_OK;
+  c->started = true;
+  const uint32_t K = c->p.k;
+  uint64_t wins = 0;   // (of the raw lengths: masking only removes windows, so the growth bound below stays one)
+  if (int rc = counter_check_batch(c, offsets, n_reads, c->filterOn, &wins)) return rc;
+  const uint64_t nbytes = offsets[n_reads] - offsets[0] + n_reads;   // one separator after each record
+  HIPCHK(hipSetDevice(c->device));
+  // growth: the bound first, the exact number only when the bound says the batch might not fit
+  if ((double)(c->distinctKnown + c->winsSince + wins) > 0.7 * (double)c->cap) {
+    unsigned long long st[2];
+    int rc = counter_sync(c, st);
+    if (rc) return rc;
+    if ((double)(c->distinctKnown + wins) > 0.7 * (double)c->cap && (rc = counter_grow(c, c->distinctKnown + wins))) return rc;
+  }
+  int b = 0;
+  if (int rc = counter_stage_text(c, bases, offsets, n_reads, nbytes, &b)) return rc;
+  const int rcMask = c->filterOn ? counter_queue_mask(c, b, quals, offsets, n_reads, nbytes, true, nullptr) : TALC_OK;
+  HIPCHK(hipEventRecord(c->stageEv[b], c->stream));   // (behind every copy that reads the staging buffers)
   c->stageBusy[b] = true;
+  if (rcMask) return rcMask;
   c->winsTotal += wins;
   const bool checked = c->countsAdded || c->winsTotal >= 0xFFFFFFFFull;   // below that no count can reach 2^32
   const uint64_t nblk = (nbytes + kCountTile - 1) / kCountTile;
@@ -1465,6 +1550,110 @@ int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets
   c->winsSince += wins;
   ++c->nBatches;
   c->nBytes += nbytes;
+  return TALC_OK;
+}
+
+int talc_counter_add(talc_counter* c, const char* bases, const uint64_t* offsets, uint32_t n_reads) {
+  return counter_add_records(c, bases, nullptr, offsets, n_reads);
+}
+
+int talc_counter_add_fastq(talc_counter* c, const char* bases, const char* quals, const uint64_t* offsets, uint32_t n_reads) {
+  return counter_add_records(c, bases, quals, offsets, n_reads);
+}
+
+// "ACGT,acgt" -> base codes; false with *why set for what talc_counter_set_filter refuses
+static bool parse_adapters(const char* text, SrAdapters& out, const char** why) {
+  memset(&out, 0, sizeof out);
+  if (!text || !*text) return true;
+  const char* p = text;
+  while (true) {
+    const char* e = strchr(p, ',');
+    const size_t m = e ? (size_t)(e - p) : strlen(p);
+    if (out.n == (uint32_t)kSrMaxAdapters) { *why = "more than 4 adapters"; return false; }
+    if (m == 0) { *why = "an empty adapter"; return false; }
+    if (m > (size_t)kSrMaxAdapterLen) { *why = "an adapter of more than 64 letters"; return false; }
+    for (size_t i = 0; i < m; ++i) {
+      const uint8_t code = ascii_to_code((uint8_t)p[i]);
+      if (code >= 4) { *why = "an adapter with a letter that is not one of ACGTacgt"; return false; }
+      out.code[out.n][i] = code;
+    }
+    out.len[out.n++] = (uint32_t)m;
+    if (!e) return true;
+    p = e + 1;
+  }
+}
+
+int talc_counter_set_filter(talc_counter* c, uint32_t min_qual, const char* adapters, uint32_t min_overlap, uint32_t max_error_pct) {
+  if (!c) return fail(TALC_ERR_INVALID, "null argument");
+  if (min_qual > 93) return fail(TALC_ERR_INVALID, "min_qual=%u: the quality floor is 0 (off) or 1..93 (Phred+33)", min_qual);
+  if (max_error_pct > 30) return fail(TALC_ERR_INVALID, "max_error_pct=%u: at most 30", max_error_pct);
+  if (min_overlap > (uint32_t)kSrMaxAdapterLen) return fail(TALC_ERR_INVALID, "min_overlap=%u: at most 64", min_overlap);
+  SrAdapters packed;
+  const char* why = nullptr;
+  if (!parse_adapters(adapters, packed, &why)) return fail(TALC_ERR_INVALID, "short-read filter: %s", why);
+  if (!min_overlap) min_overlap = 5;
+  for (uint32_t a = 0; a < packed.n; ++a)
+    if (min_overlap > packed.len[a])
+      return fail(TALC_ERR_INVALID, "min_overlap=%u is above the shortest adapter's length %u", min_overlap, packed.len[a]);
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (c->started) return fail(TALC_ERR_STATE, "the counter already holds k-mers: the filter is chosen before the first add");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));   // (a test-hook pass of an earlier setting may still run)
+  c->filterOn = false;
+  c->dAdapters.reset();
+  c->dFiltStats.reset();
+  c->filt = SrFilter{min_qual, min_overlap, max_error_pct};
+  if (!packed.n && !min_qual) return TALC_OK;   // off: talc_counter_add does what it does without a filter
+  if (c->dFiltStats.alloc(4) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the filter's counters"); }
+  HIPCHK(hipMemsetAsync(c->dFiltStats.get(), 0, 4 * 8, c->stream));
+  if (packed.n) {
+    if (c->dAdapters.alloc(1) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the filter's adapters"); }
+    HIPCHK(hipMemcpy(c->dAdapters.get(), &packed, sizeof packed, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->filterOn = true;
+  return TALC_OK;
+}
+
+int talc_counter_filter_stats(talc_counter* c, uint64_t stats[4]) {
+  if (!c || !stats) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!c->filterOn) return TALC_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  unsigned long long st[4];
+  HIPCHK(hipMemcpy(st, c->dFiltStats.get(), 4 * 8, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) stats[i] = st[i];
+  return TALC_OK;
+}
+
+// Test hook: the filter alone on one batch, through the counter's own staging and device buffers.  Counts nothing and
+// leaves the filter's counters alone.
+int talc_test_counter_mask(talc_counter* c, const char* bases, const char* quals, const uint64_t* offsets, uint32_t n_reads, char* masked_out,
+                           uint32_t* clip_out) {
+  if (!c || (n_reads && (!bases || !offsets || !clip_out))) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  if (!n_reads) return TALC_OK;
+  uint64_t wins = 0;
+  if (int rc = counter_check_batch(c, offsets, n_reads, true, &wins)) return rc;
+  const uint64_t nbytes = offsets[n_reads] - offsets[0] + n_reads;
+  if (nbytes > n_reads && !masked_out) return fail(TALC_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(c->device));
+  DevBuf<uint32_t> dClip;
+  if (dClip.alloc(n_reads) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %u clip positions", n_reads); }
+  int b = 0;
+  if (int rc = counter_stage_text(c, bases, offsets, n_reads, nbytes, &b)) return rc;
+  const int rcMask = counter_queue_mask(c, b, quals, offsets, n_reads, nbytes, false, dClip.get());
+  HIPCHK(hipEventRecord(c->stageEv[b], c->stream));
+  c->stageBusy[b] = true;
+  if (rcMask) return rcMask;
+  std::vector<char> text(nbytes);
+  HIPCHK(hipMemcpyAsync(text.data(), c->dText.get(), nbytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(clip_out, dClip.get(), (uint64_t)n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (uint32_t r = 0; r < n_reads; ++r)
+    memcpy(masked_out + (offsets[r] - offsets[0]), text.data() + (offsets[r] - offsets[0] + r), offsets[r + 1] - offsets[r]);
   return TALC_OK;
 }
 
@@ -1576,16 +1765,24 @@ static int counter_build_table(talc_counter* c, const char* junction_path, talc_
   // the hash goes before the builder allocates its buckets; the counter is spent from here on
   c->tab.reset(); c->cap = 0;
   c->dText.reset(); c->dTextCap = 0;
+  c->dQual.reset(); c->dQualCap = 0;
+  c->dOffs.reset(); c->dOffsCap = 0;
   c->spent = true;
   const double tCompact = watch.lap();
   if (c->sw.timing) {
     double kms = 0;
     for (auto& ev : c->kev) { float ms = 0; if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) kms += ms; }
+    char mask[96] = "";   // (a filtered counter only: the line of an unfiltered one is as it was)
+    if (c->filterOn) {
+      double mms = 0;
+      for (auto& ev : c->mev) { float ms = 0; if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) mms += ms; }
+      snprintf(mask, sizeof mask, ", mask kernels %.3f ms (%.3f ms per batch)", mms, c->nBatches ? mms / (double)c->nBatches : 0.0);
+    }
     fprintf(stderr, "[talc-lib] k-mer counter: %llu batches, %.0f MB, %llu windows, %llu distinct, %llu kept; pack %.3f s, count kernels %.3f ms "
-                    "(%.3f ms per batch), %llu grows %.3f s, last batch wait %.3f s, compaction %.3f s\n",
+                    "(%.3f ms per batch), %llu grows %.3f s, last batch wait %.3f s, compaction %.3f s%s\n",
             (unsigned long long)c->nBatches, (double)c->nBytes / 1e6, st[0], st[1], (unsigned long long)kept, c->packS, kms,
             c->nBatches ? kms / (double)c->nBatches : 0.0, (unsigned long long)c->nGrows, c->growS,
-            tWait, tCompact);
+            tWait, tCompact, mask);
   }
   TablePtr t;
   if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, t, 0.0, 0.0, c->sw))) return rc;

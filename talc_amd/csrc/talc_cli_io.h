@@ -82,6 +82,12 @@ class SeqReader {
   // false with ok() false from then on when a FASTQ record does not start with '@' or the sink returned false (no memory).
   template <class Sink>
   bool next(std::string& id, Sink&& sink) {
+    return next(id, sink, [](const char*, size_t) { return true; });
+  }
+  // The same, and qsink(p, n) called with every piece of a FASTQ record's qualities: as many bytes as the sequence has
+  // (multi-line qualities are joined by length; what a last line holds beyond it is dropped), fewer when truncated().
+  template <class Sink, class QSink>
+  bool next(std::string& id, Sink&& sink, QSink&& qsink) {
     if (!ok_) return false;
     if (!pending_) {
       while (true) {
@@ -96,7 +102,10 @@ class SeqReader {
       size_t n = 0;
       while (in_.getline(lp_, ll_)) { if (ll_ != 0 && lp_[0] == '+') break; if (ll_ && !sink(lp_, ll_)) { ok_ = false; return false; } n += ll_; }
       size_t got = 0;
-      while (got < n && in_.getline(lp_, ll_)) got += ll_;
+      while (got < n && in_.getline(lp_, ll_)) {
+        if (ll_ && !qsink(lp_, std::min(ll_, n - got))) { ok_ = false; return false; }
+        got += ll_;
+      }
       if (got < n) truncated_ = true;
       return true;
     }

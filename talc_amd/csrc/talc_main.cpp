@@ -41,6 +41,12 @@
 //   --both-strands   the k-mer table holds the short reads' support on either strand (docs/both_strands.md): --SRReads
 //                    counts canonical k-mers, -SR folds the counts (a `jellyfish count -C` dump, or a directional one) over
 //                    reverse complements on the GPU, and every kept k-mer is stored with its reverse complement
+//   --SRMinQual Q    with --SRReads: a base of a FASTQ short read whose Phred+33 quality is below Q (0..93, 0: none) is counted as N
+//                    (docs/sr_filter.md; `jellyfish count -Q`)
+//   --SRAdapter SEQ  (repeatable, up to 4) with --SRReads: every short read is clipped on the GPU from the first place where
+//                    SEQ, or a prefix of it that runs over the read's end, matches
+//   --SRAdapterOverlap N  with --SRAdapter: the shortest match that clips (default 5)
+//   --SRAdapterErr PCT    with --SRAdapter: mismatches allowed, in percent of the matched length (0..30, default 10)
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -118,6 +124,11 @@ struct Options {
   uint64_t maxEditCells = 0;                // --max-edit-cells (0: the library's default)
   bool autoStrand = false;                  // --auto-strand
   bool bothStrands = false;                 // --both-strands
+  uint32_t srMinQual = 0;                   // --SRMinQual (0: no floor)
+  std::vector<std::string> srAdapters;      // --SRAdapter, in order
+  uint32_t srAdapterOverlap = 0, srAdapterErr = 10;   // --SRAdapterOverlap (0: the library's default), --SRAdapterErr
+  bool haveSrMinQual = false, haveSrAdapterOverlap = false, haveSrAdapterErr = false;
+  bool srFilter() const { return srMinQual > 0 || !srAdapters.empty(); }
   bool fastq = false, haveQualRange = false;   // --fastq, --qual-range
   uint32_t qmin = 2, qmax = 40;
 };
@@ -137,6 +148,12 @@ void usage(FILE* f) {
           "                              counts are summed over a k-mer and its reverse complement on the GPU, MIN_COUNT applies\n"
           "                              to the sum and both are stored; --SRCountsOut then writes the canonical k-mers (not with\n"
           "                              --auto-strand; docs/both_strands.md)\n"
+          "  --SRMinQual INT             with --SRReads: bases of FASTQ short reads with a Phred+33 quality below this (0..93)\n"
+          "                              are counted as N (docs/sr_filter.md)\n"
+          "  --SRAdapter TEXT            with --SRReads: adapter to clip from the 3' end of every short read, 1..64 letters of\n"
+          "                              ACGT (repeat for up to 4 adapters); partial matches over the read's end clip too\n"
+          "  --SRAdapterOverlap INT      with --SRAdapter: shortest match that clips, 1..64 and at most the shortest adapter, default 5\n"
+          "  --SRAdapterErr INT          with --SRAdapter: mismatches allowed in percent of the matched length, 0..30, default 10\n"
           "  -j, --junctions TEXT        k-mers flanking junctions and their counts\n"
           "  -jf2, --pathToJF2 TEXT      directory of the jellyfish program: -qm jellyfish2 then reads the .jf through\n"
           "                              `jellyfish dump` (without it: the native .jf reader)\n"
@@ -205,6 +222,28 @@ Options parse(int argc, const char** argv) {
     else if (is(a, "SR", "SRCounts")) { o.dump = need(i); o.haveSR = true; }
     else if (a == "--SRReads") o.srReads.push_back(need(i));
     else if (a == "--SRCountsOut") o.srCountsOut = need(i);
+    else if (a == "--SRMinQual") {
+      const double v = num(need(i), "SRMinQual");
+      if (v != (double)(long long)v || v < 0 || v > 93) parse_error("value out of range for SRMinQual: 0..93");
+      o.srMinQual = (uint32_t)v; o.haveSrMinQual = true;
+    }
+    else if (a == "--SRAdapter") {
+      const std::string v = need(i);
+      if (v.empty() || v.size() > 64) parse_error("the given value '" + v + "' cannot be an SRAdapter: 1..64 letters are expected");
+      if (v.find_first_not_of("ACGTacgt") != std::string::npos) parse_error("the given value '" + v + "' cannot be an SRAdapter: it has a letter that is not one of ACGT");
+      if (o.srAdapters.size() == 4) parse_error("too many --SRAdapter: at most 4");
+      o.srAdapters.push_back(v);
+    }
+    else if (a == "--SRAdapterOverlap") {
+      const double v = num(need(i), "SRAdapterOverlap");
+      if (v != (double)(long long)v || v < 1 || v > 64) parse_error("value out of range for SRAdapterOverlap: 1..64");
+      o.srAdapterOverlap = (uint32_t)v; o.haveSrAdapterOverlap = true;
+    }
+    else if (a == "--SRAdapterErr") {
+      const double v = num(need(i), "SRAdapterErr");
+      if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for SRAdapterErr: 0..30");
+      o.srAdapterErr = (uint32_t)v; o.haveSrAdapterErr = true;
+    }
     else if (is(a, "j", "junctions")) { o.jdump = need(i); o.useJ = true; }
     else if (is(a, "jf2", "pathToJF2")) o.jf2 = need(i);
     else if (is(a, "MIN_INNER_SCORE", "MIN_INNER_SCORE")) { o.p.min_inner_score = num(need(i), "MIN_INNER_SCORE"); range(o.p.min_inner_score, 0.3, 0.9, "MIN_INNER_SCORE"); }
@@ -249,6 +288,14 @@ Options parse(int argc, const char** argv) {
   }
   if (o.seqFile.empty()) parse_error("not enough arguments were provided");
   if (!o.haveK) parse_error("option requires a value: -k, --kmerSize");
+  if (o.haveSrMinQual && o.srReads.empty()) parse_error("--SRMinQual needs --SRReads");
+  if (!o.srAdapters.empty() && o.srReads.empty()) parse_error("--SRAdapter needs --SRReads");
+  if (o.haveSrAdapterOverlap && o.srAdapters.empty()) parse_error("--SRAdapterOverlap needs --SRAdapter");
+  if (o.haveSrAdapterErr && o.srAdapters.empty()) parse_error("--SRAdapterErr needs --SRAdapter");
+  for (const std::string& ad : o.srAdapters)
+    if (ad.size() < (o.srAdapterOverlap ? o.srAdapterOverlap : 5u))
+      parse_error("value out of range for SRAdapterOverlap: " + std::to_string(o.srAdapterOverlap ? o.srAdapterOverlap : 5u) +
+                  " is above the length of the adapter " + ad);
   if (!o.haveSR && o.srReads.empty()) parse_error("option requires a value: -SR, --SRCounts");
   if (o.haveSR && !o.srReads.empty()) parse_error("-SR and --SRReads exclude each other: give the counts or the short reads");
   if (!o.srReads.empty() && o.queryMode == "jellyfish2") parse_error("--SRReads counts the k-mers itself: it does not go with -qm jellyfish2");
@@ -274,6 +321,10 @@ void outputConfig(const Options& o, const std::string& statFile) {
     << "Junction mode activated? " << (o.useJ ? 1 : 0) << "\n"
     << "queryMode=" << o.queryMode << "\n";
   if (o.bothStrands) f << "Both strands? 1" << "\n";
+  if (o.haveSrMinQual) f << "SRMinQual=" << o.srMinQual << "\n";
+  for (const std::string& ad : o.srAdapters) f << "SRAdapter=" << ad << "\n";
+  if (o.haveSrAdapterOverlap) f << "SRAdapterOverlap=" << o.srAdapterOverlap << "\n";
+  if (o.haveSrAdapterErr) f << "SRAdapterErr=" << o.srAdapterErr << "\n";
   f
     << "****************************" << "\n"
     << "MIN_INNER_SCORE=" << o.p.min_inner_score << "\n"
@@ -348,21 +399,32 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
   if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) return libError();
   struct Guard { talc_counter*& c; ~Guard() { talc_counter_destroy(c); } } guard{ctr};
   if (o.bothStrands && talc_counter_set_both_strands(ctr, 1) != TALC_OK) return libError();
+  // the short-read filter (docs/sr_filter.md): a filtered run hands every file's batches over on their own, a FASTQ file's
+  // with its qualities when there is a floor to apply
+  const bool filtered = o.srFilter();
+  if (filtered) {
+    std::string ads;
+    for (const std::string& ad : o.srAdapters) ads += (ads.empty() ? "" : ",") + ad;
+    if (talc_counter_set_filter(ctr, o.srMinQual, ads.c_str(), o.srAdapterOverlap, o.srAdapterErr) != TALC_OK) return libError();
+  }
   const size_t kBatchBytes = 64u << 20;
-  std::string buf;
+  std::string buf, qbuf;
   std::vector<uint64_t> offs{0};
   buf.reserve(kBatchBytes + (1u << 20));
+  bool withQuals = false;   // the batch being read carries qualities
   double readS = 0, addS = 0;
   uint64_t nRecords = 0, nBytes = 0, nBatches = 0;
   auto flush = [&]() -> bool {
     if (offs.size() < 2) return true;
     const auto ta = Clock::now();
-    const bool ok = talc_counter_add(ctr, buf.data(), offs.data(), (uint32_t)(offs.size() - 1)) == TALC_OK;
+    const bool ok = (filtered ? talc_counter_add_fastq(ctr, buf.data(), withQuals ? qbuf.data() : nullptr, offs.data(), (uint32_t)(offs.size() - 1))
+                              : talc_counter_add(ctr, buf.data(), offs.data(), (uint32_t)(offs.size() - 1))) == TALC_OK;
     const double dt = since(ta);
     addS += dt;
     if (sw.timing == 2) fprintf(stderr, "[talc-count] batch %llu: %zu records, %zu bytes, counter add (pack + queue) %.4f s\n", (unsigned long long)nBatches, offs.size() - 1, buf.size(), dt);
     ++nBatches;
     buf.clear();
+    qbuf.clear();
     offs.assign(1, 0);
     return ok;
   };
@@ -372,8 +434,17 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
     if (!r.ok()) { std::cerr << "talc: " << file << " is not a FASTA or FASTQ file that can be read\n"; return 2; }
     std::string id;
     uint64_t rec = 0;
+    if (filtered) {   // (a batch is one file's: its records have qualities or they have none)
+      nBytes += buf.size();
+      if (!flush()) return libError();
+      withQuals = o.srMinQual > 0 && r.fastq();
+      if (o.srMinQual > 0 && !r.fastq())
+        std::cerr << "[talc] warning: " << file << " is FASTA: it has no qualities, --SRMinQual does not apply to it\n";
+    }
     auto tr = Clock::now();
-    while (r.next(id, [&](const char* p, size_t n) { buf.append(p, n); return true; })) {
+    auto bases = [&](const char* p, size_t n) { buf.append(p, n); return true; };
+    auto quals = [&](const char* p, size_t n) { if (withQuals) qbuf.append(p, n); return true; };
+    while (r.next(id, bases, quals)) {
       ++rec;
       if (r.truncated()) { std::cerr << "talc: " << file << ": FASTQ record " << rec << " (" << id << ") is malformed: its qualities are shorter than its sequence\n"; return 2; }
       offs.push_back(buf.size());
@@ -390,6 +461,12 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
   }
   nBytes += buf.size();
   if (!flush()) return libError();
+  if (filtered) {
+    uint64_t fs[4];
+    if (talc_counter_filter_stats(ctr, fs) != TALC_OK) return libError();
+    std::cout << "[TALC]: short-read filter: " << fs[0] << " records, " << fs[1] << " clipped at an adapter, " << fs[2] << " bases clipped, " << fs[3]
+              << " bases below the quality floor" << std::endl;
+  }
   const auto t1 = Clock::now();
   if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers (--both-strands: of the canonical ones, as after count -C)
     uint64_t n = 0;

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "talc_counter_destroy",
     "talc_counter_set_both_strands", "talc_counter_add_counts", "talc_table_build_device_both_strands",
     "talc_table_from_arrays_device_both_strands",
+    "talc_counter_set_filter", "talc_counter_add_fastq", "talc_counter_filter_stats", "talc_test_counter_mask",
     "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
     "talc_ctx_get_map_timing",
     "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
@@ -208,6 +209,11 @@ def lib():
             L.talc_counter_add_counts.argtypes = [vp, vp, vp, u64]
             L.talc_table_build_device_both_strands.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), i32, C.POINTER(vp), vp]
             L.talc_table_from_arrays_device_both_strands.argtypes = [vp, vp, u64, C.POINTER(Params), i32, C.POINTER(vp)]
+        if hasattr(L, "talc_counter_set_filter"):   # (likewise: a build from before the short-read filter)
+            L.talc_counter_set_filter.argtypes = [vp, u32, C.c_char_p, u32, u32]
+            L.talc_counter_add_fastq.argtypes = [vp, vp, vp, vp, u32]
+            L.talc_counter_filter_stats.argtypes = [vp, vp]
+            L.talc_test_counter_mask.argtypes = [vp, vp, vp, vp, u32, vp, vp]
         # (a build from before the correction map, selected with TALC_LIB for an A/B, loads; asking it for a map raises)
         if hasattr(L, "talc_ctx_set_map"):
             L.talc_ctx_set_map.argtypes = [vp, i32]
@@ -523,13 +529,55 @@ class KmerCounter:
             raise ValueError("kmers and counts differ in length")
         _chk(lib().talc_counter_add_counts(self._h, kmers.ctypes.data, counts.ctypes.data, len(kmers)))
 
-    def add(self, bases, offsets):
-        """Queue a batch of records (bases: uint8 / bytes concatenated, offsets: u64[n+1]); the arrays may be reused at once."""
+    def set_filter(self, min_qual=0, adapters=(), min_overlap=0, max_error_pct=10):
+        """The short-read filter (docs/sr_filter.md), before the first add only: bases with a Phred+33 quality below min_qual
+        and everything from the first match of one of `adapters` (str / bytes, or a sequence of up to 4) are counted as N.
+        min_overlap 0 is the default 5.  No adapters and min_qual 0 switch it off."""
+        if isinstance(adapters, (str, bytes)):
+            adapters = [adapters]
+        text = b",".join(a.encode() if isinstance(a, str) else bytes(a) for a in adapters)
+        if len(adapters) and not text:
+            text = b","      # (an empty adapter is refused by the library, not dropped here)
+        _chk(lib().talc_counter_set_filter(self._h, int(min_qual), text, int(min_overlap), int(max_error_pct)))
+
+    @staticmethod
+    def _batch(bases, offsets, quals):
         if isinstance(bases, (bytes, bytearray)):
             bases = np.frombuffer(bases, dtype=np.uint8)
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        _chk(lib().talc_counter_add(self._h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1))
+        if quals is not None:
+            if isinstance(quals, (bytes, bytearray)):
+                quals = np.frombuffer(quals, dtype=np.uint8)
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            if len(quals) != len(bases):
+                raise ValueError("one quality per base is expected")
+        return bases, offsets, quals
+
+    def add(self, bases, offsets, quals=None):
+        """Queue a batch of records (bases: uint8 / bytes concatenated, offsets: u64[n+1]; quals: one Phred+33 byte per base,
+        for the filter's quality floor); the arrays may be reused at once."""
+        bases, offsets, quals = self._batch(bases, offsets, quals)
+        if quals is None:
+            _chk(lib().talc_counter_add(self._h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1))
+        else:
+            _chk(lib().talc_counter_add_fastq(self._h, bases.ctypes.data, quals.ctypes.data, offsets.ctypes.data, len(offsets) - 1))
+
+    def filter_stats(self):
+        """(records filtered, records clipped, bytes clipped, bytes below the quality floor ahead of the clip)."""
+        st = np.zeros(4, dtype=np.uint64)
+        _chk(lib().talc_counter_filter_stats(self._h, st.ctypes.data))
+        return tuple(int(x) for x in st)
+
+    def mask(self, bases, offsets, quals=None):
+        """Test hook: the filter alone on one batch: (masked bytes uint8, without separators; clip u32[n]).  Counts nothing."""
+        bases, offsets, quals = self._batch(bases, offsets, quals)
+        n = len(offsets) - 1
+        masked = np.zeros(max(int(offsets[-1] - offsets[0]), 1), dtype=np.uint8)
+        clip = np.zeros(max(n, 1), dtype=np.uint32)
+        _chk(lib().talc_test_counter_mask(self._h, bases.ctypes.data, quals.ctypes.data if quals is not None else None,
+                                          offsets.ctypes.data, n, masked.ctypes.data, clip.ctypes.data))
+        return masked[: int(offsets[-1] - offsets[0])], clip[:n]
 
     def stats(self):
         """(windows counted, distinct k-mers, distinct k-mers with count >= params.min_count)."""
@@ -565,6 +613,17 @@ class KmerCounter:
             self.close()
         except Exception:
             pass
+
+
+def mask_batch(bases, offsets, quals=None, min_qual=0, adapters=(), min_overlap=0, max_error_pct=10, params=None, device=0):
+    """Test hook (talc_test_counter_mask): the short-read filter alone on one batch, on a counter of its own.  Returns
+    (masked bytes without separators, clip u32[n])."""
+    c = KmerCounter(params or default_params(), device)
+    try:
+        c.set_filter(min_qual, adapters, min_overlap, max_error_pct)
+        return c.mask(bases, offsets, quals)
+    finally:
+        c.close()
 
 
 class Context:

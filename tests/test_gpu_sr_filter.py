@@ -1,0 +1,307 @@
+"""The short-read filter on the GPU (k_sr_mask, talc_counter_set_filter / add_fastq / filter_stats, `talc --SRAdapter --SRMinQual`)
+against the numpy reference of its contract (tests/srfilter_ref.py, docs/sr_filter.md).  Every comparison is exact."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import fold_ref as FO
+import kmer_ref as R
+import srfilter_ref as F
+from talc_amd import build as B
+from talc_amd import lib as T
+from talc_amd.synth import Synth
+
+pytestmark = pytest.mark.gpu
+
+TALC = os.path.join(B.OUT, "talc")
+AD = F.AD33
+
+
+def sorted_pairs(kmers, counts):
+    o = np.argsort(kmers, kind="stable")
+    return kmers[o], counts[o]
+
+
+def gpu_mask(records, quals, k=21, **kw):
+    b, q, o = F.to_arrays(records, quals)
+    return T.mask_batch(b, o, q, min_qual=kw.get("min_qual", 0), adapters=kw.get("adapters", ()), min_overlap=kw.get("min_overlap", 0),
+                        max_error_pct=kw.get("err_pct", 10), params=T.default_params(k=k))
+
+
+def assert_mask_equals_reference(records, quals, **kw):
+    b, q, o = F.to_arrays(records, quals)
+    want_m, want_c, _ = F.mask(b, q, o, **kw)
+    got_m, got_c = gpu_mask(records, quals, **kw)
+    assert np.array_equal(got_c, want_c), (got_c.tolist(), want_c.tolist())
+    assert np.array_equal(got_m, want_m), (F.split(got_m, o), F.split(want_m, o))
+    return want_c
+
+
+# ------------------------------------------------------------------ the pass alone
+@pytest.mark.parametrize("case", F.hand_cases(), ids=lambda c: c[0])
+def test_hand_cases_equal_reference(case):
+    name, records, quals, kw = case
+    assert_mask_equals_reference(records, quals, **kw)
+
+
+def test_random_records_equal_reference():
+    records, quals = F.random_records(3, 300, adapters=(AD, "ACGTTGCA", "ttgacc"))
+    for kw in (dict(adapters=[AD]), dict(adapters=[AD, "ACGTTGCA", "ttgacc"], min_overlap=3, err_pct=20, min_qual=5), dict(min_qual=30)):
+        assert_mask_equals_reference(records, quals, **kw)
+
+
+def edge_batch(n, seed):
+    """n records of 150 bytes; an adapter in every third one, in every record whose bytes straddle a multiple of 8192 in the
+    staged batch (record r sits at 151 r), and in the last one."""
+    rng = np.random.default_rng(seed)
+    recs, quals = [], []
+    for r in range(n):
+        s = bytearray("".join(rng.choice(list("ACGT"), size=150)).encode())
+        at = 151 * r
+        straddles = at // 8192 != (at + 149) // 8192
+        if r % 3 == 0 or straddles or r == n - 1:
+            edge = 8192 * ((at + 149) // 8192) - at if straddles else 0
+            p = int(rng.integers(max(1, edge - 20), edge - 2)) if straddles and edge > 25 else int(rng.integers(5, 146))
+            s[p:] = (AD.encode() * 5)[:150 - p]
+        recs.append(bytes(s))
+        quals.append(bytes(np.where(rng.random(150) < 0.02, 33 + 3, 33 + 38).astype(np.uint8)))
+    return recs, quals
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 300])
+def test_batches_at_the_grouping_edges(n):
+    recs, quals = edge_batch(n, 100 + n)
+    clip = assert_mask_equals_reference(recs, quals, adapters=[AD], min_qual=20)
+    assert clip[-1] < 150                               # the last record of the batch is clipped
+    if n == 300:                                         # 45 KB: several count tiles, clipped records across their edges
+        at = 151 * np.arange(n)
+        straddles = at // 8192 != (at + 149) // 8192
+        assert straddles.sum() >= 5 and (clip[straddles] < 150).all()
+        assert ((at + clip)[straddles] // 8192 == at[straddles] // 8192).any()    # ... with the clip ahead of the edge
+    # and counted: the filtered counter against an unfiltered one fed the masked records
+    b, q, o = F.to_arrays(recs, quals)
+    want_m, _, want_st = F.mask(b, q, o, adapters=[AD], min_qual=20)
+    p = T.default_params(k=21)
+    c = T.KmerCounter(p, 0)
+    c.set_filter(20, [AD])
+    c.add(b, o, q)
+    got = sorted_pairs(*c.fetch(1))
+    assert c.filter_stats() == want_st
+    c.close()
+    want = R.count(want_m, o, 21)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+# ------------------------------------------------------------------ counts
+@pytest.fixture(scope="module")
+def synth():
+    return Synth(target_kmers=150_000, k=21, seed=77)
+
+
+def with_adapters(bases, offs, seed, frac=0.3, low=0.01):
+    """A fixed-seed pass over reads of 150 bases: `frac` of them cut to a random insert length with the adapter behind it,
+    truncated at 150; a quality for every base, low at `low` of the positions."""
+    rng = np.random.default_rng(seed)
+    n = len(offs) - 1
+    rows = np.asarray(bases, dtype=np.uint8).reshape(n, 150).copy()
+    cut = rng.random(n) < frac
+    insert = rng.integers(20, 150, size=n)
+    tail = np.frombuffer((AD * 5).encode(), dtype=np.uint8)
+    col = np.arange(150)
+    behind = cut[:, None] & (col[None, :] >= insert[:, None])
+    rows[behind] = tail[(col[None, :] - insert[:, None]) % len(tail)][behind]
+    quals = np.where(rng.random((n, 150)) < low, 33 + 5, 33 + 37).astype(np.uint8)
+    return rows.reshape(-1), quals.reshape(-1), cut, insert
+
+
+@pytest.fixture(scope="module")
+def dirty(synth):
+    bases, offs = synth.short_reads(0, 20_000, length=150, sub_rate=0.005, n_rate=0.001)
+    b, q, cut, insert = with_adapters(bases, offs, 5)
+    masked, clip, stats = F.mask(b, q, offs, min_qual=20, adapters=[AD])
+    return dict(bases=b, quals=q, offs=offs, masked=masked, clip=clip, stats=stats, cut=cut, insert=insert)
+
+
+def counted(k, both, filt, bases, offs, quals=None, cuts=None):
+    c = T.KmerCounter(T.default_params(k=k), 0, both_strands=both)
+    if filt is not None:
+        c.set_filter(**filt)
+    cuts = cuts or [0, len(offs) - 1]
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        lo, hi = int(offs[a]), int(offs[b])
+        c.add(bases[lo:hi], offs[a:b + 1] - offs[a], None if quals is None else quals[lo:hi])
+    out = (sorted_pairs(*c.fetch(1)), c.stats(), c.filter_stats())
+    c.close()
+    return out
+
+
+def counts_check(d, k, both):
+    n = 6000
+    offs = d["offs"][:n + 1]
+    hi = int(offs[-1])
+    bases, quals, masked = d["bases"][:hi], d["quals"][:hi], d["masked"][:hi]
+    _, _, want_fs = F.mask(bases, quals, offs, min_qual=20, adapters=[AD])
+    filt = dict(min_qual=20, adapters=[AD])
+    got, st, fs = counted(k, both, filt, bases, offs, quals, cuts=[0, 1, 2500, n])
+    plain, pst, pfs = counted(k, both, None, masked, offs)
+    wk, wc = FO.fold_records(masked, offs, k) if both else R.count(masked, offs, k)
+    wc = wc.astype(np.uint32)
+    assert np.array_equal(got[0], wk) and np.array_equal(got[1], wc)
+    assert np.array_equal(plain[0], wk) and np.array_equal(plain[1], wc)
+    assert st == pst == (int(wc.sum()), len(wk), int((wc >= 2).sum()))
+    assert fs == want_fs and pfs == (0, 0, 0, 0)
+    return got, st, fs
+
+
+@pytest.mark.parametrize("both", [False, True], ids=["directional", "both-strands"])
+@pytest.mark.parametrize("k", [18, 21, 31])
+def test_filtered_counts_equal_unfiltered_counts_of_the_masked_records(dirty, k, both):
+    counts_check(dirty, k, both)
+
+
+@pytest.mark.parametrize("byte", [0xA5, 0x00])
+def test_counts_do_not_depend_on_what_device_memory_held(dirty, byte):
+    fresh = counts_check(dirty, 21, False)
+    before = T.guard_report()
+    with T.poisoned(byte):
+        again = counts_check(dirty, 21, False)
+    after = T.guard_report()
+    assert np.array_equal(again[0][0], fresh[0][0]) and np.array_equal(again[0][1], fresh[0][1]) and again[1:] == fresh[1:]
+    assert after["violations"] == before["violations"] and after["checked"] > before["checked"]
+
+
+def test_buffers_reused_across_batches_of_different_sizes(dirty):
+    d = dirty
+    o = d["offs"]
+    parts = [(0, 5000, True), (5000, 5700, True), (5700, 7000, False)]      # large with qualities, smaller with others, none
+    filt = dict(min_qual=20, adapters=[AD])
+    c = T.KmerCounter(T.default_params(k=21), 0)
+    c.set_filter(**filt)
+    total = {}
+    fs_sum = np.zeros(4, dtype=np.int64)
+    for a, b, wq in parts:
+        lo, hi = int(o[a]), int(o[b])
+        q = d["quals"][lo:hi] if wq else None
+        c.add(d["bases"][lo:hi], o[a:b + 1] - o[a], q)
+        (k1, c1), _, fs = counted(21, False, filt, d["bases"][lo:hi], o[a:b + 1] - o[a], q)
+        for x, y in zip(k1.tolist(), c1.tolist()):
+            total[x] = total.get(x, 0) + y
+        fs_sum += np.array(fs)
+    got = sorted_pairs(*c.fetch(1))
+    fs = c.filter_stats()
+    c.close()
+    keys = np.array(sorted(total), dtype=np.uint64)
+    assert np.array_equal(got[0], keys) and np.array_equal(got[1], np.array([total[x] for x in keys.tolist()], dtype=np.uint32))
+    assert fs == tuple(int(x) for x in fs_sum)
+    # the last batch had no floor applied: the reference says the same
+    lo, hi = int(o[5700]), int(o[7000])
+    assert F.mask(d["bases"], None, o[5700:7001], min_qual=20, adapters=[AD])[2][3] == 0 and fs_sum[3] > 0 and hi > lo
+
+
+def test_synthetic_reads_with_adapters(dirty):
+    d = dirty
+    k = 21
+    filt, st, fs = counted(k, False, dict(min_qual=20, adapters=[AD]), d["bases"], d["offs"], d["quals"], cuts=[0, 7000, 20_000])
+    raw, _, _ = counted(k, False, None, d["bases"], d["offs"])
+    wk, wc = R.count(d["masked"], d["offs"], k)
+    assert np.array_equal(filt[0], wk) and np.array_equal(filt[1], wc)
+    assert fs == d["stats"] and fs[1] > 0.9 * d["cut"].sum() and fs[3] > 0     # (an overhang of fewer than 5 bases is not clipped)
+    ak, _ = R.count(*R.records_to_arrays([AD]), k)
+    assert len(ak) == 13
+    in_raw = raw[1][np.searchsorted(raw[0], ak)]
+    assert np.isin(ak, raw[0]).all() and (in_raw >= 2).all()            # the unfiltered counter holds every k-mer of the adapter
+    solid = filt[0][filt[1] >= 2]
+    assert not np.isin(ak, solid).any()                                  # the filtered one holds none that would be kept
+
+
+# ------------------------------------------------------------------ state and arguments
+def test_set_filter_state_and_argument_errors(dirty):
+    p = T.default_params(k=21)
+    b, o = dirty["bases"][:1500], dirty["offs"][:11]
+    c = T.KmerCounter(p, 0)
+    for kw in (dict(min_qual=94), dict(max_error_pct=31, adapters=[AD]), dict(adapters=[AD] * 5), dict(adapters=["ACGTAC", ""]), dict(adapters=["A" * 65]),
+               dict(adapters=["ACGTNACGT"]), dict(adapters=[AD], min_overlap=65), dict(adapters=[AD, "ACGTAC"], min_overlap=7), dict(adapters=["ACGT"])):
+        with pytest.raises(T.TalcError, match="error -1"):
+            c.set_filter(**kw)
+    c.set_filter(20, [AD, "ACGTAC"], 6, 30)              # the largest arguments
+    c.set_filter(0, "A", 1, 0)                           # may be set again before the first add
+    c.add(b, o)
+    with pytest.raises(T.TalcError, match="error -6"):   # TALC_ERR_STATE
+        c.set_filter(20, [AD])
+    c.close()
+    for how in ("add_counts", "build_table"):
+        c = T.KmerCounter(p, 0)
+        if how == "add_counts":
+            c.add_counts(np.array([5], dtype=np.uint64), np.array([3], dtype=np.uint32))
+        else:
+            c.add(b, o)
+            c.build_table().close()
+        with pytest.raises(T.TalcError, match="error -6"):
+            c.set_filter(20, [AD])
+        c.close()
+
+
+def test_a_filter_set_to_off_equals_a_plain_counter(dirty):
+    b, o, q = dirty["bases"][:150 * 3000], dirty["offs"][:3001], dirty["quals"][:150 * 3000]
+    plain, pst, _ = counted(21, False, None, b, o)
+    off, ost, ofs = counted(21, False, dict(min_qual=0, adapters=()), b, o, q)
+    assert np.array_equal(plain[0], off[0]) and np.array_equal(plain[1], off[1]) and pst == ost and ofs == (0, 0, 0, 0)
+    m, clip = T.mask_batch(b, o, q)                      # the pass itself with nothing to do
+    assert np.array_equal(m, b) and np.array_equal(clip, np.full(3000, 150, np.uint32))
+
+
+# ------------------------------------------------------------------ the CLI
+def run(args, cwd):
+    return subprocess.run([TALC] + args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+
+
+def write_fastq(path, bases, quals, offs):
+    n = len(offs) - 1
+    rows = np.asarray(bases, dtype=np.uint8).reshape(n, 150)
+    qrows = np.asarray(quals, dtype=np.uint8).reshape(n, 150)
+    with open(path, "wb") as f:
+        f.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, rows[i].tobytes(), qrows[i].tobytes()) for i in range(n)))
+
+
+def test_cli_filter_gives_what_a_cleaned_file_gives(dirty, synth, tmp_path):
+    d = dirty
+    write_fastq(tmp_path / "raw.fq", d["bases"], d["quals"], d["offs"])
+    write_fastq(tmp_path / "cleaned.fq", d["masked"], d["quals"], d["offs"])
+    synth.write_fasta(str(tmp_path / "reads.fa"), 0, 2000)
+    common = ["reads.fa", "-k", "21"]
+    a = run(common + ["--SRReads", "raw.fq", "--SRAdapter", AD, "--SRMinQual", "20", "--SRCountsOut", "a.dump", "-o", "a"], tmp_path)
+    b = run(common + ["--SRReads", "cleaned.fq", "--SRCountsOut", "b.dump", "-o", "b"], tmp_path)
+    c = run(common + ["--SRReads", "raw.fq", "--SRCountsOut", "c.dump", "-o", "c"], tmp_path)
+    for r in (a, b, c):
+        assert r.returncode == 0, r.stderr.decode()
+    dump = lambda name: sorted((tmp_path / name).read_bytes().splitlines())
+    assert dump("a.dump") == dump("b.dump") and dump("c.dump") != dump("b.dump")
+    assert (tmp_path / "a.fa").read_bytes() == (tmp_path / "b.fa").read_bytes()
+    assert (tmp_path / "a.fa").read_bytes().count(b">") == 2000
+    m = re.search(rb"\[TALC\]: short-read filter: (\d+) records, (\d+) clipped at an adapter, (\d+) bases clipped, (\d+) bases below the quality floor\n", a.stdout)
+    assert m and tuple(int(x) for x in m.groups()) == d["stats"], a.stdout
+    assert b"short-read filter" not in b.stdout and b"short-read filter" not in c.stdout
+    ca, cb, cc = ((tmp_path / (x + ".config.txt")).read_bytes().splitlines() for x in "abc")
+    i = ca.index(b"queryMode=memory")
+    assert ca[i + 1:i + 3] == [b"SRMinQual=20", b"SRAdapter=" + AD.encode()]
+    assert [ln.replace(b"=a", b"=b").replace(b": a", b": b") for ln in ca[:i + 1] + ca[i + 3:]] == cb
+    assert [ln.replace(b"=c", b"=b").replace(b": c", b": b") for ln in cc] == cb
+
+
+def test_cli_fasta_under_a_floor_is_counted_without_it_and_named(dirty, synth, tmp_path):
+    d = dirty
+    n = 3000
+    rows = d["bases"][:150 * n].reshape(n, 150)
+    with open(tmp_path / "sr.fa", "wb") as f:
+        f.write(b"".join(b">s%d\n%s\n" % (i, rows[i].tobytes()) for i in range(n)))
+    synth.write_fasta(str(tmp_path / "reads.fa"), 0, 20)
+    r = run(["reads.fa", "-k", "21", "--SRReads", "sr.fa", "--SRMinQual", "20", "--SRAdapter", AD, "--SRCountsOut", "x.dump", "-o", "x"], tmp_path)
+    assert r.returncode in (0, 1), r.stderr.decode()          # (1: the empty graph of a small sample is the reference's exit)
+    warn = [ln for ln in r.stderr.splitlines() if ln.startswith(b"[talc] warning:")]
+    assert len(warn) == 1 and b"sr.fa" in warn[0]
+    want = F.mask(d["bases"][:150 * n], None, d["offs"][:n + 1], min_qual=20, adapters=[AD])[2]
+    m = re.search(rb"short-read filter: (\d+) records, (\d+) clipped at an adapter, (\d+) bases clipped, (\d+) bases below", r.stdout)
+    assert m and tuple(int(x) for x in m.groups()) == want and want[3] == 0
