@@ -115,6 +115,12 @@ def first_trace_diff(pair, bases, offs, idx):
     b = pair.ctx.batch(np.frombuffer(seq.encode(), dtype=np.uint8), np.array([0, len(seq)], dtype=np.uint64))
     tg = b.trace(0).splitlines()
     b.close()
+    return first_line_diff(to, tg)
+
+
+def first_line_diff(to, tg):
+    """The first line at which two traces (lists of lines: oracle, HIP path) differ, with the lines around it; None if
+    none does."""
     n = min(len(to), len(tg))
     for i in range(n):
         if to[i] != tg[i]:
