@@ -263,6 +263,42 @@ int talc_table_build_device_both_strands(const char* dump_path, const char* junc
 int talc_table_from_arrays_device_both_strands(const uint64_t* kmers, const uint32_t* counts, uint64_t n,
                                                const talc_params* p, int device, talc_table** out);
 
+/* ---------------------------------------------------------------- (1d) k-mer spectrum ------
+ * Replaces `jellyfish histo`, the command between counting and correcting (docs/kmer_spectrum.md): the number of distinct
+ * k-mers per count, from the counter's hash on the device, and the MIN_COUNT that spectrum suggests.
+ * hist has high + 2 entries: hist[c], 1 <= c <= high, the k-mers with count c; hist[high + 1] those with a larger count;
+ * hist[0] the used slots with count 0 (0 in practice; the bin stays so that index equals count).
+ * stats: distinct = the k-mers, unique = those with count 1, total = the sum of all counts, max_count = the largest. */
+typedef struct talc_spectrum_stats { uint64_t distinct, unique, total, max_count; } talc_spectrum_stats;
+
+/* hist: high + 2 entries as above (may be NULL), stats may be NULL.  high: 0 means 10000; otherwise 2 .. 16382, else
+ * TALC_ERR_INVALID.  Waits for the queued batches.  Does not spend the counter and changes nothing fetch, stats or
+ * build_table return; may be called any number of times, between adds too.  TALC_ERR_STATE on a spent counter.
+ * A both-strands counter's spectrum is that of the canonical k-mers with their folded counts. */
+int talc_counter_histo(talc_counter* c, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats);
+
+/* Measurement: device time (ms) of the last k_count_histo of this counter. */
+int talc_counter_get_histo_timing(const talc_counter* c, float* histo_ms);
+
+/* The same spectrum over the k-mers a table stores: every stored k-mer once with its count.  A both-strands table
+ * stores both strands, so both are counted.  Needs the table's image on `device` (a device-built table, or after
+ * talc_table_upload(t, device)): TALC_ERR_STATE otherwise.  stats->distinct == talc_table_size(t). */
+int talc_table_histo(talc_table* t, int device, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats);
+
+/* Host, pure, needs no GPU.  The solidity threshold a spectrum suggests: its first local minimum.
+ * limit: 0 means 32.  L = min(limit, high - 1).
+ * valley = the smallest c in [1, L] with hist[c + 1] > 0 and hist[c] <= hist[c + 1]; 0 when there is none.
+ * A spectrum that only falls, as shallow RNA-seq does, has no valley.
+ * *chosen = max(2, valley) when there is a valley, else fallback.
+ * TALC_ERR_INVALID: hist or chosen NULL, high < 2, fallback == 0.  valley_out may be NULL. */
+int talc_spectrum_threshold(const uint64_t* hist, uint32_t high, uint32_t limit, uint32_t fallback,
+                            uint32_t* chosen, uint32_t* valley_out);
+
+/* Replaces p->min_count of the counter (>= 1, else TALC_ERR_INVALID; TALC_ERR_STATE on a spent counter).
+ * talc_counter_stats()[2] and talc_counter_build_table use the new value.  The table carries it, so a context on that
+ * table must be created with it (the existing rule of talc_ctx_create). */
+int talc_counter_set_min_count(talc_counter* c, uint32_t min_count);
+
 /* ---------------------------------------------------------------- (2) per-read surface ---
  * Replaces, for a whole batch, the loop body of main.cpp:247-308:
  *   Read(id, seq); getLength()>K; reCoverage(); defineStructure2(); correct2(); getCorrSeq()

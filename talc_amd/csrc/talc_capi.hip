@@ -26,6 +26,7 @@
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
 #include "talc_kernels_solidity.h"
+#include "talc_kernels_spectrum.h"
 #include "talc_kernels_srfilter.h"
 #include "talc_kernels_strand.h"
 #include "talc_kernels_support.h"
@@ -1306,9 +1307,12 @@ struct talc_counter {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
   uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
   double packS = 0, growS = 0;
+  hipEvent_t histoEv[2] = {nullptr, nullptr};   // around the last k_count_histo (talc_counter_histo makes them)
+  float histo_ms = 0;
   ~talc_counter() {
     (void)hipSetDevice(device);
     for (auto& e : stageEv) if (e) hipEventDestroy(e);
+    for (auto& e : histoEv) if (e) hipEventDestroy(e);
     for (auto& ev : kev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto& ev : mev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     if (stream) hipStreamDestroy(stream);
@@ -1800,6 +1804,118 @@ int talc_counter_build_table(talc_counter* c, const char* junction_path, talc_ta
   if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
   if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
   return counter_build_table(c, junction_path, out, stats, nullptr, true);
+}
+
+// ------------------------------------------------------------------ k-mer spectrum (talc_kernels_spectrum.h, docs/kmer_spectrum.md)
+// Replaces `jellyfish histo`.  One pass of k_count_histo over the counter's hash, or of k_table_histo over a table's RIGHT
+// buckets; the threshold rule itself is talc_pure.h's.
+static int spectrum_high(uint32_t* high) {
+  if (*high == 0) *high = kSpectrumDefaultHigh;
+  if (*high < 2 || *high > kSpectrumMaxHigh)
+    return fail(TALC_ERR_INVALID, "high=%u: the spectrum takes 2 .. %u (0: %u)", *high, kSpectrumMaxHigh, kSpectrumDefaultHigh);
+  return TALC_OK;
+}
+
+// the CU count of a device, asked once per device and process (the properties query is slow beside a pass over a small hash)
+static int spectrum_cu_count(int device, int* cus) {
+  static std::mutex lock;
+  static std::map<int, int> known;
+  std::lock_guard<std::mutex> g(lock);
+  auto it = known.find(device);
+  if (it == known.end()) {
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    it = known.emplace(device, std::max(prop.multiProcessorCount, 1)).first;
+  }
+  *cus = it->second;
+  return TALC_OK;
+}
+
+// One spectrum pass on `stream` of the current device over n slots, of which a workgroup takes groupSlots per trip: the
+// output words zeroed, the kernel launched by launch(grid, lds bytes, out) between ev[0] and ev[1] (when given), the bins
+// and totals copied to hist / stats (either may be NULL).  The grid: a workgroup per trip, at most the fixed number per CU.
+extern "C++" template <class Launch>
+static int run_spectrum(int device, hipStream_t stream, uint64_t n, uint64_t groupSlots, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats,
+                        hipEvent_t* ev, Launch launch) {
+  const uint32_t bins = high + 2;
+  DevBuf<unsigned long long> dOut;
+  HIPCHK(dOut.alloc(bins + SPECTRUM_TOTALS));
+  HIPCHK(hipMemsetAsync(dOut.get(), 0, (uint64_t)(bins + SPECTRUM_TOTALS) * 8, stream));
+  int cus = 1;
+  if (int rc = spectrum_cu_count(device, &cus)) return rc;
+  const uint64_t grid = std::min<uint64_t>((n + groupSlots - 1) / groupSlots, (uint64_t)cus * kSpectrumGridPerCu);
+  if (ev) HIPCHK(hipEventRecord(ev[0], stream));
+  // (no slots, a table of capacity 0: nothing is launched, the zeroed words are the answer and the events time nothing)
+  if (grid) launch(dim3((unsigned)grid), (size_t)spectrum_lds_words(bins) * 4, dOut.get());
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev[1], stream));
+  std::vector<unsigned long long> h(bins + SPECTRUM_TOTALS);
+  HIPCHK(hipMemcpyAsync(h.data(), dOut.get(), h.size() * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (hist) for (uint32_t b = 0; b < bins; ++b) hist[b] = h[b];
+  if (stats) {
+    stats->distinct = h[bins + SPECTRUM_DISTINCT]; stats->unique = h[bins + SPECTRUM_UNIQUE];
+    stats->total = h[bins + SPECTRUM_TOTAL]; stats->max_count = h[bins + SPECTRUM_MAX];
+  }
+  return TALC_OK;
+}
+
+int talc_counter_histo(talc_counter* c, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats) {
+  int rc = spectrum_high(&high);
+  if (rc) return rc;
+  if (!c) return fail(TALC_ERR_INVALID, "null argument");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  unsigned long long st[2];
+  if ((rc = counter_sync(c, st))) return rc;
+  for (auto& e : c->histoEv)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  const CountSlot* tab = c->tab.get();
+  const uint64_t cap = c->cap;
+  hipStream_t stream = c->stream;
+  rc = run_spectrum(c->device, stream, cap, spectrum_group_slots<CounterSlots>(), high, hist, stats, c->histoEv, [=](dim3 grid, size_t lds, unsigned long long* out) {
+    hipLaunchKernelGGL(k_count_histo, grid, dim3(kSpectrumThreads), lds, stream, tab, cap, high, out);
+  });
+  if (rc) return rc;
+  HIPCHK(hipEventElapsedTime(&c->histo_ms, c->histoEv[0], c->histoEv[1]));
+  return TALC_OK;
+}
+
+int talc_counter_get_histo_timing(const talc_counter* c, float* histo_ms) {
+  if (!c || !histo_ms) return fail(TALC_ERR_INVALID, "null argument");
+  *histo_ms = c->histo_ms;
+  return TALC_OK;
+}
+
+int talc_table_histo(talc_table* t, int device, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats) {
+  int rc = spectrum_high(&high);
+  if (rc) return rc;
+  if (!t) return fail(TALC_ERR_INVALID, "null argument");
+  auto* at = t->image(device);
+  if (!at) return fail(TALC_ERR_STATE, "the table has no image on device %d: build it there or upload it", device);
+  HIPCHK(hipSetDevice(device));
+  const Bucket* right = at->second.right.get();
+  const uint64_t cap = t->h.capacity;
+  return run_spectrum(device, nullptr, cap, spectrum_group_slots<TableSlots>(), high, hist, stats, nullptr, [=](dim3 grid, size_t lds, unsigned long long* out) {
+    hipLaunchKernelGGL(k_table_histo, grid, dim3(kSpectrumThreads), lds, nullptr, right, cap, high, out);
+  });
+}
+
+int talc_spectrum_threshold(const uint64_t* hist, uint32_t high, uint32_t limit, uint32_t fallback, uint32_t* chosen, uint32_t* valley_out) {
+  if (!hist || !chosen) return fail(TALC_ERR_INVALID, "null argument");
+  if (high < 2) return fail(TALC_ERR_INVALID, "high=%u: a spectrum has at least the counts 1 and 2", high);
+  if (fallback == 0) return fail(TALC_ERR_INVALID, "fallback=0: MIN_COUNT is at least 1");
+  const uint32_t valley = spectrum_valley(hist, high, limit);
+  *chosen = spectrum_min_count(valley, fallback);
+  if (valley_out) *valley_out = valley;
+  return TALC_OK;
+}
+
+int talc_counter_set_min_count(talc_counter* c, uint32_t min_count) {
+  if (!c) return fail(TALC_ERR_INVALID, "null argument");
+  if (min_count < 1) return fail(TALC_ERR_INVALID, "min_count=0: MIN_COUNT is at least 1");
+  if (c->spent) return fail(TALC_ERR_STATE, "the counter's table has been built");
+  c->p.min_count = min_count;
+  return TALC_OK;
 }
 
 // ------------------------------------------------------------------ both strands from counted k-mers (docs/both_strands.md)

@@ -47,6 +47,12 @@
 //                    SEQ, or a prefix of it that runs over the read's end, matches
 //   --SRAdapterOverlap N  with --SRAdapter: the shortest match that clips (default 5)
 //   --SRAdapterErr PCT    with --SRAdapter: mismatches allowed, in percent of the matched length (0..30, default 10)
+//   --SRHisto        with --SRReads: write <o>.histo.txt, the count spectrum of the counted k-mers as `jellyfish histo` prints it
+//                    (docs/kmer_spectrum.md): one line `count k-mers` per count that occurs, the last line gathers the counts above
+//                    --SRHistoHigh; one summary line on stdout
+//   --SRHistoHigh N  with --SRHisto / --AutoMinCount: the largest count with a line of its own (2..16382, default 10000)
+//   --AutoMinCount   with --SRReads: MIN_COUNT is the first local minimum of that spectrum (at least 2; the given --MIN_COUNT
+//                    when the spectrum has none), chosen after counting and used for --SRCountsOut, the table and the correction
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -76,6 +82,7 @@
 #include "talc_cli_io.h"
 #include "talc_hip.h"
 #include "talc_jf.h"
+#include "talc_pure.h"   // the spectrum's threshold rule: its constants, as the library applies them
 #include "talc_switches.h"
 
 namespace {
@@ -128,6 +135,9 @@ struct Options {
   std::vector<std::string> srAdapters;      // --SRAdapter, in order
   uint32_t srAdapterOverlap = 0, srAdapterErr = 10;   // --SRAdapterOverlap (0: the library's default), --SRAdapterErr
   bool haveSrMinQual = false, haveSrAdapterOverlap = false, haveSrAdapterErr = false;
+  bool srHisto = false, autoMinCount = false;   // --SRHisto, --AutoMinCount
+  uint32_t srHistoHigh = 0;                     // --SRHistoHigh (0: the library's default, 10000)
+  bool haveSrHistoHigh = false;
   bool srFilter() const { return srMinQual > 0 || !srAdapters.empty(); }
   bool fastq = false, haveQualRange = false;   // --fastq, --qual-range
   uint32_t qmin = 2, qmax = 40;
@@ -154,6 +164,11 @@ void usage(FILE* f) {
           "                              ACGT (repeat for up to 4 adapters); partial matches over the read's end clip too\n"
           "  --SRAdapterOverlap INT      with --SRAdapter: shortest match that clips, 1..64 and at most the shortest adapter, default 5\n"
           "  --SRAdapterErr INT          with --SRAdapter: mismatches allowed in percent of the matched length, 0..30, default 10\n"
+          "  --SRHisto                   with --SRReads: write <o>.histo.txt, the count spectrum of the short reads' k-mers in the\n"
+          "                              format of `jellyfish histo` (docs/kmer_spectrum.md)\n"
+          "  --SRHistoHigh INT           with --SRHisto / --AutoMinCount: counts above this share the last line, 2..16382, default 10000\n"
+          "  --AutoMinCount              with --SRReads: take MIN_COUNT from the first local minimum of that spectrum (at least 2;\n"
+          "                              the given --MIN_COUNT stands when the spectrum only falls)\n"
           "  -j, --junctions TEXT        k-mers flanking junctions and their counts\n"
           "  -jf2, --pathToJF2 TEXT      directory of the jellyfish program: -qm jellyfish2 then reads the .jf through\n"
           "                              `jellyfish dump` (without it: the native .jf reader)\n"
@@ -244,6 +259,13 @@ Options parse(int argc, const char** argv) {
       if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for SRAdapterErr: 0..30");
       o.srAdapterErr = (uint32_t)v; o.haveSrAdapterErr = true;
     }
+    else if (a == "--SRHisto") o.srHisto = true;
+    else if (a == "--AutoMinCount") o.autoMinCount = true;
+    else if (a == "--SRHistoHigh") {
+      const double v = num(need(i), "SRHistoHigh");
+      if (v != (double)(long long)v || v < 2 || v > 16382) parse_error("value out of range for SRHistoHigh: 2..16382");
+      o.srHistoHigh = (uint32_t)v; o.haveSrHistoHigh = true;
+    }
     else if (is(a, "j", "junctions")) { o.jdump = need(i); o.useJ = true; }
     else if (is(a, "jf2", "pathToJF2")) o.jf2 = need(i);
     else if (is(a, "MIN_INNER_SCORE", "MIN_INNER_SCORE")) { o.p.min_inner_score = num(need(i), "MIN_INNER_SCORE"); range(o.p.min_inner_score, 0.3, 0.9, "MIN_INNER_SCORE"); }
@@ -292,6 +314,9 @@ Options parse(int argc, const char** argv) {
   if (!o.srAdapters.empty() && o.srReads.empty()) parse_error("--SRAdapter needs --SRReads");
   if (o.haveSrAdapterOverlap && o.srAdapters.empty()) parse_error("--SRAdapterOverlap needs --SRAdapter");
   if (o.haveSrAdapterErr && o.srAdapters.empty()) parse_error("--SRAdapterErr needs --SRAdapter");
+  if (o.srHisto && o.srReads.empty()) parse_error("--SRHisto needs --SRReads");
+  if (o.autoMinCount && o.srReads.empty()) parse_error("--AutoMinCount needs --SRReads");
+  if (o.haveSrHistoHigh && !o.srHisto && !o.autoMinCount) parse_error("--SRHistoHigh needs --SRHisto or --AutoMinCount");
   for (const std::string& ad : o.srAdapters)
     if (ad.size() < (o.srAdapterOverlap ? o.srAdapterOverlap : 5u))
       parse_error("value out of range for SRAdapterOverlap: " + std::to_string(o.srAdapterOverlap ? o.srAdapterOverlap : 5u) +
@@ -325,6 +350,9 @@ void outputConfig(const Options& o, const std::string& statFile) {
   for (const std::string& ad : o.srAdapters) f << "SRAdapter=" << ad << "\n";
   if (o.haveSrAdapterOverlap) f << "SRAdapterOverlap=" << o.srAdapterOverlap << "\n";
   if (o.haveSrAdapterErr) f << "SRAdapterErr=" << o.srAdapterErr << "\n";
+  if (o.srHisto) f << "SRHisto=1" << "\n";
+  if (o.haveSrHistoHigh) f << "SRHistoHigh=" << o.srHistoHigh << "\n";
+  if (o.autoMinCount) f << "AutoMinCount=1" << "\n";
   f
     << "****************************" << "\n"
     << "MIN_INNER_SCORE=" << o.p.min_inner_score << "\n"
@@ -390,10 +418,42 @@ bool jellyfishDump(const std::string& dir, const std::string& jf, uint32_t minCo
   return true;
 }
 
+// --SRHisto / --AutoMinCount (docs/kmer_spectrum.md): the spectrum of the counted k-mers from the device, once.  --SRHisto
+// writes it as `jellyfish histo` prints it with its defaults: a line `count k-mers` for every count 1 .. high + 1 that
+// occurs, ascending, the last one gathering the counts above high.  --AutoMinCount replaces MIN_COUNT, in the counter and
+// in o.p (what --SRCountsOut, the table and every context then use), by the spectrum's first local minimum.
+int spectrumOfCounts(Options& o, talc_counter* ctr, float* histoMs) {
+  const uint32_t high = o.srHistoHigh ? o.srHistoHigh : talc::kSpectrumDefaultHigh;
+  std::vector<uint64_t> hist(high + 2);
+  talc_spectrum_stats ss;
+  if (talc_counter_histo(ctr, high, hist.data(), &ss) != TALC_OK) return libError();
+  if (talc_counter_get_histo_timing(ctr, histoMs) != TALC_OK) return libError();
+  if (o.srHisto) {
+    const std::string path = o.outPrefix + ".histo.txt";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { std::cerr << "talc: cannot write " << path << "\n"; return 2; }
+    for (uint32_t c = 1; c <= high + 1; ++c)
+      if (hist[c]) fprintf(f, "%u %llu\n", c, (unsigned long long)hist[c]);
+    if (fclose(f) != 0) { std::cerr << "talc: cannot write " << path << "\n"; return 2; }
+    std::cout << "[TALC]: k-mer spectrum: " << ss.distinct << " distinct, " << ss.unique << " unique, " << ss.total << " total, max " << ss.max_count << std::endl;
+  }
+  if (o.autoMinCount) {
+    uint32_t chosen = 0, valley = 0;
+    if (talc_spectrum_threshold(hist.data(), high, 0, o.p.min_count, &chosen, &valley) != TALC_OK) return libError();
+    if (talc_counter_set_min_count(ctr, chosen) != TALC_OK) return libError();
+    o.p.min_count = chosen;
+    std::cout << "[TALC]: MIN_COUNT from the k-mer spectrum: " << chosen;
+    if (valley) std::cout << " (first minimum at " << valley << ")" << std::endl;
+    else std::cout << " (no minimum up to " << talc::spectrum_last_candidate(high, 0) << "; the given value stands)" << std::endl;
+  }
+  return 0;
+}
+
 // --SRReads: every short-read file read once, front to back (a pipe works), in batches of about 64 MB of bases handed to
 // the GPU counter, which copies them and returns while its kernel runs, so reading the next batch overlaps counting this
-// one.  Then --SRCountsOut, then the table (junction colouring with -j).  Returns 0, or the exit code after a message.
-int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table, int64_t st[3]) {
+// one.  Then the spectrum (--SRHisto, --AutoMinCount: o.p.min_count becomes the chosen value), --SRCountsOut, then the table
+// (junction colouring with -j).  Returns 0, or the exit code after a message.
+int countShortReads(Options& o, const talc::Switches& sw, TablePtr& table, int64_t st[3]) {
   if (talc_device_count() <= 0) return noGpuError();
   talc_counter* ctr = nullptr;
   if (talc_counter_create(&o.p, 0, 0, &ctr) != TALC_OK) return libError();
@@ -467,6 +527,9 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
     std::cout << "[TALC]: short-read filter: " << fs[0] << " records, " << fs[1] << " clipped at an adapter, " << fs[2] << " bases clipped, " << fs[3]
               << " bases below the quality floor" << std::endl;
   }
+  float histoMs = 0;
+  if (o.srHisto || o.autoMinCount)
+    if (const int ec = spectrumOfCounts(o, ctr, &histoMs)) return ec;
   const auto t1 = Clock::now();
   if (!o.srCountsOut.empty()) {   // `jellyfish dump -c` text of the kept k-mers (--both-strands: of the canonical ones, as after count -C)
     uint64_t n = 0;
@@ -489,11 +552,14 @@ int countShortReads(const Options& o, const talc::Switches& sw, TablePtr& table,
   talc_table* built = nullptr;
   if (talc_counter_build_table(ctr, o.useJ ? o.jdump.c_str() : nullptr, &built, st) != TALC_OK) return libError();
   table.reset(built);
-  if (sw.timing)
+  if (sw.timing) {
+    char spectrum[64] = "";   // (with --SRHisto / --AutoMinCount only: the line of a run without them is as it was)
+    if (o.srHisto || o.autoMinCount) snprintf(spectrum, sizeof spectrum, ", spectrum kernel %.3f ms", histoMs);
     fprintf(stderr, "[talc] short reads: %zu file(s), %llu records, %llu bytes in %llu batches; read %.3f s (%.4f s per batch), counter add (pack + queue) %.3f s "
-                    "(%.4f s per batch), counts out %.3f s, last batches + table build %.3f s, counting stage %.3f s\n",
+                    "(%.4f s per batch), counts out %.3f s, last batches + table build %.3f s, counting stage %.3f s%s\n",
             o.srReads.size(), (unsigned long long)nRecords, (unsigned long long)nBytes, (unsigned long long)nBatches, readS,
-            nBatches ? readS / (double)nBatches : 0.0, addS, nBatches ? addS / (double)nBatches : 0.0, secs(t1, t2), since(t2), since(t0));
+            nBatches ? readS / (double)nBatches : 0.0, addS, nBatches ? addS / (double)nBatches : 0.0, secs(t1, t2), since(t2), since(t0), spectrum);
+  }
   return 0;
 }
 
@@ -1148,7 +1214,7 @@ int prepareCounts(Options& o, TmpDumps& tmp, bool& haveTable) {
 }
 
 // main.cpp:224-238; tableSize stays 0 without a table
-int buildTable(const Options& o, const talc::Switches& sw, TablePtr& table, uint64_t& tableSize) {
+int buildTable(Options& o, const talc::Switches& sw, TablePtr& table, uint64_t& tableSize) {
   int64_t st[3] = {0, 0, 0};
   int rc = TALC_OK;
   if (!o.srReads.empty()) {   // --SRReads: counted on the GPU, no count file in between

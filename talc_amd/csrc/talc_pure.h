@@ -339,4 +339,26 @@ TALC_HD uint32_t order_key_bucket(uint32_t costEst, uint32_t costGap, uint32_t g
   return nBuckets - 2 - (k < nBuckets - 2 ? k : nBuckets - 2);
 }
 
+// ------------------------------------------------------------------ k-mer spectrum (docs/kmer_spectrum.md)
+// The solidity threshold a count spectrum suggests: its first local minimum.  hist[c], 1 <= c <= high, is the number of
+// distinct k-mers seen c times; hist[high + 1] gathers every larger count and is never read as a neighbour.  With
+// L = min(limit, high - 1): the valley is the smallest c in [1, L] with hist[c + 1] > 0 and hist[c] <= hist[c + 1], 0 when
+// there is none (a spectrum that only falls, or whose tail is empty).  No smoothing: the first count that is not above its
+// right neighbour.  Needs high >= 2.
+static const uint32_t kSpectrumDefaultHigh = 10000;   // jellyfish histo's --high
+static const uint32_t kSpectrumMaxHigh = 16382;       // high + 2 bins of 32 bits are 64 KiB of LDS (talc_kernels_spectrum.h)
+static const uint32_t kSpectrumDefaultLimit = 32;
+TALC_HD uint32_t spectrum_last_candidate(uint32_t high, uint32_t limit) {   // L; limit 0: the default
+  const uint32_t lim = limit ? limit : kSpectrumDefaultLimit;
+  return lim < high - 1 ? lim : high - 1;
+}
+TALC_HD uint32_t spectrum_valley(const uint64_t* hist, uint32_t high, uint32_t limit) {
+  const uint32_t L = spectrum_last_candidate(high, limit);
+  for (uint32_t c = 1; c <= L; ++c)
+    if (hist[c + 1] > 0 && hist[c] <= hist[c + 1]) return c;
+  return 0;
+}
+// MIN_COUNT from the valley: at least 2 (the reference's floor, main.cpp:146); without a valley the given value stands
+TALC_HD uint32_t spectrum_min_count(uint32_t valley, uint32_t fallback) { return valley ? (valley > 2 ? valley : 2) : fallback; }
+
 }  // namespace talc

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "talc_ctx_set_auto_strand", "talc_batch_strand", "talc_batch_fetch_strand", "talc_ctx_get_strand_timing",
     "talc_batch_support", "talc_batch_support_bytes", "talc_batch_fetch_support", "talc_ctx_get_support_timing",
     "talc_test_set_poison", "talc_test_get_poison", "talc_test_guard_report", "talc_test_cache_reuses", "talc_test_guard_selftest",
+    "talc_counter_histo", "talc_counter_get_histo_timing", "talc_table_histo", "talc_spectrum_threshold", "talc_counter_set_min_count",
 ]
 
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
@@ -69,6 +70,8 @@ STRAND_FIELDS = ("n_kmers", "fwd_solid", "fwd_in", "rc_solid", "rc_in", "reverse
 STRAND_DTYPE = np.dtype([(f, "<u4") for f in STRAND_FIELDS])
 # talc_support_params (docs/base_support.md)
 SUPPORT_RAW, SUPPORT_RECORD = 0, 1
+# the k-mer spectrum (docs/kmer_spectrum.md): high 0 means the default; the largest high the kernel's LDS histogram holds
+SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH = 10000, 16382
 EDIT_LETTERS = {EDIT_I: "I", EDIT_D: "D", EDIT_EQ: "=", EDIT_X: "X"}
 
 
@@ -83,6 +86,14 @@ class TalcError(RuntimeError):
 
 class SupportParams(C.Structure):
     _fields_ = [("source", C.c_uint32), ("phred", C.c_uint32), ("qmin", C.c_uint32), ("qmax", C.c_uint32)]
+
+
+class SpectrumStats(C.Structure):
+    """talc_spectrum_stats (docs/kmer_spectrum.md)"""
+    _fields_ = [("distinct", C.c_uint64), ("unique", C.c_uint64), ("total", C.c_uint64), ("max_count", C.c_uint64)]
+
+    def as_tuple(self):
+        return (int(self.distinct), int(self.unique), int(self.total), int(self.max_count))
 
 
 class Params(C.Structure):
@@ -262,6 +273,12 @@ def lib():
             L.talc_test_cache_reuses.restype = u64
             L.talc_test_cache_reuses.argtypes = []
             L.talc_test_guard_selftest.argtypes = [vp]
+        if hasattr(L, "talc_counter_histo"):   # (likewise: a TALC_LIB build from before the k-mer spectrum, for an A/B; asking it for one raises)
+            L.talc_counter_histo.argtypes = [vp, u32, vp, C.POINTER(SpectrumStats)]
+            L.talc_counter_get_histo_timing.argtypes = [vp, vp]
+            L.talc_table_histo.argtypes = [vp, i32, u32, vp, C.POINTER(SpectrumStats)]
+            L.talc_spectrum_threshold.argtypes = [vp, u32, u32, u32, vp, vp]
+            L.talc_counter_set_min_count.argtypes = [vp, u32]
         _LIB = L
     return _LIB
 
@@ -488,6 +505,14 @@ class Table:
         _chk(lib().talc_table_fetch_walk(self._h, int(device), int(direction), w.ctypes.data, w.nbytes))
         return w
 
+    def histo(self, device=0, high=0):
+        """The count spectrum of the k-mers the table stores, from its image on `device` (staged or uploaded; TalcError
+        without one): (hist u64[high + 2], (distinct, unique, total, max_count)) as KmerCounter.histo."""
+        hist = np.zeros(min(int(high) or SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH) + 2, dtype=np.uint64)   # (a high out of range is refused)
+        st = SpectrumStats()
+        _chk(lib().talc_table_histo(self._h, int(device), int(high), hist.ctypes.data, C.byref(st)))
+        return hist, st.as_tuple()
+
     def close(self):
         if self._h:
             lib().talc_table_destroy(self._h)
@@ -594,6 +619,29 @@ class KmerCounter:
         _chk(lib().talc_counter_fetch(self._h, int(min_count), kmers.ctypes.data, counts.ctypes.data, n.value, C.byref(n)))
         return kmers[: n.value], counts[: n.value]
 
+    def histo(self, high=0):
+        """The count spectrum (docs/kmer_spectrum.md; `jellyfish histo`): (hist u64[high + 2], (distinct, unique, total,
+        max_count)).  hist[c] = the k-mers with count c, hist[high + 1] those above high; high 0 is 10000.  The counter is
+        not spent and nothing it holds changes."""
+        hist = np.zeros(min(int(high) or SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH) + 2, dtype=np.uint64)   # (a high out of range is refused)
+        st = SpectrumStats()
+        _chk(lib().talc_counter_histo(self._h, int(high), hist.ctypes.data, C.byref(st)))
+        return hist, st.as_tuple()
+
+    def histo_timing(self):
+        """Device time (ms) of the last k_count_histo of this counter."""
+        ms = C.c_float()
+        _chk(lib().talc_counter_get_histo_timing(self._h, C.byref(ms)))
+        return ms.value
+
+    def set_min_count(self, min_count):
+        """Replaces params.min_count for stats()[2] and build_table(): the counter gets its own copy of the parameters, and
+        build_table() hands that copy to the Table (a Context on it must be created with table.params)."""
+        _chk(lib().talc_counter_set_min_count(self._h, int(min_count)))
+        own = Params.from_buffer_copy(self.params)
+        own.min_count = int(min_count)
+        self.params = own
+
     def build_table(self, junctions=None):
         """The table of the k-mers with count >= params.min_count (staged on the counter's GPU); the counter is spent."""
         h = C.c_void_p()
@@ -613,6 +661,16 @@ class KmerCounter:
             self.close()
         except Exception:
             pass
+
+
+def spectrum_threshold(hist, limit=0, fallback=2):
+    """(chosen, valley) of a spectrum as histo() returns it (hist[len - 1] is the catch-all bin): the first local minimum,
+    valley = the smallest c in [1, min(limit, high - 1)] with hist[c + 1] > 0 and hist[c] <= hist[c + 1], 0 when there is
+    none; chosen = max(2, valley), or fallback without a valley.  limit 0 is 32.  Host only, needs no GPU."""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    chosen, valley = C.c_uint32(), C.c_uint32()
+    _chk(lib().talc_spectrum_threshold(hist.ctypes.data, max(len(hist) - 2, 0), int(limit), int(fallback), C.byref(chosen), C.byref(valley)))
+    return chosen.value, valley.value
 
 
 def mask_batch(bases, offsets, quals=None, min_qual=0, adapters=(), min_overlap=0, max_error_pct=10, params=None, device=0):
