@@ -138,28 +138,31 @@ inline void free_registered(void* p) {
 template <typename T>
 class DevBuf {
   T* p_ = nullptr;
+  uint64_t n_ = 0;   // the elements it was allocated with; 0 while empty
 
  public:
   DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p_(o.release()) {}
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.release(); } return *this; }
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); n_ = o.n_; p_ = o.release(); } return *this; }
   ~DevBuf() { reset(); }
   // (what was held goes first: the old and the new buffer never exist side by side)
   hipError_t alloc(uint64_t n) {
     reset();
     const hipError_t e = memcheck::alloc_registered((void**)&p_, n * sizeof(T));
-    if (e != hipSuccess) p_ = nullptr;
+    if (e != hipSuccess) p_ = nullptr; else n_ = n;
     return e;
   }
   T* get() const { return p_; }
+  uint64_t size() const { return n_; }
   explicit operator bool() const { return p_ != nullptr; }
-  void reset() { if (p_) { memcheck::free_registered(p_); p_ = nullptr; } }   // free now
-  T* release() { T* p = p_; p_ = nullptr; return p; }            // hand over to a longer-lived owner
+  void reset() { if (p_) { memcheck::free_registered(p_); p_ = nullptr; n_ = 0; } }   // free now
+  T* release() { T* p = p_; p_ = nullptr; n_ = 0; return p; }    // hand over to a longer-lived owner
 };
 
 // the same for page-locked host memory, in bytes; also takes over a pointer that had left through the C ABI
 class PinnedBuf {
   char* p_ = nullptr;
+  uint64_t n_ = 0;   // the bytes it was allocated with; 0 while empty, and for a pointer that was taken over
 
  public:
   PinnedBuf() = default;
@@ -170,12 +173,13 @@ class PinnedBuf {
   hipError_t alloc(uint64_t bytes) {
     reset();
     const hipError_t e = hipHostMalloc((void**)&p_, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) p_ = nullptr;
+    if (e != hipSuccess) p_ = nullptr; else n_ = bytes;
     return e;
   }
   char* get() const { return p_; }
-  void reset() { if (p_) { (void)hipHostFree(p_); p_ = nullptr; } }
-  char* release() { char* p = p_; p_ = nullptr; return p; }
+  uint64_t size() const { return n_; }
+  void reset() { if (p_) { (void)hipHostFree(p_); p_ = nullptr; n_ = 0; } }
+  char* release() { char* p = p_; p_ = nullptr; n_ = 0; return p; }
 };
 
 // Host arrays that device-to-host copies land in (a batch's states and offsets).  Page-locked, so that the copy is one DMA

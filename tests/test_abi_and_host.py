@@ -50,7 +50,9 @@ def test_device_memory_has_one_owner_and_one_way_to_fail():
     calls = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(")
     users = sorted(f for f, t in text.items() if any(c in t for c in calls))
     assert users == ["talc_devmem.h"]
-    for f in ("talc_capi.hip", "talc_capi_correct.inc"):
+    layer = sorted(f for f in text if f == "talc_capi.hip" or (f.startswith("talc_capi_") and f.endswith(".inc")))
+    assert len(layer) >= 5 and "talc_capi_counter.inc" in layer
+    for f in layer:
         for idiom in ("BCHK", "CCHK", "auto cleanup", "auto drop", "== hipSuccess) e ="):
             assert idiom not in text[f], (f, idiom)
 

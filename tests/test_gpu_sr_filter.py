@@ -201,6 +201,48 @@ def test_buffers_reused_across_batches_of_different_sizes(dirty):
     assert F.mask(d["bases"], None, o[5700:7001], min_qual=20, adapters=[AD])[2][3] == 0 and fs_sum[3] > 0 and hi > lo
 
 
+def test_staging_buffers_grow_past_their_floor(dirty):
+    """The neighbour above never leaves the 1 MiB floor of the text and quality buffers.  Here one filtered counter takes five
+    batches of 6000, 8000, 300, 3000 and 2700 records of 151 staged bytes: only the second is above the floor, it lands in
+    the second staging slot (the slots alternate), so that slot and the device buffers grow while the first slot stays as it
+    was, and smaller batches follow in both.  Qualities come and go.  Fresh, and again over poisoned memory."""
+    d, o = dirty, dirty["offs"]
+    cuts = [0, 6000, 14000, 14300, 17300, 20000]
+    with_quals = [True, True, False, True, False]
+    assert 6000 * 151 < (1 << 20) < 8000 * 151 and len(o) == cuts[-1] + 1
+    filt = dict(min_qual=20, adapters=[AD])
+    parts = []
+    for a, b, wq in zip(cuts[:-1], cuts[1:], with_quals):
+        lo, hi = int(o[a]), int(o[b])
+        parts.append((d["bases"][lo:hi], o[a:b + 1] - o[a], d["quals"][lo:hi] if wq else None))
+    each = [counted(21, False, filt, *p) for p in parts]             # every batch alone, in a counter of its own
+    keys, inv = np.unique(np.concatenate([e[0][0] for e in each]), return_inverse=True)
+    sums = np.zeros(len(keys), dtype=np.uint64)
+    np.add.at(sums, inv, np.concatenate([e[0][1] for e in each]).astype(np.uint64))
+    want_fs = tuple(int(x) for x in np.sum([e[2] for e in each], axis=0))
+    want_st = (int(sums.sum()), len(keys), int((sums >= 2).sum()))
+    assert each[2][2][3] == 0 and each[4][2][3] == 0 and each[3][2][3] > 0     # no floor without qualities; it is back in batch 4
+
+    def all_in_one():
+        c = T.KmerCounter(T.default_params(k=21), 0)
+        c.set_filter(**filt)
+        for p in parts:
+            c.add(*p)
+        out = (sorted_pairs(*c.fetch(1)), c.stats(), c.filter_stats())
+        c.close()
+        return out
+
+    fresh = all_in_one()
+    before = T.guard_report()
+    with T.poisoned(0xA5):
+        again = all_in_one()
+    after = T.guard_report()
+    for got, st, fs in (fresh, again):
+        assert np.array_equal(got[0], keys) and np.array_equal(got[1], sums.astype(np.uint32))
+        assert st == want_st and fs == want_fs
+    assert after["violations"] == before["violations"] and after["checked"] > before["checked"]
+
+
 def test_synthetic_reads_with_adapters(dirty):
     d = dirty
     k = 21

@@ -11,8 +11,9 @@ and capacity x 16 / time for each.  There is no event around k_count_compact: it
 `rocprofv3 --kernel-trace --stats -- python tools/spectrum_bench.py ...` run, which lists both kernels by name.
 
 The capacity.  The counter sizes its hash for the windows of a batch, an upper bound of the k-mers the batch can add, not
-for the distinct k-mers it ends up with (counter_add_records in talc_capi.hip): before a batch of W windows, with D distinct
-k-mers known, it grows to the smallest power of two with D + W <= 0.7 capacity.  So the capacity depends on how the reads
+for the distinct k-mers it ends up with (counter_make_room and the rule itself, counter_capacity_for, in
+talc_capi_counter.inc): before a batch of W windows, with D distinct k-mers known, it doubles its capacity until
+D + W <= 0.7 capacity.  So the capacity depends on how the reads
 were handed over.  The tool hands them over in batches of --batch reads, reads the exact D back after every batch
 (stats(): the library then knows it too) and replays that rule; "capacity_slots" is the result.  --slots-log2 N sizes the
 hash to 2^N slots from the start (the same k-mers in a larger hash: the streaming cost at the size of a real data set); it
@@ -57,14 +58,14 @@ def main():
     hint = int(0.7 * (1 << a.slots_log2)) if a.slots_log2 else 0
     c = T.KmerCounter(T.default_params(k=a.k), 0, hint)
     capacity = 1 << 16
-    while hint > 0.7 * capacity:                         # talc_counter_create
+    while hint > 0.7 * capacity:                         # counter_capacity_for, from talc_counter_create
         capacity *= 2
     distinct = 0
     for first in range(0, a.reads, a.batch):
         o = offs[first:min(first + a.batch, a.reads) + 1]
         lens = np.diff(o.astype(np.int64))
-        bound = distinct + int(np.maximum(lens - a.k + 1, 0).sum())   # counter_add_records: D + the batch's windows
-        while bound > 0.7 * capacity:                    # counter_grow
+        bound = distinct + int(np.maximum(lens - a.k + 1, 0).sum())   # counter_make_room: D + the batch's windows
+        while bound > 0.7 * capacity:                    # counter_capacity_for, from counter_grow
             capacity *= 2
         c.add(bases[int(o[0]):int(o[-1])], o - o[0])
         windows, distinct, kept = c.stats()              # (synchronises: D is exact, in the library too)
