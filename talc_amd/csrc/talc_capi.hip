@@ -60,6 +60,35 @@ struct Stopwatch {
   double lap() { const auto t1 = Clock::now(); const double s = std::chrono::duration<double>(t1 - t0).count(); t0 = t1; return s; }
 };
 
+// The device time of the last X: an event pair of its own (made on first use), recorded around the launch on the owner's
+// stream.  Nobody waits for it: the pair is pending until whoever waits for that stream next reads it (read(); a context's
+// spans all at once, read_spans), so a span launched by one entry point and waited for by another is still reported.
+struct Span {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  float ms = 0;
+  bool pending = false;   // recorded and not yet read
+  ~Span() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }   // (the owner has made its device current)
+  // launch() on `stream` between the two events; a launch that fails leaves the span without a pair to read
+  template <class Launch>
+  int around(hipStream_t stream, Launch launch) {
+    pending = false;
+    for (auto& e : ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ev[0], stream));
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], stream));
+    pending = true;
+    return TALC_OK;
+  }
+  // once the stream has been waited for
+  int read() {
+    if (pending) HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    pending = false;
+    return TALC_OK;
+  }
+  void skip() { ms = 0; pending = false; }   // X did not run in this call: its time is exactly 0
+};
+
 // The table lives where it was built.  A host-built table has a host image (h.right / h.left) that uploads copy; a
 // table built (or imported) on a GPU has a *staged* device image there — colouring and de-colouring run on it as
 // kernels, talc_table_upload to that same GPU adopts it without any copy, and the host image is only materialised
@@ -122,21 +151,22 @@ struct Stage {
   uint32_t box_seq_cap = 0;
 };
 
-// the context's events, all recorded on its stream
-enum CtxEvent {
-  // the correction's stages, in order (read_stage_times): before k_encode, after it, after k_coverage, after k_structure,
-  // after the first k_search, around the retry passes, after k_pack
-  kEvBegin, kEvEncoded, kEvCovered, kEvStructured, kEvSearched, kEvRetry0, kEvRetry1, kEvEmitted,
-  kEvPackMap,                                  // after k_pack_map
-  kEvMaskCase0, kEvMaskCase1,                  // around k_mask_case
-  kEvSolidity0, kEvSolidity1, kEvSolidity2,    // around the two k_solidity: over the reads, over the records
-  kEvPieceCount0, kEvPieceCount1,              // around k_piece_count
-  kEvPiecePack0, kEvPiecePack1,                // around k_piece_pack
-  // the edit scripts (run_edits): around the first k_edit_align rounds, after k_edit_count, around the second rounds, after k_edit_pack
-  kEvEditAlignA0, kEvEditAlignA1, kEvEditCount, kEvEditAlignB0, kEvEditAlignB1, kEvEditPack,
-  kEvVote0, kEvVote1,                          // around k_strand_vote
-  kEvSupport0, kEvSupport1,                    // around k_base_support
-  kEvCount
+// the marks of the correction's stages, a chain of events on the context's stream (read_stage_times), in order: before
+// k_encode, after it, after k_coverage, after k_structure, after the first k_search, around the retry passes, after k_pack,
+// after k_pack_map
+enum CtxEvent { kEvBegin, kEvEncoded, kEvCovered, kEvStructured, kEvSearched, kEvRetry0, kEvRetry1, kEvEmitted, kEvPackMap, kEvCount };
+
+// the kernels of the reports, each timed by a Span of the context (read_spans)
+enum CtxSpan {
+  kSpanVote,                             // k_strand_vote
+  kSpanPackMap,                          // k_pack_map: its time comes from the chain's marks (read_stage_times), its own pair is never made
+  kSpanMaskCase,                         // k_mask_case
+  kSpanSolidityRaw, kSpanSolidityRecords,   // the two k_solidity of talc_batch_solidity: over the reads, over the records
+  kSpanPieceCount, kSpanPiecePack,       // talc_batch_pieces: k_piece_count, k_piece_pack
+  // the edit scripts (run_edits): the first k_edit_align rounds, k_edit_count, the second rounds, k_edit_pack
+  kSpanEditAlignA, kSpanEditCount, kSpanEditAlignB, kSpanEditPack,
+  kSpanSupport,                          // k_base_support
+  kSpanCount
 };
 
 struct talc_ctx {
@@ -146,18 +176,12 @@ struct talc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[kEvCount] = {};
+  Span span[kSpanCount];   // the last run of each report kernel on this context
   TableView view;
   talc_timing timing;
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
   bool autoStrand = false;   // talc_ctx_set_auto_strand: every read in the orientation k_strand_vote chooses
-  float vote_ms = 0;         // the last k_strand_vote of this context
-  bool votePending = false;  // ... has been launched and its events not yet read (vote_time)
-  float pack_map_ms = 0, mask_case_ms = 0;   // the last k_pack_map / k_mask_case of this context
-  float sol_raw_ms = 0, sol_corr_ms = 0;     // the last talc_batch_solidity: k_solidity over the reads, over the records
-  float piece_count_ms = 0, piece_pack_ms = 0;   // the last talc_batch_pieces: k_piece_count, k_piece_pack
-  float edit_align_ms = 0, edit_pack_ms = 0;     // the last edit scripts: both k_edit_align runs, k_edit_count + k_edit_pack
-  float support_ms = 0;                          // the last talc_batch_support: k_base_support
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -291,6 +315,34 @@ template <typename T>
 static int up(talc_ctx* c, CachedBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
   HIPCHK(d.alloc(c->cache, std::max<size_t>(h.size(), 1)));
   if (!h.empty()) HIPCHK(hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  return TALC_OK;
+}
+
+// what an entry point does once it has waited for the context's stream: every span launched since the last wait gets its time
+static int read_spans(talc_ctx* c) {
+  for (auto& sp : c->span)
+    if (int rc = sp.read()) return rc;
+  return TALC_OK;
+}
+
+// What a kernel that takes the reads or their records reads (talc_kmer_window.h): the batch's codes at the input offsets, or
+// the dense records of its last correction at theirs, with the reads' states and the flag that says so
+struct BatchSource { const uint8_t* bytes; const uint64_t* d_off; const uint64_t* h_off; const ReadState* states; int records; };
+static BatchSource batch_source(const talc_batch* b, bool records) {
+  if (records) return {b->d_dense.get(), b->d_dense_off.get(), b->h_dense_off.data(), b->d_state.get(), 1};
+  return {b->d_codes.get(), b->d_offsets.get(), b->h_offsets.data(), nullptr, 0};
+}
+
+// A sized result into the caller's `out` (a host buffer, or a device one: `kind`) of `capacity` units; null: nothing is
+// asked for.  `total` units of `unit` bytes from `src`, on the context's stream: a DMA transfer when a host `out` is pinned
+// (talc_pinned_alloc).  `what`, `units`: the nouns of "<what> too small: need <n> <units>".
+static int copy_out(talc_ctx* c, void* out, uint64_t capacity, const void* src, uint64_t total, size_t unit, hipMemcpyKind kind,
+                    const char* what, const char* units) {
+  if (!out) return TALC_OK;
+  if (capacity < total) return fail(TALC_ERR_CAPACITY, "%s too small: need %llu %s", what, (unsigned long long)total, units);
+  if (!total) return TALC_OK;
+  HIPCHK(hipMemcpyAsync(out, src, total * unit, kind, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return TALC_OK;
 }
 
@@ -1017,28 +1069,28 @@ int talc_ctx_set_auto_strand(talc_ctx* c, int on) {
 
 int talc_ctx_get_strand_timing(const talc_ctx* c, float* vote_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
-  if (vote_ms) *vote_ms = c->vote_ms;
+  if (vote_ms) *vote_ms = c->span[kSpanVote].ms;
   return TALC_OK;
 }
 
 int talc_ctx_get_map_timing(const talc_ctx* c, float* pack_map_ms, float* mask_case_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
-  if (pack_map_ms) *pack_map_ms = c->pack_map_ms;
-  if (mask_case_ms) *mask_case_ms = c->mask_case_ms;
+  if (pack_map_ms) *pack_map_ms = c->span[kSpanPackMap].ms;
+  if (mask_case_ms) *mask_case_ms = c->span[kSpanMaskCase].ms;
   return TALC_OK;
 }
 
 int talc_ctx_get_pieces_timing(const talc_ctx* c, float* count_ms, float* pack_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
-  if (count_ms) *count_ms = c->piece_count_ms;
-  if (pack_ms) *pack_ms = c->piece_pack_ms;
+  if (count_ms) *count_ms = c->span[kSpanPieceCount].ms;
+  if (pack_ms) *pack_ms = c->span[kSpanPiecePack].ms;
   return TALC_OK;
 }
 
 int talc_ctx_get_solidity_timing(const talc_ctx* c, float* raw_ms, float* corrected_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
-  if (raw_ms) *raw_ms = c->sol_raw_ms;
-  if (corrected_ms) *corrected_ms = c->sol_corr_ms;
+  if (raw_ms) *raw_ms = c->span[kSpanSolidityRaw].ms;
+  if (corrected_ms) *corrected_ms = c->span[kSpanSolidityRecords].ms;
   return TALC_OK;
 }
 
@@ -1109,25 +1161,17 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
 uint64_t talc_batch_num_kmers(const talc_batch* b) { return b ? b->n_kmers : 0; }
 uint64_t talc_batch_num_bases(const talc_batch* b) { return b ? b->n_bases : 0; }
 
-// ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes, kEvVote0 and kEvVote1 around it
+// ---- auto strand (docs/auto_strand.md).  k_strand_vote over the batch's raw bytes (kSpanVote)
 static int launch_vote(talc_ctx* c, talc_batch* b) {
   HIPCHK(b->d_strand.ensure(c->cache, b->n_reads));
   HIPCHK(b->d_strand_flag.ensure(c->cache, b->n_reads));
-  HIPCHK(hipEventRecord(c->ev[kEvVote0], c->stream));
-  if (b->n_reads)
-    hipLaunchKernelGGL(k_strand_vote, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, b->d_raw.get(), b->d_offsets.get(), c->p.min_count, b->n_reads,
-                       b->d_strand.get(), b->d_strand_flag.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvVote1], c->stream));
-  c->votePending = true;
+  const int rc = c->span[kSpanVote].around(c->stream, [&] {
+    if (b->n_reads)
+      hipLaunchKernelGGL(k_strand_vote, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, b->d_raw.get(), b->d_offsets.get(), c->p.min_count, b->n_reads,
+                         b->d_strand.get(), b->d_strand_flag.get());
+  });
+  if (rc) return rc;
   b->holds.voted = true;
-  return TALC_OK;
-}
-// the last vote's device time into c->vote_ms, once the stream has been waited for
-static int vote_time(talc_ctx* c) {
-  if (!c->votePending) return TALC_OK;
-  HIPCHK(hipEventElapsedTime(&c->vote_ms, c->ev[kEvVote0], c->ev[kEvVote1]));
-  c->votePending = false;
   return TALC_OK;
 }
 // What every entry point that needs the batch's codes does first: codes made under the other setting are dropped with
@@ -1153,7 +1197,7 @@ int talc_batch_strand(talc_ctx* c, talc_batch* b) {
   if ((rc = enter(c, b, "bad context/batch"))) return rc;
   if (!b->holds.voted && (rc = launch_vote(c, b))) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  return vote_time(c);
+  return read_spans(c);
 }
 
 int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows) {
@@ -1162,7 +1206,7 @@ int talc_batch_fetch_strand(talc_ctx* c, talc_batch* b, talc_strand* rows) {
   HIPCHK(hipSetDevice(c->device));
   if (rows && b->n_reads) HIPCHK(hipMemcpyAsync(rows, b->d_strand.get(), (size_t)b->n_reads * sizeof(talc_strand), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  return vote_time(c);
+  return read_spans(c);
 }
 static int launch_coverage(talc_ctx* c, talc_batch* b) {
   HIPCHK(hipMemsetAsync(b->d_nin.get(), 0, std::max<uint32_t>(b->n_reads, 1) * sizeof(int32_t), c->stream));
@@ -1181,7 +1225,7 @@ static int32_t read_status(const ReadState& st) { return st.overflow ? TALC_READ
 // the stage times into c->timing, from the events around the stages.  `last`: the last event recorded and waited for —
 // kEvCovered, kEvStructured or kEvEmitted (the whole correction).  search_ms ends with the first k_search; retry_ms spans
 // the retry passes (next to nothing when no read overflowed); emit_ms spans the offset kernels, the host's wait for their
-// totals and k_pack
+// totals and k_pack; a correction that keeps its map has kEvPackMap behind kEvEmitted, and k_pack_map's time goes to its span
 static int read_stage_times(talc_ctx* c, CtxEvent last) {
   talc_timing& t = c->timing;
   HIPCHK(hipEventElapsedTime(&t.encode_ms, c->ev[kEvBegin], c->ev[kEvEncoded]));
@@ -1191,21 +1235,30 @@ static int read_stage_times(talc_ctx* c, CtxEvent last) {
     HIPCHK(hipEventElapsedTime(&t.search_ms, c->ev[kEvStructured], c->ev[kEvSearched]));
     HIPCHK(hipEventElapsedTime(&t.retry_ms, c->ev[kEvRetry0], c->ev[kEvRetry1]));
     HIPCHK(hipEventElapsedTime(&t.emit_ms, c->ev[kEvRetry1], c->ev[kEvEmitted]));
+    if (c->map) HIPCHK(hipEventElapsedTime(&c->span[kSpanPackMap].ms, c->ev[kEvEmitted], c->ev[kEvPackMap]));
   }
   return TALC_OK;
 }
 
-int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
+// the orientation settled (prepare_strand), k_encode where the batch has no codes yet, k_coverage: kEvBegin, kEvEncoded and
+// kEvCovered around the two.  What talc_batch_coverage and the correction (launch_structure) start with
+static int launch_encode_coverage(talc_ctx* c, talc_batch* b) {
   int rc;
-  if ((rc = enter(c, b, "bad context/batch"))) return rc;
   if ((rc = prepare_strand(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvBegin], c->stream));
   if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvEncoded], c->stream));
   if ((rc = launch_coverage(c, b))) return rc;
   HIPCHK(hipEventRecord(c->ev[kEvCovered], c->stream));
+  return TALC_OK;
+}
+
+int talc_batch_coverage(talc_ctx* c, talc_batch* b) {
+  int rc;
+  if ((rc = enter(c, b, "bad context/batch"))) return rc;
+  if ((rc = launch_encode_coverage(c, b))) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((rc = read_stage_times(c, kEvCovered)) || (rc = vote_time(c))) return rc;
+  if ((rc = read_stage_times(c, kEvCovered)) || (rc = read_spans(c))) return rc;
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
   return TALC_OK;
 }

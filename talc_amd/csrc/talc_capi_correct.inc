@@ -143,12 +143,7 @@ static int launch_structure(talc_ctx* c, talc_batch* b, const TraceBuf& tb, uint
   int rc;
   memset(&c->timing, 0, sizeof c->timing);
   c->timing.n_kmers = b->n_kmers; c->timing.n_bases = b->n_bases;
-  if ((rc = prepare_strand(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvBegin], s));
-  if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvEncoded], s));
-  if ((rc = launch_coverage(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvCovered], s));
+  if ((rc = launch_encode_coverage(c, b))) return rc;
   HIPCHK(hipMemsetAsync(batch_stats(c), 0, kBatchStatsWords * sizeof(uint32_t), s));
   if (b->n_reads)
     hipLaunchKernelGGL(k_structure, dim3(b->n_reads), dim3(64), 0, s, c->dp, c->view, b->d_codes.get(), b->d_offsets.get(), b->d_koff.get(),
@@ -350,8 +345,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   const uint32_t n_failed = (uint32_t)tot[kTotOverflow];
   if ((rc = pack_dense(c, b, tot[kTotBytes]))) return rc;
   if (map && (rc = pack_map(c, b, tot[kTotSegs]))) return rc;
-  if ((rc = read_timing(c, b, map, n_failed, &counters)) || (rc = vote_time(c))) return rc;
-  if (map) HIPCHK(hipEventElapsedTime(&c->pack_map_ms, c->ev[kEvEmitted], c->ev[kEvPackMap]));
+  if ((rc = read_timing(c, b, map, n_failed, &counters)) || (rc = read_spans(c))) return rc;
 #ifdef TALC_PROF
   if ((rc = prof_report(c, b, counters))) return rc;
 #endif
@@ -375,7 +369,7 @@ int talc_batch_structure(talc_ctx* c, talc_batch* b) {
   b->holds.drop_results();
   if ((rc = launch_structure(c, b, TraceBuf{}, 0xFFFFFFFFu))) return rc;
   if ((rc = fetch_states(c, b))) return rc;
-  if ((rc = read_stage_times(c, kEvStructured)) || (rc = vote_time(c))) return rc;
+  if ((rc = read_stage_times(c, kEvStructured)) || (rc = read_spans(c))) return rc;
   b->holds.structured = true;
   return TALC_OK;
 }
@@ -451,20 +445,13 @@ static int corrected_out(talc_ctx* c, talc_batch* b, void* out, uint64_t out_cap
   if (out_offsets) memcpy(out_offsets, b->h_dense_off.data(), (b->n_reads + 1) * 8);
   if (status)
     for (uint32_t r = 0; r < b->n_reads; ++r) status[r] = read_status(b->h_state[r]);
-  if (out) {
-    if (out_capacity < total) return fail(TALC_ERR_CAPACITY, "%s buffer too small: need %llu bytes", what, (unsigned long long)total);
-    if (total) {   // on the context's stream: a DMA transfer when a host `out` is pinned (talc_pinned_alloc)
-      HIPCHK(hipMemcpyAsync(out, masked ? b->d_masked.get() : b->d_dense.get(), total, kind, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  return TALC_OK;
+  return copy_out(c, out, out_capacity, masked ? b->d_masked.get() : b->d_dense.get(), total, 1, kind, what, "bytes");
 }
 
 int talc_batch_fetch_corrected(talc_ctx* c, talc_batch* b, char* out, uint64_t out_capacity, uint64_t* out_offsets,
                                int32_t* status) {
   if (int rc = belong(c, b, "bad context/batch")) return rc;
-  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output");
+  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output buffer");
 }
 
 uint64_t talc_batch_num_segments(const talc_batch* b) { return (b && b->holds.has_map()) ? b->h_seg_off[b->n_reads] : 0; }
@@ -483,30 +470,23 @@ int talc_batch_fetch_map(talc_ctx* c, talc_batch* b, talc_segment* segs, uint64_
   if ((rc = enter_map(c, b))) return rc;
   const uint64_t total = b->h_seg_off[b->n_reads];
   if (seg_offsets) memcpy(seg_offsets, b->h_seg_off.data(), (b->n_reads + 1) * 8);
-  if (segs) {
-    if (capacity < total) return fail(TALC_ERR_CAPACITY, "segment buffer too small: need %llu segments", (unsigned long long)total);
-    if (total) {
-      HIPCHK(hipMemcpyAsync(segs, b->d_segs.get(), total * sizeof(talc_segment), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  return TALC_OK;
+  return copy_out(c, segs, capacity, b->d_segs.get(), total, sizeof(talc_segment), hipMemcpyDeviceToHost, "segment buffer", "segments");
 }
 
-// the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (kEvMaskCase0, kEvMaskCase1)
+// the second record buffer, on first use: a copy of the dense records, then k_mask_case over the RAW segments (kSpanMaskCase)
 static int mask_dense(talc_ctx* c, talc_batch* b) {
   if (b->holds.has_mask()) return TALC_OK;
   hipStream_t s = c->stream;
   const uint64_t total = b->h_dense_off[b->n_reads];
   HIPCHK(b->d_masked.ensure(c->cache, total));
   if (total) HIPCHK(hipMemcpyAsync(b->d_masked.get(), b->d_dense.get(), total, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[kEvMaskCase0], s));
-  if (b->n_reads)
-    hipLaunchKernelGGL(k_mask_case, dim3(b->n_reads), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), b->d_dense_off.get(), b->d_masked.get(), b->n_reads);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvMaskCase1], s));
+  int rc = c->span[kSpanMaskCase].around(s, [&] {
+    if (b->n_reads)
+      hipLaunchKernelGGL(k_mask_case, dim3(b->n_reads), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), b->d_dense_off.get(), b->d_masked.get(), b->n_reads);
+  });
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->mask_case_ms, c->ev[kEvMaskCase0], c->ev[kEvMaskCase1]));
+  if ((rc = read_spans(c))) return rc;
   b->holds.masked = true;
   return TALC_OK;
 }
@@ -517,11 +497,11 @@ int talc_batch_fetch_corrected_masked(talc_ctx* c, talc_batch* b, char* out, uin
   if ((rc = belong(c, b, "bad context/batch"))) return rc;
   if ((rc = enter_map(c, b))) return rc;
   if (out && (rc = mask_dense(c, b))) return rc;
-  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output", true);
+  return corrected_out(c, b, out, out_capacity, out_offsets, status, hipMemcpyDeviceToHost, "output buffer", true);
 }
 
 // ---- trimmed and split output (docs/trim_split.md): k_piece_count over the map, the reads' offsets on the host (as
-// pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (kEvPieceCount0 .. kEvPiecePack1 around the two kernels)
+// pack_dense and pack_map make theirs), k_piece_pack into buffers sized exactly (kSpanPieceCount, kSpanPiecePack)
 int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, int soft_mask) {
   if (int rc = belong(c, b, "bad context/batch")) return rc;
   if (mode != TALC_PIECES_TRIM && mode != TALC_PIECES_SPLIT) return fail(TALC_ERR_INVALID, "piece mode %d is neither TALC_PIECES_TRIM nor TALC_PIECES_SPLIT", mode);
@@ -533,10 +513,10 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   const bool masked = mode == TALC_PIECES_TRIM && soft_mask;   // (a split piece has no weak byte)
   if (masked && (rc = mask_dense(c, b))) return rc;
   HIPCHK(b->d_piece_count.ensure(c->cache, n));
-  HIPCHK(hipEventRecord(c->ev[kEvPieceCount0], s));
-  if (n) hipLaunchKernelGGL(k_piece_count, dim3(n), dim3(64), 0, s, b->d_segs.get(), b->d_seg_off.get(), n, mode, min_len, b->d_piece_count.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvPieceCount1], s));
+  rc = c->span[kSpanPieceCount].around(s, [&] {
+    if (n) hipLaunchKernelGGL(k_piece_count, dim3(n), dim3(64), 0, s, b->d_segs.get(), b->d_seg_off.get(), n, mode, min_len, b->d_piece_count.get());
+  });
+  if (rc) return rc;
   std::vector<PieceCount> counts(n);
   if (n) HIPCHK(hipMemcpyAsync(counts.data(), b->d_piece_count.get(), (size_t)n * sizeof(PieceCount), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -553,16 +533,15 @@ int talc_batch_pieces(talc_ctx* c, talc_batch* b, int mode, uint32_t min_len, in
   HIPCHK(b->d_read_piece_off.ensure(c->cache, n + 1)); HIPCHK(b->d_read_byte_off.ensure(c->cache, n + 1));
   HIPCHK(hipMemcpyAsync(b->d_read_piece_off.get(), b->h_read_piece_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(b->d_read_byte_off.get(), b->h_read_byte_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[kEvPiecePack0], s));
-  if (n && np)
-    hipLaunchKernelGGL(k_piece_pack, dim3(n), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), masked ? b->d_masked.get() : b->d_dense.get(),
-                       b->d_dense_off.get(), n, mode, min_len, b->d_read_piece_off.get(), b->d_read_byte_off.get(), b->d_pieces.get(),
-                       b->d_piece_off.get(), b->d_piece_bytes.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvPiecePack1], s));
+  rc = c->span[kSpanPiecePack].around(s, [&] {
+    if (n && np)
+      hipLaunchKernelGGL(k_piece_pack, dim3(n), dim3(256), 0, s, b->d_segs.get(), b->d_seg_off.get(), masked ? b->d_masked.get() : b->d_dense.get(),
+                         b->d_dense_off.get(), n, mode, min_len, b->d_read_piece_off.get(), b->d_read_byte_off.get(), b->d_pieces.get(),
+                         b->d_piece_off.get(), b->d_piece_bytes.get());
+  });
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->piece_count_ms, c->ev[kEvPieceCount0], c->ev[kEvPieceCount1]));
-  HIPCHK(hipEventElapsedTime(&c->piece_pack_ms, c->ev[kEvPiecePack0], c->ev[kEvPiecePack1]));
+  if ((rc = read_spans(c))) return rc;
   b->holds.pieced = true;
   return TALC_OK;
 }
@@ -591,36 +570,29 @@ int talc_batch_fetch_pieces(talc_ctx* c, talc_batch* b, char* out, uint64_t out_
 }
 
 // ---- the solidity report (docs/solidity.md): k_solidity over the batch's codes (the raw rows) and, once the batch is
-// corrected, over the dense records as talc_batch_fetch_corrected returns them (the corrected rows)
-static int launch_solidity(talc_ctx* c, talc_batch* b, bool records) {
-  CachedBuf<SolidityRow>& rows = records ? b->d_sol_corr : b->d_sol_raw;
+// corrected, over the dense records as talc_batch_fetch_corrected returns them (the corrected rows).  One launch: the rows of
+// `src` into `rows`, timed by `span`
+static int launch_solidity(talc_ctx* c, talc_batch* b, const BatchSource& src, CachedBuf<SolidityRow>& rows, Span& span) {
   HIPCHK(rows.ensure(c->cache, b->n_reads));
-  if (b->n_reads)
-    hipLaunchKernelGGL(k_solidity, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, records ? b->d_dense.get() : b->d_codes.get(),
-                       records ? b->d_dense_off.get() : b->d_offsets.get(), records ? b->d_state.get() : nullptr, records ? 1 : 0,
-                       c->p.reverse ? 1 : 0, b->rev_flags(), c->p.min_count, b->n_reads, rows.get());
-  HIPCHK(hipGetLastError());
-  return TALC_OK;
+  return span.around(c->stream, [&] {
+    if (b->n_reads)
+      hipLaunchKernelGGL(k_solidity, dim3(b->n_reads), dim3(64), 0, c->stream, c->view, src.bytes, src.d_off, src.states, src.records,
+                         c->p.reverse ? 1 : 0, b->rev_flags(), c->p.min_count, b->n_reads, rows.get());
+  });
 }
 
 int talc_batch_solidity(talc_ctx* c, talc_batch* b) {
   int rc;
   if ((rc = enter(c, b, "bad context/batch"))) return rc;
-  hipStream_t s = c->stream;
   if ((rc = prepare_strand(c, b))) return rc;   // (a batch encoded under the other setting is no longer corrected either)
   const bool records = b->holds.has_records();
   b->holds.solidity = b->holds.solidityCorrected = false;
   if (!b->holds.encoded && (rc = launch_encode(c, b))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvSolidity0], s));
-  if ((rc = launch_solidity(c, b, false))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvSolidity1], s));
-  if (records && (rc = launch_solidity(c, b, true))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvSolidity2], s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipEventElapsedTime(&c->sol_raw_ms, c->ev[kEvSolidity0], c->ev[kEvSolidity1]));
-  c->sol_corr_ms = 0;
-  if (records) HIPCHK(hipEventElapsedTime(&c->sol_corr_ms, c->ev[kEvSolidity1], c->ev[kEvSolidity2]));
-  if ((rc = vote_time(c))) return rc;
+  if ((rc = launch_solidity(c, b, batch_source(b, false), b->d_sol_raw, c->span[kSpanSolidityRaw]))) return rc;
+  c->span[kSpanSolidityRecords].skip();   // (a batch without records: the time of their rows is 0, not an earlier batch's)
+  if (records && (rc = launch_solidity(c, b, batch_source(b, true), b->d_sol_corr, c->span[kSpanSolidityRecords]))) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((rc = read_spans(c))) return rc;
   b->holds.solidity = true; b->holds.solidityCorrected = records;
   return TALC_OK;
 }
@@ -660,7 +632,7 @@ int talc_batch_fetch_read_stats(talc_ctx* c, talc_batch* b, int64_t* stats5) {
 int talc_batch_copy_corrected_device(talc_ctx* c, talc_batch* b, void* device_out, uint64_t out_capacity,
                                      uint64_t* out_offsets, int32_t* status) {
   if (int rc = belong(c, b, "bad context/batch/buffer", device_out)) return rc;
-  return corrected_out(c, b, device_out, out_capacity, out_offsets, status, hipMemcpyDeviceToDevice, "device");
+  return corrected_out(c, b, device_out, out_capacity, out_offsets, status, hipMemcpyDeviceToDevice, "device buffer");
 }
 
 int talc_correct_batch(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, char* out,

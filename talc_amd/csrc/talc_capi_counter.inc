@@ -68,12 +68,10 @@ struct talc_counter {
   LaunchTimer countTimer, maskTimer;   // around every k_count_batch, every k_sr_mask
   uint64_t nBatches = 0, nBytes = 0, nGrows = 0;
   double packS = 0, growS = 0;
-  hipEvent_t histoEv[2] = {nullptr, nullptr};   // around the last k_count_histo (talc_counter_histo makes them)
-  float histo_ms = 0;
+  Span histo;   // the last k_count_histo
   ~talc_counter() {
     (void)hipSetDevice(device);
     for (auto& s : stage) if (s.done) hipEventDestroy(s.done);
-    for (auto& e : histoEv) if (e) hipEventDestroy(e);
     if (stream) hipStreamDestroy(stream);
   }
 };
@@ -401,11 +399,11 @@ static int spectrum_cu_count(int device, int* cus) {
 }
 
 // One spectrum pass on `stream` of the current device over n slots, of which a workgroup takes groupSlots per trip: the
-// output words zeroed, the kernel launched by launch(grid, lds bytes, out) between ev[0] and ev[1] (when given), the bins
+// output words zeroed, the kernel launched by launch(grid, lds bytes, out) inside `span` (when given, and read), the bins
 // and totals copied to hist / stats (either may be NULL).  The grid: a workgroup per trip, at most the fixed number per CU.
 template <class Launch>
 static int run_spectrum(int device, hipStream_t stream, uint64_t n, uint64_t groupSlots, uint32_t high, uint64_t* hist, talc_spectrum_stats* stats,
-                        hipEvent_t* ev, Launch launch) {
+                        Span* span, Launch launch) {
   const uint32_t bins = high + 2;
   DevBuf<unsigned long long> dOut;
   HIPCHK(dOut.alloc(bins + SPECTRUM_TOTALS));
@@ -413,14 +411,14 @@ static int run_spectrum(int device, hipStream_t stream, uint64_t n, uint64_t gro
   int cus = 1;
   if (int rc = spectrum_cu_count(device, &cus)) return rc;
   const uint64_t grid = std::min<uint64_t>((n + groupSlots - 1) / groupSlots, (uint64_t)cus * kSpectrumGridPerCu);
-  if (ev) HIPCHK(hipEventRecord(ev[0], stream));
-  // (no slots, a table of capacity 0: nothing is launched, the zeroed words are the answer and the events time nothing)
-  if (grid) launch(dim3((unsigned)grid), (size_t)spectrum_lds_words(bins) * 4, dOut.get());
-  HIPCHK(hipGetLastError());
-  if (ev) HIPCHK(hipEventRecord(ev[1], stream));
+  // (no slots, a table of capacity 0: nothing is launched, the zeroed words are the answer and the span times nothing)
+  auto pass = [&] { if (grid) launch(dim3((unsigned)grid), (size_t)spectrum_lds_words(bins) * 4, dOut.get()); };
+  if (span) { if (int rc = span->around(stream, pass)) return rc; }
+  else { pass(); HIPCHK(hipGetLastError()); }
   std::vector<unsigned long long> h(bins + SPECTRUM_TOTALS);
   HIPCHK(hipMemcpyAsync(h.data(), dOut.get(), h.size() * 8, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
+  if (span) if (int rc = span->read()) return rc;
   if (hist) for (uint32_t b = 0; b < bins; ++b) hist[b] = h[b];
   if (stats) {
     stats->distinct = h[bins + SPECTRUM_DISTINCT]; stats->unique = h[bins + SPECTRUM_UNIQUE];
@@ -595,22 +593,17 @@ int talc_counter_histo(talc_counter* c, uint32_t high, uint64_t* hist, talc_spec
   if ((rc = counter_usable(c))) return rc;
   unsigned long long st[2];
   if ((rc = counter_sync(c, st))) return rc;
-  for (auto& e : c->histoEv)
-    if (!e) HIPCHK(hipEventCreate(&e));
   const CountSlot* tab = c->tab.get();
   const uint64_t cap = c->cap();
   hipStream_t stream = c->stream;
-  rc = run_spectrum(c->device, stream, cap, spectrum_group_slots<CounterSlots>(), high, hist, stats, c->histoEv, [=](dim3 grid, size_t lds, unsigned long long* out) {
+  return run_spectrum(c->device, stream, cap, spectrum_group_slots<CounterSlots>(), high, hist, stats, &c->histo, [=](dim3 grid, size_t lds, unsigned long long* out) {
     hipLaunchKernelGGL(k_count_histo, grid, dim3(kSpectrumThreads), lds, stream, tab, cap, high, out);
   });
-  if (rc) return rc;
-  HIPCHK(hipEventElapsedTime(&c->histo_ms, c->histoEv[0], c->histoEv[1]));
-  return TALC_OK;
 }
 
 int talc_counter_get_histo_timing(const talc_counter* c, float* histo_ms) {
   if (!c || !histo_ms) return fail(TALC_ERR_INVALID, "null argument");
-  *histo_ms = c->histo_ms;
+  *histo_ms = c->histo.ms;
   return TALC_OK;
 }
 

@@ -17,7 +17,7 @@ struct EditIn {
 };
 // ... and what it leaves: an EditOut (talc_capi.hip)
 
-// events kEvEditAlignA0 .. kEvEditPack: around the first k_edit_align rounds, after k_edit_count, around the second rounds, after k_edit_pack.
+// Spans kSpanEditAlignA .. kSpanEditPack: the first k_edit_align rounds, k_edit_count, the second rounds, k_edit_pack.
 // scratch_bytes: the budget of the rounds (kEditScratchBytes; the test hook passes a small one to make several rounds).
 // first_distance (may be null): the distance the DP of the first task found, -1 when there was no task.
 static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t scratch_bytes, EditOut& out, int32_t* first_distance) {
@@ -49,23 +49,22 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
   HIPCHK(d_op_off.alloc(c->cache, (uint64_t)n + 1));
   int rc;
   if ((rc = up(c, d_tasks, tasks, s))) return rc;
-  auto align = [&](int write) -> int {
+  auto align = [&](int write) {
     size_t t0 = 0;
     for (const size_t t1 : roundEnd) {   // (rounds run one after the other on the stream: they share the scratch)
       if (t1 > t0)
         hipLaunchKernelGGL(k_edit_align, dim3((unsigned)(t1 - t0)), dim3(64), 0, s, d_tasks.get() + t0, (uint32_t)(t1 - t0), in.d_segs, in.d_raw, in.d_raw_off,
                            in.d_dense, in.d_dense_off, d_scratch.get(), d_parts.get(), write, d_op_off.get(), out.d_ops.get());
-      HIPCHK(hipGetLastError());
+      if (hipPeekAtLastError() != hipSuccess) return;   // (no round after one that failed; the span reports it)
       t0 = t1;
     }
-    return TALC_OK;
   };
-  HIPCHK(hipEventRecord(c->ev[kEvEditAlignA0], s));
-  if ((rc = align(0))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvEditAlignA1], s));
-  if (n) hipLaunchKernelGGL(k_edit_count, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_rows.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvEditCount], s));
+  Span* const span = c->span;
+  if ((rc = span[kSpanEditAlignA].around(s, [&] { align(0); }))) return rc;
+  rc = span[kSpanEditCount].around(s, [&] {
+    if (n) hipLaunchKernelGGL(k_edit_count, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_rows.get());
+  });
+  if (rc) return rc;
   out.h_rows.assign(n, EditRow{0u, 0u, 0u, 0u, 0u, 0u});
   if (n) HIPCHK(hipMemcpyAsync(out.h_rows.data(), d_rows.get(), (size_t)n * sizeof(EditRow), hipMemcpyDeviceToHost, s));
   if (first_distance) {
@@ -81,18 +80,13 @@ static int run_edits(talc_ctx* c, const EditIn& in, uint64_t max_cells, uint64_t
   HIPCHK(out.d_ops.ensure(c->cache, nops));
   HIPCHK(hipMemsetAsync(out.d_ops.get(), 0, std::max<uint64_t>(nops, 1) * sizeof(uint32_t), s));   // the runs are added
   HIPCHK(hipMemcpyAsync(d_op_off.get(), out.h_op_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev[kEvEditAlignB0], s));
-  if ((rc = align(1))) return rc;
-  HIPCHK(hipEventRecord(c->ev[kEvEditAlignB1], s));
-  if (n) hipLaunchKernelGGL(k_edit_pack, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_op_off.get(), out.d_ops.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev[kEvEditPack], s));
+  if ((rc = span[kSpanEditAlignB].around(s, [&] { align(1); }))) return rc;
+  rc = span[kSpanEditPack].around(s, [&] {
+    if (n) hipLaunchKernelGGL(k_edit_pack, dim3(n), dim3(64), 0, s, in.d_segs, in.d_seg_off, d_parts.get(), n, max_cells, d_op_off.get(), out.d_ops.get());
+  });
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(s));
-  float a0 = 0, a1 = 0, p0 = 0, p1 = 0;
-  HIPCHK(hipEventElapsedTime(&a0, c->ev[kEvEditAlignA0], c->ev[kEvEditAlignA1])); HIPCHK(hipEventElapsedTime(&p0, c->ev[kEvEditAlignA1], c->ev[kEvEditCount]));
-  HIPCHK(hipEventElapsedTime(&a1, c->ev[kEvEditAlignB0], c->ev[kEvEditAlignB1])); HIPCHK(hipEventElapsedTime(&p1, c->ev[kEvEditAlignB1], c->ev[kEvEditPack]));
-  c->edit_align_ms = a0 + a1; c->edit_pack_ms = p0 + p1;
-  return TALC_OK;
+  return read_spans(c);
 }
 
 // 0 is the default; beyond what the scratch budget lets one pair take, the cap is that
@@ -125,20 +119,13 @@ int talc_batch_fetch_edits(talc_ctx* c, talc_batch* b, uint32_t* ops, uint64_t o
   const uint64_t nops = b->edits.h_op_off[b->n_reads];
   if (op_offsets) memcpy(op_offsets, b->edits.h_op_off.data(), ((size_t)b->n_reads + 1) * 8);
   if (rows && b->n_reads) memcpy(rows, b->edits.h_rows.data(), (size_t)b->n_reads * sizeof(talc_edit_row));
-  if (ops) {
-    if (op_capacity < nops) return fail(TALC_ERR_CAPACITY, "op buffer too small: need %llu ops", (unsigned long long)nops);
-    if (nops) {
-      HIPCHK(hipMemcpyAsync(ops, b->edits.d_ops.get(), nops * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  return TALC_OK;
+  return copy_out(c, ops, op_capacity, b->edits.d_ops.get(), nops, sizeof(uint32_t), hipMemcpyDeviceToHost, "op buffer", "ops");
 }
 
 int talc_ctx_get_edits_timing(const talc_ctx* c, float* align_ms, float* pack_ms) {
   if (!c) return fail(TALC_ERR_INVALID, "null context");
-  if (align_ms) *align_ms = c->edit_align_ms;
-  if (pack_ms) *pack_ms = c->edit_pack_ms;
+  if (align_ms) *align_ms = c->span[kSpanEditAlignA].ms + c->span[kSpanEditAlignB].ms;
+  if (pack_ms) *pack_ms = c->span[kSpanEditCount].ms + c->span[kSpanEditPack].ms;
   return TALC_OK;
 }
 

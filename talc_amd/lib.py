@@ -19,38 +19,6 @@ LOG_MESSAGES = {
     READ_NO_STRUCTURE: "Unable to define convenient structure.",  # main.cpp:290
 }
 
-# every symbol include/talc_hip.h declares
-ABI_SYMBOLS = [
-    "talc_abi_version", "talc_last_error", "talc_params_default", "talc_device_count", "talc_pinned_alloc", "talc_pinned_free",
-    "talc_table_build", "talc_table_from_arrays", "talc_table_build_device", "talc_table_from_arrays_device",
-    "talc_table_colour", "talc_table_decolour_repeats",
-    "talc_table_size", "talc_table_device_bytes", "talc_table_upload", "talc_table_capacity", "talc_table_image_bytes",
-    "talc_table_export_device", "talc_table_import_device", "talc_table_lookup_batch",
-    "talc_table_next_counts_batch", "talc_table_lookup_host_batch", "talc_table_destroy",
-    "talc_ctx_create", "talc_ctx_destroy", "talc_batch_create", "talc_batch_destroy",
-    "talc_batch_coverage", "talc_batch_fetch_coverage", "talc_batch_num_kmers", "talc_batch_num_bases",
-    "talc_batch_correct", "talc_batch_corrected_bytes", "talc_batch_fetch_corrected", "talc_batch_fetch_read_stats",
-    "talc_batch_copy_corrected_device", "talc_correct_batch",
-    "talc_ctx_get_timing", "talc_batch_trace_read", "talc_test_dp",
-    "talc_table_fetch_walk", "talc_batch_fetch_coverage_degrees", "talc_batch_structure", "talc_batch_fetch_structure",
-    "talc_batch_order",
-    "talc_counter_create", "talc_counter_add", "talc_counter_stats", "talc_counter_fetch", "talc_counter_build_table",
-    "talc_counter_destroy",
-    "talc_counter_set_both_strands", "talc_counter_add_counts", "talc_table_build_device_both_strands",
-    "talc_table_from_arrays_device_both_strands",
-    "talc_counter_set_filter", "talc_counter_add_fastq", "talc_counter_filter_stats", "talc_test_counter_mask",
-    "talc_ctx_set_map", "talc_batch_num_segments", "talc_batch_fetch_map", "talc_batch_fetch_corrected_masked",
-    "talc_ctx_get_map_timing",
-    "talc_batch_solidity", "talc_batch_fetch_solidity", "talc_ctx_get_solidity_timing",
-    "talc_batch_pieces", "talc_batch_num_pieces", "talc_batch_pieces_bytes", "talc_batch_fetch_pieces", "talc_ctx_get_pieces_timing",
-    "talc_batch_edits", "talc_batch_num_edit_ops", "talc_batch_fetch_edits", "talc_ctx_get_edits_timing", "talc_test_edit_script",
-    "talc_test_batch_edits", "talc_test_parse_text",
-    "talc_ctx_set_auto_strand", "talc_batch_strand", "talc_batch_fetch_strand", "talc_ctx_get_strand_timing",
-    "talc_batch_support", "talc_batch_support_bytes", "talc_batch_fetch_support", "talc_ctx_get_support_timing",
-    "talc_test_set_poison", "talc_test_get_poison", "talc_test_guard_report", "talc_test_cache_reuses", "talc_test_guard_selftest",
-    "talc_counter_histo", "talc_counter_get_histo_timing", "talc_table_histo", "talc_spectrum_threshold", "talc_counter_set_min_count",
-]
-
 SEG_SOLID, SEG_CORRECTED, SEG_RAW = range(3)
 SEG_LETTERS = "SCR"
 # talc_segment (docs/correction_map.md)
@@ -141,6 +109,115 @@ class Timing(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+def _abi():
+    """Every symbol include/talc_hip.h declares: name -> (restype, argtypes).  Handles and buffers are void pointers."""
+    vp, u64, u32, i32, txt = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p
+    par, out, stats = C.POINTER(Params), C.POINTER(C.c_void_p), C.POINTER(SpectrumStats)
+    return {
+        "talc_abi_version": (i32, []),
+        "talc_last_error": (txt, []),
+        "talc_params_default": (i32, [par]),
+        "talc_device_count": (i32, []),
+        "talc_pinned_alloc": (vp, [u64]),
+        "talc_pinned_free": (None, [vp]),
+        "talc_table_build": (i32, [txt, txt, par, out, vp]),
+        "talc_table_from_arrays": (i32, [vp, vp, u64, par, out]),
+        "talc_table_build_device": (i32, [txt, txt, par, i32, out, vp]),
+        "talc_table_from_arrays_device": (i32, [vp, vp, u64, par, i32, out]),
+        "talc_table_colour": (i32, [vp, vp, vp, u64]),
+        "talc_table_decolour_repeats": (i32, [vp]),
+        "talc_table_size": (u64, [vp]),
+        "talc_table_device_bytes": (u64, [vp]),
+        "talc_table_upload": (i32, [vp, i32]),
+        "talc_table_capacity": (u64, [vp]),
+        "talc_table_image_bytes": (u64, [vp]),
+        "talc_table_export_device": (i32, [vp, i32, vp, vp]),
+        "talc_table_import_device": (i32, [par, u64, u64, vp, vp, i32, out]),
+        "talc_table_lookup_batch": (i32, [vp, i32, vp, u64, vp, vp]),
+        "talc_table_next_counts_batch": (i32, [vp, i32, vp, u64, i32, vp, vp]),
+        "talc_table_lookup_host_batch": (i32, [vp, vp, u64, vp, vp]),
+        "talc_table_fetch_walk": (i32, [vp, i32, i32, vp, u64]),
+        "talc_table_destroy": (None, [vp]),
+        "talc_ctx_create": (i32, [vp, par, i32, out]),
+        "talc_ctx_destroy": (None, [vp]),
+        "talc_batch_create": (i32, [vp, vp, vp, u32, out]),
+        "talc_batch_destroy": (None, [vp]),
+        "talc_batch_coverage": (i32, [vp, vp]),
+        "talc_batch_fetch_coverage": (i32, [vp, vp, vp, vp, vp, vp]),
+        "talc_batch_fetch_coverage_degrees": (i32, [vp, vp, vp]),
+        "talc_batch_structure": (i32, [vp, vp]),
+        "talc_batch_fetch_structure": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "talc_batch_order": (i32, [vp, vp, vp, vp]),
+        "talc_batch_num_kmers": (u64, [vp]),
+        "talc_batch_num_bases": (u64, [vp]),
+        "talc_batch_correct": (i32, [vp, vp]),
+        "talc_batch_corrected_bytes": (u64, [vp]),
+        "talc_batch_fetch_corrected": (i32, [vp, vp, vp, u64, vp, vp]),
+        "talc_batch_copy_corrected_device": (i32, [vp, vp, vp, u64, vp, vp]),
+        "talc_batch_fetch_read_stats": (i32, [vp, vp, vp]),
+        "talc_correct_batch": (i32, [vp, vp, vp, u32, vp, u64, vp, vp]),
+        "talc_ctx_get_timing": (i32, [vp, C.POINTER(Timing)]),
+        "talc_batch_trace_read": (C.c_int64, [vp, vp, u32, vp, u64]),
+        "talc_test_dp": (i32, [vp, i32, txt, i32, txt, i32, i32, i32, i32, i32, vp]),
+        "talc_counter_create": (i32, [par, i32, u64, out]),
+        "talc_counter_add": (i32, [vp, vp, vp, u32]),
+        "talc_counter_stats": (i32, [vp, vp]),
+        "talc_counter_fetch": (i32, [vp, u32, vp, vp, u64, vp]),
+        "talc_counter_build_table": (i32, [vp, txt, out, vp]),
+        "talc_counter_destroy": (None, [vp]),
+        "talc_counter_set_both_strands": (i32, [vp, i32]),
+        "talc_counter_add_counts": (i32, [vp, vp, vp, u64]),
+        "talc_table_build_device_both_strands": (i32, [txt, txt, par, i32, out, vp]),
+        "talc_table_from_arrays_device_both_strands": (i32, [vp, vp, u64, par, i32, out]),
+        "talc_counter_set_filter": (i32, [vp, u32, txt, u32, u32]),
+        "talc_counter_add_fastq": (i32, [vp, vp, vp, vp, u32]),
+        "talc_counter_filter_stats": (i32, [vp, vp]),
+        "talc_test_counter_mask": (i32, [vp, vp, vp, vp, u32, vp, vp]),
+        "talc_ctx_set_map": (i32, [vp, i32]),
+        "talc_batch_num_segments": (u64, [vp]),
+        "talc_batch_fetch_map": (i32, [vp, vp, vp, u64, vp]),
+        "talc_batch_fetch_corrected_masked": (i32, [vp, vp, vp, u64, vp, vp]),
+        "talc_ctx_get_map_timing": (i32, [vp, vp, vp]),
+        "talc_batch_solidity": (i32, [vp, vp]),
+        "talc_batch_fetch_solidity": (i32, [vp, vp, vp, vp]),
+        "talc_ctx_get_solidity_timing": (i32, [vp, vp, vp]),
+        "talc_batch_pieces": (i32, [vp, vp, i32, u32, i32]),
+        "talc_batch_num_pieces": (u64, [vp]),
+        "talc_batch_pieces_bytes": (u64, [vp]),
+        "talc_batch_fetch_pieces": (i32, [vp, vp, vp, u64, vp, vp, u64, vp]),
+        "talc_ctx_get_pieces_timing": (i32, [vp, vp, vp]),
+        "talc_batch_edits": (i32, [vp, vp, u64]),
+        "talc_batch_num_edit_ops": (u64, [vp]),
+        "talc_batch_fetch_edits": (i32, [vp, vp, vp, u64, vp, vp]),
+        "talc_ctx_get_edits_timing": (i32, [vp, vp, vp]),
+        "talc_test_batch_edits": (i32, [vp, vp, u64, u64]),
+        "talc_test_edit_script": (i32, [vp, txt, u32, txt, u32, u64, vp, u64, vp, vp]),
+        "talc_test_parse_text": (i32, [txt, u32, u32, i32, i32, u64, i32, vp, vp, u64, vp, vp, vp]),
+        "talc_ctx_set_auto_strand": (i32, [vp, i32]),
+        "talc_batch_strand": (i32, [vp, vp]),
+        "talc_batch_fetch_strand": (i32, [vp, vp, vp]),
+        "talc_ctx_get_strand_timing": (i32, [vp, vp]),
+        "talc_batch_support": (i32, [vp, vp, C.POINTER(SupportParams)]),
+        "talc_batch_support_bytes": (u64, [vp]),
+        "talc_batch_fetch_support": (i32, [vp, vp, vp, u64, vp]),
+        "talc_ctx_get_support_timing": (i32, [vp, vp]),
+        "talc_test_set_poison": (i32, [i32, u32]),
+        "talc_test_get_poison": (i32, [vp, vp]),
+        "talc_test_guard_report": (i32, [vp]),
+        "talc_test_cache_reuses": (u64, []),
+        "talc_test_guard_selftest": (i32, [vp]),
+        "talc_counter_histo": (i32, [vp, u32, vp, stats]),
+        "talc_counter_get_histo_timing": (i32, [vp, vp]),
+        "talc_table_histo": (i32, [vp, i32, u32, vp, stats]),
+        "talc_spectrum_threshold": (i32, [vp, u32, u32, u32, vp, vp]),
+        "talc_counter_set_min_count": (i32, [vp, u32]),
+    }
+
+
+ABI = _abi()
+ABI_SYMBOLS = list(ABI)
+
+
 def lib_path():
     # TALC_LIB selects another build of the same library (e.g. the -DTALC_PROF diagnostic build)
     return os.environ.get("TALC_LIB") or os.path.join(_build.OUT, "libtalc_hip.so")
@@ -155,130 +232,11 @@ def lib():
             raise TalcError("libtalc_hip.so is missing: run `python -m talc_amd.build` (needs hipcc); "
                             "there is no CPU fallback for the correction path")
         L = C.CDLL(path)
-        vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
-        L.talc_last_error.restype = C.c_char_p
-        L.talc_params_default.argtypes = [C.POINTER(Params)]
-        L.talc_pinned_alloc.restype = vp
-        L.talc_pinned_alloc.argtypes = [u64]
-        L.talc_pinned_free.argtypes = [vp]
-        L.talc_table_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), C.POINTER(vp), vp]
-        L.talc_table_from_arrays.argtypes = [vp, vp, u64, C.POINTER(Params), C.POINTER(vp)]
-        L.talc_table_build_device.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), i32, C.POINTER(vp), vp]
-        L.talc_table_from_arrays_device.argtypes = [vp, vp, u64, C.POINTER(Params), i32, C.POINTER(vp)]
-        L.talc_table_colour.argtypes = [vp, vp, vp, u64]
-        L.talc_table_decolour_repeats.argtypes = [vp]
-        L.talc_table_size.restype = u64
-        L.talc_table_size.argtypes = [vp]
-        L.talc_table_device_bytes.restype = u64
-        L.talc_table_device_bytes.argtypes = [vp]
-        L.talc_table_upload.argtypes = [vp, i32]
-        L.talc_table_capacity.restype = u64
-        L.talc_table_capacity.argtypes = [vp]
-        L.talc_table_image_bytes.restype = u64
-        L.talc_table_image_bytes.argtypes = [vp]
-        L.talc_table_export_device.argtypes = [vp, i32, vp, vp]
-        L.talc_table_import_device.argtypes = [C.POINTER(Params), u64, u64, vp, vp, i32, C.POINTER(vp)]
-        L.talc_table_lookup_batch.argtypes = [vp, i32, vp, u64, vp, vp]
-        L.talc_table_next_counts_batch.argtypes = [vp, i32, vp, u64, i32, vp, vp]
-        L.talc_table_lookup_host_batch.argtypes = [vp, vp, u64, vp, vp]
-        L.talc_table_fetch_walk.argtypes = [vp, i32, i32, vp, u64]
-        L.talc_table_destroy.argtypes = [vp]
-        L.talc_ctx_create.argtypes = [vp, C.POINTER(Params), i32, C.POINTER(vp)]
-        L.talc_ctx_destroy.argtypes = [vp]
-        L.talc_batch_create.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
-        L.talc_batch_destroy.argtypes = [vp]
-        L.talc_batch_coverage.argtypes = [vp, vp]
-        L.talc_batch_fetch_coverage.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.talc_batch_fetch_coverage_degrees.argtypes = [vp, vp, vp]
-        L.talc_batch_structure.argtypes = [vp, vp]
-        L.talc_batch_fetch_structure.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
-        if hasattr(L, "talc_batch_order"):   # (a TALC_LIB build from before the hook still loads: A/B against a parent)
-            L.talc_batch_order.argtypes = [vp, vp, vp, vp]
-        L.talc_batch_num_kmers.restype = u64
-        L.talc_batch_num_kmers.argtypes = [vp]
-        L.talc_batch_num_bases.restype = u64
-        L.talc_batch_num_bases.argtypes = [vp]
-        L.talc_batch_correct.argtypes = [vp, vp]
-        L.talc_batch_corrected_bytes.restype = u64
-        L.talc_batch_corrected_bytes.argtypes = [vp]
-        L.talc_batch_fetch_corrected.argtypes = [vp, vp, vp, u64, vp, vp]
-        L.talc_batch_copy_corrected_device.argtypes = [vp, vp, vp, u64, vp, vp]
-        L.talc_batch_fetch_read_stats.argtypes = [vp, vp, vp]
-        L.talc_correct_batch.argtypes = [vp, vp, vp, u32, vp, u64, vp, vp]
-        L.talc_ctx_get_timing.argtypes = [vp, C.POINTER(Timing)]
-        L.talc_batch_trace_read.restype = C.c_int64
-        L.talc_batch_trace_read.argtypes = [vp, vp, u32, vp, u64]
-        L.talc_test_dp.argtypes = [vp, i32, C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, i32, vp]
-        L.talc_counter_create.argtypes = [C.POINTER(Params), i32, u64, C.POINTER(vp)]
-        L.talc_counter_add.argtypes = [vp, vp, vp, u32]
-        L.talc_counter_stats.argtypes = [vp, vp]
-        L.talc_counter_fetch.argtypes = [vp, u32, vp, vp, u64, vp]
-        L.talc_counter_build_table.argtypes = [vp, C.c_char_p, C.POINTER(vp), vp]
-        L.talc_counter_destroy.argtypes = [vp]
-        if hasattr(L, "talc_counter_set_both_strands"):   # (a build from before both strands loads; asking it for them raises)
-            L.talc_counter_set_both_strands.argtypes = [vp, i32]
-            L.talc_counter_add_counts.argtypes = [vp, vp, vp, u64]
-            L.talc_table_build_device_both_strands.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), i32, C.POINTER(vp), vp]
-            L.talc_table_from_arrays_device_both_strands.argtypes = [vp, vp, u64, C.POINTER(Params), i32, C.POINTER(vp)]
-        if hasattr(L, "talc_counter_set_filter"):   # (likewise: a build from before the short-read filter)
-            L.talc_counter_set_filter.argtypes = [vp, u32, C.c_char_p, u32, u32]
-            L.talc_counter_add_fastq.argtypes = [vp, vp, vp, vp, u32]
-            L.talc_counter_filter_stats.argtypes = [vp, vp]
-            L.talc_test_counter_mask.argtypes = [vp, vp, vp, vp, u32, vp, vp]
-        # (a build from before the correction map, selected with TALC_LIB for an A/B, loads; asking it for a map raises)
-        if hasattr(L, "talc_ctx_set_map"):
-            L.talc_ctx_set_map.argtypes = [vp, i32]
-            L.talc_batch_num_segments.restype = u64
-            L.talc_batch_num_segments.argtypes = [vp]
-            L.talc_batch_fetch_map.argtypes = [vp, vp, vp, u64, vp]
-            L.talc_batch_fetch_corrected_masked.argtypes = [vp, vp, vp, u64, vp, vp]
-            L.talc_ctx_get_map_timing.argtypes = [vp, vp, vp]
-        if hasattr(L, "talc_batch_solidity"):   # (likewise: a build from before the solidity report)
-            L.talc_batch_solidity.argtypes = [vp, vp]
-            L.talc_batch_fetch_solidity.argtypes = [vp, vp, vp, vp]
-            L.talc_ctx_get_solidity_timing.argtypes = [vp, vp, vp]
-        if hasattr(L, "talc_batch_pieces"):     # (likewise: a build from before the trimmed / split output)
-            L.talc_batch_pieces.argtypes = [vp, vp, i32, u32, i32]
-            L.talc_batch_num_pieces.restype = u64
-            L.talc_batch_num_pieces.argtypes = [vp]
-            L.talc_batch_pieces_bytes.restype = u64
-            L.talc_batch_pieces_bytes.argtypes = [vp]
-            L.talc_batch_fetch_pieces.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
-            L.talc_ctx_get_pieces_timing.argtypes = [vp, vp, vp]
-        if hasattr(L, "talc_batch_edits"):      # (likewise: a build from before the edit scripts)
-            L.talc_batch_edits.argtypes = [vp, vp, u64]
-            L.talc_batch_num_edit_ops.restype = u64
-            L.talc_batch_num_edit_ops.argtypes = [vp]
-            L.talc_batch_fetch_edits.argtypes = [vp, vp, vp, u64, vp, vp]
-            L.talc_ctx_get_edits_timing.argtypes = [vp, vp, vp]
-            L.talc_test_batch_edits.argtypes = [vp, vp, u64, u64]
-            L.talc_test_edit_script.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, u64, vp, u64, vp, vp]
-        if hasattr(L, "talc_test_parse_text"):  # (likewise: a build from before the parser's test hook)
-            L.talc_test_parse_text.argtypes = [C.c_char_p, u32, u32, i32, i32, u64, i32, vp, vp, u64, vp, vp, vp]
-        if hasattr(L, "talc_ctx_set_auto_strand"):   # (likewise: a build from before auto strand)
-            L.talc_ctx_set_auto_strand.argtypes = [vp, i32]
-            L.talc_batch_strand.argtypes = [vp, vp]
-            L.talc_batch_fetch_strand.argtypes = [vp, vp, vp]
-            L.talc_ctx_get_strand_timing.argtypes = [vp, vp]
-        if hasattr(L, "talc_batch_support"):
-            L.talc_batch_support.argtypes = [vp, vp, C.POINTER(SupportParams)]
-            L.talc_batch_support_bytes.restype = u64
-            L.talc_batch_support_bytes.argtypes = [vp]
-            L.talc_batch_fetch_support.argtypes = [vp, vp, vp, u64, vp]
-            L.talc_ctx_get_support_timing.argtypes = [vp, vp]
-        if hasattr(L, "talc_test_set_poison"):
-            L.talc_test_set_poison.argtypes = [i32, u32]
-            L.talc_test_get_poison.argtypes = [vp, vp]
-            L.talc_test_guard_report.argtypes = [vp]
-            L.talc_test_cache_reuses.restype = u64
-            L.talc_test_cache_reuses.argtypes = []
-            L.talc_test_guard_selftest.argtypes = [vp]
-        if hasattr(L, "talc_counter_histo"):   # (likewise: a TALC_LIB build from before the k-mer spectrum, for an A/B; asking it for one raises)
-            L.talc_counter_histo.argtypes = [vp, u32, vp, C.POINTER(SpectrumStats)]
-            L.talc_counter_get_histo_timing.argtypes = [vp, vp]
-            L.talc_table_histo.argtypes = [vp, i32, u32, vp, C.POINTER(SpectrumStats)]
-            L.talc_spectrum_threshold.argtypes = [vp, u32, u32, u32, vp, vp]
-            L.talc_counter_set_min_count.argtypes = [vp, u32]
+        # (a TALC_LIB build of a parent commit that lacks a symbol still loads, for an A/B; asking it for that call raises)
+        for name, (restype, argtypes) in ABI.items():
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 
@@ -390,8 +348,33 @@ class PinnedArray:
             pass
 
 
-class Table:
+class _Owner:
+    """What owns one object of the library: `_h` is its handle, `_destroy` the name of the call that gives it back."""
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _histo(call, *args):
+    """One spectrum call (its own arguments end with `high`): (hist u64[high + 2], (distinct, unique, total, max_count))."""
+    hist = np.zeros(min(args[-1] or SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH) + 2, dtype=np.uint64)   # (a high out of range is refused)
+    st = SpectrumStats()
+    _chk(call(*args, hist.ctypes.data, C.byref(st)))
+    return hist, st.as_tuple()
+
+
+class Table(_Owner):
     """The SR k-mer table (replaces buildCDBG, Jellyfish.cpp:236-295)."""
+    _destroy = "talc_table_destroy"
 
     def __init__(self, handle, params):
         self._h = handle
@@ -508,28 +491,15 @@ class Table:
     def histo(self, device=0, high=0):
         """The count spectrum of the k-mers the table stores, from its image on `device` (staged or uploaded; TalcError
         without one): (hist u64[high + 2], (distinct, unique, total, max_count)) as KmerCounter.histo."""
-        hist = np.zeros(min(int(high) or SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH) + 2, dtype=np.uint64)   # (a high out of range is refused)
-        st = SpectrumStats()
-        _chk(lib().talc_table_histo(self._h, int(device), int(high), hist.ctypes.data, C.byref(st)))
-        return hist, st.as_tuple()
-
-    def close(self):
-        if self._h:
-            lib().talc_table_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _histo(lib().talc_table_histo, self._h, int(device), int(high))
 
 
-class KmerCounter:
+class KmerCounter(_Owner):
     """Short-read k-mer counter on GPU `device` (replaces `jellyfish count -m K` + `dump -c`; docs/kmer_counting.md):
     every window of K bases of ACGTacgt inside one record counts once, directional, 2 bits per base.  both_strands
     (docs/both_strands.md): every observation counts for the canonical k-mer min(x, rc(x)); fetch returns canonical k-mers
     and build_table stores each kept one with its reverse complement."""
+    _destroy = "talc_counter_destroy"
 
     def __init__(self, params, device=0, expected_distinct=0, both_strands=False):
         self.params = params
@@ -623,10 +593,7 @@ class KmerCounter:
         """The count spectrum (docs/kmer_spectrum.md; `jellyfish histo`): (hist u64[high + 2], (distinct, unique, total,
         max_count)).  hist[c] = the k-mers with count c, hist[high + 1] those above high; high 0 is 10000.  The counter is
         not spent and nothing it holds changes."""
-        hist = np.zeros(min(int(high) or SPECTRUM_DEFAULT_HIGH, SPECTRUM_MAX_HIGH) + 2, dtype=np.uint64)   # (a high out of range is refused)
-        st = SpectrumStats()
-        _chk(lib().talc_counter_histo(self._h, int(high), hist.ctypes.data, C.byref(st)))
-        return hist, st.as_tuple()
+        return _histo(lib().talc_counter_histo, self._h, int(high))
 
     def histo_timing(self):
         """Device time (ms) of the last k_count_histo of this counter."""
@@ -651,17 +618,6 @@ class KmerCounter:
         t.build_stats = st
         return t
 
-    def close(self):
-        if self._h:
-            lib().talc_counter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def spectrum_threshold(hist, limit=0, fallback=2):
     """(chosen, valley) of a spectrum as histo() returns it (hist[len - 1] is the catch-all bin): the first local minimum,
@@ -684,7 +640,9 @@ def mask_batch(bases, offsets, quals=None, min_qual=0, adapters=(), min_overlap=
         c.close()
 
 
-class Context:
+class Context(_Owner):
+    _destroy = "talc_ctx_destroy"
+
     def __init__(self, table, params=None, device=0):
         self.table = table
         self.params = params or table.params
@@ -776,20 +734,10 @@ class Context:
         finally:
             b.close()
 
-    def close(self):
-        if self._h:
-            lib().talc_ctx_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Batch:
+class Batch(_Owner):
     """A batch of reads resident in HBM."""
+    _destroy = "talc_batch_destroy"
 
     def __init__(self, ctx, bases, offsets):
         self.ctx = ctx
@@ -1000,14 +948,3 @@ class Batch:
             if need <= cap:
                 return buf.value.decode()
             cap = int(need) + 16
-
-    def close(self):
-        if self._h:
-            lib().talc_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -26,6 +26,16 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
     assert set(T.ABI_SYMBOLS) == declared
     assert L.talc_abi_version() == 1
+    # every call is bound with as many arguments as its prototype takes ((void): none), so ctypes refuses a wrong arity
+    protos = re.findall(r"\b(talc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert {name for name, _ in protos} == declared
+    wrong = {}
+    for name, params in protos:
+        want = 0 if params.strip() == "void" else params.count(",") + 1
+        bound = getattr(L, name).argtypes
+        if bound is None or len(bound) != want:
+            wrong[name] = (want, bound)
+    assert not wrong, wrong
 
 
 def test_environment_is_read_in_one_place_and_documented():

@@ -171,6 +171,73 @@ def test_every_step_drops_what_was_made_from_what_it_replaces():
         ctx.close()
 
 
+# ---------------------------------------------------------------- 1b. the device times of the reports
+def report_times(ctx):
+    """Every device time the context's getters report, by the kernel(s) it is the time of."""
+    (pack_map, mask_case), (sol_raw, sol_records) = ctx.map_timing(), ctx.solidity_timing()
+    (piece_count, piece_pack), (edit_align, edit_pack) = ctx.pieces_timing(), ctx.edits_timing()
+    return dict(pack_map=pack_map, mask_case=mask_case, sol_raw=sol_raw, sol_records=sol_records, piece_count=piece_count,
+                piece_pack=piece_pack, edit_align=edit_align, edit_pack=edit_pack, support=ctx.support_timing(), vote=ctx.strand_timing())
+
+
+def test_every_report_keeps_its_own_time_and_a_pending_one_is_read_by_the_next_wait():
+    """Each call sets the times of its own kernels and of no other's: what was read after an earlier call reads the same
+    after every later one, and what has not run yet reads exactly 0.  A time is > 0 where a kernel ran over the 24 reads
+    between its two events; the pieces' and the edit scripts' are held to >= 0, as their own tests hold them.  A vote that
+    auto strand launches inside another call is timed by that call, and an uncorrected batch's solidity has no time for
+    the records' rows, whatever an earlier batch of the context left."""
+    s = inputs()
+    table, p = s["s"].pair.ttab, s["s"].pair.p
+    packed = PU.pack_reads(s["reads"])
+    ctx = T.Context(table, p, 0)
+    ctx.record_map(True)
+    b = ctx.batch(*packed)
+    try:
+        steps = [(b.correct, ("pack_map",), ()),
+                 (b.solidity, ("sol_raw", "sol_records"), ()),
+                 (lambda: b.pieces(T.PIECES_TRIM, soft_mask=True), ("mask_case",), ("piece_count", "piece_pack")),
+                 (b.edits, (), ("edit_align", "edit_pack")),
+                 (b.support, ("support",), ()),
+                 (b.strand, ("vote",), ())]
+        seen = {}
+        assert report_times(ctx) == dict.fromkeys(report_times(ctx), 0.0)
+        for i, (call, positive, not_negative) in enumerate(steps):
+            call()
+            now = report_times(ctx)
+            print("step", i, {k: now[k] for k in positive + not_negative})
+            for name in positive:
+                assert now[name] > 0, (i, name, now[name])
+            for name in not_negative:
+                assert now[name] >= 0, (i, name, now[name])
+            for name, v in now.items():
+                if name not in positive + not_negative:
+                    assert v == seen.get(name, 0.0), (i, name, v, seen.get(name, 0.0))
+            seen.update((name, now[name]) for name in positive + not_negative)
+        fresh = ctx.batch(*packed)          # not corrected, on a context whose last solidity had records
+        try:
+            fresh.solidity()
+            assert ctx.solidity_timing()[0] > 0 and ctx.solidity_timing()[1] == 0.0
+        finally:
+            fresh.close()
+    finally:
+        b.close()
+        ctx.close()
+    for first in ("solidity", "correct"):   # auto strand, no strand(): the vote runs inside the call and is timed by it
+        ctx = T.Context(table, p, 0)
+        ctx.auto_strand(True)
+        b = ctx.batch(*packed)
+        try:
+            assert ctx.strand_timing() == 0.0
+            getattr(b, first)()
+            print(first, "vote", ctx.strand_timing())
+            assert ctx.strand_timing() > 0, first
+            if first == "solidity":
+                assert ctx.solidity_timing()[1] == 0.0
+        finally:
+            b.close()
+            ctx.close()
+
+
 # ---------------------------------------------------------------- 2. the buffers a batch keeps or grows
 def same_pieces(got, want, what):
     for name, g, w in zip(("bytes", "piece offsets", "pieces", "read offsets"), got, want):

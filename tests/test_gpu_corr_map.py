@@ -1,6 +1,7 @@
 """The correction map on the device (docs/correction_map.md; k_search's leave_outcome, k_pack_map, k_mask_case) against
 the map rebuilt from the oracle's trace (tests/corr_map_ref.py).  Every map-on run is also held against a map-off run of
 the same batch: same records, offsets, statuses and work counters."""
+import ctypes as C
 import os
 import random
 import subprocess
@@ -195,6 +196,48 @@ def test_map_calls_report_capacity_and_state():
     finally:
         b.close()
         ctx.record_map(False)
+
+
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_record_calls_report_capacity_and_leave_the_buffer(where):
+    """talc_batch_fetch_corrected / talc_batch_copy_corrected_device with room for one byte less than the records take:
+    TALC_ERR_CAPACITY naming the total, offsets and statuses filled as by a full call, not a byte of the buffer written."""
+    s = M.map_set("default")
+    ctx = ctx_of(s)
+    n = 20
+    bases, offs = PU.pack_reads(s.reads[:n])
+    L = T.lib()
+    b = ctx.batch(bases, offs)
+    hip = dev = None
+    try:
+        b.correct()
+        want, woo, wst = b.fetch_corrected()
+        total = int(woo[n])
+        assert total == b.corrected_bytes > 1
+        oo, st = np.zeros(n + 1, dtype=np.uint64), np.full(n, -1, dtype=np.int32)
+        buf = np.full(total, 0xEE, dtype=np.uint8)
+        if where == "host":
+            call, ptr, read = L.talc_batch_fetch_corrected, buf.ctypes.data, lambda: buf
+        else:   # a device buffer of the test's own, filled with the same sentinel
+            hip, dev = PU._hip(), C.c_void_p()
+            assert hip.hipMalloc(C.byref(dev), total) == 0
+            assert hip.hipMemcpy(dev, buf.ctypes.data, total, 1) == 0      # (1: host to device)
+
+            def read():
+                back = np.zeros(total, dtype=np.uint8)
+                assert hip.hipMemcpy(back.ctypes.data, dev, total, 2) == 0     # (2: device to host)
+                return back
+            call, ptr = L.talc_batch_copy_corrected_device, dev
+        assert call(ctx._h, b._h, ptr, total - 1, oo.ctypes.data, st.ctypes.data) == ERR_CAPACITY
+        assert str(total).encode() in L.talc_last_error()
+        assert np.array_equal(oo, woo) and np.array_equal(st, wst)
+        assert (read() == 0xEE).all()
+        assert call(ctx._h, b._h, ptr, total, None, None) == 0
+        assert np.array_equal(read(), want)
+    finally:
+        if dev:
+            hip.hipFree(dev)
+        b.close()
 
 
 def test_one_context_with_the_map_off_on_and_off_again():
