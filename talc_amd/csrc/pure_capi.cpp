@@ -118,6 +118,27 @@ int pure_edit_plan(const uint32_t* n, const uint32_t* m, uint32_t count, uint64_
   *most = plan.mostWords;
   return (int)plan.roundEnd.size();
 }
+// walk_repeat_possible (talc_pure.h) beside the comparison it stands for, on n cases of K + TALC_WALK_LEVELS bases each
+// (codes 0..3, growth order: the tip oldest base first, then the bases of levels 0, 1, ...).  pair[c]: bit p is set when
+// two of the record's k-mers p levels apart are equal, compared base by base on the array; pred[c]: bit p is the
+// predicate for period p on the tip packed as a walk in that direction holds it.
+void pure_walk_repeat_check(const uint8_t* g, uint64_t n, uint32_t K, int dir_right, uint32_t* pair, uint32_t* pred) {
+  const int L = TALC_WALK_LEVELS;
+  for (uint64_t c = 0; c < n; ++c) {
+    const uint8_t* G = g + c * (K + L);
+    uint32_t pm = 0;
+    for (int i = 0; i < L; ++i)            // level i's k-mer is G[i+1 .. i+K]
+      for (int j = i + 1; j < L; ++j)
+        if (std::equal(G + i + 1, G + i + 1 + K, G + j + 1)) pm |= 1u << (j - i);
+    uint64_t kmer = 0;                     // RIGHT: the oldest base on top; LEFT: the newest
+    for (uint32_t t = 0; t < K; ++t) kmer |= (uint64_t)G[t] << (dir_right ? 2 * (K - 1 - t) : 2 * t);
+    uint32_t qm = 0;
+    for (int p = 1; p < L; ++p)
+      if (walk_repeat_possible(kmer, K, (uint32_t)p, dir_right != 0)) qm |= 1u << p;
+    pair[c] = pm; pred[c] = qm;
+  }
+}
+
 uint64_t pure_edit_scratch_words(uint32_t n, uint32_t m) { return edit_scratch_words(n, m); }
 int pure_edit_in_lds(uint32_t n, uint32_t m) { return edit_in_lds(n, m) ? 1 : 0; }
 }  // extern "C"

@@ -89,12 +89,12 @@ static const uint32_t kCntWaveLog = 128, kCntMaxWaves = 8192, kCounterWords = kC
 
 enum { PF_PROBE = 0, PF_CHILD, PF_AIMS, PF_CYCLE, PF_FFWD, PF_SCOREBR, PF_GARDEN, PF_EVALFULL, PF_XDROP, PF_EXTNW,
        PF_EDGEMISC, PF_ANCHORS, PF_ASSEMBLE, PF_STEPB, PF_STEPE, PF_SRCHB, PF_SRCHE, PF_PROLOG, PF_INITTR, PF_TOTAL, PF_NCALLS, PF_NSTEPS,
-       PF_FFLOAD, PF_FFREC, PF_FFFLUSH, PF_FFENTRY, PF_NRECS, PF_RD0, PF_RD1, PF_RD2, PF_RD3, PF_RD4, PF_RD5, PF_RDMAX,
+       PF_FFLOAD, PF_FFREC, PF_FFFLUSH, PF_FFENTRY, PF_NRECS, PF_NDUP, PF_RD0, PF_RD1, PF_RD2, PF_RD3, PF_RD4, PF_RD5, PF_RDMAX,
        PF_XSTAGE, PF_XLEV, PF_XSEL, PF_REFB, PF_RESULT, PF_CYQ, PF_CYX, PF_CYHIT, PF_CYFILL,
        PF_SB11, PF_SB12, PF_SB21, PF_SB10, PF_SBOTHER, PF_SEGEN, PF_XCALLS, PF_XNLEV, PF_FSFORK, PF_FSDEAD, PF_FSFILT, PF_FSLIM, PF_FK1, PF_FK2, PF_FKBAIL, PF_FORK, PF_ANCCALLS, PF_ANCITER, PF_TPUB, PF_TOWN, PF_TSTOLEN, PF_TWAIT, PF_TRUN, PF_EA0, PF_EA1, PF_EA2, PF_EA3, PF_EA4, PF_EASUM3, PF_EASUM4, PF_RANCH, PF_RANCHMAX, PF_RBR, PF_RBRMAX, PF_EDGELANE, PF_N };
 #define TALC_PF_NAMES {"probe", "child", "aims", "cycle", "ffwd", "scorebr", "garden", "evalfull", "xdrop", "extnw", "edgemisc", \
                        "anchors", "assemble", "stepb*", "stepe*", "srchb*", "srche*", "prolog", "inittr", "total", "#ffcalls", "#ffsteps", \
-                       "ff.load", "ff.record", "ff.flush", "ff.entry", "#ffrecords", "#reads<0.25ms", "#reads<1ms", "#reads<4ms", \
+                       "ff.load", "ff.record", "ff.flush", "ff.entry", "#ffrecords", "#ffdup chain", "#reads<0.25ms", "#reads<1ms", "#reads<4ms", \
                        "#reads<16ms", "#reads<64ms", "#reads>=64ms", "maxread(10ns)", "x.stage", "x.levels", "x.select", "b.ref", "b.result", \
                        "#cyc.query", "#cyc.exact", "#cyc.found", "cyc.fill%sum", \
                        "#stepb 1->1", "#stepb 1->2", "#stepb 2->1", "#stepb 1->0", "#stepb other", "#stepe generic", "#xdrop calls", "#xdrop levels", \
@@ -2692,9 +2692,12 @@ TALC_D int fast_forward_dir(int len_, uint32_t& stepCounter_, uint32_t PATH_MAXL
 // together, one level per lane: lane j < 12 loads level j (lanes 12, 13 the key), the lanes test "exactly one successor"
 // and build their k-mers from the prefix of the levels' bases, hash them, query the search's filter (LDS) — a
 // ballot gives the number of steps that can be committed, and those lanes insert their k-mers, store their bases
-// and record their counts.  One dependent memory access and ~130 instructions per record instead of per step.
+// and record their counts.  One dependent memory access and 56 vector instructions per record (gfx950, counted from the
+// end of the probe loop to the commit on the path without an aim; 85 before the test below) instead of per step.
 // A k-mer that repeats WITHIN a record (a cycle of period <= 11) would not be seen by a query that precedes the
-// record's inserts: lanes compare their hashes with the lower lanes' (equal hash = possible cycle = stop there).
+// record's inserts: lanes compare their hashes with the lower lanes' (equal hash = possible cycle = stop there) — in the
+// records where walk_repeat_possible (talc_pure.h) finds the tip periodic enough for such a repeat to exist, one in
+// 25 000 on the flagship workload; everywhere else no two of the record's k-mers can be equal and the chain is skipped.
 template <int P>
 TALC_D uint32_t dpp_row_shr(uint32_t v, uint32_t old) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x110 + P, 0xF, 0xF, false);
@@ -2705,7 +2708,8 @@ TALC_D uint32_t dpp_row_shr(uint32_t v, uint32_t old) {
 // here (no record, a first level that is not "single", a filter hit on the first level).  nOK: the plain steps among them;
 // aimIdx >= 0: the last step taken reached that aim (bridges; nAims == 0 never looks).  `also(position, base)` is run by
 // each committing lane next to its store into the Trail's buffer.
-struct WalkLanes { uint32_t laneOff, laneShift, laneSingle; int lj; };                       // per-lane constants
+// per-lane constants (repShift: 2 x the period the lane tests for a cycle inside a record, lanes 1..11 of the first row)
+struct WalkLanes { uint32_t laneOff, laneShift, laneSingle, repShift; int lj; };
 struct WalkTip { uint64_t kmer, key; uint32_t hh, cnt; uint32_t ePre; bool havePre; int done, flushed; };   // (ePre: per lane)
 template <bool dirRight, bool WIDEF, class Also>
 TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t TALC_AS1* wtab, uint64_t cap, uint32_t K, gu8 seq, int len0,
@@ -2720,6 +2724,11 @@ TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t
   nOK = 0; aimIdx = -1;
     PROF_BEGIN();
     uint64_t slot = ((uint64_t)hh * (uint64_t)(uint32_t)cap) >> 32;
+    // Can two k-mers of this record be equal?  Lane p = 1..11 asks walk_repeat_possible (talc_pure.h) about period p on the
+    // tip the record starts from: a handful of instructions on a wave-uniform k-mer, no need of the record itself (so
+    // they run while its load is under way), and on all but one record in tens of thousands no lane says yes.  (Lane 0's
+    // shift is 0 and the lanes from 12 on repeat lane 11: masked out of the ballot.)
+    const unsigned long long mayRepeat = ballot64(walk_repeat_possible_shift(kmer, K, WL.repShift, dirRight)) & 0xFFEull;
     uint32_t e = havePre ? ePre : wtab[slot * 8 + laneOff];
     havePre = false;
     bool found = true;
@@ -2766,32 +2775,41 @@ TALC_D int walk_record(const WalkLanes& WL, WalkTip& W, int room, const uint32_t
       const uint64_t slotN = ((uint64_t)(uint32_t)lane_get((int)hv, TALC_WALK_LEVELS - 1) * (uint64_t)(uint32_t)cap) >> 32;
       ePre = wtab[slotN * 8 + laneOff];
     }
-    // possible cycle inside the record: the same hash on a lower lane
-    // (gfx950 has no DPP form of the vector compares — "dpp variant of this instruction is not supported" — so each
-    //  distance stays a copy, a DPP move and a compare)
-    bool dup = dpp_row_shr<1>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<2>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<3>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<4>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<5>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<6>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<7>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<8>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<9>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<10>(hv, ~hv) == hv;
-    dup |= dpp_row_shr<11>(hv, ~hv) == hv;
-    static_assert(TALC_WALK_LEVELS == 12, "the lane roles above are written for 12 levels (+ 2 key lanes) in a 16-lane row");
-    // aim / cycle query against the search's filter (init_first_trail entered the aims)
+    // aim / cycle query against the search's filter (init_first_trail entered the aims): its word is asked for here, so
+    // that the LDS round trip runs under what follows
     const int bwi = (int)(hv >> 25);     // bloom_word / bloom_mask on the upper half of the hash
     const unsigned long long bm = (1ull << ((hv >> 19) & 63u)) | (1ull << ((hv >> 13) & 63u));
-    bool seen = (g_bloom[bwi] & bm) == bm;
+    const unsigned long long bv = g_bloom[bwi];
+    // possible cycle inside the record: the same hash on a lower lane — looked for only where two of the record's k-mers
+    // CAN be equal (mayRepeat, above), which is all but never; dropping the chain elsewhere drops only stops on equal
+    // hashes of different k-mers, which the generic step would have walked through.
+    // (gfx950 has no DPP form of the vector compares — "dpp variant of this instruction is not supported" — so each
+    //  distance of the chain stays a copy, a DPP move and a compare: 33 vector instructions)
+    unsigned long long dupMask = 0ull;
+    if (__builtin_expect(mayRepeat != 0ull, 0)) {
+      PROF_COUNT(PF_NDUP, 1);
+      bool dup = dpp_row_shr<1>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<2>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<3>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<4>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<5>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<6>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<7>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<8>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<9>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<10>(hv, ~hv) == hv;
+      dup |= dpp_row_shr<11>(hv, ~hv) == hv;
+      dupMask = ballot64(dup);
+    }
+    static_assert(TALC_WALK_LEVELS == 12, "the lane roles above are written for 12 levels (+ 2 key lanes) in a 16-lane row");
+    bool seen = (bv & bm) == bm;
     unsigned long long* const wideW = WIDEF ? wideBloom + wide_word(hv, wideMask) : nullptr;
     const unsigned long long bmW = WIDEF ? wide_bits(hv) : 0ull;
     if (WIDEF) {   // a long search's filter (HBM): only the levels the LDS filter cannot clear ask it
       const bool ask = seen && (l < TALC_WALK_LEVELS);
       if (ballot64(ask) != 0ull) { const unsigned long long bvW = ask ? wide_load(wideW) : 0ull; seen = ask && ((bvW & bmW) == bmW); }
     }
-    const unsigned long long hitMask = ballot64(seen || dup) | (1ull << TALC_WALK_LEVELS);
+    const unsigned long long hitMask = ballot64(seen) | dupMask | (1ull << TALC_WALK_LEVELS);   // (lane masks, OR-ed as scalars)
     const int hitLevel = __builtin_ctzll(hitMask);
     // a filter hit on a level that could otherwise be taken: if its k-mer is an aim, that step is a plain step that
     // also records the bridge (oneMoreStep, Explorer.cpp:566-583) — taken here as well; anything else (a possible
@@ -2897,6 +2915,7 @@ TALC_D int fast_forward_walk(int len_, uint32_t& stepCounter_, uint32_t PATH_MAX
   WL.laneShift = (l < TALC_WALK_LEVELS && (l & 1)) ? 16u : 0u;
   WL.lj = min(l, TALC_WALK_LEVELS - 1);                // shift amounts stay in range on the idle lanes
   WL.laneSingle = (l < TALC_WALK_LEVELS) ? kWalkSingle : 0u;
+  WL.repShift = 2u * (uint32_t)WL.lj;
   W.key = dirRight ? (kmer & m1) : (kmer >> 2);
   W.hh = (uint32_t)(table_hash(W.key) >> 32);
   PROF_END2(PF_FFENTRY);
@@ -3044,6 +3063,7 @@ TALC_D EdgeLaneRet edge_lane_dir(int len_, uint32_t stepCounter_, uint32_t PATH_
   WL.laneShift = (l < TALC_WALK_LEVELS && (l & 1)) ? 16u : 0u;
   WL.lj = min(l, TALC_WALK_LEVELS - 1);
   WL.laneSingle = (l < TALC_WALK_LEVELS) ? kWalkSingle : 0u;
+  WL.repShift = 2u * (uint32_t)WL.lj;
   W.key = dirRight ? (kmer & m1) : (kmer >> 2);
   W.hh = (uint32_t)(table_hash(W.key) >> 32);
   W.ePre = 0;

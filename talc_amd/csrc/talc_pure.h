@@ -339,6 +339,41 @@ TALC_HD uint32_t order_key_bucket(uint32_t costEst, uint32_t costGap, uint32_t g
   return nBuckets - 2 - (k < nBuckets - 2 ? k : nBuckets - 2);
 }
 
+// ------------------------------------------------------------------ cycles inside one walk record
+// A walk record (talc_common.h: WalkEntry) appends up to L = TALC_WALK_LEVELS bases to a Trail at once, and the filter
+// is asked about all of its k-mers before any of them is entered: a k-mer that equals a LOWER LEVEL's k-mer of the same
+// record is something only the record itself can notice (walk_record's hash chain).  This is the test for whether that
+// can happen at all, from the tip the record starts at.
+//
+// Growth order: G[e] is the newest base, the tip is G[e-K+1 .. e], level j (0 <= j < L) appends G[e+j+1] and its k-mer
+// is T_j = G[e+j+2-K .. e+j+1].  For levels i < j with p = j - i (1 <= p <= L-1):
+//   T_i == T_j  <=>  G[t] == G[t-p] for every t in [e+j+2-K, e+j+1]                       (K equalities, one per base)
+// Of those, keep the t whose two bases both lie in the tip, where they are known before the record is read:
+//   t <= e, and t - p >= e-K+1.  Since j <= L-1 the window starts at e+j+2-K <= e+L+1-K, so it contains every t in
+//   [e+L+1-K, e] — the newest w = K - L bases of the tip, whatever i and j are.  Their partners t - p are at least
+//   e+L+1-K-p >= e+2-K > e-K+1 for p <= L-1: inside the tip as well, which is why the periods stop at L-1 = 11.
+// So a pair of equal k-mers p levels apart needs
+//   G[t] == G[t-p] for every t in [e+L+1-K, e]                                            (w equalities, all in the tip)
+// and walk_repeat_possible(tip, K, p) is exactly that; necessary for every 0 <= i < j <= L-1 with j - i = p, not
+// sufficient (the new bases must continue the period).  For w <= 0 (K <= L) nothing of the window is in the tip: true.
+// On random sequence it holds for some p with probability (L-1) x 4^-w: 4.2e-5 at K = 21.
+//
+// Packed (2 bits per base, K <= 31), with s = e - t in [0, w-1] the age of the base:
+//   RIGHT: a step is ((kmer << 2) | base) & kmask, so base G[e-s] sits at bits 2s and its partner G[e-s-p] at bits
+//          2(s+p): (kmer ^ (kmer >> 2p)) must be 0 in the low 2w bits.
+//   LEFT:  a step is (base << 2(K-1)) | (kmer >> 2), so G[e-s] sits at bits 2(K-1-s) and its partner at 2(K-1-s-p):
+//          (kmer ^ (kmer << 2p)) must be 0 in bits 2(K-w) = 2L .. 2K-1.
+// (walk_record keeps 2p, the shift, as a lane constant: the form that takes it)
+TALC_HD bool walk_repeat_possible_shift(uint64_t kmer, uint32_t K, uint32_t shift2p, bool dirRight) {
+  const uint32_t w = K > (uint32_t)TALC_WALK_LEVELS ? K - (uint32_t)TALC_WALK_LEVELS : 0u;   // (w = 0: both masks are empty)
+  const uint64_t kmask = (1ULL << (2 * K)) - 1;
+  if (dirRight) return ((kmer ^ (kmer >> shift2p)) & ((1ULL << (2 * w)) - 1)) == 0;
+  return ((kmer ^ (kmer << shift2p)) & kmask & ~((1ULL << (2 * TALC_WALK_LEVELS)) - 1)) == 0;
+}
+TALC_HD bool walk_repeat_possible(uint64_t kmer, uint32_t K, uint32_t p, bool dirRight) {
+  return walk_repeat_possible_shift(kmer, K, 2 * p, dirRight);
+}
+
 // ------------------------------------------------------------------ k-mer spectrum (docs/kmer_spectrum.md)
 // The solidity threshold a count spectrum suggests: its first local minimum.  hist[c], 1 <= c <= high, is the number of
 // distinct k-mers seen c times; hist[high + 1] gathers every larger count and is never read as a neighbour.  With
