@@ -617,6 +617,46 @@ int talc_batch_fetch_support(talc_ctx* c, talc_batch* b, uint8_t* out, uint64_t 
 /* Measurement: device time (ms) of the k_base_support launch of the context's last talc_batch_support. */
 int talc_ctx_get_support_timing(const talc_ctx* c, float* support_ms);
 
+/* Long-read end clean-up (docs/read_ends.md): cDNA primers and poly-A/T tails at the two ends of every read, found on the
+ * device from the batch's raw bytes — as the caller gave them, before any orientation (-rev, auto strand).  A byte is
+ * upper-cased; a byte outside ACGT is its own letter: it matches no adapter letter and is neither A nor T.
+ * Head rule H(S) for a read S of L bytes:
+ *   adapter  T = S[0, min(L, window)).  For adapter a of m letters, D_a[e], 1 <= e <= |T|, is the smallest unit-cost edit
+ *            distance between the adapter and any substring of T that ends at e (Sellers: top row 0, first column i).
+ *            k_a = floor(max_error_pct * m / 100); e is accepted when D_a[e] <= k_a; the adapter's match is the accepted e
+ *            with the smallest D_a[e], the largest e among ties; the head's adapter is the one whose match has the largest e,
+ *            the lowest index among ties.  adapter_len = e, adapter = index + 1, adapter_err = D; all 0 without a match.
+ *   poly-T   U = S[adapter_len, min(L, adapter_len + window)); score(j) = sum over i < j of (+1 if U[i] is 'T', else -2);
+ *            p = the smallest j that maximises score; poly_len = p when poly_min > 0 and p >= poly_min, else 0.
+ * The tail is H(revcomp(S)): an adapter's reverse complement near the end, and a poly-A run.  Each end is evaluated on the
+ * whole read; head = head_adapter_len + head_poly_len, tail likewise; kept_start = head,
+ * kept_len = L - head - min(tail, L - head).  orient = +1 when only the tail has a poly run, -1 when only the head has. */
+typedef struct talc_end_row {
+  uint32_t head_adapter_len, head_poly_len, tail_adapter_len, tail_poly_len;
+  uint8_t  head_adapter, head_adapter_err, tail_adapter, tail_adapter_err;  /* adapter: 0 none, else 1-based */
+  uint32_t kept_start, kept_len;
+  int32_t  orient;
+} talc_end_row;
+/* adapters: NUL-terminated, comma-separated, NULL or "" for none; at most 4, each 12..64 letters of ACGTacgt.
+ * max_error_pct 0..30; poly_min 0 (off) or 8..window; window 0 (: 512) or 32..4096.  TALC_ERR_INVALID names the bad value.
+ * No adapters and poly_min 0 switches the clean-up off: nothing of it exists then. */
+int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct, uint32_t poly_min,
+                      uint32_t window /* 0: 512 */);
+/* The scan (k_read_ends) on the batch's raw bytes, with the context's setting.  On a batch made by
+ * talc_batch_create_clipped the rows are those of the scan that made it — of the original reads — and nothing is launched.
+ * TALC_ERR_STATE when the clean-up is off (and the batch holds no rows of its making). */
+int talc_batch_ends(talc_ctx* c, talc_batch* b);
+/* rows: n_reads rows.  TALC_ERR_STATE when no scan has run on b. */
+int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows);
+/* talc_batch_create of the kept intervals: the raw bytes go to the device once, the scan runs on them, and the kept
+ * intervals are gathered on the device into the batch's text (k_clip_gather).  From then on every call on the batch returns,
+ * byte for byte, what it returns on talc_batch_create of the reads clipped on the host — under -rev and auto strand too.
+ * TALC_ERR_STATE when the clean-up is off. */
+int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads,
+                              talc_batch** out);
+/* Measurement: device time (ms) of the context's last k_read_ends and k_clip_gather.  Either pointer may be NULL. */
+int talc_ctx_get_ends_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

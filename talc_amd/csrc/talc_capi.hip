@@ -22,6 +22,7 @@
 #include "talc_kernels_build.h"
 #include "talc_kernels_count.h"
 #include "talc_kernels_edits.h"
+#include "talc_kernels_ends.h"
 #include "talc_kernels_pieces.h"
 #include "talc_kernels_probe.h"
 #include "talc_kernels_search.h"
@@ -166,6 +167,7 @@ enum CtxSpan {
   // the edit scripts (run_edits): the first k_edit_align rounds, k_edit_count, the second rounds, k_edit_pack
   kSpanEditAlignA, kSpanEditCount, kSpanEditAlignB, kSpanEditPack,
   kSpanSupport,                          // k_base_support
+  kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_clip_gather
   kSpanCount
 };
 
@@ -182,6 +184,9 @@ struct talc_ctx {
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
   bool autoStrand = false;   // talc_ctx_set_auto_strand: every read in the orientation k_strand_vote chooses
+  bool endsOn = false;       // talc_ctx_set_ends (docs/read_ends.md): nothing of it exists while it is off
+  uint32_t endsGen = 0;      // ... counts the settings: a plain batch's rows are those of the setting they were made under
+  EndsParams ends;           // ... as k_read_ends takes it
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -207,6 +212,7 @@ struct EditOut {
 // What a batch holds and what drops it.  A result is valid while its flag is set; "->" reads "is made from", and
 // what drops a result drops everything made from it:
 //   voted                                  from the raw bytes; never dropped
+//   ended                                  from the raw bytes (of a clipped batch: from those it was made from); never dropped
 //   encoded(encodedAuto) -> covered
 //   encoded -> solidity (raw rows), supported (RAW)
 //   encoded -> structured            (test hook; k_search consumes the region lists)
@@ -214,6 +220,8 @@ struct EditOut {
 // A call that makes one result clears that result's flag first and sets it when everything has succeeded.
 struct BatchHolds {
   bool voted = false;         // d_strand, d_strand_flag: k_strand_vote runs once per batch
+  bool ended = false;         // d_ends: k_read_ends under the context's setting number endsGen
+  bool clipped = false;       // ... and the batch was made from those rows (talc_batch_create_clipped): they are never made again
   bool encoded = false;       // d_codes
   bool encodedAuto = false;   // ... made with the vote's flags: k_pack, k_pack_map, k_solidity and k_base_support then take them too
   bool covered = false;       // d_cov, d_covw, d_nin
@@ -255,6 +263,8 @@ struct talc_batch {
   std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte (talc_batch_pieces)
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  CachedBuf<EndRow> d_ends;           // one row per read (k_read_ends)
+  uint32_t endsGen = 0;               // the setting those rows were made under
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
   CachedBuf<uint8_t> d_strand_flag;   // ... and its choice as one byte per read: what the four kernels that orient a read take
   const uint8_t* rev_flags() const { return holds.encodedAuto ? d_strand_flag.get() : nullptr; }
@@ -298,6 +308,7 @@ static_assert(sizeof(OutPiece) == sizeof(talc_piece) && sizeof(talc_piece) == 12
 static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) == 24 && sizeof(EditPart) == 32 && sizeof(EditTask) == 16, "k_edit_count writes talc_edit_row records");
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
+static_assert(sizeof(EndRow) == sizeof(talc_end_row) && sizeof(talc_end_row) == 32, "k_read_ends writes talc_end_row records");
 
 // What an entry point that takes a context and a batch checks first: they belong together and the `rest` of its arguments is there
 // (`msg`: the call's own wording).  enter() makes the context's device current as well; belong() where a state check comes before that.
@@ -1103,10 +1114,11 @@ int talc_ctx_get_timing(const talc_ctx* c, talc_timing* out) {
 // ------------------------------------------------------------------ batch
 void talc_batch_destroy(talc_batch* b) { delete b; }
 
-int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
-  if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(c->device));
-  auto b = std::make_unique<talc_batch>();
+// The batch laid out on the host from its reads' offsets, its device buffers made and the layout sent; fill(stream) puts the
+// n_bases raw bytes into b->d_raw, ordered on that stream behind the upload of the offsets.  Returns once the stream is idle.
+extern "C++" {   // (a template has no C linkage)
+template <class Fill>
+static int batch_build(talc_ctx* c, talc_batch* b, const uint64_t* offsets, uint32_t n_reads, Fill fill) {
   b->ctx = c; b->n_reads = n_reads;
   b->h_state.use_pool(&c->host_pool); b->h_dense_off.use_pool(&c->host_pool); b->h_seg_off.use_pool(&c->host_pool);
   b->h_offsets.assign(offsets, offsets + n_reads + 1);
@@ -1136,8 +1148,8 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   HIPCHK(b->d_raw.alloc(c->cache, std::max<uint64_t>(b->n_bases, 1)));
   // (+ 64: a search may read a stretch of a read in place, and the wave routines fetch whole 8- and 16-byte words)
   HIPCHK(b->d_codes.alloc(c->cache, std::max<uint64_t>(b->n_bases, 1) + 64));
-  if (b->n_bases) HIPCHK(hipMemcpyAsync(b->d_raw.get(), bases, b->n_bases, hipMemcpyHostToDevice, s));
   if ((rc = up(c, b->d_offsets, b->h_offsets, s))) return rc;
+  if ((rc = fill(s))) return rc;
   if ((rc = up(c, b->d_koff, b->h_koff, s))) return rc;
   if ((rc = up(c, b->d_regoff, b->h_regoff, s))) return rc;
   if ((rc = up(c, b->d_outoff, b->h_outoff, s))) return rc;
@@ -1154,6 +1166,20 @@ int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, u
   HIPCHK(b->d_regions.alloc(c->cache, std::max<uint64_t>(ro, 1) * 3));
   HIPCHK(b->d_out.alloc(c->cache, std::max<uint64_t>(oo, 1)));
   HIPCHK(hipStreamSynchronize(s));
+  return TALC_OK;
+}
+}  // extern "C++"
+
+int talc_batch_create(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
+  if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(c->device));
+  auto b = std::make_unique<talc_batch>();
+  talc_batch* const bp = b.get();
+  const int rc = batch_build(c, bp, offsets, n_reads, [&](hipStream_t s) {
+    if (bp->n_bases) HIPCHK(hipMemcpyAsync(bp->d_raw.get(), bases, bp->n_bases, hipMemcpyHostToDevice, s));
+    return (int)TALC_OK;
+  });
+  if (rc) return rc;
   *out = b.release();
   return TALC_OK;
 }
@@ -1322,5 +1348,6 @@ extern "C" {
 #include "talc_capi_correct.inc"
 #include "talc_capi_edits.inc"
 #include "talc_capi_support.inc"
+#include "talc_capi_ends.inc"
 
 }  // extern "C"

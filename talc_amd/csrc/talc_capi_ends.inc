@@ -1,0 +1,122 @@
+// talc_capi_ends.inc — host side of the long-read end clean-up (docs/read_ends.md, talc_kernels_ends.h); included by
+// talc_capi.hip inside its extern "C" block, after talc_capi_support.inc.
+
+int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct, uint32_t poly_min, uint32_t window) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (max_error_pct > 30) return fail(TALC_ERR_INVALID, "max_error_pct=%u: at most 30", max_error_pct);
+  if (!window) window = 512;
+  if (window < 32 || window > ENDS_MAX_WINDOW) return fail(TALC_ERR_INVALID, "window=%u: 32 .. %u (0: 512)", window, (uint32_t)ENDS_MAX_WINDOW);
+  if (poly_min && (poly_min < 8 || poly_min > window)) return fail(TALC_ERR_INVALID, "poly_min=%u: 0 (off) or 8 .. window (%u)", poly_min, window);
+  EndsParams P;
+  memset(&P, 0, sizeof P);
+  P.polyMin = poly_min; P.window = window;
+  for (const char* p = adapters && *adapters ? adapters : nullptr; p;) {
+    const char* e = strchr(p, ',');
+    const size_t m = e ? (size_t)(e - p) : strlen(p);
+    if (P.nAdapters == ENDS_MAX_ADAPTERS) return fail(TALC_ERR_INVALID, "adapters: more than %u", (uint32_t)ENDS_MAX_ADAPTERS);
+    if (m < 12 || m > 64) return fail(TALC_ERR_INVALID, "adapters: adapter %u has %llu letters: 12 .. 64", P.nAdapters + 1, (unsigned long long)m);
+    for (size_t i = 0; i < m; ++i) {
+      const uint8_t code = ascii_to_code((uint8_t)p[i]);
+      if (code >= 4) return fail(TALC_ERR_INVALID, "adapters: adapter %u has a letter that is not one of ACGTacgt", P.nAdapters + 1);
+      P.peq[P.nAdapters][code] |= 1ull << i;
+    }
+    P.m[P.nAdapters] = (uint32_t)m;
+    P.k[P.nAdapters] = (uint32_t)(max_error_pct * m / 100);
+    ++P.nAdapters;
+    p = e ? e + 1 : nullptr;
+  }
+  c->ends = P;
+  c->endsOn = P.nAdapters || poly_min;
+  ++c->endsGen;
+  return TALC_OK;
+}
+
+// k_read_ends over n_reads reads of `raw` at `off` (device), under the context's setting, into `rows`: kSpanEndsScan
+static int launch_ends(talc_ctx* c, const uint8_t* raw, const uint64_t* off, uint32_t n_reads, EndRow* rows) {
+  return c->span[kSpanEndsScan].around(c->stream, [&] {
+    if (n_reads) hipLaunchKernelGGL(k_read_ends, dim3(n_reads), dim3(64), 0, c->stream, raw, off, n_reads, c->ends, rows);
+  });
+}
+
+int talc_batch_ends(talc_ctx* c, talc_batch* b) {
+  int rc;
+  if ((rc = belong(c, b, "bad context/batch"))) return rc;
+  const bool made = b->holds.ended && (b->holds.clipped || (c->endsOn && b->endsGen == c->endsGen));
+  if (!made && !c->endsOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!made) {
+    b->holds.ended = false;
+    HIPCHK(b->d_ends.ensure(c->cache, b->n_reads));
+    if ((rc = launch_ends(c, b->d_raw.get(), b->d_offsets.get(), b->n_reads, b->d_ends.get()))) return rc;
+    b->endsGen = c->endsGen;
+    b->holds.ended = true;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return read_spans(c);
+}
+
+int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows) {
+  if (int rc = belong(c, b, "bad context/batch")) return rc;
+  if (!b->holds.ended) return fail(TALC_ERR_STATE, "no end scan has run on this batch (talc_batch_ends, talc_batch_create_clipped)");
+  HIPCHK(hipSetDevice(c->device));
+  if (rows && b->n_reads) HIPCHK(hipMemcpyAsync(rows, b->d_ends.get(), (size_t)b->n_reads * sizeof(talc_end_row), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return read_spans(c);
+}
+
+// The raw bytes go up once, into a staging buffer of the context's cache; the scan's rows come to the host, which lays the
+// batch out from the kept lengths (batch_build, as talc_batch_create); k_clip_gather then fills the batch's text from the
+// staging buffer, device to device.  The staging buffers go back to the cache when the batch stands.
+int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
+  if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
+  if (!c->endsOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");
+  if (offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
+  for (uint32_t r = 0; r < n_reads; ++r) {
+    if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must be non-decreasing");
+    if (offsets[r + 1] - offsets[r] > 0x7fffff00ull) return fail(TALC_ERR_INVALID, "read %u too long", r);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const uint64_t nb = offsets[n_reads];
+  auto b = std::make_unique<talc_batch>();
+  talc_batch* const bp = b.get();
+  bp->ctx = c;
+  CachedBuf<uint8_t> stage;
+  CachedBuf<uint64_t> stageOff;
+  HIPCHK(stage.alloc(c->cache, std::max<uint64_t>(nb, 1)));
+  HIPCHK(stageOff.alloc(c->cache, (uint64_t)n_reads + 1));
+  HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
+  if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  int rc;
+  if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
+  std::vector<EndRow> rows(n_reads);
+  if (n_reads) HIPCHK(hipMemcpyAsync(rows.data(), bp->d_ends.get(), (size_t)n_reads * sizeof(EndRow), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::vector<uint64_t> kept((size_t)n_reads + 1, 0);
+  for (uint32_t r = 0; r < n_reads; ++r) {
+    const uint64_t L = offsets[r + 1] - offsets[r];
+    if ((uint64_t)rows[r].keptStart + rows[r].keptLen > L)
+      return fail(TALC_ERR_DEVICE, "the end scan left read %u an interval beyond its %llu bytes", r, (unsigned long long)L);
+    kept[r + 1] = kept[r] + rows[r].keptLen;
+  }
+  rc = batch_build(c, bp, kept.data(), n_reads, [&](hipStream_t s) {
+    return c->span[kSpanEndsGather].around(s, [&] {
+      if (n_reads)
+        hipLaunchKernelGGL(k_clip_gather, dim3(n_reads), dim3(256), 0, s, stage.get(), stageOff.get(), bp->d_ends.get(), n_reads, bp->d_raw.get(),
+                           bp->d_offsets.get());
+    });
+  });
+  if (rc) return rc;
+  if ((rc = read_spans(c))) return rc;
+  bp->endsGen = c->endsGen;
+  bp->holds.ended = bp->holds.clipped = true;
+  *out = b.release();
+  return TALC_OK;
+}
+
+int talc_ctx_get_ends_timing(const talc_ctx* c, float* scan_ms, float* gather_ms) {
+  if (!c) return fail(TALC_ERR_INVALID, "null context");
+  if (scan_ms) *scan_ms = c->span[kSpanEndsScan].ms;
+  if (gather_ms) *gather_ms = c->span[kSpanEndsGather].ms;
+  return TALC_OK;
+}

@@ -53,6 +53,12 @@
 //   --SRHistoHigh N  with --SRHisto / --AutoMinCount: the largest count with a line of its own (2..16382, default 10000)
 //   --AutoMinCount   with --SRReads: MIN_COUNT is the first local minimum of that spectrum (at least 2; the given --MIN_COUNT
 //                    when the spectrum has none), chosen after counting and used for --SRCountsOut, the table and the correction
+//   --LRAdapter SEQ  (repeatable, up to 4) a primer to look for at both ends of every long read (docs/read_ends.md): within
+//                    --LRAdapterErr PCT (0..30, default 20) per cent of its length in edits, inside the first --LREndWindow N
+//                    (32..4096, default 512) bases, and as its reverse complement inside the last; writes <o>.ends.tsv, one
+//                    line per read in input order, and one summary line on stdout
+//   --LRPolyA N      a poly-T head / poly-A tail of at least N bases (8..LREndWindow; 0: off), behind the primer if there is one
+//   --LRClip         the reads are corrected without the ends found: clipped on the GPU, every output is that of the clipped reads
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -141,6 +147,11 @@ struct Options {
   bool srFilter() const { return srMinQual > 0 || !srAdapters.empty(); }
   bool fastq = false, haveQualRange = false;   // --fastq, --qual-range
   uint32_t qmin = 2, qmax = 40;
+  std::vector<std::string> lrAdapters;      // --LRAdapter, in order
+  uint32_t lrAdapterErr = 20, lrPolyA = 0, lrEndWindow = 512;   // --LRAdapterErr, --LRPolyA (0: off), --LREndWindow
+  bool haveLrAdapterErr = false, haveLrPolyA = false, haveLrEndWindow = false;
+  bool lrClip = false;                      // --LRClip
+  bool lrEnds() const { return !lrAdapters.empty() || lrPolyA > 0; }   // the long-read end clean-up is on
 };
 
 void usage(FILE* f) {
@@ -203,6 +214,15 @@ void usage(FILE* f) {
           "                              also <o>.trim.fq / <o>.split.fq\n"
           "  --qual-range MIN,MAX        with --fastq: the quality of a base no solid k-mer holds and of one all of them hold,\n"
           "                              0 <= MIN <= MAX <= 93, default 2,40\n"
+          "  --LRAdapter TEXT            primer / adapter to look for at both ends of every long read, 12..64 letters of ACGT (repeat\n"
+          "                              for up to 4): found on the GPU within --LREndWindow bases of the head, and as its reverse\n"
+          "                              complement of the tail; writes <o>.ends.tsv (docs/read_ends.md)\n"
+          "  --LRAdapterErr INT          with --LRAdapter: edits allowed in percent of the adapter's length, 0..30, default 20\n"
+          "  --LRPolyA INT               shortest poly-T head / poly-A tail (behind the adapter, if any) to report, 8..LREndWindow;\n"
+          "                              0: off (default)\n"
+          "  --LREndWindow INT           with --LRAdapter / --LRPolyA: bases of each end that are searched, 32..4096, default 512\n"
+          "  --LRClip                    with --LRAdapter / --LRPolyA: correct the reads without the ends found (clipped on the GPU);\n"
+          "                              every output is that of the clipped reads under their names\n"
           "  -h, --help / --version\n");
 }
 
@@ -299,6 +319,29 @@ Options parse(int argc, const char** argv) {
       if (lo != (double)(long long)lo || hi != (double)(long long)hi || lo < 0 || lo > hi || hi > 93) parse_error("value out of range for qual-range: 0 <= MIN <= MAX <= 93");
       o.qmin = (uint32_t)lo; o.qmax = (uint32_t)hi; o.haveQualRange = true;
     }
+    else if (a == "--LRAdapter") {
+      const std::string v = need(i);
+      if (v.size() < 12 || v.size() > 64) parse_error("the given value '" + v + "' cannot be an LRAdapter: 12..64 letters are expected");
+      if (v.find_first_not_of("ACGTacgt") != std::string::npos) parse_error("the given value '" + v + "' cannot be an LRAdapter: it has a letter that is not one of ACGT");
+      if (o.lrAdapters.size() == 4) parse_error("too many --LRAdapter: at most 4");
+      o.lrAdapters.push_back(v);
+    }
+    else if (a == "--LRAdapterErr") {
+      const double v = num(need(i), "LRAdapterErr");
+      if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for LRAdapterErr: 0..30");
+      o.lrAdapterErr = (uint32_t)v; o.haveLrAdapterErr = true;
+    }
+    else if (a == "--LRPolyA") {
+      const double v = num(need(i), "LRPolyA");
+      if (v != (double)(long long)v || v < 0 || v > 4096 || (v > 0 && v < 8)) parse_error("value out of range for LRPolyA: 0 (off) or 8..LREndWindow");
+      o.lrPolyA = (uint32_t)v; o.haveLrPolyA = true;
+    }
+    else if (a == "--LREndWindow") {
+      const double v = num(need(i), "LREndWindow");
+      if (v != (double)(long long)v || v < 32 || v > 4096) parse_error("value out of range for LREndWindow: 32..4096");
+      o.lrEndWindow = (uint32_t)v; o.haveLrEndWindow = true;
+    }
+    else if (a == "--LRClip") o.lrClip = true;
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -329,6 +372,10 @@ Options parse(int argc, const char** argv) {
   if (o.autoStrand && o.p.reverse) parse_error("--auto-strand chooses every read's orientation: it does not go with -rev");
   if (o.bothStrands && o.autoStrand)
     parse_error("--both-strands makes the k-mer table symmetric, so every vote of --auto-strand is a tie: they do not go together");
+  if (o.haveLrAdapterErr && o.lrAdapters.empty()) parse_error("--LRAdapterErr needs --LRAdapter");
+  if (o.haveLrEndWindow && !o.lrEnds()) parse_error("--LREndWindow needs --LRAdapter or --LRPolyA");
+  if (o.lrClip && !o.lrEnds()) parse_error("--LRClip needs --LRAdapter or --LRPolyA");
+  if (o.lrPolyA > o.lrEndWindow) parse_error("value out of range for LRPolyA: " + std::to_string(o.lrPolyA) + " is above LREndWindow " + std::to_string(o.lrEndWindow));
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
 }
@@ -345,6 +392,11 @@ void outputConfig(const Options& o, const std::string& statFile) {
     << "KmerSize=" << o.p.k << "\n"
     << "Junction mode activated? " << (o.useJ ? 1 : 0) << "\n"
     << "queryMode=" << o.queryMode << "\n";
+  for (const std::string& ad : o.lrAdapters) f << "LRAdapter=" << ad << "\n";
+  if (o.haveLrAdapterErr) f << "LRAdapterErr=" << o.lrAdapterErr << "\n";
+  if (o.haveLrPolyA) f << "LRPolyA=" << o.lrPolyA << "\n";
+  if (o.haveLrEndWindow) f << "LREndWindow=" << o.lrEndWindow << "\n";
+  if (o.lrClip) f << "LRClip=1" << "\n";
   if (o.bothStrands) f << "Both strands? 1" << "\n";
   if (o.haveSrMinQual) f << "SRMinQual=" << o.srMinQual << "\n";
   for (const std::string& ad : o.srAdapters) f << "SRAdapter=" << ad << "\n";
@@ -373,11 +425,11 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
         trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv"),
-        fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq") {}
+        fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq"), ends(prefix + ".ends.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -583,6 +635,8 @@ struct Chunk {
   std::string strandText;               // ... and the lines of <o>.strand.tsv
   uint64_t strandSums[2] = {0, 0};      // reads taken forward, reverse
   std::string fqText, trimFqText, splitFqText;   // ... and to <o>.fq, <o>.trim.fq, <o>.split.fq (--fastq)
+  std::string endsText;                 // ... and to <o>.ends.tsv (--LRAdapter, --LRPolyA)
+  uint64_t endSums[4] = {0, 0, 0, 0};   // of the batch: reads, those with an adapter at either end, those with a poly run, bases outside the kept intervals
   // the read was corrected as under -rev: the whole file's -rev, or the read's own vote
   bool reversed(const talc_params& p, size_t r) const { return p.reverse || (!strand.empty() && strand[r].reverse); }
 };
@@ -597,6 +651,26 @@ void formatStrand(Chunk& k) {
     k.strandText += k.ids[r];
     k.strandText.append(num, (size_t)m);
     k.strandSums[w.reverse ? 1 : 0] += 1;
+  }
+}
+
+// the lines of <o>.ends.tsv for one batch, from the scan's rows (k.offsets: the reads as they came)
+const char* const kEndsHeader = "read_name\traw_length\thead_adapter\thead_adapter_len\thead_adapter_err\thead_poly\ttail_adapter\ttail_adapter_len\t"
+                                "tail_adapter_err\ttail_poly\tkept_start\tkept_len\torient\n";
+void formatEnds(Chunk& k, const talc_end_row* rows) {
+  char num[192];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const talc_end_row& w = rows[r];
+    const uint64_t L = k.offsets[r + 1] - k.offsets[r];
+    const int m = snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%d\n", (unsigned long long)L, w.head_adapter, w.head_adapter_len,
+                           w.head_adapter_err, w.head_poly_len, w.tail_adapter, w.tail_adapter_len, w.tail_adapter_err, w.tail_poly_len, w.kept_start, w.kept_len,
+                           w.orient);
+    k.endsText += k.ids[r];
+    k.endsText.append(num, (size_t)m);
+    k.endSums[0] += 1;
+    k.endSums[1] += (w.head_adapter || w.tail_adapter) ? 1 : 0;
+    k.endSums[2] += (w.head_poly_len || w.tail_poly_len) ? 1 : 0;
+    k.endSums[3] += L - w.kept_len;
   }
 }
 
@@ -801,6 +875,7 @@ struct PipelineTotals {
   uint64_t solSums[4] = {0, 0, 0, 0};      // --solidity: the sums of four columns of <o>.solidity.tsv (Chunk::solSums)
   uint64_t pieceSums[4] = {0, 0, 0, 0};    // --trim / --split: trimmed reads, their bases, split pieces, their bases
   uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // --corr-edits: Chunk::editSums
+  uint64_t endSums[4] = {0, 0, 0, 0};          // --LRAdapter / --LRPolyA: Chunk::endSums
   WorkerTally workers;
 };
 
@@ -834,9 +909,9 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf;
     double busy = 0;
-    uint64_t strandSums[2] = {0, 0};
+    uint64_t strandSums[2] = {0, 0}, endSums[4] = {0, 0, 0, 0};
     uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
   };
   bool fail(std::string msg);
@@ -917,6 +992,11 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     if (!wr.wf) return fail("cannot write " + files_.strand);
     wr.wf << kStrandHeader;
   }
+  if (o_.lrEnds()) {
+    wr.xf.open(files_.ends, std::ios_base::trunc);
+    if (!wr.xf) return fail("cannot write " + files_.ends);
+    wr.xf << kEndsHeader;
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -943,8 +1023,9 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.qf.is_open()) wr.qf.close();
   if (wr.tqf.is_open()) wr.tqf.close();
   if (wr.pqf.is_open()) wr.pqf.close();
+  if (wr.xf.is_open()) wr.xf.close();
   for (int i = 0; i < 2; ++i) tot.strandSums[i] = wr.strandSums[i];
-  for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; }
+  for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; tot.endSums[i] = wr.endSums[i]; }
   for (int i = 0; i < 6; ++i) tot.editSums[i] = wr.editSums[i];
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
@@ -1008,6 +1089,11 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
     ctx.reset(made);
     if ((o_.corrMap || o_.softMask || o_.trim || o_.split || o_.corrEdits) && talc_ctx_set_map(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
     if (o_.autoStrand && talc_ctx_set_auto_strand(made, 1) != TALC_OK) { fail(talc_last_error()); return; }
+    if (o_.lrEnds()) {
+      std::string adapters;
+      for (const std::string& ad : o_.lrAdapters) adapters += (adapters.empty() ? "" : ",") + ad;
+      if (talc_ctx_set_ends(made, adapters.c_str(), o_.lrAdapterErr, o_.lrPolyA, o_.lrEndWindow) != TALC_OK) { fail(talc_last_error()); return; }
+    }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -1055,8 +1141,16 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
   const auto td0 = Clock::now();
   struct Busy { double& sum; Clock::time_point t0; ~Busy() { sum += since(t0); } } busy{t.busy, td0};   // batch create .. the batch's release
   talc_batch* made = nullptr;
-  if (talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made) != TALC_OK) return fail(talc_last_error());
+  const int mrc = o_.lrClip ? talc_batch_create_clipped(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made)
+                            : talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made);
+  if (mrc != TALC_OK) return fail(talc_last_error());
   BatchPtr b(made);
+  if (o_.lrEnds()) {   // the scan sees the reads as they came; with --LRClip it has made the batch, whose reads are the kept intervals from here on
+    std::vector<talc_end_row> rows(std::max<uint32_t>(n, 1));
+    if (talc_batch_ends(ctx, b.get()) != TALC_OK || talc_batch_fetch_ends(ctx, b.get(), rows.data()) != TALC_OK) return fail(talc_last_error());
+    formatEnds(c, rows.data());
+    if (o_.lrClip) for (uint32_t r = 0; r < n; ++r) c.offsets[r + 1] = c.offsets[r] + rows[r].kept_len;
+  }
   t.create += since(td0);
   const auto tk0 = Clock::now();
   // < 0: a real HIP / argument error stops the run; TALC_WARN_READ_ERRORS (> 0) is a complete batch in which some
@@ -1157,6 +1251,8 @@ void Pipeline::writerMain(WriterSide& w) {
     if (w.tqf.is_open()) w.tqf.write(c->trimFqText.data(), (std::streamsize)c->trimFqText.size());
     if (w.pqf.is_open()) w.pqf.write(c->splitFqText.data(), (std::streamsize)c->splitFqText.size());
     for (int i = 0; i < 2; ++i) w.strandSums[i] += c->strandSums[i];
+    if (w.xf.is_open()) w.xf.write(c->endsText.data(), (std::streamsize)c->endsText.size());
+    for (int i = 0; i < 4; ++i) w.endSums[i] += c->endSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -1322,6 +1418,10 @@ static int run(int argc, const char** argv) {
       if (const int ec = buildTable(o, sw, table, tableSize)) return ec;
   }
   t[2] = Clock::now();
+  if (!haveTable && o.lrEnds()) {
+    std::cerr << "talc: --LRAdapter / --LRPolyA look at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
+    return 2;
+  }
   if (haveTable && tableSize == 0) {
     std::cout << "[TALC]: The de Bruijn Graph is empty...Correction aborted." << std::endl;  // main.cpp:319-320
     return 1;
@@ -1367,6 +1467,11 @@ static int run(int argc, const char** argv) {
   if (o.autoStrand)
     std::cout << "[TALC]: strand: " << totals.strandSums[0] << " forward, " << totals.strandSums[1] << " reverse of " << totals.strandSums[0] + totals.strandSums[1]
               << " reads" << std::endl;
+  if (o.lrEnds()) {
+    const uint64_t* y = totals.endSums;
+    std::cout << "[TALC]: read ends: " << y[0] << " reads, " << y[1] << " with an adapter, " << y[2] << " with a poly run, " << y[3] << " bases "
+              << (o.lrClip ? "clipped" : "found (not clipped: no --LRClip)") << std::endl;
+  }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   if (sw.timing && o.fastq && ndev)
     fprintf(stderr, "[talc-lib] base support: %llu batches, k_base_support %.3f ms\n", (unsigned long long)totals.batches, totals.workers.supportMs);

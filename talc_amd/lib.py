@@ -36,6 +36,10 @@ EDIT_I, EDIT_D, EDIT_EQ, EDIT_X = 1, 2, 7, 8
 # talc_strand (docs/auto_strand.md)
 STRAND_FIELDS = ("n_kmers", "fwd_solid", "fwd_in", "rc_solid", "rc_in", "reverse")
 STRAND_DTYPE = np.dtype([(f, "<u4") for f in STRAND_FIELDS])
+# talc_end_row (docs/read_ends.md)
+ENDS_DTYPE = np.dtype([("head_adapter_len", "<u4"), ("head_poly_len", "<u4"), ("tail_adapter_len", "<u4"), ("tail_poly_len", "<u4"),
+                       ("head_adapter", "u1"), ("head_adapter_err", "u1"), ("tail_adapter", "u1"), ("tail_adapter_err", "u1"),
+                       ("kept_start", "<u4"), ("kept_len", "<u4"), ("orient", "<i4")])
 # talc_support_params (docs/base_support.md)
 SUPPORT_RAW, SUPPORT_RECORD = 0, 1
 # the k-mer spectrum (docs/kmer_spectrum.md): high 0 means the default; the largest high the kernel's LDS histogram holds
@@ -201,6 +205,11 @@ def _abi():
         "talc_batch_support_bytes": (u64, [vp]),
         "talc_batch_fetch_support": (i32, [vp, vp, vp, u64, vp]),
         "talc_ctx_get_support_timing": (i32, [vp, vp]),
+        "talc_ctx_set_ends": (i32, [vp, txt, u32, u32, u32]),
+        "talc_batch_ends": (i32, [vp, vp]),
+        "talc_batch_fetch_ends": (i32, [vp, vp, vp]),
+        "talc_batch_create_clipped": (i32, [vp, vp, vp, u32, out]),
+        "talc_ctx_get_ends_timing": (i32, [vp, vp, vp]),
         "talc_test_set_poison": (i32, [i32, u32]),
         "talc_test_get_poison": (i32, [vp, vp]),
         "talc_test_guard_report": (i32, [vp]),
@@ -691,6 +700,21 @@ class Context(_Owner):
         _chk(lib().talc_ctx_get_strand_timing(self._h, C.byref(a)))
         return a.value
 
+    def set_ends(self, adapters=(), max_error_pct=20, poly_min=0, window=512):
+        """The long-read end clean-up (docs/read_ends.md): up to 4 adapters of 12..64 letters, found within max_error_pct
+        (0..30) per cent of their length in edits inside the first / last `window` (32..4096) bytes, and a poly-T head /
+        poly-A tail of at least poly_min (0: off, else 8..window) bases behind them.  No adapters and poly_min 0: off."""
+        if isinstance(adapters, (str, bytes)):
+            adapters = [adapters]
+        text = ",".join(a.decode() if isinstance(a, bytes) else a for a in adapters)
+        _chk(lib().talc_ctx_set_ends(self._h, text.encode(), int(max_error_pct), int(poly_min), int(window)))
+
+    def ends_timing(self):
+        """(k_read_ends ms, k_clip_gather ms) of the context's last end scan and last clipped batch."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_ends_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def support_timing(self):
         """Device time (ms) of the k_base_support launch of the context's last Batch.support()."""
         a = C.c_float()
@@ -715,8 +739,9 @@ class Context(_Owner):
         _chk(L.talc_test_edit_script(self._h, a, len(a), b, len(b), int(max_cells), ops.ctypes.data, n.value, C.byref(n), C.byref(d)))
         return ops[:n.value], d.value
 
-    def batch(self, bases, offsets):
-        return Batch(self, bases, offsets)
+    def batch(self, bases, offsets, clip=False):
+        """clip: the batch is made from the reads' kept intervals (set_ends; Batch.ends() then has the rows of the reads as given)."""
+        return Batch(self, bases, offsets, clip=clip)
 
     def test_dp(self, mode, a, b, p0=0, p1=0, p2=0, p3=0):
         out = np.zeros(max(12, p2) if (mode == 3 and p1) else 12, dtype=np.int32)   # (mode 3's table form: one word per record)
@@ -739,13 +764,14 @@ class Batch(_Owner):
     """A batch of reads resident in HBM."""
     _destroy = "talc_batch_destroy"
 
-    def __init__(self, ctx, bases, offsets):
+    def __init__(self, ctx, bases, offsets, clip=False):
         self.ctx = ctx
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.n_reads = len(offsets) - 1
         h = C.c_void_p()
-        _chk(lib().talc_batch_create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
+        create = lib().talc_batch_create_clipped if clip else lib().talc_batch_create
+        _chk(create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
         self._h = h
         self._corrected = False   # the batch holds the records of a correction (solidity() then has corrected rows)
         self._enc_auto = None     # the auto-strand setting the batch's codes were made under
@@ -888,6 +914,14 @@ class Batch(_Owner):
         _chk(lib().talc_batch_strand(self.ctx._h, self._h))
         rows = np.zeros(self.n_reads, dtype=STRAND_DTYPE)
         _chk(lib().talc_batch_fetch_strand(self.ctx._h, self._h, rows.ctypes.data))
+        return rows
+
+    def ends(self):
+        """The end scan (docs/read_ends.md) as an ENDS_DTYPE array of one row per read; on a clipped batch the rows of the
+        reads it was made from."""
+        _chk(lib().talc_batch_ends(self.ctx._h, self._h))
+        rows = np.zeros(self.n_reads, dtype=ENDS_DTYPE)
+        _chk(lib().talc_batch_fetch_ends(self.ctx._h, self._h, rows.ctypes.data))
         return rows
 
     def pieces(self, mode, min_len=0, soft_mask=False):
