@@ -657,6 +657,55 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
 /* Measurement: device time (ms) of the context's last k_read_ends and k_clip_gather.  Either pointer may be NULL. */
 int talc_ctx_get_ends_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
 
+/* Chimeric long reads (docs/chimeras.md): the adapters of the end clean-up searched over the whole of every read, on both
+ * strands, and the reads cut where they are found.  Codes as above: bytes are upper-cased, a byte outside ACGT matches nothing.
+ * Adapter a of m letters gives two patterns, strand 0 the adapter and strand 1 its reverse complement, both matched against
+ * the read S (L bytes) as it lies.  For a pattern, D[e], 1 <= e <= L, is the Sellers distance of the pattern against the
+ * substrings of S that end at e (top row 0, first column i); k_a = floor(max_error_pct * m / 100); C[e] = min(D[e], k_a + 1);
+ * w = ceil(m / 2).  Column e is a hit end when C[e] <= k_a, C[e] < C[e'] for every e < e' <= min(L, e + w), and
+ * C[e] <= C[e'] for every max(1, e - w) <= e' < e.  The hit is [e - j, e), j the smallest j >= 0 for which the global
+ * unit-cost edit distance of the pattern and S[e - j, e) is D[e]; err = D[e].  A batch's hits are ordered by
+ * (read, end, adapter, strand). */
+typedef struct talc_chimera_hit {
+  uint32_t read, start, end;
+  uint8_t  adapter;  /* 1-based */
+  uint8_t  strand;   /* 0 as given, 1 reverse complement */
+  uint8_t  err;
+  uint8_t  pad;
+} talc_chimera_hit;  /* 16 bytes */
+/* The pieces of a read with at least one hit are the maximal non-empty intervals of [0, L) that no hit's [start, end)
+ * covers, in order; those shorter than min_piece are dropped and the kept ones numbered from 1 (such a read may keep none).
+ * A read without a hit is one piece [0, L) with ordinal 0, whatever its length. */
+typedef struct talc_split_piece {
+  uint32_t read, start, len;
+  uint32_t ordinal;  /* 1-based among the read's kept pieces; 0 for an uncut read */
+} talc_split_piece;
+/* on != 0 switches the scan on with its own bound max_error_pct (0..30) and min_piece; the adapters are those of the
+ * context's ends setting at the time of each scan.  TALC_ERR_INVALID names the bad value and changes nothing. */
+int talc_ctx_set_chimera(talc_ctx* c, int on, uint32_t max_error_pct, uint32_t min_piece);
+/* The scan (k_read_chimera) on the batch's raw bytes; on a plain batch once per setting, on a batch made by
+ * talc_batch_create_split never: its hits are those of the source reads.  TALC_ERR_STATE while the setting is off or the
+ * ends setting holds no adapter (and the batch holds no hits of its making), and on a batch made by
+ * talc_batch_create_clipped: it no longer holds the reads as they came, in which the hits are positions. */
+int talc_batch_chimera(talc_ctx* c, talc_batch* b);
+uint64_t talc_batch_num_chimera_hits(const talc_batch* b);
+/* hits: capacity entries (may be NULL with capacity 0); read_hit_offsets: one per scanned read, plus one (may be NULL).
+ * TALC_ERR_CAPACITY names the size needed; TALC_ERR_STATE when no scan has run on b. */
+int talc_batch_fetch_chimera(talc_ctx* c, talc_batch* b, talc_chimera_hit* hits, uint64_t capacity, uint64_t* read_hit_offsets);
+/* talc_batch_create of the kept pieces: the bytes go to the device once, the scan runs on them, the host computes the
+ * pieces from the hits and k_split_gather fills the batch's text.  The batch has one read per piece.  clip != 0 (needs the
+ * end clean-up, else TALC_ERR_STATE): the pieces are gathered into a staging text and the batch is made from it as
+ * talc_batch_create_clipped makes one, so the end rule applies to every piece.  From then on every call on the batch
+ * returns, byte for byte, what it returns on talc_batch_create of the pieces cut (and clipped) on the host. */
+int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, int clip,
+                            talc_batch** out);
+uint64_t talc_batch_num_split_pieces(const talc_batch* b);
+/* pieces: talc_batch_num_split_pieces rows; read_piece_offsets: n_reads + 1 of the source reads.  Either may be NULL.
+ * TALC_ERR_STATE on a batch that talc_batch_create_split did not make. */
+int talc_batch_fetch_split(talc_ctx* c, talc_batch* b, talc_split_piece* pieces, uint64_t* read_piece_offsets);
+/* Measurement: device time (ms) of the context's last k_read_chimera and k_split_gather.  Either pointer may be NULL. */
+int talc_ctx_get_chimera_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "talc_edit_plan.h"
+#include "talc_kernels_chimera.h"
 #include "talc_pure.h"
 #include "talc_wfa.h"
 
@@ -141,4 +142,47 @@ void pure_walk_repeat_check(const uint8_t* g, uint64_t n, uint32_t K, int dir_ri
 
 uint64_t pure_edit_scratch_words(uint32_t n, uint32_t m) { return edit_scratch_words(n, m); }
 int pure_edit_in_lds(uint32_t n, uint32_t m) { return edit_in_lds(n, m) ? 1 : 0; }
+
+// ---- chimeras (docs/chimeras.md): k_read_chimera's lanes one after another, and the piece rule
+// out3: lanes per pattern, chunk, tile of a read of L bytes under nPatterns patterns
+void pure_chimera_geometry(uint32_t L, uint32_t nPatterns, uint32_t* out3) {
+  const ChimeraGeometry g = chimera_geometry(L, nPatterns);
+  out3[0] = g.lanesPerPattern; out3[1] = g.chunk; out3[2] = g.tile;
+}
+// adapters: comma-separated ACGTacgt, as talc_ctx_set_ends takes them (not validated again: at most 4 of 12 .. 64 letters).
+// The sorted hits of the batch; returns their number and writes those that fit.
+int64_t pure_chimera_scan(const char* adapters, uint32_t max_error_pct, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
+                          ChimeraHit* out, uint64_t capacity) {
+  ChimeraParams P;
+  P.nPatterns = 0; P.pad_ = 0;
+  for (const char* p = adapters && *adapters ? adapters : nullptr; p;) {
+    const char* e = p;
+    while (*e && *e != ',') ++e;
+    const size_t m = (size_t)(e - p);
+    if (m < 12 || m > 64 || P.nPatterns + 2 > kChimeraMaxPatterns) return -1;
+    uint8_t codes[64];
+    for (size_t i = 0; i < m; ++i) { codes[i] = ascii_to_code((uint8_t)p[i]); if (codes[i] >= 4) return -1; }
+    chimera_params_add(P, codes, (uint32_t)m, max_error_pct);
+    p = *e ? e + 1 : nullptr;
+  }
+  std::vector<ChimeraHit> hits;
+  for (uint32_t r = 0; r < n_reads; ++r) chimera_scan_host(bases + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), r, P, hits);
+  chimera_sort(hits);
+  for (size_t i = 0; i < hits.size() && i < capacity; ++i) out[i] = hits[i];
+  return (int64_t)hits.size();
+}
+// the pieces of a batch from its sorted hits; returns their number and writes those that fit; read_piece_off: n_reads + 1;
+// dropped2: pieces dropped, their bytes
+int64_t pure_split_pieces(const ChimeraHit* hits, uint64_t n_hits, const uint64_t* offsets, uint32_t n_reads, uint32_t min_piece, SplitPiece* out,
+                          uint64_t capacity, uint64_t* read_piece_off, uint64_t* dropped2) {
+  std::vector<ChimeraHit> h(hits, hits + n_hits);
+  for (const ChimeraHit& x : h) if (x.read >= n_reads) return -1;
+  std::vector<uint64_t> hitOff, pieceOff;
+  chimera_read_offsets(h, n_reads, hitOff);
+  std::vector<SplitPiece> pieces;
+  split_pieces(h.data(), hitOff.data(), offsets, n_reads, min_piece, pieces, pieceOff, dropped2, dropped2 + 1);
+  for (size_t i = 0; i < pieces.size() && i < capacity; ++i) out[i] = pieces[i];
+  for (uint32_t r = 0; r <= n_reads; ++r) read_piece_off[r] = pieceOff[r];
+  return (int64_t)pieces.size();
+}
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "talc_kernels_srfilter.h"
 #include "talc_kernels_strand.h"
 #include "talc_kernels_support.h"
+#include "talc_kernels_chimera.h"   // (last: the code object lays kernels out in this order; the correction's kernels keep the places they had: docs/chimeras.md)
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -168,6 +169,7 @@ enum CtxSpan {
   kSpanEditAlignA, kSpanEditCount, kSpanEditAlignB, kSpanEditPack,
   kSpanSupport,                          // k_base_support
   kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_clip_gather
+  kSpanChimeraScan, kSpanChimeraGather,  // the chimera split: k_read_chimera, k_split_gather
   kSpanCount
 };
 
@@ -187,6 +189,10 @@ struct talc_ctx {
   bool endsOn = false;       // talc_ctx_set_ends (docs/read_ends.md): nothing of it exists while it is off
   uint32_t endsGen = 0;      // ... counts the settings: a plain batch's rows are those of the setting they were made under
   EndsParams ends;           // ... as k_read_ends takes it
+  uint8_t endsCodes[ENDS_MAX_ADAPTERS][64] = {};   // ... and its adapters' letters as codes (the chimera scan makes its patterns from them)
+  bool chimeraOn = false;    // talc_ctx_set_chimera (docs/chimeras.md): nothing of it exists while it is off
+  uint32_t chimeraGen = 0;   // ... counts the settings, as endsGen does
+  uint32_t chimeraPct = 0, chimeraMinPiece = 0;
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -213,6 +219,7 @@ struct EditOut {
 // what drops a result drops everything made from it:
 //   voted                                  from the raw bytes; never dropped
 //   ended                                  from the raw bytes (of a clipped batch: from those it was made from); never dropped
+//   chimera                                from the raw bytes (of a split batch: from those it was made from); never dropped
 //   encoded(encodedAuto) -> covered
 //   encoded -> solidity (raw rows), supported (RAW)
 //   encoded -> structured            (test hook; k_search consumes the region lists)
@@ -222,6 +229,8 @@ struct BatchHolds {
   bool voted = false;         // d_strand, d_strand_flag: k_strand_vote runs once per batch
   bool ended = false;         // d_ends: k_read_ends under the context's setting number endsGen
   bool clipped = false;       // ... and the batch was made from those rows (talc_batch_create_clipped): they are never made again
+  bool chimera = false;       // h_hits: k_read_chimera under the settings chimeraGen and chimeraEndsGen; never dropped
+  bool split = false;         // ... and the batch was made from those hits (talc_batch_create_split): they are never made again
   bool encoded = false;       // d_codes
   bool encodedAuto = false;   // ... made with the vote's flags: k_pack, k_pack_map, k_solidity and k_base_support then take them too
   bool covered = false;       // d_cov, d_covw, d_nin
@@ -263,6 +272,13 @@ struct talc_batch {
   std::vector<uint64_t> h_read_piece_off, h_read_byte_off;   // n_reads + 1 each: the reads' first piece, first kept byte (talc_batch_pieces)
   // device buffers, from the context's cache.  Members go last to first, so the cache (which drops its oldest entries
   // first) gets them back from d_raw to d_headcov
+  // the chimera scan: the hits of the scanned reads in the contract's order and each read's first hit; of a split batch the
+  // source reads' hits, its pieces and each source read's first piece
+  std::vector<ChimeraHit> h_hits;
+  std::vector<uint64_t> h_read_hit_off;
+  std::vector<SplitPiece> h_split;
+  std::vector<uint64_t> h_read_split_off;
+  uint32_t chimeraGen = 0, chimeraEndsGen = 0;
   CachedBuf<EndRow> d_ends;           // one row per read (k_read_ends)
   uint32_t endsGen = 0;               // the setting those rows were made under
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
@@ -309,6 +325,8 @@ static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) 
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
 static_assert(sizeof(EndRow) == sizeof(talc_end_row) && sizeof(talc_end_row) == 32, "k_read_ends writes talc_end_row records");
+static_assert(sizeof(ChimeraHit) == sizeof(talc_chimera_hit) && sizeof(talc_chimera_hit) == 16 && sizeof(SplitPiece) == sizeof(talc_split_piece) &&
+              sizeof(talc_split_piece) == 16, "k_read_chimera writes talc_chimera_hit records, k_split_gather reads talc_split_piece records");
 
 // What an entry point that takes a context and a batch checks first: they belong together and the `rest` of its arguments is there
 // (`msg`: the call's own wording).  enter() makes the context's device current as well; belong() where a state check comes before that.
@@ -1349,5 +1367,6 @@ extern "C" {
 #include "talc_capi_edits.inc"
 #include "talc_capi_support.inc"
 #include "talc_capi_ends.inc"
+#include "talc_capi_chimera.inc"
 
 }  // extern "C"

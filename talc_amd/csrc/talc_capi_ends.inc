@@ -8,7 +8,9 @@ int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct,
   if (window < 32 || window > ENDS_MAX_WINDOW) return fail(TALC_ERR_INVALID, "window=%u: 32 .. %u (0: 512)", window, (uint32_t)ENDS_MAX_WINDOW);
   if (poly_min && (poly_min < 8 || poly_min > window)) return fail(TALC_ERR_INVALID, "poly_min=%u: 0 (off) or 8 .. window (%u)", poly_min, window);
   EndsParams P;
+  uint8_t codes[ENDS_MAX_ADAPTERS][64];
   memset(&P, 0, sizeof P);
+  memset(codes, 0, sizeof codes);
   P.polyMin = poly_min; P.window = window;
   for (const char* p = adapters && *adapters ? adapters : nullptr; p;) {
     const char* e = strchr(p, ',');
@@ -19,6 +21,7 @@ int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct,
       const uint8_t code = ascii_to_code((uint8_t)p[i]);
       if (code >= 4) return fail(TALC_ERR_INVALID, "adapters: adapter %u has a letter that is not one of ACGTacgt", P.nAdapters + 1);
       P.peq[P.nAdapters][code] |= 1ull << i;
+      codes[P.nAdapters][i] = code;
     }
     P.m[P.nAdapters] = (uint32_t)m;
     P.k[P.nAdapters] = (uint32_t)(max_error_pct * m / 100);
@@ -26,6 +29,7 @@ int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct,
     p = e ? e + 1 : nullptr;
   }
   c->ends = P;
+  memcpy(c->endsCodes, codes, sizeof codes);
   c->endsOn = P.nAdapters || poly_min;
   ++c->endsGen;
   return TALC_OK;
@@ -64,6 +68,9 @@ int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows) {
   return read_spans(c);
 }
 
+static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
+                               uint32_t n_reads);
+
 // The raw bytes go up once, into a staging buffer of the context's cache; the scan's rows come to the host, which lays the
 // batch out from the kept lengths (batch_build, as talc_batch_create); k_clip_gather then fills the batch's text from the
 // staging buffer, device to device.  The staging buffers go back to the cache when the batch stands.
@@ -84,9 +91,19 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
   CachedBuf<uint64_t> stageOff;
   HIPCHK(stage.alloc(c->cache, std::max<uint64_t>(nb, 1)));
   HIPCHK(stageOff.alloc(c->cache, (uint64_t)n_reads + 1));
-  HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
   if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (int rc = clipped_from_staged(c, bp, stage, stageOff, offsets, n_reads)) return rc;
+  *out = b.release();
+  return TALC_OK;
+}
+
+// The clipped batch `bp` from n_reads reads that stand on the device already (`stage` at `stageOff`, ordered on the
+// context's stream; `offsets` are the same offsets on the host): the scan, the rows to the host, the layout from the kept
+// lengths, k_clip_gather.  What talc_batch_create_clipped does behind its upload, and talc_batch_create_split behind its gather.
+static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
+                               uint32_t n_reads) {
+  HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
   int rc;
   if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
   std::vector<EndRow> rows(n_reads);
@@ -110,7 +127,6 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
   if ((rc = read_spans(c))) return rc;
   bp->endsGen = c->endsGen;
   bp->holds.ended = bp->holds.clipped = true;
-  *out = b.release();
   return TALC_OK;
 }
 

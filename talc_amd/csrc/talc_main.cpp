@@ -59,6 +59,13 @@
 //                    line per read in input order, and one summary line on stdout
 //   --LRPolyA N      a poly-T head / poly-A tail of at least N bases (8..LREndWindow; 0: off), behind the primer if there is one
 //   --LRClip         the reads are corrected without the ends found: clipped on the GPU, every output is that of the clipped reads
+//   --LRChimeras     with --LRAdapter: the adapters are searched over the whole of every read, on both strands, within
+//                    --LRChimeraErr PCT (0..30, default 10) per cent of their length in edits (docs/chimeras.md); writes
+//                    <o>.chimera.tsv, one line per hit, and one summary line on stdout
+//                    (not with --LRClip alone: the hits are positions in the reads as they came)
+//   --LRSplit        ... and the reads are cut there on the GPU: the pieces of at least --LRMinPiece N (default 100) bases are
+//                    corrected as reads of their own (name_c1, name_c2, ...), every output is that of the pieces; writes
+//                    <o>.chimera_pieces.tsv; with --LRClip every piece is clipped
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -85,6 +92,7 @@
 #include <sys/stat.h>
 #include <sys/wait.h>
 
+#include "talc_chimera_plan.h"   // the piece rule, as the library applies it: what a report without --LRSplit would keep
 #include "talc_cli_io.h"
 #include "talc_hip.h"
 #include "talc_jf.h"
@@ -151,6 +159,10 @@ struct Options {
   uint32_t lrAdapterErr = 20, lrPolyA = 0, lrEndWindow = 512;   // --LRAdapterErr, --LRPolyA (0: off), --LREndWindow
   bool haveLrAdapterErr = false, haveLrPolyA = false, haveLrEndWindow = false;
   bool lrClip = false;                      // --LRClip
+  bool lrChimeras = false, lrSplit = false; // --LRChimeras, --LRSplit (docs/chimeras.md)
+  uint32_t lrChimeraErr = 10, lrMinPiece = 100;   // --LRChimeraErr, --LRMinPiece
+  bool haveLrChimeraErr = false, haveLrMinPiece = false;
+  bool lrChimeraScan() const { return lrChimeras || lrSplit; }   // the chimera scan is on
   bool lrEnds() const { return !lrAdapters.empty() || lrPolyA > 0; }   // the long-read end clean-up is on
 };
 
@@ -223,6 +235,12 @@ void usage(FILE* f) {
           "  --LREndWindow INT           with --LRAdapter / --LRPolyA: bases of each end that are searched, 32..4096, default 512\n"
           "  --LRClip                    with --LRAdapter / --LRPolyA: correct the reads without the ends found (clipped on the GPU);\n"
           "                              every output is that of the clipped reads under their names\n"
+          "  --LRChimeras                with --LRAdapter: look for the adapters inside the reads too, on both strands; writes\n"
+          "                              <o>.chimera.tsv (docs/chimeras.md); with --LRClip only together with --LRSplit\n"
+          "  --LRSplit                   with --LRAdapter: ... and cut the reads there on the GPU; the pieces are corrected as reads of\n"
+          "                              their own (name_c1, name_c2, ...); writes <o>.chimera_pieces.tsv; combines with --LRClip\n"
+          "  --LRChimeraErr INT          with --LRChimeras / --LRSplit: edits allowed in percent of the adapter's length, 0..30, default 10\n"
+          "  --LRMinPiece INT            with --LRChimeras / --LRSplit: pieces shorter than this are dropped, default 100\n"
           "  -h, --help / --version\n");
 }
 
@@ -342,6 +360,18 @@ Options parse(int argc, const char** argv) {
       o.lrEndWindow = (uint32_t)v; o.haveLrEndWindow = true;
     }
     else if (a == "--LRClip") o.lrClip = true;
+    else if (a == "--LRChimeras") o.lrChimeras = true;
+    else if (a == "--LRSplit") o.lrSplit = true;
+    else if (a == "--LRChimeraErr") {
+      const double v = num(need(i), "LRChimeraErr");
+      if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for LRChimeraErr: 0..30");
+      o.lrChimeraErr = (uint32_t)v; o.haveLrChimeraErr = true;
+    }
+    else if (a == "--LRMinPiece") {
+      const double v = num(need(i), "LRMinPiece");
+      if (v != (double)(long long)v || v < 0 || v > 2e9) parse_error("value out of range for LRMinPiece: 0..2000000000");
+      o.lrMinPiece = (uint32_t)v; o.haveLrMinPiece = true;
+    }
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -375,6 +405,13 @@ Options parse(int argc, const char** argv) {
   if (o.haveLrAdapterErr && o.lrAdapters.empty()) parse_error("--LRAdapterErr needs --LRAdapter");
   if (o.haveLrEndWindow && !o.lrEnds()) parse_error("--LREndWindow needs --LRAdapter or --LRPolyA");
   if (o.lrClip && !o.lrEnds()) parse_error("--LRClip needs --LRAdapter or --LRPolyA");
+  if (o.lrChimeras && o.lrAdapters.empty()) parse_error("--LRChimeras needs --LRAdapter");
+  if (o.lrSplit && o.lrAdapters.empty()) parse_error("--LRSplit needs --LRAdapter");
+  // (a clipped batch no longer holds the reads as they came, and the hits are positions in those: only the split route scans
+  //  before it clips)
+  if (o.lrChimeras && o.lrClip && !o.lrSplit) parse_error("--LRChimeras with --LRClip needs --LRSplit: the report is of the reads as they came, which a clipped run no longer holds");
+  if (o.haveLrChimeraErr && !(o.lrChimeraScan() && !o.lrAdapters.empty())) parse_error("--LRChimeraErr needs --LRAdapter and --LRChimeras or --LRSplit");
+  if (o.haveLrMinPiece && !(o.lrChimeraScan() && !o.lrAdapters.empty())) parse_error("--LRMinPiece needs --LRAdapter and --LRChimeras or --LRSplit");
   if (o.lrPolyA > o.lrEndWindow) parse_error("value out of range for LRPolyA: " + std::to_string(o.lrPolyA) + " is above LREndWindow " + std::to_string(o.lrEndWindow));
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
@@ -397,6 +434,10 @@ void outputConfig(const Options& o, const std::string& statFile) {
   if (o.haveLrPolyA) f << "LRPolyA=" << o.lrPolyA << "\n";
   if (o.haveLrEndWindow) f << "LREndWindow=" << o.lrEndWindow << "\n";
   if (o.lrClip) f << "LRClip=1" << "\n";
+  if (o.lrChimeras) f << "LRChimeras=1" << "\n";
+  if (o.lrSplit) f << "LRSplit=1" << "\n";
+  if (o.haveLrChimeraErr) f << "LRChimeraErr=" << o.lrChimeraErr << "\n";
+  if (o.haveLrMinPiece) f << "LRMinPiece=" << o.lrMinPiece << "\n";
   if (o.bothStrands) f << "Both strands? 1" << "\n";
   if (o.haveSrMinQual) f << "SRMinQual=" << o.srMinQual << "\n";
   for (const std::string& ad : o.srAdapters) f << "SRAdapter=" << ad << "\n";
@@ -425,11 +466,12 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends, chimera, chimeraPieces;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
         trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv"),
-        fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq"), ends(prefix + ".ends.tsv") {}
+        fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq"), ends(prefix + ".ends.tsv"),
+        chimera(prefix + ".chimera.tsv"), chimeraPieces(prefix + ".chimera_pieces.tsv") {}
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -637,6 +679,8 @@ struct Chunk {
   std::string fqText, trimFqText, splitFqText;   // ... and to <o>.fq, <o>.trim.fq, <o>.split.fq (--fastq)
   std::string endsText;                 // ... and to <o>.ends.tsv (--LRAdapter, --LRPolyA)
   uint64_t endSums[4] = {0, 0, 0, 0};   // of the batch: reads, those with an adapter at either end, those with a poly run, bases outside the kept intervals
+  std::string chimeraText, chimeraPiecesText;   // ... and to <o>.chimera.tsv, <o>.chimera_pieces.tsv (--LRChimeras, --LRSplit)
+  uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch: reads, hits, reads with a hit, pieces kept, pieces dropped, their bases
   // the read was corrected as under -rev: the whole file's -rev, or the read's own vote
   bool reversed(const talc_params& p, size_t r) const { return p.reverse || (!strand.empty() && strand[r].reverse); }
 };
@@ -672,6 +716,56 @@ void formatEnds(Chunk& k, const talc_end_row* rows) {
     k.endSums[2] += (w.head_poly_len || w.tail_poly_len) ? 1 : 0;
     k.endSums[3] += L - w.kept_len;
   }
+}
+
+// the lines of <o>.chimera.tsv for one batch from the scan's hits (k.ids, k.offsets: the reads as they came), and the sums:
+// the pieces come from the same rule the library cuts by (talc_chimera_plan.h), so a report without --LRSplit says what a
+// split would keep
+const char* const kChimeraHeader = "read_name\traw_length\tadapter\tstrand\tstart\tend\terr\n";
+const char* const kChimeraPiecesHeader = "piece_name\tread_name\tstart\tlen\n";
+void formatChimera(Chunk& k, const std::vector<talc_chimera_hit>& hits, const std::vector<uint64_t>& hitOff, uint32_t minPiece,
+                   std::vector<talc::SplitPiece>& pieces, std::vector<uint64_t>& pieceOff) {
+  char num[160];
+  const size_t n = k.ids.size();
+  for (size_t r = 0; r < n; ++r)
+    for (uint64_t h = hitOff[r]; h < hitOff[r + 1]; ++h) {
+      const talc_chimera_hit& w = hits[h];
+      const int m = snprintf(num, sizeof num, "\t%llu\t%u\t%c\t%u\t%u\t%u\n", (unsigned long long)(k.offsets[r + 1] - k.offsets[r]), w.adapter, w.strand ? '-' : '+',
+                             w.start, w.end, w.err);
+      k.chimeraText += k.ids[r];
+      k.chimeraText.append(num, (size_t)m);
+    }
+  static_assert(sizeof(talc::ChimeraHit) == sizeof(talc_chimera_hit), "one record");
+  uint64_t dropped = 0, droppedBases = 0;
+  talc::split_pieces(reinterpret_cast<const talc::ChimeraHit*>(hits.data()), hitOff.data(), k.offsets.data(), (uint32_t)n, minPiece, pieces, pieceOff, &dropped,
+                     &droppedBases);
+  k.chimeraSums[0] += n;
+  k.chimeraSums[1] += hits.size();
+  for (size_t r = 0; r < n; ++r) k.chimeraSums[2] += hitOff[r + 1] > hitOff[r] ? 1 : 0;
+  k.chimeraSums[3] += pieces.size();
+  k.chimeraSums[4] += dropped;
+  k.chimeraSums[5] += droppedBases;
+}
+// --LRSplit: the chunk's reads become the pieces (name_c<ordinal> for a cut read's, the name itself for an uncut read),
+// their lines go to <o>.chimera_pieces.tsv
+void takePieces(Chunk& k, const talc_split_piece* pieces, size_t np) {
+  std::vector<std::string> ids;
+  std::vector<uint64_t> offsets{0};
+  ids.reserve(np); offsets.reserve(np + 1);
+  char num[96];
+  for (size_t p = 0; p < np; ++p) {
+    const talc_split_piece& w = pieces[p];
+    const std::string& name = k.ids[w.read];
+    ids.push_back(w.ordinal ? name + "_c" + std::to_string(w.ordinal) : name);
+    offsets.push_back(offsets.back() + w.len);
+    const int m = snprintf(num, sizeof num, "\t%u\t%u\n", w.start, w.len);
+    k.chimeraPiecesText += ids.back();
+    k.chimeraPiecesText += '\t';
+    k.chimeraPiecesText += name;
+    k.chimeraPiecesText.append(num, (size_t)m);
+  }
+  k.ids.swap(ids);
+  k.offsets.swap(offsets);
 }
 
 // the lines of <o>.edits.tsv for one batch (k.status filled; oo: the records' offsets; the ops of read r are ops[po[r] ..
@@ -876,6 +970,7 @@ struct PipelineTotals {
   uint64_t pieceSums[4] = {0, 0, 0, 0};    // --trim / --split: trimmed reads, their bases, split pieces, their bases
   uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // --corr-edits: Chunk::editSums
   uint64_t endSums[4] = {0, 0, 0, 0};          // --LRAdapter / --LRPolyA: Chunk::endSums
+  uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // --LRChimeras / --LRSplit: Chunk::chimeraSums
   WorkerTally workers;
 };
 
@@ -909,9 +1004,9 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf, cf, cpf;
     double busy = 0;
-    uint64_t strandSums[2] = {0, 0}, endSums[4] = {0, 0, 0, 0};
+    uint64_t strandSums[2] = {0, 0}, endSums[4] = {0, 0, 0, 0}, chimeraSums[6] = {0, 0, 0, 0, 0, 0};
     uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
   };
   bool fail(std::string msg);
@@ -997,6 +1092,16 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
     if (!wr.xf) return fail("cannot write " + files_.ends);
     wr.xf << kEndsHeader;
   }
+  if (o_.lrChimeraScan()) {
+    wr.cf.open(files_.chimera, std::ios_base::trunc);
+    if (!wr.cf) return fail("cannot write " + files_.chimera);
+    wr.cf << kChimeraHeader;
+    if (o_.lrSplit) {
+      wr.cpf.open(files_.chimeraPieces, std::ios_base::trunc);
+      if (!wr.cpf) return fail("cannot write " + files_.chimeraPieces);
+      wr.cpf << kChimeraPiecesHeader;
+    }
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -1026,6 +1131,7 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.xf.is_open()) wr.xf.close();
   for (int i = 0; i < 2; ++i) tot.strandSums[i] = wr.strandSums[i];
   for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; tot.endSums[i] = wr.endSums[i]; }
+  for (int i = 0; i < 6; ++i) tot.chimeraSums[i] = wr.chimeraSums[i];
   for (int i = 0; i < 6; ++i) tot.editSums[i] = wr.editSums[i];
   tot.readerBusy = rd.busy; tot.bases = rd.bases; tot.batches = rd.batches;
   tot.writerBusy = wr.busy;
@@ -1094,6 +1200,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
       for (const std::string& ad : o_.lrAdapters) adapters += (adapters.empty() ? "" : ",") + ad;
       if (talc_ctx_set_ends(made, adapters.c_str(), o_.lrAdapterErr, o_.lrPolyA, o_.lrEndWindow) != TALC_OK) { fail(talc_last_error()); return; }
     }
+    if (o_.lrChimeraScan() && talc_ctx_set_chimera(made, 1, o_.lrChimeraErr, o_.lrMinPiece) != TALC_OK) { fail(talc_last_error()); return; }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -1136,15 +1243,35 @@ bool Pipeline::fetchPieces(talc_ctx* ctx, talc_batch* b, Chunk& c, bool split, c
 
 // one batch through the device and into text; false after fail()
 bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTally& t) {
-  const uint32_t n = (uint32_t)c.ids.size();
-  c.status.assign(n, TALC_READ_SKIPPED_SHORT);
+  uint32_t n = (uint32_t)c.ids.size();
   const auto td0 = Clock::now();
   struct Busy { double& sum; Clock::time_point t0; ~Busy() { sum += since(t0); } } busy{t.busy, td0};   // batch create .. the batch's release
   talc_batch* made = nullptr;
-  const int mrc = o_.lrClip ? talc_batch_create_clipped(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made)
-                            : talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made);
+  const int mrc = o_.lrSplit  ? talc_batch_create_split(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, o_.lrClip ? 1 : 0, &made)
+                  : o_.lrClip ? talc_batch_create_clipped(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made)
+                              : talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made);
   if (mrc != TALC_OK) return fail(talc_last_error());
   BatchPtr b(made);
+  if (o_.lrChimeraScan()) {   // the scan sees the reads as they came (never a clipped batch: parse()); with --LRSplit it has made the batch, whose reads are the kept pieces from here on
+    if (talc_batch_chimera(ctx, b.get()) != TALC_OK) return fail(talc_last_error());
+    std::vector<talc_chimera_hit> hits(talc_batch_num_chimera_hits(b.get()));
+    std::vector<uint64_t> hitOff((size_t)n + 1);
+    if (talc_batch_fetch_chimera(ctx, b.get(), hits.data(), hits.size(), hitOff.data()) != TALC_OK) return fail(talc_last_error());
+    std::vector<talc::SplitPiece> ruled;
+    std::vector<uint64_t> ruledOff;
+    formatChimera(c, hits, hitOff, o_.lrMinPiece, ruled, ruledOff);
+    if (o_.lrSplit) {
+      std::vector<talc_split_piece> pieces(std::max<uint64_t>(talc_batch_num_split_pieces(b.get()), 1));
+      const size_t np = (size_t)talc_batch_num_split_pieces(b.get());
+      if (talc_batch_fetch_split(ctx, b.get(), pieces.data(), nullptr) != TALC_OK) return fail(talc_last_error());
+      static_assert(sizeof(talc::SplitPiece) == sizeof(talc_split_piece), "one record");
+      if (np != ruled.size() || (np && memcmp(pieces.data(), ruled.data(), np * sizeof(talc_split_piece)) != 0))   // (the sums above are those of these very rows)
+        return fail("the split batch's " + std::to_string(np) + " pieces are not the " + std::to_string(ruled.size()) + " the piece rule gives for its hits");
+      takePieces(c, pieces.data(), np);
+      n = (uint32_t)np;
+    }
+  }
+  c.status.assign(n, TALC_READ_SKIPPED_SHORT);
   if (o_.lrEnds()) {   // the scan sees the reads as they came; with --LRClip it has made the batch, whose reads are the kept intervals from here on
     std::vector<talc_end_row> rows(std::max<uint32_t>(n, 1));
     if (talc_batch_ends(ctx, b.get()) != TALC_OK || talc_batch_fetch_ends(ctx, b.get(), rows.data()) != TALC_OK) return fail(talc_last_error());
@@ -1253,6 +1380,9 @@ void Pipeline::writerMain(WriterSide& w) {
     for (int i = 0; i < 2; ++i) w.strandSums[i] += c->strandSums[i];
     if (w.xf.is_open()) w.xf.write(c->endsText.data(), (std::streamsize)c->endsText.size());
     for (int i = 0; i < 4; ++i) w.endSums[i] += c->endSums[i];
+    if (w.cf.is_open()) w.cf.write(c->chimeraText.data(), (std::streamsize)c->chimeraText.size());
+    if (w.cpf.is_open()) w.cpf.write(c->chimeraPiecesText.data(), (std::streamsize)c->chimeraPiecesText.size());
+    for (int i = 0; i < 6; ++i) w.chimeraSums[i] += c->chimeraSums[i];
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -1471,6 +1601,11 @@ static int run(int argc, const char** argv) {
     const uint64_t* y = totals.endSums;
     std::cout << "[TALC]: read ends: " << y[0] << " reads, " << y[1] << " with an adapter, " << y[2] << " with a poly run, " << y[3] << " bases "
               << (o.lrClip ? "clipped" : "found (not clipped: no --LRClip)") << std::endl;
+  }
+  if (o.lrChimeraScan()) {
+    const uint64_t* y = totals.chimeraSums;
+    std::cout << "[TALC]: chimeras: " << y[0] << " reads, " << y[1] << " hits in " << y[2] << " reads, " << y[3] << " pieces kept, " << y[4]
+              << " pieces dropped (" << y[5] << " bases)" << std::endl;
   }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   if (sw.timing && o.fastq && ndev)

@@ -40,6 +40,20 @@ STRAND_DTYPE = np.dtype([(f, "<u4") for f in STRAND_FIELDS])
 ENDS_DTYPE = np.dtype([("head_adapter_len", "<u4"), ("head_poly_len", "<u4"), ("tail_adapter_len", "<u4"), ("tail_poly_len", "<u4"),
                        ("head_adapter", "u1"), ("head_adapter_err", "u1"), ("tail_adapter", "u1"), ("tail_adapter_err", "u1"),
                        ("kept_start", "<u4"), ("kept_len", "<u4"), ("orient", "<i4")])
+# talc_chimera_hit, talc_split_piece (docs/chimeras.md)
+CHIMERA_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("end", "<u4"), ("adapter", "u1"), ("strand", "u1"), ("err", "u1"), ("pad", "u1")])
+SPLIT_PIECE_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("len", "<u4"), ("ordinal", "<u4")])
+# how k_read_chimera walks a read (talc_chimera_plan.h: chimera_geometry), for tests that aim at its borders
+CHIMERA_CHUNK_MIN, CHIMERA_CHUNK_MAX = 36, 252
+
+
+def chimera_geometry(length, n_patterns):
+    """(lanes per pattern, chunk, tile) of a read of `length` bytes under n_patterns = 2 * adapters patterns: lane q of a
+    pattern owns columns [tile_start + q * chunk, + chunk) of every tile."""
+    lanes = 64 // n_patterns
+    chunk = min(CHIMERA_CHUNK_MAX, max(CHIMERA_CHUNK_MIN, -(-length // lanes)))
+    chunk += (4 - chunk % 8) % 8
+    return lanes, chunk, lanes * chunk
 # talc_support_params (docs/base_support.md)
 SUPPORT_RAW, SUPPORT_RECORD = 0, 1
 # the k-mer spectrum (docs/kmer_spectrum.md): high 0 means the default; the largest high the kernel's LDS histogram holds
@@ -210,6 +224,14 @@ def _abi():
         "talc_batch_fetch_ends": (i32, [vp, vp, vp]),
         "talc_batch_create_clipped": (i32, [vp, vp, vp, u32, out]),
         "talc_ctx_get_ends_timing": (i32, [vp, vp, vp]),
+        "talc_ctx_set_chimera": (i32, [vp, i32, u32, u32]),
+        "talc_batch_chimera": (i32, [vp, vp]),
+        "talc_batch_num_chimera_hits": (u64, [vp]),
+        "talc_batch_fetch_chimera": (i32, [vp, vp, vp, u64, vp]),
+        "talc_batch_create_split": (i32, [vp, vp, vp, u32, i32, out]),
+        "talc_batch_num_split_pieces": (u64, [vp]),
+        "talc_batch_fetch_split": (i32, [vp, vp, vp, vp]),
+        "talc_ctx_get_chimera_timing": (i32, [vp, vp, vp]),
         "talc_test_set_poison": (i32, [i32, u32]),
         "talc_test_get_poison": (i32, [vp, vp]),
         "talc_test_guard_report": (i32, [vp]),
@@ -715,6 +737,18 @@ class Context(_Owner):
         _chk(lib().talc_ctx_get_ends_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_chimera(self, on=True, max_error_pct=10, min_piece=0):
+        """The chimera scan (docs/chimeras.md): the adapters of set_ends searched over the whole of every read on both
+        strands within max_error_pct (0..30) per cent of their length in edits; split batches drop pieces shorter than
+        min_piece."""
+        _chk(lib().talc_ctx_set_chimera(self._h, 1 if on else 0, int(max_error_pct), int(min_piece)))
+
+    def chimera_timing(self):
+        """(k_read_chimera ms, k_split_gather ms) of the context's last chimera scan and last split batch."""
+        a, b = C.c_float(), C.c_float()
+        _chk(lib().talc_ctx_get_chimera_timing(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def support_timing(self):
         """Device time (ms) of the k_base_support launch of the context's last Batch.support()."""
         a = C.c_float()
@@ -739,9 +773,11 @@ class Context(_Owner):
         _chk(L.talc_test_edit_script(self._h, a, len(a), b, len(b), int(max_cells), ops.ctypes.data, n.value, C.byref(n), C.byref(d)))
         return ops[:n.value], d.value
 
-    def batch(self, bases, offsets, clip=False):
-        """clip: the batch is made from the reads' kept intervals (set_ends; Batch.ends() then has the rows of the reads as given)."""
-        return Batch(self, bases, offsets, clip=clip)
+    def batch(self, bases, offsets, clip=False, split=False):
+        """clip: the batch is made from the reads' kept intervals (set_ends; Batch.ends() then has the rows of the reads as given).
+        split: its reads are the kept pieces of the given reads (set_chimera; Batch.split_pieces() says which); with clip
+        too, every piece is clipped."""
+        return Batch(self, bases, offsets, clip=clip, split=split)
 
     def test_dp(self, mode, a, b, p0=0, p1=0, p2=0, p3=0):
         out = np.zeros(max(12, p2) if (mode == 3 and p1) else 12, dtype=np.int32)   # (mode 3's table form: one word per record)
@@ -764,14 +800,18 @@ class Batch(_Owner):
     """A batch of reads resident in HBM."""
     _destroy = "talc_batch_destroy"
 
-    def __init__(self, ctx, bases, offsets, clip=False):
+    def __init__(self, ctx, bases, offsets, clip=False, split=False):
         self.ctx = ctx
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        self.n_reads = len(offsets) - 1
+        self.n_reads = self.n_source_reads = len(offsets) - 1
         h = C.c_void_p()
-        create = lib().talc_batch_create_clipped if clip else lib().talc_batch_create
-        _chk(create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
+        if split:
+            _chk(lib().talc_batch_create_split(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, 1 if clip else 0, C.byref(h)))
+            self.n_reads = int(lib().talc_batch_num_split_pieces(h))   # (one read per kept piece)
+        else:
+            create = lib().talc_batch_create_clipped if clip else lib().talc_batch_create
+            _chk(create(ctx._h, bases.ctypes.data, offsets.ctypes.data, self.n_reads, C.byref(h)))
         self._h = h
         self._corrected = False   # the batch holds the records of a correction (solidity() then has corrected rows)
         self._enc_auto = None     # the auto-strand setting the batch's codes were made under
@@ -915,6 +955,24 @@ class Batch(_Owner):
         rows = np.zeros(self.n_reads, dtype=STRAND_DTYPE)
         _chk(lib().talc_batch_fetch_strand(self.ctx._h, self._h, rows.ctypes.data))
         return rows
+
+    def chimera(self):
+        """The chimera scan (docs/chimeras.md): (hits as a CHIMERA_DTYPE array in the order (read, end, adapter, strand),
+        read_hit_offsets); on a split batch the hits of the reads it was made from."""
+        _chk(lib().talc_batch_chimera(self.ctx._h, self._h))
+        n = int(lib().talc_batch_num_chimera_hits(self._h))
+        hits = np.zeros(n, dtype=CHIMERA_DTYPE)
+        off = np.zeros(self.n_source_reads + 1, dtype=np.uint64)
+        _chk(lib().talc_batch_fetch_chimera(self.ctx._h, self._h, hits.ctypes.data, n, off.ctypes.data))
+        return hits, off
+
+    def split_pieces(self):
+        """Of a split batch: (pieces as a SPLIT_PIECE_DTYPE array, one per read of the batch; read_piece_offsets of the
+        source reads)."""
+        pieces = np.zeros(int(lib().talc_batch_num_split_pieces(self._h)), dtype=SPLIT_PIECE_DTYPE)
+        off = np.zeros(self.n_source_reads + 1, dtype=np.uint64)
+        _chk(lib().talc_batch_fetch_split(self.ctx._h, self._h, pieces.ctypes.data, off.ctypes.data))
+        return pieces, off
 
     def ends(self):
         """The end scan (docs/read_ends.md) as an ENDS_DTYPE array of one row per read; on a clipped batch the rows of the
