@@ -706,6 +706,40 @@ int talc_batch_fetch_split(talc_ctx* c, talc_batch* b, talc_split_piece* pieces,
 /* Measurement: device time (ms) of the context's last k_read_chimera and k_split_gather.  Either pointer may be NULL. */
 int talc_ctx_get_chimera_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
 
+/* Barcode demultiplexing (docs/demux.md): the sample barcode of every read, called on the device from the batch's raw bytes.
+ * B barcodes of one length m; k = floor(max_error_pct * m / 100).  Codes as above: bytes are upper-cased, a byte outside ACGT
+ * matches nothing.  End rule E(S) for a read S of L bytes: T = S[0, min(L, window)); for barcode b, D_b[e], 1 <= e <= |T|,
+ * is the Sellers distance of the barcode against the substrings of T that end at e (top row 0, first column i);
+ * d_b = min over e of D_b[e] (m when T is empty); c_b = min(d_b, k + 1).  best is the b with the smallest c_b, the lowest
+ * index among ties; it is accepted when c_best <= k: err = c_best, end = the largest e with D_best[e] = d_best,
+ * margin = (the smallest c_b of the other barcodes, k + 1 when there is none) - err; otherwise best, err, end and margin
+ * are 0.  The end calls best when it is accepted and margin >= min_margin.  The head is E(S), the tail E(revcomp(S)); each
+ * end is evaluated on the whole read.  With h and t the two calls (0: none): h == t != 0 gives barcode h, status BOTH;
+ * only h gives status HEAD_ONLY and only t TAIL_ONLY, with that barcode when both_ends is 0 and barcode 0 when it is 1;
+ * h != t, both called, gives barcode 0, status CONFLICT; neither gives 0, NONE. */
+enum talc_demux_status { TALC_DEMUX_NONE = 0, TALC_DEMUX_BOTH = 1, TALC_DEMUX_HEAD_ONLY = 2, TALC_DEMUX_TAIL_ONLY = 3, TALC_DEMUX_CONFLICT = 4 };
+typedef struct talc_demux_row {
+  uint8_t  barcode, status;                  /* barcode: 0 none, else 1-based in the order given */
+  uint8_t  head_best, head_err, head_margin; /* filled whenever the end's best is accepted, called or not */
+  uint8_t  tail_best, tail_err, tail_margin;
+  uint32_t head_end, tail_end;               /* tail_end counts from the read's end */
+} talc_demux_row;  /* 16 bytes */
+/* barcodes: NUL-terminated, comma-separated; 1..96 of one length 12..64, letters of ACGTacgt; NULL or "" switches the
+ * setting off.  max_error_pct 0..30; min_margin 0..k + 1; window 0 (: 256) or 32..4096; both_ends 0 or 1.  TALC_ERR_INVALID
+ * names the bad value and changes nothing.  The barcodes' match masks live in a small device buffer of the context, written
+ * here and freed with the context.  Never switched on: nothing of it exists. */
+int talc_ctx_set_demux(talc_ctx* c, const char* barcodes, uint32_t max_error_pct, uint32_t min_margin,
+                       uint32_t window /* 0: 256 */, int both_ends);
+/* The scan (k_read_demux) on the batch's raw bytes; on a plain batch once per setting.  talc_batch_create_clipped and
+ * talc_batch_create_split run it themselves on the reads as they came when the setting is on, and on such a batch nothing
+ * is ever launched: its rows are those.  TALC_ERR_STATE when the setting is off (and the batch holds no rows of its making). */
+int talc_batch_demux(talc_ctx* c, talc_batch* b);
+/* rows: one per source read — n_reads of a plain or clipped batch, the reads a split batch was made from.
+ * TALC_ERR_STATE when no scan has run on b. */
+int talc_batch_fetch_demux(talc_ctx* c, talc_batch* b, talc_demux_row* rows);
+/* Measurement: device time (ms) of the context's last k_read_demux; 0 after a talc_batch_demux that found the rows made. */
+int talc_ctx_get_demux_timing(const talc_ctx* c, float* scan_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

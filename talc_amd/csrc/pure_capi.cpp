@@ -8,6 +8,7 @@
 
 #include "talc_edit_plan.h"
 #include "talc_kernels_chimera.h"
+#include "talc_kernels_demux.h"
 #include "talc_pure.h"
 #include "talc_wfa.h"
 
@@ -184,5 +185,33 @@ int64_t pure_split_pieces(const ChimeraHit* hits, uint64_t n_hits, const uint64_
   for (size_t i = 0; i < pieces.size() && i < capacity; ++i) out[i] = pieces[i];
   for (uint32_t r = 0; r <= n_reads; ++r) read_piece_off[r] = pieceOff[r];
   return (int64_t)pieces.size();
+}
+
+// ---- barcode demultiplexing (docs/demux.md): k_read_demux's lanes one after another
+// out3: chunks per pattern, passes, the tails' first slot under n_barcodes barcodes
+void pure_demux_geometry(uint32_t n_barcodes, uint32_t* out3) {
+  const DemuxGeometry g = demux_geometry(n_barcodes);
+  out3[0] = g.chunks; out3[1] = g.passes; out3[2] = g.tailSlot;
+}
+// the slot of pattern (end, b) and the columns [c0, c1) of its chunk q in a text of n columns: out3 = slot, c0, c1
+void pure_demux_place(uint32_t n_barcodes, uint32_t end, uint32_t b, uint32_t q, uint32_t n, uint32_t* out3) {
+  const DemuxGeometry g = demux_geometry(n_barcodes);
+  out3[0] = demux_pattern_slot(g, end, b) + q;
+  demux_chunk(g, n, q, &out3[1], &out3[2]);
+}
+// The setting as talc_ctx_set_demux takes it, validated the same way: -1 and the message in `why` when it is refused or off.
+// One row per read.
+int pure_demux_scan(const char* barcodes, uint32_t max_error_pct, uint32_t min_margin, uint32_t window, int both_ends, const uint8_t* bases,
+                    const uint64_t* offsets, uint32_t n_reads, DemuxRow* rows, char* why, uint64_t why_len) {
+  DemuxParams P;
+  std::vector<uint64_t> peq((size_t)kDemuxMaxBarcodes * 4, 0);
+  if (why && why_len) why[0] = 0;
+  char msg[256] = "the setting is off";
+  if (!demux_make_setting(barcodes, max_error_pct, min_margin, window, both_ends, P, peq.data(), msg, sizeof msg) || !P.nBarcodes) {
+    if (why && why_len) snprintf(why, (size_t)why_len, "%s", msg);
+    return -1;
+  }
+  for (uint32_t r = 0; r < n_reads; ++r) rows[r] = demux_scan_host(bases + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), P, peq.data());
+  return 0;
 }
 }  // extern "C"

@@ -32,6 +32,7 @@
 #include "talc_kernels_strand.h"
 #include "talc_kernels_support.h"
 #include "talc_kernels_chimera.h"   // (last: the code object lays kernels out in this order; the correction's kernels keep the places they had: docs/chimeras.md)
+#include "talc_kernels_demux.h"     // (behind it, for the same reason: docs/demux.md)
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -170,6 +171,7 @@ enum CtxSpan {
   kSpanSupport,                          // k_base_support
   kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_clip_gather
   kSpanChimeraScan, kSpanChimeraGather,  // the chimera split: k_read_chimera, k_split_gather
+  kSpanDemuxScan,                        // barcode demultiplexing: k_read_demux
   kSpanCount
 };
 
@@ -193,6 +195,10 @@ struct talc_ctx {
   bool chimeraOn = false;    // talc_ctx_set_chimera (docs/chimeras.md): nothing of it exists while it is off
   uint32_t chimeraGen = 0;   // ... counts the settings, as endsGen does
   uint32_t chimeraPct = 0, chimeraMinPiece = 0;
+  bool demuxOn = false;      // talc_ctx_set_demux (docs/demux.md): nothing of it exists while it is off
+  uint32_t demuxGen = 0;     // ... counts the settings, as endsGen does
+  DemuxParams demux;         // ... as k_read_demux takes it
+  DevBuf<uint64_t> d_demux_peq;   // ... and the barcodes' match masks (kDemuxMaxBarcodes x 4 words), written when a setting is accepted
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -220,6 +226,7 @@ struct EditOut {
 //   voted                                  from the raw bytes; never dropped
 //   ended                                  from the raw bytes (of a clipped batch: from those it was made from); never dropped
 //   chimera                                from the raw bytes (of a split batch: from those it was made from); never dropped
+//   demuxed                                from the raw bytes (of a clipped or split batch: from those it was made from); never dropped
 //   encoded(encodedAuto) -> covered
 //   encoded -> solidity (raw rows), supported (RAW)
 //   encoded -> structured            (test hook; k_search consumes the region lists)
@@ -231,6 +238,7 @@ struct BatchHolds {
   bool clipped = false;       // ... and the batch was made from those rows (talc_batch_create_clipped): they are never made again
   bool chimera = false;       // h_hits: k_read_chimera under the settings chimeraGen and chimeraEndsGen; never dropped
   bool split = false;         // ... and the batch was made from those hits (talc_batch_create_split): they are never made again
+  bool demuxed = false;       // d_demux: k_read_demux under the setting demuxGen; of a clipped or split batch the rows of the reads it was made from
   bool encoded = false;       // d_codes
   bool encodedAuto = false;   // ... made with the vote's flags: k_pack, k_pack_map, k_solidity and k_base_support then take them too
   bool covered = false;       // d_cov, d_covw, d_nin
@@ -279,6 +287,8 @@ struct talc_batch {
   std::vector<SplitPiece> h_split;
   std::vector<uint64_t> h_read_split_off;
   uint32_t chimeraGen = 0, chimeraEndsGen = 0;
+  CachedBuf<DemuxRow> d_demux;        // one row per source read (k_read_demux): n_demux of them
+  uint32_t n_demux = 0, demuxGen = 0; // ... and the setting they were made under
   CachedBuf<EndRow> d_ends;           // one row per read (k_read_ends)
   uint32_t endsGen = 0;               // the setting those rows were made under
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
@@ -325,6 +335,7 @@ static_assert(sizeof(EditRow) == sizeof(talc_edit_row) && sizeof(talc_edit_row) 
 static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidity) == 24, "k_solidity writes talc_solidity records");
 static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
 static_assert(sizeof(EndRow) == sizeof(talc_end_row) && sizeof(talc_end_row) == 32, "k_read_ends writes talc_end_row records");
+static_assert(sizeof(DemuxRow) == sizeof(talc_demux_row) && sizeof(talc_demux_row) == 16 && TALC_DEMUX_CONFLICT == DEMUX_CONFLICT, "k_read_demux writes talc_demux_row records");
 static_assert(sizeof(ChimeraHit) == sizeof(talc_chimera_hit) && sizeof(talc_chimera_hit) == 16 && sizeof(SplitPiece) == sizeof(talc_split_piece) &&
               sizeof(talc_split_piece) == 16, "k_read_chimera writes talc_chimera_hit records, k_split_gather reads talc_split_piece records");
 
@@ -1366,6 +1377,7 @@ extern "C" {
 #include "talc_capi_correct.inc"
 #include "talc_capi_edits.inc"
 #include "talc_capi_support.inc"
+#include "talc_capi_demux.inc"
 #include "talc_capi_ends.inc"
 #include "talc_capi_chimera.inc"
 

@@ -114,6 +114,7 @@ int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offs
   if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
   int rc;
+  if (c->demuxOn && (rc = demux_scan(c, bp, stage.get(), stageOff.get(), n_reads))) return rc;   // (docs/demux.md: the rows of the source reads)
   if ((rc = run_chimera_scan(c, stage.get(), stageOff.get(), offsets, n_reads, bp->h_hits, bp->h_read_hit_off))) return rc;
   split_pieces(bp->h_hits.data(), bp->h_read_hit_off.data(), offsets, n_reads, c->chimeraMinPiece, bp->h_split, bp->h_read_split_off, nullptr, nullptr);
   if (bp->h_split.size() > 0xffffff00ull) return fail(TALC_ERR_INVALID, "%llu pieces: more than a batch holds", (unsigned long long)bp->h_split.size());

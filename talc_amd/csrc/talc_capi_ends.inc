@@ -93,6 +93,8 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
   HIPCHK(stageOff.alloc(c->cache, (uint64_t)n_reads + 1));
   if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (c->demuxOn)   // (docs/demux.md: the batch will not hold the reads as they came)
+    if (int rc = demux_scan(c, bp, stage.get(), stageOff.get(), n_reads)) return rc;
   if (int rc = clipped_from_staged(c, bp, stage, stageOff, offsets, n_reads)) return rc;
   *out = b.release();
   return TALC_OK;

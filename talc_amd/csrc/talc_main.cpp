@@ -66,6 +66,13 @@
 //   --LRSplit        ... and the reads are cut there on the GPU: the pieces of at least --LRMinPiece N (default 100) bases are
 //                    corrected as reads of their own (name_c1, name_c2, ...), every output is that of the pieces; writes
 //                    <o>.chimera_pieces.tsv; with --LRClip every piece is clipped
+//   --LRBarcodes FILE  a FASTA of 1..96 sample barcodes of one length (docs/demux.md): every read's barcode is called on the GPU
+//                    at its head and, reverse-complemented, at its tail, within --LRBarcodeErr PCT (0..30, default 20) per cent
+//                    of the length in edits inside --LRBarcodeWindow N (32..4096, default 256) bases, when the runner-up is at
+//                    least --LRBarcodeMargin N (default 2) edits worse; --LRBarcodeBothEnds: only reads whose ends agree get a
+//                    barcode; writes <o>.demux.tsv (one line per read as it came), <o>.demux_counts.tsv and one summary line;
+//                    --LRDemuxOut: every record of <o>.fa also goes to <o>.<name>.fa or <o>.unclassified.fa (a piece of
+//                    --LRSplit where its source read goes)
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -164,6 +171,12 @@ struct Options {
   bool haveLrChimeraErr = false, haveLrMinPiece = false;
   bool lrChimeraScan() const { return lrChimeras || lrSplit; }   // the chimera scan is on
   bool lrEnds() const { return !lrAdapters.empty() || lrPolyA > 0; }   // the long-read end clean-up is on
+  std::string lrBarcodesFile;               // --LRBarcodes (docs/demux.md)
+  std::vector<std::string> lrBarcodeNames, lrBarcodeSeqs;   // ... its records, in order
+  uint32_t lrBarcodeErr = 20, lrBarcodeMargin = 2, lrBarcodeWindow = 256;   // --LRBarcodeErr, --LRBarcodeMargin, --LRBarcodeWindow
+  bool haveLrBarcodeErr = false, haveLrBarcodeMargin = false, haveLrBarcodeWindow = false;
+  bool lrBarcodeBothEnds = false, lrDemuxOut = false;   // --LRBarcodeBothEnds, --LRDemuxOut
+  bool lrDemux() const { return !lrBarcodesFile.empty(); }   // barcode demultiplexing is on
 };
 
 void usage(FILE* f) {
@@ -241,6 +254,15 @@ void usage(FILE* f) {
           "                              their own (name_c1, name_c2, ...); writes <o>.chimera_pieces.tsv; combines with --LRClip\n"
           "  --LRChimeraErr INT          with --LRChimeras / --LRSplit: edits allowed in percent of the adapter's length, 0..30, default 10\n"
           "  --LRMinPiece INT            with --LRChimeras / --LRSplit: pieces shorter than this are dropped, default 100\n"
+          "  --LRBarcodes FILE           FASTA of 1..96 sample barcodes of one length, 12..64 letters of ACGT: every read's barcode is\n"
+          "                              called on the GPU at its head and, reverse-complemented, at its tail; writes <o>.demux.tsv and\n"
+          "                              <o>.demux_counts.tsv (docs/demux.md); names: 1..32 of A-Za-z0-9_.-, unique, not 'unclassified'\n"
+          "  --LRBarcodeErr INT          with --LRBarcodes: edits allowed in percent of the barcode's length, 0..30, default 20\n"
+          "  --LRBarcodeMargin INT       with --LRBarcodes: an end calls its best barcode when the runner-up is at least this many edits\n"
+          "                              worse, 0..k + 1, default 2\n"
+          "  --LRBarcodeWindow INT       with --LRBarcodes: bases of each end that are searched, 32..4096, default 256\n"
+          "  --LRBarcodeBothEnds         with --LRBarcodes: only reads whose two ends call the same barcode get it\n"
+          "  --LRDemuxOut                with --LRBarcodes: every record of <o>.fa also goes to <o>.<name>.fa or <o>.unclassified.fa\n"
           "  -h, --help / --version\n");
 }
 
@@ -257,6 +279,43 @@ double num(const char* s, const char* name) {
 }
 void range(double v, double lo, double hi, const char* name) {
   if (v < lo || v > hi) parse_error(std::string("value out of range for ") + name);
+}
+
+// --LRBarcodes: the FASTA's records into o.lrBarcodeNames / o.lrBarcodeSeqs.  The names become file names; every fault is a
+// parse error (exit 1, nothing written).
+void loadBarcodes(Options& o) {
+  std::ifstream f(o.lrBarcodesFile);
+  if (!f) parse_error("LRBarcodes: cannot read " + o.lrBarcodesFile);
+  std::string line;
+  while (std::getline(f, line)) {
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    if (line.empty()) continue;
+    if (line[0] == '>') {
+      const std::string name = line.substr(1, line.find_first_of(" \t") == std::string::npos ? std::string::npos : line.find_first_of(" \t") - 1);
+      if (name.empty() || name.size() > 32 || name.find_first_not_of("ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789_.-") != std::string::npos)
+        parse_error("LRBarcodes: the name '" + name + "' cannot be a barcode's: 1..32 of A-Za-z0-9_.- are expected");
+      if (name == "unclassified") parse_error("LRBarcodes: the name 'unclassified' is taken by the reads without a barcode");
+      for (const std::string& other : o.lrBarcodeNames)
+        if (other == name) parse_error("LRBarcodes: the name '" + name + "' is given twice");
+      if (o.lrBarcodeNames.size() == 96) parse_error("LRBarcodes: more than 96 barcodes");
+      o.lrBarcodeNames.push_back(name);
+      o.lrBarcodeSeqs.emplace_back();
+    } else {
+      if (o.lrBarcodeSeqs.empty()) parse_error("LRBarcodes: " + o.lrBarcodesFile + " does not start with a '>' line");
+      o.lrBarcodeSeqs.back() += line;
+    }
+  }
+  if (o.lrBarcodeSeqs.empty()) parse_error("LRBarcodes: no barcode in " + o.lrBarcodesFile);
+  for (size_t b = 0; b < o.lrBarcodeSeqs.size(); ++b) {
+    const std::string& v = o.lrBarcodeSeqs[b];
+    if (v.size() < 12 || v.size() > 64) parse_error("LRBarcodes: the barcode " + o.lrBarcodeNames[b] + " has " + std::to_string(v.size()) + " letters: 12..64 are expected");
+    if (v.find_first_not_of("ACGTacgt") != std::string::npos) parse_error("LRBarcodes: the barcode " + o.lrBarcodeNames[b] + " has a letter that is not one of ACGT");
+    if (v.size() != o.lrBarcodeSeqs[0].size())
+      parse_error("LRBarcodes: the barcode " + o.lrBarcodeNames[b] + " has " + std::to_string(v.size()) + " letters, " + o.lrBarcodeNames[0] + " has " +
+                  std::to_string(o.lrBarcodeSeqs[0].size()) + ": one length for all");
+  }
+  const uint32_t k = o.lrBarcodeErr * (uint32_t)o.lrBarcodeSeqs[0].size() / 100u;
+  if (o.lrBarcodeMargin > k + 1) parse_error("value out of range for LRBarcodeMargin: " + std::to_string(o.lrBarcodeMargin) + " is above k + 1 = " + std::to_string(k + 1));
 }
 
 Options parse(int argc, const char** argv) {
@@ -372,6 +431,24 @@ Options parse(int argc, const char** argv) {
       if (v != (double)(long long)v || v < 0 || v > 2e9) parse_error("value out of range for LRMinPiece: 0..2000000000");
       o.lrMinPiece = (uint32_t)v; o.haveLrMinPiece = true;
     }
+    else if (a == "--LRBarcodes") o.lrBarcodesFile = need(i);
+    else if (a == "--LRBarcodeErr") {
+      const double v = num(need(i), "LRBarcodeErr");
+      if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for LRBarcodeErr: 0..30");
+      o.lrBarcodeErr = (uint32_t)v; o.haveLrBarcodeErr = true;
+    }
+    else if (a == "--LRBarcodeMargin") {
+      const double v = num(need(i), "LRBarcodeMargin");
+      if (v != (double)(long long)v || v < 0 || v > 20) parse_error("value out of range for LRBarcodeMargin: 0..k + 1");
+      o.lrBarcodeMargin = (uint32_t)v; o.haveLrBarcodeMargin = true;
+    }
+    else if (a == "--LRBarcodeWindow") {
+      const double v = num(need(i), "LRBarcodeWindow");
+      if (v != (double)(long long)v || v < 32 || v > 4096) parse_error("value out of range for LRBarcodeWindow: 32..4096");
+      o.lrBarcodeWindow = (uint32_t)v; o.haveLrBarcodeWindow = true;
+    }
+    else if (a == "--LRBarcodeBothEnds") o.lrBarcodeBothEnds = true;
+    else if (a == "--LRDemuxOut") o.lrDemuxOut = true;
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
     else if (a == "-h" || a == "--help") { usage(stdout); exit(0); }
     else if (a == "--version") { std::cout << "talc version: 1.01\nLast update: September 2019\n"; exit(0); }
@@ -413,6 +490,12 @@ Options parse(int argc, const char** argv) {
   if (o.haveLrChimeraErr && !(o.lrChimeraScan() && !o.lrAdapters.empty())) parse_error("--LRChimeraErr needs --LRAdapter and --LRChimeras or --LRSplit");
   if (o.haveLrMinPiece && !(o.lrChimeraScan() && !o.lrAdapters.empty())) parse_error("--LRMinPiece needs --LRAdapter and --LRChimeras or --LRSplit");
   if (o.lrPolyA > o.lrEndWindow) parse_error("value out of range for LRPolyA: " + std::to_string(o.lrPolyA) + " is above LREndWindow " + std::to_string(o.lrEndWindow));
+  if (o.haveLrBarcodeErr && !o.lrDemux()) parse_error("--LRBarcodeErr needs --LRBarcodes");
+  if (o.haveLrBarcodeMargin && !o.lrDemux()) parse_error("--LRBarcodeMargin needs --LRBarcodes");
+  if (o.haveLrBarcodeWindow && !o.lrDemux()) parse_error("--LRBarcodeWindow needs --LRBarcodes");
+  if (o.lrBarcodeBothEnds && !o.lrDemux()) parse_error("--LRBarcodeBothEnds needs --LRBarcodes");
+  if (o.lrDemuxOut && !o.lrDemux()) parse_error("--LRDemuxOut needs --LRBarcodes");
+  if (o.lrDemux()) loadBarcodes(o);
   o.p.use_junctions = o.useJ ? 1 : 0;
   return o;
 }
@@ -438,6 +521,12 @@ void outputConfig(const Options& o, const std::string& statFile) {
   if (o.lrSplit) f << "LRSplit=1" << "\n";
   if (o.haveLrChimeraErr) f << "LRChimeraErr=" << o.lrChimeraErr << "\n";
   if (o.haveLrMinPiece) f << "LRMinPiece=" << o.lrMinPiece << "\n";
+  if (o.lrDemux()) f << "LRBarcodes=" << o.lrBarcodesFile << "\n";
+  if (o.haveLrBarcodeErr) f << "LRBarcodeErr=" << o.lrBarcodeErr << "\n";
+  if (o.haveLrBarcodeMargin) f << "LRBarcodeMargin=" << o.lrBarcodeMargin << "\n";
+  if (o.haveLrBarcodeWindow) f << "LRBarcodeWindow=" << o.lrBarcodeWindow << "\n";
+  if (o.lrBarcodeBothEnds) f << "LRBarcodeBothEnds=1" << "\n";
+  if (o.lrDemuxOut) f << "LRDemuxOut=1" << "\n";
   if (o.bothStrands) f << "Both strands? 1" << "\n";
   if (o.haveSrMinQual) f << "SRMinQual=" << o.srMinQual << "\n";
   for (const std::string& ad : o.srAdapters) f << "SRAdapter=" << ad << "\n";
@@ -466,12 +555,15 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends, chimera, chimeraPieces;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends, chimera, chimeraPieces, demux, demuxCounts, prefix;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
         trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv"),
         fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq"), ends(prefix + ".ends.tsv"),
-        chimera(prefix + ".chimera.tsv"), chimeraPieces(prefix + ".chimera_pieces.tsv") {}
+        chimera(prefix + ".chimera.tsv"), chimeraPieces(prefix + ".chimera_pieces.tsv"), demux(prefix + ".demux.tsv"), demuxCounts(prefix + ".demux_counts.tsv"),
+        prefix(prefix) {}
+  // --LRDemuxOut: where the records of barcode b (0-based; the number of barcodes: unclassified) go
+  std::string demuxFa(const Options& o, size_t b) const { return prefix + "." + (b < o.lrBarcodeNames.size() ? o.lrBarcodeNames[b] : std::string("unclassified")) + ".fa"; }
 };
 
 // the temporary dumps of -qm jellyfish2 -jf2: gone once the table is built, whichever way that ends
@@ -681,6 +773,11 @@ struct Chunk {
   uint64_t endSums[4] = {0, 0, 0, 0};   // of the batch: reads, those with an adapter at either end, those with a poly run, bases outside the kept intervals
   std::string chimeraText, chimeraPiecesText;   // ... and to <o>.chimera.tsv, <o>.chimera_pieces.tsv (--LRChimeras, --LRSplit)
   uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch: reads, hits, reads with a hit, pieces kept, pieces dropped, their bases
+  std::string demuxText;                // ... and to <o>.demux.tsv (--LRBarcodes)
+  uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch: reads, classified at both ends, head only, tail only, conflicts, the rest
+  std::vector<uint64_t> demuxCounts;    // per barcode, then unclassified: reads, their bases as they came
+  std::vector<uint8_t> recBarcode;      // the barcode of every record's source read (0: none)
+  std::vector<size_t> textEnd;          // --LRDemuxOut: where every record ends in `text`
   // the read was corrected as under -rev: the whole file's -rev, or the read's own vote
   bool reversed(const talc_params& p, size_t r) const { return p.reverse || (!strand.empty() && strand[r].reverse); }
 };
@@ -715,6 +812,33 @@ void formatEnds(Chunk& k, const talc_end_row* rows) {
     k.endSums[1] += (w.head_adapter || w.tail_adapter) ? 1 : 0;
     k.endSums[2] += (w.head_poly_len || w.tail_poly_len) ? 1 : 0;
     k.endSums[3] += L - w.kept_len;
+  }
+}
+
+// the lines of <o>.demux.tsv for one batch from the scan's rows (k.ids, k.offsets: the reads as they came), the sums and the
+// counts; k.recBarcode: every read's barcode
+const char* const kDemuxHeader = "read_name\traw_length\tbarcode\tstatus\thead_barcode\thead_err\thead_margin\thead_end\ttail_barcode\ttail_err\ttail_margin\ttail_end\n";
+void formatDemux(const Options& o, Chunk& k, const talc_demux_row* rows) {
+  const size_t B = o.lrBarcodeNames.size();
+  auto name = [&](uint32_t b) -> const char* { return b >= 1 && b <= B ? o.lrBarcodeNames[b - 1].c_str() : "-"; };
+  k.demuxCounts.assign(2 * (B + 1), 0);
+  k.recBarcode.resize(k.ids.size());
+  char num[256];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const talc_demux_row& w = rows[r];
+    const uint64_t L = k.offsets[r + 1] - k.offsets[r];
+    const int m = snprintf(num, sizeof num, "\t%llu\t%s\t%u\t%s\t%u\t%u\t%u\t%s\t%u\t%u\t%u\n", (unsigned long long)L, name(w.barcode), w.status, name(w.head_best),
+                           w.head_err, w.head_margin, w.head_end, name(w.tail_best), w.tail_err, w.tail_margin, w.tail_end);
+    k.demuxText += k.ids[r];
+    k.demuxText.append(num, (size_t)m);
+    const uint32_t b = w.barcode >= 1 && w.barcode <= B ? w.barcode : 0;
+    k.recBarcode[r] = (uint8_t)b;
+    const size_t slot = b ? b - 1 : B;
+    k.demuxCounts[2 * slot] += 1;
+    k.demuxCounts[2 * slot + 1] += L;
+    k.demuxSums[0] += 1;
+    if (b) k.demuxSums[w.status == TALC_DEMUX_BOTH ? 1 : w.status == TALC_DEMUX_HEAD_ONLY ? 2 : 3] += 1;
+    else k.demuxSums[w.status == TALC_DEMUX_CONFLICT ? 4 : 5] += 1;
   }
 }
 
@@ -887,6 +1011,7 @@ void formatChunk(const Options& o, Chunk& k, const char* recs, const uint64_t* o
     const char* q = recs + oo[r];
     const size_t L = (size_t)(oo[r + 1] - oo[r]);
     for (size_t p = 0; p < L; p += 70) { const size_t m = std::min<size_t>(70, L - p); memcpy(w, q + p, m); w += m; *w++ = '\n'; }
+    if (o.lrDemuxOut) k.textEnd.push_back((size_t)(w - k.text.data()));
   }
   k.text.resize((size_t)(w - k.text.data()));
 }
@@ -971,6 +1096,7 @@ struct PipelineTotals {
   uint64_t editSums[6] = {0, 0, 0, 0, 0, 0};   // --corr-edits: Chunk::editSums
   uint64_t endSums[4] = {0, 0, 0, 0};          // --LRAdapter / --LRPolyA: Chunk::endSums
   uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // --LRChimeras / --LRSplit: Chunk::chimeraSums
+  uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};     // --LRBarcodes: Chunk::demuxSums
   WorkerTally workers;
 };
 
@@ -1004,7 +1130,10 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf, cf, cpf;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf, cf, cpf, df;
+    std::vector<std::ofstream> bf;        // --LRDemuxOut: one per barcode, then unclassified
+    uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<uint64_t> demuxCounts;    // Chunk::demuxCounts, summed
     double busy = 0;
     uint64_t strandSums[2] = {0, 0}, endSums[4] = {0, 0, 0, 0}, chimeraSums[6] = {0, 0, 0, 0, 0, 0};
     uint64_t solSums[4] = {0, 0, 0, 0}, pieceSums[4] = {0, 0, 0, 0}, editSums[6] = {0, 0, 0, 0, 0, 0};
@@ -1102,6 +1231,19 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
       wr.cpf << kChimeraPiecesHeader;
     }
   }
+  if (o_.lrDemux()) {
+    wr.df.open(files_.demux, std::ios_base::trunc);
+    if (!wr.df) return fail("cannot write " + files_.demux);
+    wr.df << kDemuxHeader;
+    wr.demuxCounts.assign(2 * (o_.lrBarcodeNames.size() + 1), 0);
+    if (o_.lrDemuxOut) {   // (a barcode without a read keeps an empty file)
+      wr.bf.resize(o_.lrBarcodeNames.size() + 1);
+      for (size_t b = 0; b < wr.bf.size(); ++b) {
+        wr.bf[b].open(files_.demuxFa(o_, b), std::ios_base::trunc);
+        if (!wr.bf[b]) return fail("cannot write " + files_.demuxFa(o_, b));
+      }
+    }
+  }
   if (batchBytesEstimate_) {
     // the page-locked buffers are allocated once, at the estimated size, by as many threads as there are buffers (an
     // allocation of a few hundred MB takes tens of milliseconds)
@@ -1129,6 +1271,16 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.tqf.is_open()) wr.tqf.close();
   if (wr.pqf.is_open()) wr.pqf.close();
   if (wr.xf.is_open()) wr.xf.close();
+  if (wr.df.is_open()) wr.df.close();
+  for (auto& f : wr.bf) f.close();
+  if (o_.lrDemux() && !q_.failed) {
+    std::ofstream cf(files_.demuxCounts, std::ios_base::trunc);
+    if (!cf) return fail("cannot write " + files_.demuxCounts);
+    cf << "barcode\treads\tbases\n";
+    const size_t B = o_.lrBarcodeNames.size();
+    for (size_t b = 0; b <= B; ++b) cf << (b < B ? o_.lrBarcodeNames[b] : std::string("unclassified")) << "\t" << wr.demuxCounts[2 * b] << "\t" << wr.demuxCounts[2 * b + 1] << "\n";
+  }
+  for (int i = 0; i < 6; ++i) tot.demuxSums[i] = wr.demuxSums[i];
   for (int i = 0; i < 2; ++i) tot.strandSums[i] = wr.strandSums[i];
   for (int i = 0; i < 4; ++i) { tot.solSums[i] = wr.solSums[i]; tot.pieceSums[i] = wr.pieceSums[i]; tot.endSums[i] = wr.endSums[i]; }
   for (int i = 0; i < 6; ++i) tot.chimeraSums[i] = wr.chimeraSums[i];
@@ -1201,6 +1353,11 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
       if (talc_ctx_set_ends(made, adapters.c_str(), o_.lrAdapterErr, o_.lrPolyA, o_.lrEndWindow) != TALC_OK) { fail(talc_last_error()); return; }
     }
     if (o_.lrChimeraScan() && talc_ctx_set_chimera(made, 1, o_.lrChimeraErr, o_.lrMinPiece) != TALC_OK) { fail(talc_last_error()); return; }
+    if (o_.lrDemux()) {
+      std::string barcodes;
+      for (const std::string& bc : o_.lrBarcodeSeqs) barcodes += (barcodes.empty() ? "" : ",") + bc;
+      if (talc_ctx_set_demux(made, barcodes.c_str(), o_.lrBarcodeErr, o_.lrBarcodeMargin, o_.lrBarcodeWindow, o_.lrBarcodeBothEnds ? 1 : 0) != TALC_OK) { fail(talc_last_error()); return; }
+    }
     t.ctx += since(tc0);
   }
   HostBuf outb;   // the corrected records of this worker's batches, kept for the whole run
@@ -1252,6 +1409,11 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
                               : talc_batch_create(ctx, inBufs_[c.inBuf].p, c.offsets.data(), n, &made);
   if (mrc != TALC_OK) return fail(talc_last_error());
   BatchPtr b(made);
+  if (o_.lrDemux()) {   // the scan sees the reads as they came: a clipped or split batch ran it on them while it was made
+    std::vector<talc_demux_row> rows(std::max<uint32_t>(n, 1));
+    if (talc_batch_demux(ctx, b.get()) != TALC_OK || talc_batch_fetch_demux(ctx, b.get(), rows.data()) != TALC_OK) return fail(talc_last_error());
+    formatDemux(o_, c, rows.data());
+  }
   if (o_.lrChimeraScan()) {   // the scan sees the reads as they came (never a clipped batch: parse()); with --LRSplit it has made the batch, whose reads are the kept pieces from here on
     if (talc_batch_chimera(ctx, b.get()) != TALC_OK) return fail(talc_last_error());
     std::vector<talc_chimera_hit> hits(talc_batch_num_chimera_hits(b.get()));
@@ -1267,6 +1429,11 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
       static_assert(sizeof(talc::SplitPiece) == sizeof(talc_split_piece), "one record");
       if (np != ruled.size() || (np && memcmp(pieces.data(), ruled.data(), np * sizeof(talc_split_piece)) != 0))   // (the sums above are those of these very rows)
         return fail("the split batch's " + std::to_string(np) + " pieces are not the " + std::to_string(ruled.size()) + " the piece rule gives for its hits");
+      if (o_.lrDemux()) {   // a piece goes where its source read goes
+        std::vector<uint8_t> of(np);
+        for (size_t p = 0; p < np; ++p) of[p] = c.recBarcode[pieces[p].read];
+        c.recBarcode.swap(of);
+      }
       takePieces(c, pieces.data(), np);
       n = (uint32_t)np;
     }
@@ -1383,6 +1550,17 @@ void Pipeline::writerMain(WriterSide& w) {
     if (w.cf.is_open()) w.cf.write(c->chimeraText.data(), (std::streamsize)c->chimeraText.size());
     if (w.cpf.is_open()) w.cpf.write(c->chimeraPiecesText.data(), (std::streamsize)c->chimeraPiecesText.size());
     for (int i = 0; i < 6; ++i) w.chimeraSums[i] += c->chimeraSums[i];
+    if (w.df.is_open()) {
+      w.df.write(c->demuxText.data(), (std::streamsize)c->demuxText.size());
+      for (int i = 0; i < 6; ++i) w.demuxSums[i] += c->demuxSums[i];
+      for (size_t i = 0; i < c->demuxCounts.size() && i < w.demuxCounts.size(); ++i) w.demuxCounts[i] += c->demuxCounts[i];
+      size_t from = 0;
+      for (size_t r = 0; r < c->textEnd.size() && r < c->recBarcode.size() && !w.bf.empty(); ++r) {
+        const size_t slot = c->recBarcode[r] ? c->recBarcode[r] - 1u : w.bf.size() - 1;
+        if (slot < w.bf.size() && c->textEnd[r] <= c->text.size()) w.bf[slot].write(c->text.data() + from, (std::streamsize)(c->textEnd[r] - from));
+        from = c->textEnd[r];
+      }
+    }
     w.busy += since(tw0);
     std::lock_guard<std::mutex> g(q_.mu);
     ++q_.nextToWrite;
@@ -1548,6 +1726,10 @@ static int run(int argc, const char** argv) {
       if (const int ec = buildTable(o, sw, table, tableSize)) return ec;
   }
   t[2] = Clock::now();
+  if (!haveTable && o.lrDemux()) {
+    std::cerr << "talc: --LRBarcodes looks at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
+    return 2;
+  }
   if (!haveTable && o.lrEnds()) {
     std::cerr << "talc: --LRAdapter / --LRPolyA look at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
     return 2;
@@ -1606,6 +1788,11 @@ static int run(int argc, const char** argv) {
     const uint64_t* y = totals.chimeraSums;
     std::cout << "[TALC]: chimeras: " << y[0] << " reads, " << y[1] << " hits in " << y[2] << " reads, " << y[3] << " pieces kept, " << y[4]
               << " pieces dropped (" << y[5] << " bases)" << std::endl;
+  }
+  if (o.lrDemux()) {
+    const uint64_t* y = totals.demuxSums;
+    std::cout << "[TALC]: demux: " << y[0] << " reads, " << y[1] + y[2] + y[3] << " classified (" << y[1] << " both ends, " << y[2] << " head only, " << y[3]
+              << " tail only), " << y[4] << " conflicts, " << y[5] << " without a barcode" << std::endl;
   }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   if (sw.timing && o.fastq && ndev)

@@ -54,6 +54,26 @@ def chimera_geometry(length, n_patterns):
     chunk = min(CHIMERA_CHUNK_MAX, max(CHIMERA_CHUNK_MIN, -(-length // lanes)))
     chunk += (4 - chunk % 8) % 8
     return lanes, chunk, lanes * chunk
+# talc_demux_row and its status codes (docs/demux.md)
+DEMUX_DTYPE = np.dtype([("barcode", "u1"), ("status", "u1"), ("head_best", "u1"), ("head_err", "u1"), ("head_margin", "u1"),
+                        ("tail_best", "u1"), ("tail_err", "u1"), ("tail_margin", "u1"), ("head_end", "<u4"), ("tail_end", "<u4")])
+DEMUX_NONE, DEMUX_BOTH, DEMUX_HEAD_ONLY, DEMUX_TAIL_ONLY, DEMUX_CONFLICT = range(5)
+DEMUX_MAX_BARCODES, DEMUX_DEFAULT_WINDOW = 96, 256
+# the defaults of the command line and of Context.set_demux (docs/demux.md, "Why 20 per cent and a margin of 2")
+DEMUX_DEFAULT_ERR, DEMUX_DEFAULT_MARGIN = 20, 2
+
+
+def demux_geometry(n_barcodes, window=DEMUX_DEFAULT_WINDOW):
+    """How k_read_demux deals its 2 * n_barcodes patterns (end, barcode) over the lanes of its wave (talc_kernels_demux.h:
+    demux_geometry), for tests that aim at its borders: (chunks, passes, tail_slot, chunk).  A slot is lane + 64 * pass.
+    Up to 16 barcodes: one pass, every pattern gets `chunks` lanes, each `chunk` columns of a text of `window` columns behind
+    a warm-up; pattern (end, b) starts at slot (end * n_barcodes + b) * chunks.  From 17 on: chunks is 1, the head of barcode
+    b is slot b and its tail slot tail_slot + b, tail_slot = n_barcodes rounded up to 32."""
+    if 2 * n_barcodes <= 32:
+        chunks = 64 // (2 * n_barcodes)
+        return chunks, 1, n_barcodes * chunks, -(-window // chunks)
+    tail_slot = -(-n_barcodes // 32) * 32
+    return 1, -(-(tail_slot + n_barcodes) // 64), tail_slot, window
 # talc_support_params (docs/base_support.md)
 SUPPORT_RAW, SUPPORT_RECORD = 0, 1
 # the k-mer spectrum (docs/kmer_spectrum.md): high 0 means the default; the largest high the kernel's LDS histogram holds
@@ -232,6 +252,10 @@ def _abi():
         "talc_batch_num_split_pieces": (u64, [vp]),
         "talc_batch_fetch_split": (i32, [vp, vp, vp, vp]),
         "talc_ctx_get_chimera_timing": (i32, [vp, vp, vp]),
+        "talc_ctx_set_demux": (i32, [vp, txt, u32, u32, u32, i32]),
+        "talc_batch_demux": (i32, [vp, vp]),
+        "talc_batch_fetch_demux": (i32, [vp, vp, vp]),
+        "talc_ctx_get_demux_timing": (i32, [vp, vp]),
         "talc_test_set_poison": (i32, [i32, u32]),
         "talc_test_get_poison": (i32, [vp, vp]),
         "talc_test_guard_report": (i32, [vp]),
@@ -749,6 +773,22 @@ class Context(_Owner):
         _chk(lib().talc_ctx_get_chimera_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_demux(self, barcodes=(), max_error_pct=DEMUX_DEFAULT_ERR, min_margin=DEMUX_DEFAULT_MARGIN, window=DEMUX_DEFAULT_WINDOW, both_ends=False):
+        """Barcode demultiplexing (docs/demux.md): 1..96 barcodes of one length (12..64 letters), searched within
+        max_error_pct (0..30) per cent of that length in edits inside the first `window` (32..4096) bytes of every read and,
+        reverse-complemented, inside the last; an end calls its best barcode when the runner-up is at least min_margin edits
+        worse; both_ends: only reads whose two ends call the same barcode get it.  No barcodes: off."""
+        if isinstance(barcodes, (str, bytes)):
+            barcodes = [barcodes]
+        text = ",".join(a.decode() if isinstance(a, bytes) else a for a in barcodes)
+        _chk(lib().talc_ctx_set_demux(self._h, text.encode(), int(max_error_pct), int(min_margin), int(window), 1 if both_ends else 0))
+
+    def demux_timing(self):
+        """Device time (ms) of the context's last k_read_demux; 0.0 after a Batch.demux() that found its rows made."""
+        a = C.c_float()
+        _chk(lib().talc_ctx_get_demux_timing(self._h, C.byref(a)))
+        return a.value
+
     def support_timing(self):
         """Device time (ms) of the k_base_support launch of the context's last Batch.support()."""
         a = C.c_float()
@@ -973,6 +1013,14 @@ class Batch(_Owner):
         off = np.zeros(self.n_source_reads + 1, dtype=np.uint64)
         _chk(lib().talc_batch_fetch_split(self.ctx._h, self._h, pieces.ctypes.data, off.ctypes.data))
         return pieces, off
+
+    def demux(self):
+        """The barcode calls (docs/demux.md) as a DEMUX_DTYPE array of one row per source read: the reads of a plain or
+        clipped batch, the reads a split batch was made from."""
+        _chk(lib().talc_batch_demux(self.ctx._h, self._h))
+        rows = np.zeros(self.n_source_reads, dtype=DEMUX_DTYPE)
+        _chk(lib().talc_batch_fetch_demux(self.ctx._h, self._h, rows.ctypes.data))
+        return rows
 
     def ends(self):
         """The end scan (docs/read_ends.md) as an ENDS_DTYPE array of one row per read; on a clipped batch the rows of the
