@@ -740,6 +740,46 @@ int talc_batch_fetch_demux(talc_ctx* c, talc_batch* b, talc_demux_row* rows);
 /* Measurement: device time (ms) of the context's last k_read_demux; 0 after a talc_batch_demux that found the rows made. */
 int talc_ctx_get_demux_timing(const talc_ctx* c, float* scan_ms);
 
+/* UMI read-out (docs/umi.md): one degenerate pattern found at either end of every read, aligned on the device, and the
+ * read's bases under the pattern's degenerate positions reported.  pattern: m = 12..64 letters of ACGTRYSWKMBDHVN in
+ * either case; a letter stands for its IUPAC set of bases; the degenerate positions are those whose set has more than one
+ * base, u = 1..32 of them.  k = floor(max_error_pct * m / 100).  Codes as above: a read byte is upper-cased, a byte outside
+ * ACGT matches nothing.  End rule U(S) for a read S of L bytes, T = S[0, min(L, window)): D[i][j] is the Sellers matrix of
+ * the pattern against T (top row 0, first column i, substitution 0 when T[j-1] is in the set of pattern letter i, else 1,
+ * indel 1); d = min over j >= 1 of D[m][j], m for an empty T; the end is accepted when d <= k: err = d, stop = the largest
+ * j with D[m][j] = d.  The canonical alignment is the traceback from (m, stop) that at (i, j), i > 0, takes the first that
+ * holds of: the diagonal, when j > 0 and D[i-1][j-1] + cost = D[i][j]; up, when D[i-1][j] + 1 = D[i][j] (pattern letter i
+ * faces a gap); left (T[j-1] is an inserted base).  It ends at i = 0, and start is the j it ends at.  The UMI is u
+ * characters, one per degenerate position in pattern order: the upper-cased text base the diagonal step put under it
+ * (mismatches included), N when that byte is not of ACGT, - when the position faces a gap.  The head is U(S), the tail
+ * U(revcomp(S)): the UMI of a tail hit is in the pattern's orientation, start and stop count from the read's end.  The
+ * read's UMI is that of the accepted end with the smaller err, the head's on equal err. */
+typedef struct talc_umi_row {
+  uint8_t  end, err, other_err, umi_len;     /* end: 1 head, 2 tail, 0 none; other_err: the other end's err when it is
+                                                accepted too, else 255; umi_len: u, 0 without a UMI */
+  uint32_t start, stop;                      /* 0 without a UMI */
+  uint32_t kept_start, kept_len;             /* always set: cut_head = stop when end = 1, cut_tail = stop when end = 2;
+                                                with head and tail what the end clean-up claims (0 on a plain batch and
+                                                without it), head' = max(head, cut_head), tail' likewise:
+                                                kept_start = head', kept_len = L - head' - min(tail', L - head') */
+  char     umi[32];                          /* zero-padded */
+  uint32_t pad_;
+} talc_umi_row;  /* 56 bytes */
+/* pattern: NUL-terminated; NULL or "" switches the setting off.  max_error_pct 0..30; window 0 (: 256) or 32..4096.
+ * TALC_ERR_INVALID names the bad value and changes nothing.  Never switched on: nothing of it exists.  With the setting
+ * on, talc_batch_create_clipped (allowed then with the end clean-up off too) and the clipping of talc_batch_create_split
+ * run the scan on the text the end scan runs on, once per read or piece, and cut at kept_start, kept_len; the end rows
+ * stay what the end scan wrote. */
+int talc_ctx_set_umi(talc_ctx* c, const char* pattern, uint32_t max_error_pct, uint32_t window /* 0: 256 */);
+/* The scan (k_read_umi) on the batch's raw bytes; on a plain batch once per setting.  On a clipped or split batch nothing
+ * is ever launched: its rows are those of the scan that made it.  TALC_ERR_STATE when the setting is off and the batch
+ * holds no rows. */
+int talc_batch_umi(talc_ctx* c, talc_batch* b);
+/* rows: one per read of the batch.  TALC_ERR_STATE when no scan has run on b. */
+int talc_batch_fetch_umi(talc_ctx* c, talc_batch* b, talc_umi_row* rows);
+/* Measurement: device time (ms) of the context's last k_read_umi; 0 after a talc_batch_umi that found the rows made. */
+int talc_ctx_get_umi_timing(const talc_ctx* c, float* scan_ms);
+
 /* The rows Read::outputBasicReadStats (Read.cpp:418-433) appends to <o>.stats_basics.txt — the reference has the call
  * commented out (main.cpp:305), so its file only ever holds the header; the numbers exist on the device anyway.
  * stats5[5 r ..] = {row written (length > K, main.cpp:262), raw length, sum over the IN regions of end - start + 1 as

@@ -9,6 +9,7 @@
 #include "talc_edit_plan.h"
 #include "talc_kernels_chimera.h"
 #include "talc_kernels_demux.h"
+#include "talc_kernels_umi.h"
 #include "talc_pure.h"
 #include "talc_wfa.h"
 
@@ -213,5 +214,28 @@ int pure_demux_scan(const char* barcodes, uint32_t max_error_pct, uint32_t min_m
   }
   for (uint32_t r = 0; r < n_reads; ++r) rows[r] = demux_scan_host(bases + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), P, peq.data());
   return 0;
+}
+
+// ---- UMI read-out (docs/umi.md): k_read_umi's lanes one after another
+// The setting as talc_ctx_set_umi takes it, validated the same way: -1 and the message in `why` when it is refused or off.
+// One row per read, as on a plain batch.
+int pure_umi_scan(const char* pattern, uint32_t max_error_pct, uint32_t window, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
+                  UmiRow* rows, char* why, uint64_t why_len) {
+  UmiParams P;
+  if (why && why_len) why[0] = 0;
+  char msg[256] = "the setting is off";
+  if (!umi_make_setting(pattern, max_error_pct, window, P, msg, sizeof msg) || !P.m) {
+    if (why && why_len) snprintf(why, (size_t)why_len, "%s", msg);
+    return -1;
+  }
+  for (uint32_t r = 0; r < n_reads; ++r) rows[r] = umi_scan_host(bases + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), P);
+  return 0;
+}
+// the kept interval of a read of L bytes: out2 = kept_start, kept_len (umi_row_fill); end 0, 1, 2
+void pure_umi_kept(uint32_t L, uint32_t end, uint32_t stop, uint32_t head, uint32_t tail, uint32_t* out2) {
+  UmiRow row;
+  const UmiPick pk = {end, 0u, 255u, stop};
+  umi_row_fill(row, pk, 0u, 0u, L, head, tail);
+  out2[0] = row.keptStart; out2[1] = row.keptLen;
 }
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "talc_kernels_support.h"
 #include "talc_kernels_chimera.h"   // (last: the code object lays kernels out in this order; the correction's kernels keep the places they had: docs/chimeras.md)
 #include "talc_kernels_demux.h"     // (behind it, for the same reason: docs/demux.md)
+#include "talc_kernels_umi.h"       // (and last of all, for the same reason: docs/umi.md)
 #include "talc_switches.h"
 #include "talc_table_host.h"
 
@@ -172,6 +173,7 @@ enum CtxSpan {
   kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_clip_gather
   kSpanChimeraScan, kSpanChimeraGather,  // the chimera split: k_read_chimera, k_split_gather
   kSpanDemuxScan,                        // barcode demultiplexing: k_read_demux
+  kSpanUmiScan,                          // the UMI read-out: k_read_umi
   kSpanCount
 };
 
@@ -199,6 +201,9 @@ struct talc_ctx {
   uint32_t demuxGen = 0;     // ... counts the settings, as endsGen does
   DemuxParams demux;         // ... as k_read_demux takes it
   DevBuf<uint64_t> d_demux_peq;   // ... and the barcodes' match masks (kDemuxMaxBarcodes x 4 words), written when a setting is accepted
+  bool umiOn = false;        // talc_ctx_set_umi (docs/umi.md): nothing of it exists while it is off
+  uint32_t umiGen = 0;       // ... counts the settings, as endsGen does
+  UmiParams umi;             // ... as k_read_umi takes it
   Stage stage;          // default scratch
   DevBuf<uint32_t> d_queue;      // work-queue counters
   DevBuf<uint32_t> d_hist;       // kHistWords: the buckets of the work-queue ordering, then the batch statistics
@@ -227,6 +232,7 @@ struct EditOut {
 //   ended                                  from the raw bytes (of a clipped batch: from those it was made from); never dropped
 //   chimera                                from the raw bytes (of a split batch: from those it was made from); never dropped
 //   demuxed                                from the raw bytes (of a clipped or split batch: from those it was made from); never dropped
+//   umi                                    from the raw bytes (of a clipped batch: from those it was made from); never dropped
 //   encoded(encodedAuto) -> covered
 //   encoded -> solidity (raw rows), supported (RAW)
 //   encoded -> structured            (test hook; k_search consumes the region lists)
@@ -239,6 +245,7 @@ struct BatchHolds {
   bool chimera = false;       // h_hits: k_read_chimera under the settings chimeraGen and chimeraEndsGen; never dropped
   bool split = false;         // ... and the batch was made from those hits (talc_batch_create_split): they are never made again
   bool demuxed = false;       // d_demux: k_read_demux under the setting demuxGen; of a clipped or split batch the rows of the reads it was made from
+  bool umi = false;           // d_umi: k_read_umi under the setting umiGen; of a clipped or split batch the rows of the scan that made it
   bool encoded = false;       // d_codes
   bool encodedAuto = false;   // ... made with the vote's flags: k_pack, k_pack_map, k_solidity and k_base_support then take them too
   bool covered = false;       // d_cov, d_covw, d_nin
@@ -289,6 +296,8 @@ struct talc_batch {
   uint32_t chimeraGen = 0, chimeraEndsGen = 0;
   CachedBuf<DemuxRow> d_demux;        // one row per source read (k_read_demux): n_demux of them
   uint32_t n_demux = 0, demuxGen = 0; // ... and the setting they were made under
+  CachedBuf<UmiRow> d_umi;            // one row per read (k_read_umi)
+  uint32_t umiGen = 0;                // the setting those rows were made under
   CachedBuf<EndRow> d_ends;           // one row per read (k_read_ends)
   uint32_t endsGen = 0;               // the setting those rows were made under
   CachedBuf<StrandRow> d_strand;      // one row per read (k_strand_vote)
@@ -336,6 +345,7 @@ static_assert(sizeof(SolidityRow) == sizeof(talc_solidity) && sizeof(talc_solidi
 static_assert(sizeof(StrandRow) == sizeof(talc_strand) && sizeof(talc_strand) == 24, "k_strand_vote writes talc_strand records");
 static_assert(sizeof(EndRow) == sizeof(talc_end_row) && sizeof(talc_end_row) == 32, "k_read_ends writes talc_end_row records");
 static_assert(sizeof(DemuxRow) == sizeof(talc_demux_row) && sizeof(talc_demux_row) == 16 && TALC_DEMUX_CONFLICT == DEMUX_CONFLICT, "k_read_demux writes talc_demux_row records");
+static_assert(sizeof(UmiRow) == sizeof(talc_umi_row) && sizeof(talc_umi_row) == 56 && sizeof(UmiRow) == kUmiRowWords * 4, "k_read_umi writes talc_umi_row records");
 static_assert(sizeof(ChimeraHit) == sizeof(talc_chimera_hit) && sizeof(talc_chimera_hit) == 16 && sizeof(SplitPiece) == sizeof(talc_split_piece) &&
               sizeof(talc_split_piece) == 16, "k_read_chimera writes talc_chimera_hit records, k_split_gather reads talc_split_piece records");
 
@@ -1378,6 +1388,7 @@ extern "C" {
 #include "talc_capi_edits.inc"
 #include "talc_capi_support.inc"
 #include "talc_capi_demux.inc"
+#include "talc_capi_umi.inc"
 #include "talc_capi_ends.inc"
 #include "talc_capi_chimera.inc"
 

@@ -131,6 +131,10 @@ int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offs
   };
   if (!clip) {
     if ((rc = batch_build(c, bp, pieceOff.data(), n_pieces, [&](hipStream_t s) { return gather(s, bp->d_raw.get(), bp->d_offsets.get()); }))) return rc;
+    if (c->umiOn) {   // (docs/umi.md: a row per piece, nothing cut)
+      if ((rc = umi_scan(c, bp, bp->d_raw.get(), bp->d_offsets.get(), n_pieces, nullptr))) return rc;
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
   } else {
     CachedBuf<uint8_t> dense;
     CachedBuf<uint64_t> denseOff;

@@ -47,6 +47,8 @@ int talc_batch_ends(talc_ctx* c, talc_batch* b) {
   if ((rc = belong(c, b, "bad context/batch"))) return rc;
   const bool made = b->holds.ended && (b->holds.clipped || (c->endsOn && b->endsGen == c->endsGen));
   if (!made && !c->endsOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");
+  if (!made && b->holds.clipped)   // (docs/umi.md: clipped by the UMI alone; its bytes are no longer the reads as they came)
+    return fail(TALC_ERR_STATE, "a clipped batch holds the end rows of the scan that made it, and the end clean-up was off then");
   HIPCHK(hipSetDevice(c->device));
   if (!made) {
     b->holds.ended = false;
@@ -70,13 +72,15 @@ int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows) {
 
 static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
                                uint32_t n_reads);
+static int clipped_from_staged_umi(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
+                                   uint32_t n_reads);
 
 // The raw bytes go up once, into a staging buffer of the context's cache; the scan's rows come to the host, which lays the
 // batch out from the kept lengths (batch_build, as talc_batch_create); k_clip_gather then fills the batch's text from the
 // staging buffer, device to device.  The staging buffers go back to the cache when the batch stands.
 int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
   if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
-  if (!c->endsOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");
+  if (!c->endsOn && !c->umiOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");   // (docs/umi.md: the UMI alone clips too)
   if (offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
   for (uint32_t r = 0; r < n_reads; ++r) {
     if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must be non-decreasing");
@@ -105,6 +109,7 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
 // lengths, k_clip_gather.  What talc_batch_create_clipped does behind its upload, and talc_batch_create_split behind its gather.
 static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
                                uint32_t n_reads) {
+  if (c->umiOn) return clipped_from_staged_umi(c, bp, stage, stageOff, offsets, n_reads);
   HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
   int rc;
   if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
@@ -129,6 +134,41 @@ static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint
   if ((rc = read_spans(c))) return rc;
   bp->endsGen = c->endsGen;
   bp->holds.ended = bp->holds.clipped = true;
+  return TALC_OK;
+}
+
+// ... with the UMI read-out on (docs/umi.md): k_read_ends when the end clean-up is on, whose rows stay what it wrote;
+// k_read_umi on the same text, whose rows hold the combined intervals; the layout from those; k_clip_gather_umi.
+static int clipped_from_staged_umi(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
+                                   uint32_t n_reads) {
+  int rc;
+  if (c->endsOn) {
+    HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
+    if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
+  }
+  if ((rc = umi_scan(c, bp, stage.get(), stageOff.get(), n_reads, c->endsOn ? bp->d_ends.get() : nullptr))) return rc;
+  std::vector<UmiRow> rows(n_reads);
+  if (n_reads) HIPCHK(hipMemcpyAsync(rows.data(), bp->d_umi.get(), (size_t)n_reads * sizeof(UmiRow), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::vector<uint64_t> kept((size_t)n_reads + 1, 0);
+  for (uint32_t r = 0; r < n_reads; ++r) {
+    const uint64_t L = offsets[r + 1] - offsets[r];
+    if ((uint64_t)rows[r].keptStart + rows[r].keptLen > L)
+      return fail(TALC_ERR_DEVICE, "the UMI scan left read %u an interval beyond its %llu bytes", r, (unsigned long long)L);
+    kept[r + 1] = kept[r] + rows[r].keptLen;
+  }
+  rc = batch_build(c, bp, kept.data(), n_reads, [&](hipStream_t s) {
+    return c->span[kSpanEndsGather].around(s, [&] {
+      if (n_reads)
+        hipLaunchKernelGGL(k_clip_gather_umi, dim3(n_reads), dim3(256), 0, s, stage.get(), stageOff.get(), bp->d_umi.get(), n_reads, bp->d_raw.get(),
+                           bp->d_offsets.get());
+    });
+  });
+  if (rc) return rc;
+  if ((rc = read_spans(c))) return rc;
+  bp->endsGen = c->endsGen;
+  bp->holds.ended = c->endsOn;
+  bp->holds.clipped = true;
   return TALC_OK;
 }
 

@@ -73,6 +73,11 @@
 //                    barcode; writes <o>.demux.tsv (one line per read as it came), <o>.demux_counts.tsv and one summary line;
 //                    --LRDemuxOut: every record of <o>.fa also goes to <o>.<name>.fa or <o>.unclassified.fa (a piece of
 //                    --LRSplit where its source read goes)
+//   --LRUmi PATTERN  a UMI pattern of 12..64 IUPAC letters with 1..32 degenerate ones (docs/umi.md): found on the GPU at every read's
+//                    head and, reverse-complemented, at its tail, within --LRUmiErr PCT (0..30, default 10) per cent of its length
+//                    in edits inside --LRUmiWindow N (32..4096, default 256) bases, and aligned: the read's bases under the
+//                    degenerate letters are its UMI; writes <o>.umi.tsv (one line per read, per piece under --LRSplit) and one
+//                    summary line; with --LRClip the reads are cut behind the pattern too, also without --LRAdapter / --LRPolyA
 // -t/--num_threads is accepted and ignored (the parallelism is on the device).
 // Differences, all documented in INTEGRATION.md: stdout carries the [TALC] banners but none of
 // the reference's always-on debug dumps; log lines are written in input order.
@@ -103,6 +108,7 @@
 #include "talc_cli_io.h"
 #include "talc_hip.h"
 #include "talc_jf.h"
+#include "talc_kernels_umi.h"   // iupac_set: the letters of --LRUmi, as the library reads them
 #include "talc_pure.h"   // the spectrum's threshold rule: its constants, as the library applies them
 #include "talc_switches.h"
 
@@ -177,6 +183,10 @@ struct Options {
   bool haveLrBarcodeErr = false, haveLrBarcodeMargin = false, haveLrBarcodeWindow = false;
   bool lrBarcodeBothEnds = false, lrDemuxOut = false;   // --LRBarcodeBothEnds, --LRDemuxOut
   bool lrDemux() const { return !lrBarcodesFile.empty(); }   // barcode demultiplexing is on
+  std::string lrUmiPattern;                 // --LRUmi (docs/umi.md)
+  uint32_t lrUmiErr = 10, lrUmiWindow = 256;   // --LRUmiErr (lib.UMI_DEFAULT_ERR: tools/umi_defaults.py), --LRUmiWindow
+  bool haveLrUmi = false, haveLrUmiErr = false, haveLrUmiWindow = false;
+  bool lrUmi() const { return haveLrUmi; }   // the UMI read-out is on
 };
 
 void usage(FILE* f) {
@@ -263,6 +273,12 @@ void usage(FILE* f) {
           "  --LRBarcodeWindow INT       with --LRBarcodes: bases of each end that are searched, 32..4096, default 256\n"
           "  --LRBarcodeBothEnds         with --LRBarcodes: only reads whose two ends call the same barcode get it\n"
           "  --LRDemuxOut                with --LRBarcodes: every record of <o>.fa also goes to <o>.<name>.fa or <o>.unclassified.fa\n"
+          "  --LRUmi PATTERN             a UMI pattern of 12..64 letters of ACGTRYSWKMBDHVN, 1..32 of them degenerate: found on the GPU at\n"
+          "                              every read's head and, reverse-complemented, at its tail, and aligned; the bases under the\n"
+          "                              degenerate letters are the read's UMI; writes <o>.umi.tsv (docs/umi.md); with --LRClip the reads\n"
+          "                              are cut behind the pattern too; include fixed primer letters: the bare UMI is found by chance\n"
+          "  --LRUmiErr INT              with --LRUmi: edits allowed in percent of the pattern's length, 0..30, default 10\n"
+          "  --LRUmiWindow INT           with --LRUmi: bases of each end that are searched, 32..4096, default 256\n"
           "  -h, --help / --version\n");
 }
 
@@ -447,6 +463,17 @@ Options parse(int argc, const char** argv) {
       if (v != (double)(long long)v || v < 32 || v > 4096) parse_error("value out of range for LRBarcodeWindow: 32..4096");
       o.lrBarcodeWindow = (uint32_t)v; o.haveLrBarcodeWindow = true;
     }
+    else if (a == "--LRUmi") { o.lrUmiPattern = need(i); o.haveLrUmi = true; }
+    else if (a == "--LRUmiErr") {
+      const double v = num(need(i), "LRUmiErr");
+      if (v != (double)(long long)v || v < 0 || v > 30) parse_error("value out of range for LRUmiErr: 0..30");
+      o.lrUmiErr = (uint32_t)v; o.haveLrUmiErr = true;
+    }
+    else if (a == "--LRUmiWindow") {
+      const double v = num(need(i), "LRUmiWindow");
+      if (v != (double)(long long)v || v < 32 || v > 4096) parse_error("value out of range for LRUmiWindow: 32..4096");
+      o.lrUmiWindow = (uint32_t)v; o.haveLrUmiWindow = true;
+    }
     else if (a == "--LRBarcodeBothEnds") o.lrBarcodeBothEnds = true;
     else if (a == "--LRDemuxOut") o.lrDemuxOut = true;
     else if (a == "--min-piece-len") { double v = num(need(i), "min-piece-len"); range(v, 0, 4e9, "min-piece-len"); o.minPieceLen = (uint32_t)v; }
@@ -481,7 +508,20 @@ Options parse(int argc, const char** argv) {
     parse_error("--both-strands makes the k-mer table symmetric, so every vote of --auto-strand is a tie: they do not go together");
   if (o.haveLrAdapterErr && o.lrAdapters.empty()) parse_error("--LRAdapterErr needs --LRAdapter");
   if (o.haveLrEndWindow && !o.lrEnds()) parse_error("--LREndWindow needs --LRAdapter or --LRPolyA");
-  if (o.lrClip && !o.lrEnds()) parse_error("--LRClip needs --LRAdapter or --LRPolyA");
+  if (o.haveLrUmiErr && !o.lrUmi()) parse_error("--LRUmiErr needs --LRUmi");
+  if (o.haveLrUmiWindow && !o.lrUmi()) parse_error("--LRUmiWindow needs --LRUmi");
+  if (o.lrUmi()) {
+    const std::string& v = o.lrUmiPattern;
+    if (v.size() < 12 || v.size() > 64) parse_error("LRUmi: " + std::to_string(v.size()) + " letters: 12..64 are expected");
+    uint32_t u = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+      const uint32_t set = talc::iupac_set((uint8_t)v[i]);
+      if (!set) parse_error("LRUmi: letter " + std::to_string(i + 1) + " is not one of ACGTRYSWKMBDHVN");
+      u += (set & (set - 1)) ? 1 : 0;
+    }
+    if (u < 1 || u > 32) parse_error("LRUmi: " + std::to_string(u) + " degenerate letters: 1..32 are expected");
+  }
+  if (o.lrClip && !o.lrEnds() && !o.lrUmi()) parse_error("--LRClip needs --LRAdapter or --LRPolyA, or --LRUmi");
   if (o.lrChimeras && o.lrAdapters.empty()) parse_error("--LRChimeras needs --LRAdapter");
   if (o.lrSplit && o.lrAdapters.empty()) parse_error("--LRSplit needs --LRAdapter");
   // (a clipped batch no longer holds the reads as they came, and the hits are positions in those: only the split route scans
@@ -521,6 +561,9 @@ void outputConfig(const Options& o, const std::string& statFile) {
   if (o.lrSplit) f << "LRSplit=1" << "\n";
   if (o.haveLrChimeraErr) f << "LRChimeraErr=" << o.lrChimeraErr << "\n";
   if (o.haveLrMinPiece) f << "LRMinPiece=" << o.lrMinPiece << "\n";
+  if (o.lrUmi()) f << "LRUmi=" << o.lrUmiPattern << "\n";
+  if (o.haveLrUmiErr) f << "LRUmiErr=" << o.lrUmiErr << "\n";
+  if (o.haveLrUmiWindow) f << "LRUmiWindow=" << o.lrUmiWindow << "\n";
   if (o.lrDemux()) f << "LRBarcodes=" << o.lrBarcodesFile << "\n";
   if (o.haveLrBarcodeErr) f << "LRBarcodeErr=" << o.lrBarcodeErr << "\n";
   if (o.haveLrBarcodeMargin) f << "LRBarcodeMargin=" << o.lrBarcodeMargin << "\n";
@@ -555,13 +598,13 @@ void setBasicReadStatsHeader(const std::string& statFile) {
 
 // the three files next to <o>.config.txt
 struct Files {
-  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends, chimera, chimeraPieces, demux, demuxCounts, prefix;
+  const std::string fa, stats, log, map, solidity, trim, split, edits, strand, fq, trimFq, splitFq, ends, chimera, chimeraPieces, demux, demuxCounts, umi, prefix;
   explicit Files(const std::string& prefix)
       : fa(prefix + ".fa"), stats(prefix + ".stats_basics.txt"), log(prefix + ".log"), map(prefix + ".map.tsv"), solidity(prefix + ".solidity.tsv"),
         trim(prefix + ".trim.fa"), split(prefix + ".split.fa"), edits(prefix + ".edits.tsv"), strand(prefix + ".strand.tsv"),
         fq(prefix + ".fq"), trimFq(prefix + ".trim.fq"), splitFq(prefix + ".split.fq"), ends(prefix + ".ends.tsv"),
         chimera(prefix + ".chimera.tsv"), chimeraPieces(prefix + ".chimera_pieces.tsv"), demux(prefix + ".demux.tsv"), demuxCounts(prefix + ".demux_counts.tsv"),
-        prefix(prefix) {}
+        umi(prefix + ".umi.tsv"), prefix(prefix) {}
   // --LRDemuxOut: where the records of barcode b (0-based; the number of barcodes: unclassified) go
   std::string demuxFa(const Options& o, size_t b) const { return prefix + "." + (b < o.lrBarcodeNames.size() ? o.lrBarcodeNames[b] : std::string("unclassified")) + ".fa"; }
 };
@@ -773,6 +816,8 @@ struct Chunk {
   uint64_t endSums[4] = {0, 0, 0, 0};   // of the batch: reads, those with an adapter at either end, those with a poly run, bases outside the kept intervals
   std::string chimeraText, chimeraPiecesText;   // ... and to <o>.chimera.tsv, <o>.chimera_pieces.tsv (--LRChimeras, --LRSplit)
   uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch: reads, hits, reads with a hit, pieces kept, pieces dropped, their bases
+  std::string umiText;                  // ... and to <o>.umi.tsv (--LRUmi)
+  uint64_t umiSums[5] = {0, 0, 0, 0, 0};   // of the batch: reads, a UMI at the head only, at the tail only, both ends accepted, none
   std::string demuxText;                // ... and to <o>.demux.tsv (--LRBarcodes)
   uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};   // of the batch: reads, classified at both ends, head only, tail only, conflicts, the rest
   std::vector<uint64_t> demuxCounts;    // per barcode, then unclassified: reads, their bases as they came
@@ -812,6 +857,28 @@ void formatEnds(Chunk& k, const talc_end_row* rows) {
     k.endSums[1] += (w.head_adapter || w.tail_adapter) ? 1 : 0;
     k.endSums[2] += (w.head_poly_len || w.tail_poly_len) ? 1 : 0;
     k.endSums[3] += L - w.kept_len;
+  }
+}
+
+// the lines of <o>.umi.tsv for one batch from the scan's rows (k.ids, k.offsets: the reads, or the pieces, as they came),
+// and the sums
+const char* const kUmiHeader = "read_name\tlength\tend\terr\tother_err\tstart\tstop\tumi\tkept_start\tkept_len\n";
+void formatUmi(Chunk& k, const talc_umi_row* rows) {
+  char num[192];
+  for (size_t r = 0; r < k.ids.size(); ++r) {
+    const talc_umi_row& w = rows[r];
+    const uint64_t L = k.offsets[r + 1] - k.offsets[r];
+    char umi[33], other[8];
+    const size_t u = w.end ? std::min<size_t>(w.umi_len, 32) : 0;
+    memcpy(umi, w.umi, u); umi[u] = 0;
+    if (!u) { umi[0] = '-'; umi[1] = 0; }
+    if (w.other_err == 255) snprintf(other, sizeof other, "-"); else snprintf(other, sizeof other, "%u", w.other_err);
+    const int m = snprintf(num, sizeof num, "\t%llu\t%u\t%u\t%s\t%u\t%u\t%s\t%u\t%u\n", (unsigned long long)L, w.end, w.err, other, w.start, w.stop, umi,
+                           w.kept_start, w.kept_len);
+    k.umiText += k.ids[r];
+    k.umiText.append(num, (size_t)m);
+    k.umiSums[0] += 1;
+    k.umiSums[!w.end ? 4 : w.other_err != 255 ? 3 : w.end] += 1;
   }
 }
 
@@ -1097,6 +1164,7 @@ struct PipelineTotals {
   uint64_t endSums[4] = {0, 0, 0, 0};          // --LRAdapter / --LRPolyA: Chunk::endSums
   uint64_t chimeraSums[6] = {0, 0, 0, 0, 0, 0};   // --LRChimeras / --LRSplit: Chunk::chimeraSums
   uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};     // --LRBarcodes: Chunk::demuxSums
+  uint64_t umiSums[5] = {0, 0, 0, 0, 0};          // --LRUmi: Chunk::umiSums
   WorkerTally workers;
 };
 
@@ -1130,7 +1198,8 @@ class Pipeline {
     explicit ReaderSide(const std::string& file) : in(file) {}
   };
   struct WriterSide {   // the writer thread's own
-    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf, cf, cpf, df;
+    std::ofstream of, lf, sf, mf, yf, tf, pf, ef, wf, qf, tqf, pqf, xf, cf, cpf, df, uf;
+    uint64_t umiSums[5] = {0, 0, 0, 0, 0};
     std::vector<std::ofstream> bf;        // --LRDemuxOut: one per barcode, then unclassified
     uint64_t demuxSums[6] = {0, 0, 0, 0, 0, 0};
     std::vector<uint64_t> demuxCounts;    // Chunk::demuxCounts, summed
@@ -1231,6 +1300,11 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
       wr.cpf << kChimeraPiecesHeader;
     }
   }
+  if (o_.lrUmi()) {
+    wr.uf.open(files_.umi, std::ios_base::trunc);
+    if (!wr.uf) return fail("cannot write " + files_.umi);
+    wr.uf << kUmiHeader;
+  }
   if (o_.lrDemux()) {
     wr.df.open(files_.demux, std::ios_base::trunc);
     if (!wr.df) return fail("cannot write " + files_.demux);
@@ -1272,6 +1346,8 @@ bool Pipeline::run(std::ofstream of, PipelineTotals& tot) {
   if (wr.pqf.is_open()) wr.pqf.close();
   if (wr.xf.is_open()) wr.xf.close();
   if (wr.df.is_open()) wr.df.close();
+  if (wr.uf.is_open()) wr.uf.close();
+  for (int i = 0; i < 5; ++i) tot.umiSums[i] = wr.umiSums[i];
   for (auto& f : wr.bf) f.close();
   if (o_.lrDemux() && !q_.failed) {
     std::ofstream cf(files_.demuxCounts, std::ios_base::trunc);
@@ -1353,6 +1429,7 @@ void Pipeline::correctChunks(int device, WorkerTally& t) {
       if (talc_ctx_set_ends(made, adapters.c_str(), o_.lrAdapterErr, o_.lrPolyA, o_.lrEndWindow) != TALC_OK) { fail(talc_last_error()); return; }
     }
     if (o_.lrChimeraScan() && talc_ctx_set_chimera(made, 1, o_.lrChimeraErr, o_.lrMinPiece) != TALC_OK) { fail(talc_last_error()); return; }
+    if (o_.lrUmi() && talc_ctx_set_umi(made, o_.lrUmiPattern.c_str(), o_.lrUmiErr, o_.lrUmiWindow) != TALC_OK) { fail(talc_last_error()); return; }
     if (o_.lrDemux()) {
       std::string barcodes;
       for (const std::string& bc : o_.lrBarcodeSeqs) barcodes += (barcodes.empty() ? "" : ",") + bc;
@@ -1443,6 +1520,12 @@ bool Pipeline::correctOnDevice(talc_ctx* ctx, Chunk& c, HostBuf& outb, WorkerTal
     std::vector<talc_end_row> rows(std::max<uint32_t>(n, 1));
     if (talc_batch_ends(ctx, b.get()) != TALC_OK || talc_batch_fetch_ends(ctx, b.get(), rows.data()) != TALC_OK) return fail(talc_last_error());
     formatEnds(c, rows.data());
+    if (o_.lrClip && !o_.lrUmi()) for (uint32_t r = 0; r < n; ++r) c.offsets[r + 1] = c.offsets[r] + rows[r].kept_len;
+  }
+  if (o_.lrUmi()) {   // a clipped or split batch ran the scan while it was made, on its reads or pieces as they came; with --LRClip the rows hold the combined intervals
+    std::vector<talc_umi_row> rows(std::max<uint32_t>(n, 1));
+    if (talc_batch_umi(ctx, b.get()) != TALC_OK || talc_batch_fetch_umi(ctx, b.get(), rows.data()) != TALC_OK) return fail(talc_last_error());
+    formatUmi(c, rows.data());
     if (o_.lrClip) for (uint32_t r = 0; r < n; ++r) c.offsets[r + 1] = c.offsets[r] + rows[r].kept_len;
   }
   t.create += since(td0);
@@ -1550,6 +1633,10 @@ void Pipeline::writerMain(WriterSide& w) {
     if (w.cf.is_open()) w.cf.write(c->chimeraText.data(), (std::streamsize)c->chimeraText.size());
     if (w.cpf.is_open()) w.cpf.write(c->chimeraPiecesText.data(), (std::streamsize)c->chimeraPiecesText.size());
     for (int i = 0; i < 6; ++i) w.chimeraSums[i] += c->chimeraSums[i];
+    if (w.uf.is_open()) {
+      w.uf.write(c->umiText.data(), (std::streamsize)c->umiText.size());
+      for (int i = 0; i < 5; ++i) w.umiSums[i] += c->umiSums[i];
+    }
     if (w.df.is_open()) {
       w.df.write(c->demuxText.data(), (std::streamsize)c->demuxText.size());
       for (int i = 0; i < 6; ++i) w.demuxSums[i] += c->demuxSums[i];
@@ -1730,6 +1817,10 @@ static int run(int argc, const char** argv) {
     std::cerr << "talc: --LRBarcodes looks at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
     return 2;
   }
+  if (!haveTable && o.lrUmi()) {
+    std::cerr << "talc: --LRUmi looks at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
+    return 2;
+  }
   if (!haveTable && o.lrEnds()) {
     std::cerr << "talc: --LRAdapter / --LRPolyA look at the reads on the GPU, beside the k-mer table: this run has no table (-qm jellyfish2 without -jf2 or a .jf)\n";
     return 2;
@@ -1793,6 +1884,11 @@ static int run(int argc, const char** argv) {
     const uint64_t* y = totals.demuxSums;
     std::cout << "[TALC]: demux: " << y[0] << " reads, " << y[1] + y[2] + y[3] << " classified (" << y[1] << " both ends, " << y[2] << " head only, " << y[3]
               << " tail only), " << y[4] << " conflicts, " << y[5] << " without a barcode" << std::endl;
+  }
+  if (o.lrUmi()) {
+    const uint64_t* y = totals.umiSums;
+    std::cout << "[TALC]: umi: " << y[0] << " reads, " << y[1] << " at the head, " << y[2] << " at the tail, " << y[3] << " at both ends, " << y[4] << " without"
+              << std::endl;
   }
   std::cout << "[TALC]: Looks like we are done now." << std::endl;
   if (sw.timing && o.fastq && ndev)

@@ -74,6 +74,13 @@ def demux_geometry(n_barcodes, window=DEMUX_DEFAULT_WINDOW):
         return chunks, 1, n_barcodes * chunks, -(-window // chunks)
     tail_slot = -(-n_barcodes // 32) * 32
     return 1, -(-(tail_slot + n_barcodes) // 64), tail_slot, window
+# talc_umi_row (docs/umi.md)
+UMI_DTYPE = np.dtype([("end", "u1"), ("err", "u1"), ("other_err", "u1"), ("umi_len", "u1"), ("start", "<u4"), ("stop", "<u4"),
+                      ("kept_start", "<u4"), ("kept_len", "<u4"), ("umi", "S32"), ("pad_", "<u4")])
+UMI_NONE, UMI_HEAD, UMI_TAIL = range(3)
+UMI_DEFAULT_WINDOW = 256
+# the default of the command line and of Context.set_umi (docs/umi.md, "The default max_error_pct"; tools/umi_defaults.py)
+UMI_DEFAULT_ERR = 10
 # talc_support_params (docs/base_support.md)
 SUPPORT_RAW, SUPPORT_RECORD = 0, 1
 # the k-mer spectrum (docs/kmer_spectrum.md): high 0 means the default; the largest high the kernel's LDS histogram holds
@@ -256,6 +263,10 @@ def _abi():
         "talc_batch_demux": (i32, [vp, vp]),
         "talc_batch_fetch_demux": (i32, [vp, vp, vp]),
         "talc_ctx_get_demux_timing": (i32, [vp, vp]),
+        "talc_ctx_set_umi": (i32, [vp, txt, u32, u32]),
+        "talc_batch_umi": (i32, [vp, vp]),
+        "talc_batch_fetch_umi": (i32, [vp, vp, vp]),
+        "talc_ctx_get_umi_timing": (i32, [vp, vp]),
         "talc_test_set_poison": (i32, [i32, u32]),
         "talc_test_get_poison": (i32, [vp, vp]),
         "talc_test_guard_report": (i32, [vp]),
@@ -789,6 +800,20 @@ class Context(_Owner):
         _chk(lib().talc_ctx_get_demux_timing(self._h, C.byref(a)))
         return a.value
 
+    def set_umi(self, pattern="", max_error_pct=UMI_DEFAULT_ERR, window=UMI_DEFAULT_WINDOW):
+        """The UMI read-out (docs/umi.md): one pattern of 12..64 IUPAC letters (ACGTRYSWKMBDHVN) with 1..32 degenerate ones,
+        searched within max_error_pct (0..30) per cent of its length in edits inside the first `window` (32..4096) bytes of
+        every read and, reverse-complemented, inside the last; the alignment gives the read's bases under the degenerate
+        letters.  batch(clip=True) then cuts the pattern off too.  No pattern: off."""
+        text = pattern.decode() if isinstance(pattern, bytes) else pattern
+        _chk(lib().talc_ctx_set_umi(self._h, text.encode(), int(max_error_pct), int(window)))
+
+    def umi_timing(self):
+        """Device time (ms) of the context's last k_read_umi; 0.0 after a Batch.umi() that found its rows made."""
+        a = C.c_float()
+        _chk(lib().talc_ctx_get_umi_timing(self._h, C.byref(a)))
+        return a.value
+
     def support_timing(self):
         """Device time (ms) of the k_base_support launch of the context's last Batch.support()."""
         a = C.c_float()
@@ -814,7 +839,8 @@ class Context(_Owner):
         return ops[:n.value], d.value
 
     def batch(self, bases, offsets, clip=False, split=False):
-        """clip: the batch is made from the reads' kept intervals (set_ends; Batch.ends() then has the rows of the reads as given).
+        """clip: the batch is made from the reads' kept intervals (set_ends and / or set_umi, whose intervals combine;
+        Batch.ends() and Batch.umi() then have the rows of the reads as given).
         split: its reads are the kept pieces of the given reads (set_chimera; Batch.split_pieces() says which); with clip
         too, every piece is clipped."""
         return Batch(self, bases, offsets, clip=clip, split=split)
@@ -1020,6 +1046,14 @@ class Batch(_Owner):
         _chk(lib().talc_batch_demux(self.ctx._h, self._h))
         rows = np.zeros(self.n_source_reads, dtype=DEMUX_DTYPE)
         _chk(lib().talc_batch_fetch_demux(self.ctx._h, self._h, rows.ctypes.data))
+        return rows
+
+    def umi(self):
+        """The UMI read-out (docs/umi.md) as a UMI_DTYPE array of one row per read of the batch; on a clipped or split
+        batch the rows of the scan that made it."""
+        _chk(lib().talc_batch_umi(self.ctx._h, self._h))
+        rows = np.zeros(self.n_reads, dtype=UMI_DTYPE)
+        _chk(lib().talc_batch_fetch_umi(self.ctx._h, self._h, rows.ctypes.data))
         return rows
 
     def ends(self):
