@@ -309,3 +309,204 @@ def test_kept_and_grown_buffers_hold_every_result():
             finally:
                 b.close()
                 ctx.close()
+
+
+# ---------------------------------------------------------------- 3. the preparation reports: what a batch holds of them, what rescans
+def prep_probe(L, ctx, b):
+    """({fetch: return code}, {fetch: what it wrote}, {count: value}) of the five preparation reports of the batch as it
+    stands; the buffers have the sizes the batch's own counts give."""
+    h = (ctx._h, b._h)
+    n, src = b.n_reads, b.n_source_reads
+    nh, npc = int(L.talc_batch_num_chimera_hits(b._h)), int(L.talc_batch_num_split_pieces(b._h))
+    ends, demux, umi = np.zeros(max(n, 1), T.ENDS_DTYPE), np.zeros(max(src, 1), T.DEMUX_DTYPE), np.zeros(max(n, 1), T.UMI_DTYPE)
+    hits, hit_off = np.zeros(max(nh, 1), T.CHIMERA_DTYPE), np.zeros(src + 1, np.uint64)
+    pieces, piece_off = np.zeros(max(npc, 1), T.SPLIT_PIECE_DTYPE), np.zeros(src + 1, np.uint64)
+    codes = dict(ends=L.talc_batch_fetch_ends(*h, ends.ctypes.data), chimera=L.talc_batch_fetch_chimera(*h, hits.ctypes.data, nh, hit_off.ctypes.data),
+                 split=L.talc_batch_fetch_split(*h, pieces.ctypes.data, piece_off.ctypes.data), demux=L.talc_batch_fetch_demux(*h, demux.ctypes.data),
+                 umi=L.talc_batch_fetch_umi(*h, umi.ctypes.data))
+    wrote = dict(ends=(ends[:n],), chimera=(hits[:nh], hit_off), split=(pieces[:npc], piece_off), demux=(demux[:src],), umi=(umi[:n],))
+    return codes, wrote, dict(hits=nh, pieces=npc)
+
+
+def prep_holds(L, ctx, b, step, want):
+    """The fetches named in `want` succeed and give those arrays; every other fetch is TALC_ERR_STATE; the two counts are
+    those of the wanted hits and pieces, else 0."""
+    codes, wrote, counts = prep_probe(L, ctx, b)
+    expect = {name: (0 if name in want else ERR_STATE) for name in codes}
+    assert codes == expect, (step, {x: (codes[x], expect[x]) for x in codes if codes[x] != expect[x]})
+    assert counts == dict(hits=len(want["chimera"][0]) if "chimera" in want else 0, pieces=len(want["split"][0]) if "split" in want else 0), (step, counts)
+    for name, arrays in want.items():
+        for i, (g, w) in enumerate(zip(wrote[name], arrays)):
+            assert g.dtype == w.dtype and len(g) == len(w), (step, name, i, len(g), len(w))
+            bad = np.flatnonzero(g != w)
+            assert len(bad) == 0, (step, name, i, len(bad), int(bad[0]), g[bad[0]].tolist(), w[bad[0]].tolist())
+
+
+def held(k, *names):
+    """prep_holds' `want` from a prep_ref.chain result."""
+    every = dict(ends=(k["ends"],), chimera=(k["hits"], k["hit_off"]), split=(k["pieces"], k["piece_off"]), demux=(k["demux"],), umi=(k["umi"],))
+    return {name: every[name] for name in names}
+
+
+def scan_times(ctx):
+    return dict(ends=ctx.ends_timing()[0], chimera=ctx.chimera_timing()[0], demux=ctx.demux_timing(), umi=ctx.umi_timing())
+
+
+def test_the_preparation_reports_rescan_only_under_their_own_setting_and_remade_batches_keep_theirs():
+    """The walk of test_every_step_drops_what_was_made_from_what_it_replaces over the four preparation settings.  What the
+    times say: docs/demux.md and docs/umi.md promise 0 after a call that found its rows made.  docs/read_ends.md and
+    docs/chimeras.md promise only "the context's last k_read_ends / k_read_chimera": talc_batch_ends and talc_batch_chimera
+    that find their rows made launch nothing and leave the span as it was, so the time reads exactly what it read before."""
+    import chimera_ref as CR
+    import demux_ref as DR
+    import ends_ref as R
+    import prep_ref as PR
+    import test_gpu_prep_chain as PC
+    import umi_ref as U
+    s = PC.inputs()
+    reads = s["reads"][:26] + s["reads"][-4:]
+    n = len(reads)
+    assert n == 30
+    ENDS_B = dict(PR.ENDS_KW, adapters=PR.ENDS_KW["adapters"][::-1])
+    CHIMERA_B, DEMUX_B, UMI_B = (True, 0, 100), (PR.BC24, 10, 0), (PR.UMI[0], 5, 256)
+    A = (PR.ENDS_KW, PR.CHIMERA, PR.DEMUX, PR.UMI)
+    a = PR.chain(reads, *A)
+    a_swapped = PR.chain(reads, ENDS_B, PR.CHIMERA, PR.DEMUX, PR.UMI)                 # step 3: the adapters in the other order
+    b_all = PR.chain(reads, ENDS_B, CHIMERA_B, DEMUX_B, UMI_B)
+    differ = lambda x, y: len(x) != len(y) or bool((x != y).any())
+    assert differ(a["ends"], a_swapped["ends"]) and differ(a["hits"], a_swapped["hits"]) and len(a["hits"]) >= 10       # from the reference alone: each step is seen
+    assert differ(a["demux"], b_all["demux"]) and differ(a["umi"], b_all["umi"]) and differ(a_swapped["hits"], b_all["hits"])
+    L = T.lib()
+    ctx = T.Context(s["c"].ttab, s["c"].p, 0)
+    bases, offs = R.batch(reads)
+    plain = ctx.batch(bases, offs)
+    h = (ctx._h, plain._h)
+    SCAN = dict(ends=L.talc_batch_ends, chimera=L.talc_batch_chimera, demux=L.talc_batch_demux, umi=L.talc_batch_umi)
+    made = []
+
+    def no_scan(b, names, step):
+        """The scans named answer TALC_OK on batch b and launch nothing."""
+        for name in names:
+            before = scan_times(ctx)
+            assert SCAN[name](ctx._h, b._h) == 0, (step, name, L.talc_last_error())
+            after = scan_times(ctx)
+            assert after[name] == (0.0 if name in ("demux", "umi") else before[name]), (step, name, before, after)
+            assert {k: v for k, v in after.items() if k != name} == {k: v for k, v in before.items() if k != name}, (step, name)
+
+    def rescans(b, name, step):
+        assert SCAN[name](ctx._h, b._h) == 0, (step, name, L.talc_last_error())
+        assert scan_times(ctx)[name] > 0, (step, name)
+
+    try:
+        # 1. everything off
+        prep_holds(L, ctx, plain, "1: a fresh batch, every setting off", {})
+        for name in SCAN:
+            assert SCAN[name](*h) == ERR_STATE and b"off" in L.talc_last_error(), name
+        assert scan_times(ctx) == dict(ends=0.0, chimera=0.0, demux=0.0, umi=0.0)
+        prep_holds(L, ctx, plain, "1: after the refused scans", {})
+
+        # 2. all four on: each scan runs once
+        ctx.set_ends(**PR.ENDS_KW)
+        ctx.set_chimera(*PR.CHIMERA)
+        ctx.set_demux(*PR.DEMUX)
+        ctx.set_umi(*PR.UMI)
+        prep_holds(L, ctx, plain, "2: the settings alone make nothing", {})
+        done = []
+        for name in ("ends", "chimera", "demux", "umi"):
+            rescans(plain, name, "2: first call")
+            done.append(name)
+            prep_holds(L, ctx, plain, "2: after " + name, held(a, *done))
+        no_scan(plain, ("ends", "chimera", "demux", "umi"), "2: the same call again")
+        prep_holds(L, ctx, plain, "2: every report made", held(a, "ends", "chimera", "demux", "umi"))
+
+        # 3. the adapters in the other order: the ends and, through chimeraEndsGen, the hits; neither demux nor UMI
+        ctx.set_ends(**ENDS_B)
+        no_scan(plain, ("demux", "umi"), "3")
+        rescans(plain, "ends", "3")
+        rescans(plain, "chimera", "3")
+        prep_holds(L, ctx, plain, "3: a new ends setting", held(a_swapped, "ends", "chimera", "demux", "umi"))
+        no_scan(plain, ("ends", "chimera", "demux", "umi"), "3: again")
+
+        # 4. a new demux setting: demux alone; a new UMI setting: the UMI alone
+        ctx.set_demux(*DEMUX_B)
+        no_scan(plain, ("ends", "chimera", "umi"), "4: demux")
+        rescans(plain, "demux", "4: demux")
+        want = dict(held(a_swapped, "ends", "chimera", "umi"), demux=(b_all["demux"],))
+        prep_holds(L, ctx, plain, "4: a new demux setting", want)
+        ctx.set_umi(*UMI_B)
+        no_scan(plain, ("ends", "chimera", "demux"), "4: umi")
+        rescans(plain, "umi", "4: umi")
+        want["umi"] = (b_all["umi"],)
+        prep_holds(L, ctx, plain, "4: a new UMI setting", want)
+        no_scan(plain, ("ends", "chimera", "demux", "umi"), "4: again")
+
+        # 5. four remade batches under A
+        ctx.set_ends(**PR.ENDS_KW)
+        ctx.set_chimera(*PR.CHIMERA)
+        ctx.set_demux(*PR.DEMUX)
+        ctx.set_umi(*PR.UMI)
+        kinds = {}
+        for name, clip, split in PR.KINDS[1:]:
+            k = PR.chain(reads, *A, clip=clip, split=split)
+            b = ctx.batch(bases, offs, clip=clip, split=split)
+            made.append(b)
+            # (a split batch made without clip has no end rows of its own: like a plain batch it would scan its pieces when asked)
+            kinds[name] = (b, held(k, *(("ends",) if clip else ()) + (("chimera", "split") if split else ()) + ("demux", "umi")),
+                           (("ends",) if clip else ()) + (("chimera",) if split else ()) + ("demux", "umi"))
+        ctx.set_ends()
+        k = PR.chain(reads, None, None, PR.DEMUX, PR.UMI, clip=True)
+        b = ctx.batch(bases, offs, clip=True)
+        made.append(b)
+        kinds["clip, the UMI alone"] = (b, held(k, "demux", "umi"), ("demux", "umi"))
+        assert differ(k["umi"], kinds["clip"][1]["umi"][0])                           # (the claims of the ends are in the one, not in the other)
+
+        def remade_keep(step):
+            for name, (b, want, scans) in kinds.items():
+                prep_holds(L, ctx, b, "%s: %s" % (step, name), want)
+                no_scan(b, scans, "%s: %s" % (step, name))
+                prep_holds(L, ctx, b, "%s: %s, after the calls" % (step, name), want)
+            for name in ("clip", "clip, the UMI alone"):                              # no longer the reads as they came
+                assert L.talc_batch_chimera(ctx._h, kinds[name][0]._h) == ERR_STATE, (step, name)
+            assert L.talc_batch_ends(ctx._h, kinds["clip, the UMI alone"][0]._h) == ERR_STATE, step
+            assert L.talc_batch_fetch_ends(ctx._h, kinds["clip, the UMI alone"][0]._h, None) == ERR_STATE, step
+
+        remade_keep("5: as they were made")
+        ctx.set_ends(**ENDS_B)
+        ctx.set_chimera(*CHIMERA_B)
+        ctx.set_demux(*DEMUX_B)
+        ctx.set_umi(*UMI_B)
+        remade_keep("5: every setting changed to B")
+        for name in SCAN:                                                             # the plain batch follows the new settings
+            rescans(plain, name, "5: B")
+        prep_holds(L, ctx, plain, "5: the plain batch under B", held(b_all, "ends", "chimera", "demux", "umi"))
+        ctx.set_ends()
+        ctx.set_chimera(False)
+        ctx.set_demux()
+        ctx.set_umi()
+        remade_keep("5: every setting off")
+        for name in SCAN:
+            assert SCAN[name](*h) == ERR_STATE, name
+        prep_holds(L, ctx, plain, "5: the plain batch keeps the rows of its last scans", held(b_all, "ends", "chimera", "demux", "umi"))
+        assert L.talc_batch_ends(ctx._h, kinds["split"][0]._h) == ERR_STATE                # (nothing to scan its pieces under)
+
+        # 6. made while demux and the UMI were off: never, even once they are on
+        ctx.set_ends(**PR.ENDS_KW)
+        ctx.set_chimera(*PR.CHIMERA)
+        late = []
+        for name, clip, split in PR.KINDS[1:]:
+            b = ctx.batch(bases, offs, clip=clip, split=split)
+            made.append(b)
+            k = PR.chain(reads, PR.ENDS_KW, PR.CHIMERA, None, None, clip=clip, split=split)
+            late.append((name, b, held(k, *(("ends",) if clip else ()) + (("chimera", "split") if split else ()))))
+        ctx.set_demux(*PR.DEMUX)
+        ctx.set_umi(*PR.UMI)
+        for name, b, want in late:
+            before = scan_times(ctx)
+            assert L.talc_batch_demux(ctx._h, b._h) == ERR_STATE and L.talc_batch_umi(ctx._h, b._h) == ERR_STATE, name
+            assert scan_times(ctx) == before, name
+            prep_holds(L, ctx, b, "6: " + name, want)
+    finally:
+        for b in made:
+            b.close()
+        plain.close()
+        ctx.close()
