@@ -17,7 +17,10 @@
  * Threading (reference: any number of OpenMP threads on one shared read-only map,
  * main.cpp:247): a talc_table is immutable after talc_table_upload and may be shared by any
  * number of contexts; a talc_ctx is bound to one device + one HIP stream and must be used by
- * one host thread at a time.
+ * one host thread at a time.  The calls that only read an uploaded table (talc_table_lookup_batch,
+ * talc_table_next_counts_batch, talc_table_histo) may run from any number of threads beside the
+ * contexts that use it; nothing that changes a table, and not talc_table_lookup_host_batch, which
+ * may make the host image on first use, runs beside another call on that table (docs/threading.md).
  */
 #ifndef TALC_HIP_H
 #define TALC_HIP_H
