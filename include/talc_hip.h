@@ -37,7 +37,7 @@ typedef enum talc_error {
   TALC_OK = 0,
   TALC_ERR_INVALID = -1,     /* bad argument / parameter out of the supported range */
   TALC_ERR_IO = -2,          /* cannot open / parse an input file */
-  TALC_ERR_NOMEM = -3,       /* host or device allocation failed */
+  TALC_ERR_NOMEM = -3,       /* host or device allocation failed (the contract: docs/out_of_memory.md) */
   TALC_ERR_DEVICE = -4,      /* HIP runtime error (no GPU, launch failure, ...) */
   TALC_ERR_CAPACITY = -5,    /* caller-provided output buffer too small (needed size reported) */
   TALC_ERR_STATE = -6,       /* call sequence error (e.g. table not uploaded) */
@@ -555,6 +555,20 @@ uint64_t talc_test_cache_reuses(void);
  * the two writes caused: 2; where the first buffer's was found, where the second's was: side << 32 | offset}.  Its
  * checks do not enter talc_test_guard_report. */
 int talc_test_guard_selftest(uint64_t out[4]);
+/* Test hooks: allocations that fail on request (docs/out_of_memory.md).  talc_test_fail_alloc arms a process-wide setting:
+ * kinds is a mask, bit 0 the device requests (every buffer the library asks the runtime for; a request a context's cache
+ * serves from its pool is none), bit 1 the page-locked host requests; 0 switches the hook off, a value above 3 is
+ * TALC_ERR_INVALID (as are skip < 0 and a real other than 0 or 1).  From the arming call on, the requests of the selected
+ * kinds are numbered from 0 in the order they are made, and requests skip .. skip + count - 1 fail; count 0 fails nothing
+ * and only counts.  real 0: the library answers the request with hipErrorOutOfMemory itself; real 1: it asks the runtime
+ * for 2^60 bytes instead and passes on what the runtime answers, so that the runtime's own error state is that of a true
+ * failure.  Switching off keeps the report's numbers.  Off, the hook costs one relaxed load per request. */
+int talc_test_fail_alloc(uint32_t kinds, int64_t skip, uint32_t count, int real);
+/* out = {device requests seen since the arming call, page-locked requests seen, failures injected, the owner of the last
+ * injected failure (1 a buffer of its own, 2 a context's cache, 3 a page-locked buffer, 4 a page-locked host block; 0: none),
+ * the bytes it asked for, the code the runtime returned for the last real = 1 failure, the device buffers the library holds
+ * now (since it was loaded; the arming call does not reset it), the kinds armed}.  Needs no device. */
+int talc_test_alloc_report(uint64_t out[8]);
 
 /* Auto strand (docs/auto_strand.md): the k-mer table is directional and a long cDNA read arrives in either orientation; -rev
  * (talc_params.reverse) turns the whole file.  With auto strand every read is corrected in the orientation the short reads

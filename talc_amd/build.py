@@ -96,15 +96,19 @@ def build_pure(force=False):
 HIP_SOURCES = ["talc_capi.hip"]
 
 
+def hip_command(tgt, extra_flags=()):
+    """The one hipcc line of the library.  -Wno-unused-value silences -Wunused-result with it, so that one comes back behind
+    it as an error: a dropped [[nodiscard]] result (the allocating calls of talc_devmem.h's owners) does not build."""
+    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
+    return [HIPCC, "--offload-arch=" + ARCH, "-std=c++17", "-O3", "-fPIC", "-shared", "-fopenmp",
+            "-ffp-contract=off", "-fno-gpu-rdc",
+            "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Werror=unused-result", "-Wno-pass-failed", "-I", INCLUDE, "-I", CSRC, *extra_flags, *srcs, "-o", tgt]
+
+
 def build_hip(force=False, extra_flags=(), name="libtalc_hip.so"):
     os.makedirs(OUT, exist_ok=True)
     tgt = os.path.join(OUT, name)
-    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    _build_if_stale(tgt, _deps(*HIP_SOURCES),
-                    [HIPCC, "--offload-arch=" + ARCH, "-std=c++17", "-O3", "-fPIC", "-shared", "-fopenmp",
-                     "-ffp-contract=off", "-fno-gpu-rdc",
-                     "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-pass-failed", "-I", INCLUDE, "-I", CSRC, *extra_flags, *srcs, "-o", tgt],
-                    force)
+    _build_if_stale(tgt, _deps(*HIP_SOURCES), hip_command(tgt, extra_flags), force)
     return tgt
 
 

@@ -50,10 +50,12 @@ static int fail(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
+// (what does not fit is TALC_ERR_NOMEM, every other failure a device error: docs/out_of_memory.md)
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
     hipError_t _e = (x);                                                                   \
-    if (_e != hipSuccess) return fail(TALC_ERR_DEVICE, "%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
+    if (_e != hipSuccess)                                                                  \
+      return fail(_e == hipErrorOutOfMemory ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
 
 // seconds on the steady clock, since the start or since the last lap (where a build's wall time goes, TALC_TIMING)
@@ -420,7 +422,7 @@ int talc_device_count(void) {
 // page-locked host memory for read / record buffers: copies to and from it are DMA transfers that run beside kernels
 void* talc_pinned_alloc(uint64_t bytes) {
   PinnedBuf p;
-  if (p.alloc(std::max<uint64_t>(bytes, 1)) != hipSuccess) { (void)hipGetLastError(); fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned host memory", (unsigned long long)bytes); return nullptr; }
+  if (p.alloc(std::max<uint64_t>(bytes, 1)) != hipSuccess) { fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned host memory", (unsigned long long)bytes); return nullptr; }
   return p.release();
 }
 void talc_pinned_free(void* p) { PinnedBuf gone(p); }
@@ -448,6 +450,20 @@ int talc_test_guard_report(uint64_t out[4]) {
 uint64_t talc_test_cache_reuses(void) {
   std::lock_guard<std::mutex> lk(memcheck::lock());
   return memcheck::global_tally().reused;
+}
+// ---- Test hooks: allocations that fail on request (talc_devmem.h: failhook; docs/out_of_memory.md)
+int talc_test_fail_alloc(uint32_t kinds, int64_t skip, uint32_t count, int real) {
+  if (kinds > 3) return fail(TALC_ERR_INVALID, "kinds is a mask of 1 (device) and 2 (pinned host), 0 switches the hook off: %u given", kinds);
+  if (skip < 0 || (real != 0 && real != 1)) return fail(TALC_ERR_INVALID, "skip is >= 0 and real is 0 or 1: %lld, %d given", (long long)skip, real);
+  failhook::arm(kinds, skip, count, (uint32_t)real);
+  return TALC_OK;
+}
+int talc_test_alloc_report(uint64_t out[8]) {
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  const failhook::State& s = failhook::state();
+  out[0] = s.seen[0].load(); out[1] = s.seen[1].load(); out[2] = s.injected.load(); out[3] = s.lastOwner.load();
+  out[4] = s.lastBytes.load(); out[5] = s.lastRuntimeCode.load(); out[6] = (uint64_t)s.live.load(); out[7] = s.kinds.load();
+  return TALC_OK;
 }
 // the checks of a scope go to a tally of its own
 struct TallyScope {
@@ -607,15 +623,16 @@ int talc_table_from_arrays_device(const uint64_t* kmers, const uint32_t* counts,
 
 // The text dump parsed ON the device (talc_kernels_build.h): the file's bytes are read by a few host threads into
 // page-locked buffers and copied as they are; two kernels make the builder's arrays.  Returns TALC_OK with *out set, or
-// a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory):
+// a positive value when the file is not for this route (too small to matter, a line that is not canonical, no memory: 2):
 // the caller then parses on the host, as before.
-static int parse_on_host_instead() { (void)hipGetLastError(); return 1; }   // (an allocation or a copy failed: no error is left behind)
+static int parse_on_host_instead() { (void)hipGetLastError(); return 1; }   // (a copy or a launch failed: no error is left behind)
+static int parse_on_host_no_memory() { return 2; }                          // (an allocation failed: its owner has left none behind)
 
 // Step 1, the file's bytes to the device as they are: reader threads (one per chunk of chunkBytes, at most maxReaders),
 // each with its own descriptor, page-locked buffer and stream, claim the chunks in turn; chunk i lands at byte
 // i * chunkBytes of dText (size + 64 bytes).  0, or a positive value when memory or a read failed.
 static int text_to_device(const char* path, uint64_t size, uint64_t chunkBytes, int maxReaders, int device, DevBuf<uint8_t>& dText, int* readers) {
-  if (dText.alloc(size + 64) != hipSuccess) return parse_on_host_instead();
+  if (dText.alloc(size + 64) != hipSuccess) return parse_on_host_no_memory();
   const uint64_t CH = chunkBytes;
   const uint64_t nch = (size + CH - 1) / CH;
   const int T = (int)std::min<uint64_t>(nch, (uint64_t)maxReaders);
@@ -626,7 +643,9 @@ static int text_to_device(const char* path, uint64_t size, uint64_t chunkBytes, 
     int fd = open(path, O_RDONLY);
     PinnedBuf pin;
     hipStream_t st = nullptr;
-    bool ok = fd >= 0 && hipSetDevice(device) == hipSuccess && pin.alloc(CH) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+    bool ok = fd >= 0 && hipSetDevice(device) == hipSuccess;
+    if (ok && pin.alloc(CH) != hipSuccess) { ok = false; err.store(2); }   // (2: no memory)
+    ok = ok && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     while (ok && !err.load()) {
       const uint64_t i = next.fetch_add(1);
       if (i >= nch) break;
@@ -636,11 +655,11 @@ static int text_to_device(const char* path, uint64_t size, uint64_t chunkBytes, 
       if (!ok) break;
       if (hipMemcpyAsync(dText.get() + off, pin.get(), len, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) ok = false;
     }
-    if (!ok) err.store(1);
+    if (!ok) { int none = 0; err.compare_exchange_strong(none, 1); }
     if (st) hipStreamDestroy(st);
     if (fd >= 0) close(fd);
   }
-  if (err.load()) return parse_on_host_instead();
+  if (err.load()) return err.load() == 2 ? parse_on_host_no_memory() : parse_on_host_instead();
   *readers = T;
   return 0;
 }
@@ -653,8 +672,9 @@ struct ParsedText { DevBuf<uint64_t> kmers; DevBuf<uint32_t> counts; uint64_t nl
 static int parse_device_text(const uint8_t* dText, uint64_t size, uint32_t K, uint32_t minc, ParsedText& out) {
   const uint64_t ntiles = (size + kParseTile - 1) / kParseTile;
   DevBuf<uint32_t> dCount; DevBuf<uint64_t> dFirst; DevBuf<ParseStats> dPS;
-  if (ntiles == 0 || ntiles >= (1ull << 31) || dCount.alloc(ntiles) != hipSuccess || dFirst.alloc(ntiles) != hipSuccess ||
-      dPS.alloc(1) != hipSuccess || hipMemset(dPS.get(), 0, sizeof(ParseStats)) != hipSuccess) return parse_on_host_instead();
+  if (ntiles == 0 || ntiles >= (1ull << 31)) return parse_on_host_instead();
+  if (dCount.alloc(ntiles) != hipSuccess || dFirst.alloc(ntiles) != hipSuccess || dPS.alloc(1) != hipSuccess) return parse_on_host_no_memory();
+  if (hipMemset(dPS.get(), 0, sizeof(ParseStats)) != hipSuccess) return parse_on_host_instead();
   hipLaunchKernelGGL(k_parse_count, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dCount.get());
   std::vector<uint32_t> hCount(ntiles);
   if (hipMemcpy(hCount.data(), dCount.get(), ntiles * 4, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
@@ -662,8 +682,8 @@ static int parse_device_text(const uint8_t* dText, uint64_t size, uint32_t K, ui
   uint64_t nlines = 0;
   for (uint64_t i = 0; i < ntiles; ++i) { hFirst[i] = nlines; nlines += hCount[i]; }
   if (nlines == 0 || nlines >= 0xFFFFFFFEull) return parse_on_host_instead();
-  if (hipMemcpy(dFirst.get(), hFirst.data(), ntiles * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      out.kmers.alloc(nlines) != hipSuccess || out.counts.alloc(nlines) != hipSuccess) return parse_on_host_instead();
+  if (hipMemcpy(dFirst.get(), hFirst.data(), ntiles * 8, hipMemcpyHostToDevice) != hipSuccess) return parse_on_host_instead();
+  if (out.kmers.alloc(nlines) != hipSuccess || out.counts.alloc(nlines) != hipSuccess) return parse_on_host_no_memory();
   hipLaunchKernelGGL(k_parse_lines, dim3((unsigned)ntiles), dim3(kParseThreads), 0, 0, dText, size, dFirst.get(), K, minc, out.kmers.get(), out.counts.get(), dPS.get());
   if (hipGetLastError() != hipSuccess || hipMemcpy(&out.stats, dPS.get(), sizeof out.stats, hipMemcpyDeviceToHost) != hipSuccess) return parse_on_host_instead();
   out.nlines = nlines;
@@ -740,9 +760,12 @@ int talc_test_parse_text(const char* path, uint32_t k, uint32_t min_count, int w
     if (hipSetDevice(device) != hipSuccess || hip_runtime_start() != hipSuccess) return fail(TALC_ERR_DEVICE, "device %d cannot be used", device);
     DevBuf<uint8_t> dText;
     int T = 0;
-    if (text_to_device(path, size, chunk_bytes, reader_threads, device, dText, &T)) return fail(TALC_ERR_DEVICE, "the text of %s did not reach the device", path);
+    // (the hook has no host route to fall back to: what the production route answers by parsing on the host is an error here)
+    if (const int why = text_to_device(path, size, chunk_bytes, reader_threads, device, dText, &T))
+      return fail(why == 2 ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "the text of %s did not reach the device", path);
     ParsedText parsed;
-    if (parse_device_text(dText.get(), size, k, min_count, parsed)) return fail(TALC_ERR_DEVICE, "the text of %s was not parsed on the device", path);
+    if (const int why = parse_device_text(dText.get(), size, k, min_count, parsed))
+      return fail(why == 2 ? TALC_ERR_NOMEM : TALC_ERR_DEVICE, "the text of %s was not parsed on the device", path);
     n = parsed.nlines; kept = parsed.stats.kept; flags = parsed.stats.flags;
     report();
     if (kmers_out || counts_out) {
@@ -907,7 +930,6 @@ static int derive_tables(DeviceImage& img, const HostTable& h, const Switches& s
   const bool want = sw.walk >= 0 ? sw.walk != 0 : ((uint64_t)freeB >= 2 * wbytes + reserve);
   if (!want || !h.capacity) return TALC_OK;
   if (img.walkRight.alloc(h.capacity) != hipSuccess || img.walkLeft.alloc(h.capacity) != hipSuccess) {
-    (void)hipGetLastError();
     img.walkRight.reset(); img.walkLeft.reset();
     if (sw.walk == 1) return fail(TALC_ERR_NOMEM, "TALC_WALK=1 but the walk tables (%llu bytes) do not fit the device", (unsigned long long)(2 * wbytes));
     return TALC_OK;

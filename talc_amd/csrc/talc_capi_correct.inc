@@ -22,7 +22,7 @@ static void ensure_edge_boxes(talc_ctx* c, Stage& st) {
   }
   if (need > st.boxes_bytes || seqCap != st.box_seq_cap) {
     st.boxes.reset(); st.boxes_bytes = 0;   // (the old boxes go before the larger ones are asked for)
-    if (st.boxes.alloc(need) != hipSuccess) { (void)hipGetLastError(); return; }   // (the search runs without)
+    if (st.boxes.alloc(need) != hipSuccess) return;   // (the search runs without)
     st.boxes_bytes = need; st.box_seq_cap = seqCap;
   }
 }
@@ -54,7 +54,6 @@ static int ensure_stage(talc_ctx* c, Stage& st, uint32_t maxLen, uint32_t scale,
     if (need > st.scratch_bytes) {
       st.scratch.reset(); st.scratch_bytes = 0;   // (the old scratch goes before the larger one is asked for)
       if (st.scratch.alloc(need) != hipSuccess) {
-        (void)hipGetLastError();
         if (attempt == 0) { c->cache.trim(0); continue; }
         return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of search scratch", (unsigned long long)need);
       }
@@ -254,7 +253,7 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
       return rc;
     }
     DevBuf<uint32_t> d_retry;
-    if (d_retry.alloc(retry.size()) != hipSuccess) { (void)hipGetLastError(); break; }
+    if (d_retry.alloc(retry.size()) != hipSuccess) break;
     HIPCHK(hipMemcpyAsync(d_retry.get(), retry.data(), retry.size() * 4, hipMemcpyHostToDevice, s));
     for (uint32_t r : retry) {
       b->h_state[r].overflow = 0;

@@ -115,7 +115,7 @@ static int counter_compact(talc_counter* c, uint32_t thr, uint64_t* outK, uint32
 // the n entries that a counting counter_compact(c, thr, ..., expand) has just found, as device arrays of exactly that size
 // (`nomem`: the caller's wording, n its one argument)
 static int counter_kept_arrays(talc_counter* c, uint32_t thr, bool expand, uint64_t n, const char* nomem, DevBuf<uint64_t>& dK, DevBuf<uint32_t>& dC) {
-  if (dK.alloc(std::max<uint64_t>(n, 1)) != hipSuccess || dC.alloc(std::max<uint64_t>(n, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, nomem, (unsigned long long)n); }
+  if (dK.alloc(std::max<uint64_t>(n, 1)) != hipSuccess || dC.alloc(std::max<uint64_t>(n, 1)) != hipSuccess) { return fail(TALC_ERR_NOMEM, nomem, (unsigned long long)n); }
   uint64_t got = 0;
   if (int rc = counter_compact(c, thr, dK.get(), dC.get(), n, &got, expand)) return rc;
   if (got != n) return fail(TALC_ERR_STATE, "the counter changed between two compactions (%llu, %llu)", (unsigned long long)n, (unsigned long long)got);
@@ -135,7 +135,6 @@ static int counter_grow(talc_counter* c, uint64_t need) {
   const uint64_t nc = counter_capacity_for(need, c->cap());
   DevBuf<CountSlot> nt;
   if (nt.alloc(nc) != hipSuccess) {
-    (void)hipGetLastError();
     return fail(TALC_ERR_NOMEM, "the k-mer counter cannot grow to %llu slots (%llu bytes) after %llu distinct k-mers",
                 (unsigned long long)nc, (unsigned long long)(nc * sizeof(CountSlot)), (unsigned long long)c->distinctKnown);
   }
@@ -185,7 +184,7 @@ static int counter_check_batch(const talc_counter* c, const uint64_t* offsets, u
 static int counter_pinned(PinnedBuf& buf, uint64_t need, uint64_t floor) {
   if (buf.size() >= need) return TALC_OK;
   const uint64_t want = std::max<uint64_t>(need, floor);
-  if (buf.alloc(want) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want); }
+  if (buf.alloc(want) != hipSuccess) { return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes of pinned staging memory", (unsigned long long)want); }
   return TALC_OK;
 }
 template <class T>
@@ -194,7 +193,6 @@ static int counter_devbuf(talc_counter* c, DevBuf<T>& buf, uint64_t need, uint64
   HIPCHK(hipStreamSynchronize(c->stream));   // (the previous kernel may still read the old buffer)
   const uint64_t want = std::max<uint64_t>(need, floor);
   if (buf.alloc(want) != hipSuccess) {
-    (void)hipGetLastError();
     return fail(TALC_ERR_NOMEM, "cannot allocate %llu bytes for a batch of the k-mer counter (%llu distinct k-mers so far)",
                 (unsigned long long)(want * sizeof(T)), (unsigned long long)c->distinctKnown);
   }
@@ -341,13 +339,48 @@ static int counter_build_table(talc_counter* c, const char* junction_path, talc_
   if (kept >= 0xFFFFFFFEull)
     return fail(TALC_ERR_INVALID, expand ? "%llu k-mers (both strands of those that reach MIN_COUNT) are too many: the device builder takes fewer than 2^32-2"
                                          : "%llu k-mers reach MIN_COUNT: the device builder takes fewer than 2^32-2", (unsigned long long)kept);
-  DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
-  if ((rc = counter_kept_arrays(c, c->p.min_count, expand, kept, "cannot allocate the %llu kept k-mers", dK, dC))) return rc;
-  // the hash and the batches' buffers go before the builder allocates its buckets; the counter is spent from here on
-  c->tab.reset();
-  c->dText.reset(); c->dQual.reset(); c->dOffs.reset();
-  c->spent = true;
-  const double tCompact = watch.lap();
+  DumpStats ds;
+  ds.nread = lines ? lines->nread : (int64_t)st[1];
+  ds.nkept = (int64_t)kept;
+  ds.nbad = lines ? lines->nbad : 0;
+  double tCompact = watch.lap();
+  // The kept k-mers as arrays, the builder over them, the colouring: everything that allocates.  spendFirst: the hash and
+  // the batches' buffers go once the kept k-mers are copied out, before the builder allocates its buckets, and the
+  // counter is spent from there on; else they go when the table is there.  On failure nothing is left of the build.
+  auto build = [&](bool spendFirst, talc_table** made) -> int {
+    auto spend = [&] {
+      c->tab.reset();
+      c->dText.reset(); c->dQual.reset(); c->dOffs.reset();
+      c->spent = true;
+    };
+    watch.lap();
+    DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
+    if (int brc = counter_kept_arrays(c, c->p.min_count, expand, kept, "cannot allocate the %llu kept k-mers", dK, dC)) return brc;
+    if (spendFirst) spend();
+    tCompact += watch.lap();
+    TablePtr t;
+    if (int brc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, t, 0.0, 0.0, c->sw)) return brc;
+    if (finish) {
+      if (int brc = table_finish(std::move(t), junction_path, &c->p, ds, made, stats)) return brc;
+    } else {
+      if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
+      *made = t.release();
+    }
+    if (!spendFirst) spend();
+    return TALC_OK;
+  };
+  // Beside the hash where the device has the room for it (docs/out_of_memory.md): a -3 there leaves the counter as it
+  // was, at the price of the work done so far, and the build is made once more the frugal way.  Where the free memory
+  // does not hold the kept arrays, the buckets and the builder's bids beside the hash, the frugal way is taken at once,
+  // as it always was; a -3 from there on leaves the counter spent.
+  size_t freeB = 0, totalB = 0;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemGetInfo(&freeB, &totalB));
+  const uint64_t besideBytes = kept * (8 + 4 + 2 * 4) + 2 * HostTable::capacity_for(kept, (uint64_t)totalB, c->sw.tableSlotsX10) * sizeof(Bucket);
+  talc_table* made = nullptr;
+  rc = (uint64_t)freeB >= besideBytes ? build(false, &made) : TALC_ERR_NOMEM;
+  if (rc == TALC_ERR_NOMEM) rc = build(true, &made);
+  if (rc) return rc;
   if (c->sw.timing) {
     const double kms = c->countTimer.ms();
     char mask[96] = "";   // (a filtered counter only: the line of an unfiltered one is as it was)
@@ -361,15 +394,7 @@ static int counter_build_table(talc_counter* c, const char* junction_path, talc_
             c->nBatches ? kms / (double)c->nBatches : 0.0, (unsigned long long)c->nGrows, c->growS,
             tWait, tCompact, mask);
   }
-  TablePtr t;
-  if ((rc = build_table_from_device_arrays(std::move(dK), std::move(dC), kept, kept, &c->p, c->device, t, 0.0, 0.0, c->sw))) return rc;
-  DumpStats ds;
-  ds.nread = lines ? lines->nread : (int64_t)st[1];
-  ds.nkept = (int64_t)kept;
-  ds.nbad = lines ? lines->nbad : 0;
-  if (finish) return table_finish(std::move(t), junction_path, &c->p, ds, out, stats);
-  if (stats) { stats[0] = ds.nread; stats[1] = ds.nkept; stats[2] = ds.nbad; }
-  *out = t.release();
+  *out = made;
   return TALC_OK;
 }
 
@@ -486,10 +511,10 @@ int talc_counter_set_filter(talc_counter* c, uint32_t min_qual, const char* adap
   c->dFiltStats.reset();
   c->filt = SrFilter{min_qual, min_overlap, max_error_pct};
   if (!packed.n && !min_qual) return TALC_OK;   // off: talc_counter_add does what it does without a filter
-  if (c->dFiltStats.alloc(4) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the filter's counters"); }
+  if (c->dFiltStats.alloc(4) != hipSuccess) { return fail(TALC_ERR_NOMEM, "cannot allocate the filter's counters"); }
   HIPCHK(hipMemsetAsync(c->dFiltStats.get(), 0, 4 * 8, c->stream));
   if (packed.n) {
-    if (c->dAdapters.alloc(1) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate the filter's adapters"); }
+    if (c->dAdapters.alloc(1) != hipSuccess) { return fail(TALC_ERR_NOMEM, "cannot allocate the filter's adapters"); }
     HIPCHK(hipMemcpy(c->dAdapters.get(), &packed, sizeof packed, hipMemcpyHostToDevice));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -519,7 +544,7 @@ int talc_test_counter_mask(talc_counter* c, const char* bases, const char* quals
   if (nbytes > n_reads && !masked_out) return fail(TALC_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(c->device));
   DevBuf<uint32_t> dClip;
-  if (dClip.alloc(n_reads) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %u clip positions", n_reads); }
+  if (dClip.alloc(n_reads) != hipSuccess) { return fail(TALC_ERR_NOMEM, "cannot allocate %u clip positions", n_reads); }
   if (int rc = counter_stage_batch(c, bases, quals, offsets, n_reads, nbytes, true, dClip.get())) return rc;
   std::vector<char> text(nbytes);
   HIPCHK(hipMemcpyAsync(text.data(), c->dText.get(), nbytes, hipMemcpyDeviceToHost, c->stream));
@@ -547,7 +572,7 @@ int talc_counter_add_counts(talc_counter* c, const uint64_t* kmers, const uint32
   if (nWide) return fail(TALC_ERR_INVALID, "%llu of the counted k-mers are wider than 2 K = %u bits", (unsigned long long)nWide, 2 * c->p.k);
   HIPCHK(hipSetDevice(c->device));
   DevBuf<uint64_t> dK; DevBuf<uint32_t> dC;
-  if (dK.alloc(n) != hipSuccess || dC.alloc(n) != hipSuccess) { (void)hipGetLastError(); return fail(TALC_ERR_NOMEM, "cannot allocate %llu counted k-mers on the device", (unsigned long long)n); }
+  if (dK.alloc(n) != hipSuccess || dC.alloc(n) != hipSuccess) { return fail(TALC_ERR_NOMEM, "cannot allocate %llu counted k-mers on the device", (unsigned long long)n); }
   HIPCHK(hipMemcpy(dK.get(), kmers, n * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dC.get(), counts, n * 4, hipMemcpyHostToDevice));
   return counter_add_counts_device(c, dK.get(), dC.get(), n);

@@ -19,6 +19,95 @@ namespace talc {
 // the runtime's own start-up, as the call that does nothing else
 inline hipError_t hip_runtime_start() { return hipFree(nullptr); }
 
+// Test hook (talc_test_fail_alloc, include/talc_hip.h; docs/out_of_memory.md): allocations that fail on request.  While it is
+// armed, the device requests (everything that goes through memcheck::alloc; a request a DevCache serves from its pool is
+// none) and the page-locked ones (PinnedBuf::alloc, host_block_alloc) of the selected kinds are numbered from 0 in the order
+// they are made, process-wide, and requests skip .. skip + count - 1 fail: with hipErrorOutOfMemory made here (real 0), or
+// with whatever the runtime answers when it is asked for 2^60 bytes (real 1: its own error state is then that of a true
+// failure).  It also keeps the number of device buffers the owners of this file hold.  Off, a request costs one relaxed load.
+namespace failhook {
+
+enum Kind : uint32_t { kDevice = 1, kPinned = 2 };
+enum Owner : uint32_t { kDevBuf = 1, kDevCache = 2, kPinnedBuf = 3, kHostBlock = 4 };
+constexpr uint64_t kHuge = 1ull << 60;
+
+struct State {
+  std::atomic<uint32_t> kinds{0};        // 0: off
+  std::atomic<int64_t> skip{0};
+  std::atomic<uint32_t> count{0}, real{0};
+  std::atomic<uint64_t> seen[2];         // requests since the arming call: device, pinned
+  std::atomic<uint64_t> next{0};         // ... of the selected kinds: the number of the next one
+  std::atomic<uint64_t> injected{0}, lastOwner{0}, lastBytes{0}, lastRuntimeCode{0};
+  std::atomic<int64_t> live{0};          // device buffers held (never reset)
+  State() { seen[0] = 0; seen[1] = 0; }
+};
+inline State& state() { static State s; return s; }
+
+inline void arm(uint32_t kinds, int64_t skip, uint32_t count, uint32_t real) {
+  State& s = state();
+  s.kinds.store(0);
+  if (!kinds) return;   // (off: the numbers stay for the report)
+  s.skip.store(skip); s.count.store(count); s.real.store(real);
+  s.seen[0].store(0); s.seen[1].store(0); s.next.store(0);
+  s.injected.store(0); s.lastOwner.store(0); s.lastBytes.store(0); s.lastRuntimeCode.store(0);
+  s.kinds.store(kinds);
+}
+// Is this request to fail?  0: no.  1: yes, with hipErrorOutOfMemory made by the owner.  2: yes, by asking the runtime for kHuge.
+inline int decide(Kind kind, Owner owner, uint64_t bytes) {
+  State& s = state();
+  const uint32_t kinds = s.kinds.load(std::memory_order_relaxed);
+  if (!kinds) return 0;
+  s.seen[kind == kDevice ? 0 : 1].fetch_add(1);
+  if (!(kinds & kind)) return 0;
+  const int64_t i = (int64_t)s.next.fetch_add(1), skip = s.skip.load();
+  if (i < skip || i - skip >= (int64_t)s.count.load()) return 0;
+  s.injected.fetch_add(1); s.lastOwner.store(owner); s.lastBytes.store(bytes);
+  return s.real.load() ? 2 : 1;
+}
+// what the runtime answered to the request for kHuge bytes (a runtime that grants it: the memory goes back, out of memory it is)
+inline hipError_t runtime_said(hipError_t e) {
+  state().lastRuntimeCode.store((uint64_t)(uint32_t)e);
+  return e == hipSuccess ? hipErrorOutOfMemory : e;
+}
+inline void born() { state().live.fetch_add(1, std::memory_order_relaxed); }
+inline void gone() { state().live.fetch_sub(1, std::memory_order_relaxed); }
+
+}  // namespace failhook
+
+// The runtime's device allocation as every owner below sees it: the request hook first; a success counts one live buffer; a
+// failure leaves no error behind in the runtime (the caller has the code: nothing is left for a later hipGetLastError()).
+inline hipError_t device_malloc(void** out, uint64_t bytes, failhook::Owner owner) {
+  hipError_t e;
+  switch (failhook::decide(failhook::kDevice, owner, bytes)) {
+    case 0: e = hipMalloc(out, bytes); break;
+    case 1: e = hipErrorOutOfMemory; break;
+    default: {
+      e = hipMalloc(out, failhook::kHuge);
+      if (e == hipSuccess) (void)hipFree(*out);
+      e = failhook::runtime_said(e);
+    }
+  }
+  if (e == hipSuccess) failhook::born();
+  else { *out = nullptr; (void)hipGetLastError(); }
+  return e;
+}
+inline void device_free(void* p) { failhook::gone(); (void)hipFree(p); }
+// ... and its page-locked allocation
+inline hipError_t pinned_malloc(void** out, uint64_t bytes, failhook::Owner owner) {
+  hipError_t e;
+  switch (failhook::decide(failhook::kPinned, owner, bytes)) {
+    case 0: e = hipHostMalloc(out, bytes, hipHostMallocDefault); break;
+    case 1: e = hipErrorOutOfMemory; break;
+    default: {
+      e = hipHostMalloc(out, failhook::kHuge, hipHostMallocDefault);
+      if (e == hipSuccess) (void)hipHostFree(*out);
+      e = failhook::runtime_said(e);
+    }
+  }
+  if (e != hipSuccess) { *out = nullptr; (void)hipGetLastError(); }
+  return e;
+}
+
 // Test hook (talc_test_set_poison, include/talc_hip.h): poisoned allocations and red zones.  While the setting is on, every
 // buffer the two owners below hand out is filled with `byte` over its whole capacity (a pooled buffer's slack included)
 // before its pointer is returned, and sits between two red zones of `guard` bytes of ~byte that are read back and compared
@@ -54,12 +143,12 @@ inline void count_reuse() {
 struct Guard { uint32_t guard = 0; uint8_t fill = 0; uint64_t asked = 0; };
 
 // `bytes` of device memory, poisoned and between red zones when the setting is on (g says what was made)
-inline hipError_t alloc(void** out, uint64_t bytes, Guard& g) {
+inline hipError_t alloc(void** out, uint64_t bytes, Guard& g, failhook::Owner owner) {
   const Setting s = setting();
   g = Guard();
-  if (!s.on) return hipMalloc(out, bytes);
+  if (!s.on) return device_malloc(out, bytes, owner);
   char* base = nullptr;
-  hipError_t e = hipMalloc((void**)&base, bytes + 2ull * s.guard);
+  hipError_t e = device_malloc((void**)&base, bytes + 2ull * s.guard, owner);
   if (e != hipSuccess) return e;
   g.guard = s.guard; g.fill = (uint8_t)~s.byte; g.asked = bytes;
   if (s.guard) {
@@ -68,7 +157,7 @@ inline hipError_t alloc(void** out, uint64_t bytes, Guard& g) {
   }
   if (e == hipSuccess) e = hipMemset(base + s.guard, s.byte, bytes);
   if (e == hipSuccess) e = hipDeviceSynchronize();   // (the null stream is not ordered with the contexts' non-blocking streams)
-  if (e != hipSuccess) { (void)hipFree(base); return e; }
+  if (e != hipSuccess) { device_free(base); (void)hipGetLastError(); return e; }
   *out = base + s.guard;
   return hipSuccess;
 }
@@ -101,7 +190,7 @@ inline void check(const void* p, uint64_t capacity, const Guard& g) {
 }
 inline void free_checked(void* p, uint64_t capacity, const Guard& g) {
   check(p, capacity, g);
-  (void)hipFree((char*)p - g.guard);
+  device_free((char*)p - g.guard);
 }
 
 // the guarded buffers that DevBuf owns, by the caller's pointer (DevBuf::release() hands a pointer to another DevBuf: the
@@ -111,7 +200,7 @@ inline std::map<void*, Registered>& registry() { static std::map<void*, Register
 inline std::atomic<uint64_t>& n_registered() { static std::atomic<uint64_t> n{0}; return n; }
 inline hipError_t alloc_registered(void** out, uint64_t bytes) {
   Guard g;
-  const hipError_t e = alloc(out, bytes, g);
+  const hipError_t e = alloc(out, bytes, g, failhook::kDevBuf);
   if (e == hipSuccess && g.guard) {
     std::lock_guard<std::mutex> lk(lock());
     registry()[*out] = Registered{bytes, g};
@@ -129,7 +218,7 @@ inline void free_registered(void* p) {
     }
     if (r.g.guard) { free_checked(p, r.bytes, r.g); return; }
   }
-  (void)hipFree(p);
+  device_free(p);
 }
 
 }  // namespace memcheck
@@ -146,7 +235,7 @@ class DevBuf {
   DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); n_ = o.n_; p_ = o.release(); } return *this; }
   ~DevBuf() { reset(); }
   // (what was held goes first: the old and the new buffer never exist side by side)
-  hipError_t alloc(uint64_t n) {
+  [[nodiscard]] hipError_t alloc(uint64_t n) {
     reset();
     const hipError_t e = memcheck::alloc_registered((void**)&p_, n * sizeof(T));
     if (e != hipSuccess) p_ = nullptr; else n_ = n;
@@ -170,9 +259,9 @@ class PinnedBuf {
   PinnedBuf(const PinnedBuf&) = delete;
   PinnedBuf& operator=(const PinnedBuf&) = delete;
   ~PinnedBuf() { reset(); }
-  hipError_t alloc(uint64_t bytes) {
+  [[nodiscard]] hipError_t alloc(uint64_t bytes) {
     reset();
-    const hipError_t e = hipHostMalloc((void**)&p_, bytes, hipHostMallocDefault);
+    const hipError_t e = pinned_malloc((void**)&p_, bytes, failhook::kPinnedBuf);
     if (e != hipSuccess) p_ = nullptr; else n_ = bytes;
     return e;
   }
@@ -190,8 +279,7 @@ struct HostBlock { void* p = nullptr; uint64_t bytes = 0; bool pinned = false; }
 inline HostBlock host_block_alloc(uint64_t bytes) {
   HostBlock b;
   bytes = std::max<uint64_t>(bytes, 64);
-  if (hipHostMalloc(&b.p, bytes, hipHostMallocDefault) == hipSuccess) { b.bytes = bytes; b.pinned = true; return b; }
-  (void)hipGetLastError();
+  if (pinned_malloc(&b.p, bytes, failhook::kHostBlock) == hipSuccess) { b.bytes = bytes; b.pinned = true; return b; }
   b.p = malloc(bytes);
   b.bytes = b.p ? bytes : 0;
   return b;
@@ -297,7 +385,7 @@ struct DevCache {
   // a device buffer of at least `bytes` from the cache (smallest cached one that fits and is not more than twice as
   // large), or a fresh one.  (Test hook: only a cached buffer with the red zones of the current setting fits, and it is
   // poisoned again, slack included.)
-  hipError_t alloc(void** out, uint64_t bytes) {
+  [[nodiscard]] hipError_t alloc(void** out, uint64_t bytes) {
     bytes = std::max<uint64_t>(bytes, 256);
     const memcheck::Setting ms = memcheck::setting();
     const uint32_t guard = ms.on ? ms.guard : 0;
@@ -318,11 +406,10 @@ struct DevCache {
       return hipSuccess;
     }
     memcheck::Guard g;
-    if (memcheck::alloc(out, bytes, g) != hipSuccess) {
+    if (memcheck::alloc(out, bytes, g, failhook::kDevCache) != hipSuccess) {
       // out of memory: drop the cache and try once more
-      (void)hipGetLastError();
       trim(0);
-      const hipError_t e = memcheck::alloc(out, bytes, g);
+      const hipError_t e = memcheck::alloc(out, bytes, g, failhook::kDevCache);
       if (e != hipSuccess) { *out = nullptr; return e; }   // (nothing is handed out)
     }
     hand_out(out, Buf{bytes, *out, g});
@@ -332,7 +419,7 @@ struct DevCache {
   void release(void* p) {
     if (!p) return;
     auto it = live.find(p);
-    if (it == live.end()) { (void)hipFree(p); return; }
+    if (it == live.end()) { device_free(p); return; }
     const Buf b = it->second;
     live.erase(it);
     live_bytes -= b.bytes;
@@ -362,7 +449,7 @@ class CachedBuf {
   CachedBuf& operator=(const CachedBuf&) = delete;
   ~CachedBuf() { reset(); }
   // (what was held goes back first: the cache may serve the request from it; a failure leaves the buffer empty)
-  hipError_t alloc(DevCache& cache, uint64_t n) {
+  [[nodiscard]] hipError_t alloc(DevCache& cache, uint64_t n) {
     reset();
     cache_ = &cache;
     const hipError_t e = cache.alloc((void**)&p_, n * sizeof(T));
@@ -370,7 +457,7 @@ class CachedBuf {
     return e;
   }
   // the buffer as it is when it was asked for at least n elements, else a new one of exactly max(n, 1)
-  hipError_t ensure(DevCache& cache, uint64_t n) { return p_ && n_ >= n ? hipSuccess : alloc(cache, std::max<uint64_t>(n, 1)); }
+  [[nodiscard]] hipError_t ensure(DevCache& cache, uint64_t n) { return p_ && n_ >= n ? hipSuccess : alloc(cache, std::max<uint64_t>(n, 1)); }
   T* get() const { return p_; }
   explicit operator bool() const { return p_ != nullptr; }
   void reset() { if (p_) { cache_->release(p_); p_ = nullptr; n_ = 0; } }

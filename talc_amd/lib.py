@@ -94,7 +94,11 @@ def cigar_text(ops):
 
 
 class TalcError(RuntimeError):
-    pass
+    """`code`: the library's talc_error (negative), or None where the wrapper itself refuses."""
+
+    def __init__(self, message, code=None):
+        super().__init__(message)
+        self.code = code
 
 
 class SupportParams(C.Structure):
@@ -272,6 +276,8 @@ def _abi():
         "talc_test_guard_report": (i32, [vp]),
         "talc_test_cache_reuses": (u64, []),
         "talc_test_guard_selftest": (i32, [vp]),
+        "talc_test_fail_alloc": (i32, [u32, C.c_int64, u32, i32]),
+        "talc_test_alloc_report": (i32, [vp]),
         "talc_counter_histo": (i32, [vp, u32, vp, stats]),
         "talc_counter_get_histo_timing": (i32, [vp, vp]),
         "talc_table_histo": (i32, [vp, i32, u32, vp, stats]),
@@ -307,13 +313,14 @@ def lib():
     return _LIB
 
 
+ERR_NOMEM = -3          # TALC_ERR_NOMEM (docs/out_of_memory.md)
 WARN_READ_ERRORS = 1   # TALC_WARN_READ_ERRORS: the batch is valid, some reads carry READ_ERROR
 
 
 def _chk(rc):
     """Negative codes are errors; positive ones (TALC_WARN_READ_ERRORS) are returned to the caller."""
     if rc < 0:
-        raise TalcError("libtalc_hip error %d: %s" % (rc, lib().talc_last_error().decode(errors="replace")))
+        raise TalcError("libtalc_hip error %d: %s" % (rc, lib().talc_last_error().decode(errors="replace")), rc)
     return rc
 
 
@@ -369,6 +376,33 @@ def guard_selftest():
     return dict(fills=int(r[0]), violations=int(r[1]), behind=where[0], in_front=where[1])
 
 
+KIND_DEVICE, KIND_PINNED = 1, 2                                          # talc_test_fail_alloc's kinds
+OWNER_DEVBUF, OWNER_DEVCACHE, OWNER_PINNED, OWNER_HOST_BLOCK = 1, 2, 3, 4   # talc_test_alloc_report's owners
+
+
+@contextlib.contextmanager
+def failing_allocs(kinds, skip, count, real=False):
+    """Test hook (docs/out_of_memory.md): inside the block the library's allocation requests of `kinds` (1 device, 2 pinned
+    host, 3 both) are numbered from 0 and requests skip .. skip + count - 1 fail (count 0: they are only counted,
+    alloc_report()); real: the runtime is asked for 2^60 bytes, so that its own error state is that of a true failure.
+    Process-wide; always switched off again; the report keeps what the block saw until the hook is armed again."""
+    _chk(lib().talc_test_fail_alloc(int(kinds), int(skip), int(count), 1 if real else 0))
+    try:
+        yield
+    finally:
+        _chk(lib().talc_test_fail_alloc(0, 0, 0, 0))
+
+
+def alloc_report():
+    """Test hook: dict of device (requests seen since the hook was last armed), pinned, injected, owner and bytes of the last
+    injected failure, runtime_code of the last real failure, live (device buffers the library holds now) and kinds (0: off).
+    Switching the hook off keeps the numbers: after a failing_allocs block they are what the block saw.  Needs no GPU."""
+    r = np.zeros(8, dtype=np.uint64)
+    _chk(lib().talc_test_alloc_report(r.ctypes.data))
+    return dict(device=int(r[0]), pinned=int(r[1]), injected=int(r[2]), owner=int(r[3]), bytes=int(r[4]), runtime_code=int(r[5]),
+                live=int(r[6].astype(np.int64)), kinds=int(r[7]))
+
+
 def parse_text_hook(path, k, min_count=2, where=1, device=0, chunk_bytes=32 << 20, reader_threads=8, arrays=True):
     """Test hook: the text-dump parser alone on a file of any size.  where=1: the file goes to GPU `device` in chunks of
     chunk_bytes read by at most reader_threads threads and is parsed there; where=0: the host parser, unfiltered (no GPU).
@@ -398,7 +432,7 @@ class PinnedArray:
         self.nbytes = int(nbytes)
         self._p = lib().talc_pinned_alloc(max(self.nbytes, 1))
         if not self._p:
-            raise TalcError("talc_pinned_alloc(%d) failed: %s" % (nbytes, lib().talc_last_error().decode(errors="replace")))
+            raise TalcError("talc_pinned_alloc(%d) failed: %s" % (nbytes, lib().talc_last_error().decode(errors="replace")), ERR_NOMEM)
         self.array = np.ctypeslib.as_array((C.c_uint8 * max(self.nbytes, 1)).from_address(self._p))[: self.nbytes]
 
     def close(self):

@@ -83,6 +83,52 @@ def test_poison_hooks_are_exported_and_take_only_what_the_header_allows():
     assert T.poison_setting() == (-1, 0) and T.guard_report() == before
 
 
+def test_alloc_failure_hooks_are_exported_refuse_unknown_kinds_and_report_without_a_device():
+    L = T.lib()
+    for sym in ("talc_test_fail_alloc", "talc_test_alloc_report"):
+        assert hasattr(L, sym) and sym in T.ABI_SYMBOLS, sym
+    assert L.talc_test_alloc_report(None) == -1
+    before = T.alloc_report()
+    assert before["kinds"] == 0                                  # off
+    for kinds, skip, count, real in ((4, 0, 1, 0), (7, 0, 0, 0), (1, -1, 1, 0), (1, 0, 1, 2)):
+        assert L.talc_test_fail_alloc(kinds, skip, count, real) == -1 and T.alloc_report() == before, (kinds, skip, count, real)   # TALC_ERR_INVALID
+        assert L.talc_last_error()
+    try:
+        assert L.talc_test_fail_alloc(3, 5, 2, 1) == 0
+        armed = T.alloc_report()
+        assert armed == dict(device=0, pinned=0, injected=0, owner=0, bytes=0, runtime_code=0, live=before["live"], kinds=3)
+    finally:
+        assert L.talc_test_fail_alloc(0, 0, 0, 0) == 0
+    assert T.alloc_report()["kinds"] == 0
+    with pytest.raises(ZeroDivisionError):                        # the context manager switches off when its body raises
+        with T.failing_allocs(T.KIND_PINNED, 0, 1):
+            assert T.alloc_report()["kinds"] == 2
+            1 // 0
+    assert T.alloc_report()["kinds"] == 0
+    with pytest.raises(T.TalcError) as e:                         # a setting the library refuses switches nothing on
+        with T.failing_allocs(4, 0, 1):
+            pass
+    assert e.value.code == -1 and T.alloc_report()["kinds"] == 0
+
+
+def test_every_owner_must_have_its_result_looked_at(tmp_path):
+    """The five allocating calls of talc_devmem.h are [[nodiscard]], and the library's build makes a dropped result an error:
+    -Wno-unused-value, which the build passes, silences -Wunused-result too, so -Werror=unused-result stands behind it.  A
+    two-line program that drops such a result is refused by the build's own flags, and compiles once it looks at it."""
+    import subprocess
+    from talc_amd import build as B
+    text = open(os.path.join(ROOT, "talc_amd", "csrc", "talc_devmem.h")).read()
+    assert len(re.findall(r"\[\[nodiscard\]\] hipError_t (alloc|ensure)\(", text)) == 5
+    flags = [f for f in B.hip_command(str(tmp_path / "unused.so")) if f.startswith("-W")]
+    assert "-Werror=unused-result" in flags and flags.index("-Werror=unused-result") > flags.index("-Wno-unused-value"), flags
+    src = tmp_path / "drop.hip"
+    for body, ok in (("f();", False), ("return f();", True)):
+        src.write_text("[[nodiscard]] int f() { return 0; }\nint main() { %s }\n" % body)
+        r = subprocess.run([B.HIPCC, "--offload-arch=" + B.ARCH, "-std=c++17", "-fsyntax-only", *flags, str(src)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert (r.returncode == 0) == ok, (body, r.stdout.decode()[-600:])
+        assert ok or b"unused-result" in r.stdout, r.stdout.decode()[-600:]
+
+
 def test_poisoned_switches_off_again_when_its_body_raises():
     assert T.poison_setting() == (-1, 0)
     with pytest.raises(ZeroDivisionError):
