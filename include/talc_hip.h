@@ -569,6 +569,15 @@ int talc_test_fail_alloc(uint32_t kinds, int64_t skip, uint32_t count, int real)
  * the bytes it asked for, the code the runtime returned for the last real = 1 failure, the device buffers the library holds
  * now (since it was loaded; the arming call does not reset it), the kinds armed}.  Needs no device. */
 int talc_test_alloc_report(uint64_t out[8]);
+/* Test hook: the retry passes of the context's last correction (talc_batch_correct, talc_correct_batch, or the one-read
+ * correction inside talc_batch_trace_read).  Reads whose per-wave scratch overflowed in the first pass are searched again in
+ * a stage with capacities x 8, what is still flagged behind it in one with x 64.  out = {reads the x 8 stage searched, reads
+ * the x 64 stage searched, reads still flagged behind the last stage that ran (talc_timing.n_failed: they leave as they
+ * came, TALC_READ_ERROR), stages that were refused (the scratch or the work list did not fit: the passes end there)}.  A
+ * stage that was refused searched 0 reads; a correction without an overflow reports four zeros.  The library switch
+ * TALC_TEST_TINY_CAPS = 1, 2, 3 shrinks the capacities of the first pass, of the x 8 stage as well, of
+ * every stage, so that reads get to each of these ends.  Needs no device. */
+int talc_test_retry_report(const talc_ctx* c, uint32_t out[4]);
 
 /* Auto strand (docs/auto_strand.md): the k-mer table is directional and a long cDNA read arrives in either orientation; -rev
  * (talc_params.reverse) turns the whole file.  With auto strand every read is corrected in the orientation the short reads

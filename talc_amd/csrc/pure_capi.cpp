@@ -9,6 +9,7 @@
 #include "talc_edit_plan.h"
 #include "talc_kernels_chimera.h"
 #include "talc_kernels_demux.h"
+#include "talc_kernels_search.h"
 #include "talc_kernels_umi.h"
 #include "talc_pure.h"
 #include "talc_wfa.h"
@@ -24,6 +25,17 @@ uint32_t talc_pure_order_bucket(uint32_t cost_est, uint32_t cost_gap, uint32_t g
 uint32_t talc_pure_ascii_to_code_select(uint32_t c) { return ascii_to_code_select(c); }
 uint32_t talc_pure_ascii_to_code(uint32_t c) { return ascii_to_code((uint8_t)c); }
 uint32_t talc_pure_complement_code(uint32_t c) { return complement_code((uint8_t)c); }
+
+// the per-wave scratch of a search stage (talc_kernels_search.h: make_caps) as 36 words: the ten capacities in SearchLimits'
+// order, slotBytes, the 23 offsets in layout order (o_setA .. o_trace), what follows the last region (o_trace + 64), and caps_hold_read
+void talc_pure_make_caps(uint32_t max_len, uint32_t k, uint32_t scale, uint32_t arena_limit, int tiny, uint64_t* out36) {
+  const SearchCaps c = make_caps(max_len, k, scale, arena_limit, tiny != 0);
+  const uint64_t w[36] = {c.seqCap, c.seqArena, c.refCap, c.edgeCap, c.anchCap, c.fullCap, c.fullPool, c.dpCap, c.regCap, c.weakPool, c.slotBytes,
+                          c.o_setA, c.o_setB, c.o_seqPool, c.o_ref, c.o_ancL, c.o_ancR, c.o_ancPos, c.o_fullMeta, c.o_fullPoolB, c.o_edgeLong,
+                          c.o_edgeShort, c.o_edgeTmp, c.o_dp, c.o_gard, c.o_regS, c.o_regE, c.o_wOff, c.o_wLen, c.o_weak, c.o_wideBloom, c.o_rowPool,
+                          c.o_regH, c.o_trace, c.o_trace + 64, caps_hold_read(c, max_len) ? 1u : 0u};
+  for (int i = 0; i < 36; ++i) out36[i] = w[i];
+}
 
 int pure_is_expected_by_model(double alpha, uint32_t nextc, uint32_t cc, int classe_unexpected) {
   return is_expected_by_model(alpha, nextc, cc, classe_unexpected != 0) ? 1 : 0;

@@ -189,6 +189,7 @@ struct talc_ctx {
   Span span[kSpanCount];   // the last run of each report kernel on this context
   TableView view;
   talc_timing timing;
+  uint32_t retryReport[4] = {};   // talc_test_retry_report: the last correction's retry passes (search_retry_passes)
   Switches sw;          // the environment's switches when the context was created (talc_switches.h)
   bool map = false;     // talc_ctx_set_map: corrections keep the correction map
   bool autoStrand = false;   // talc_ctx_set_auto_strand: every read in the orientation k_strand_vote chooses
@@ -463,6 +464,12 @@ int talc_test_alloc_report(uint64_t out[8]) {
   const failhook::State& s = failhook::state();
   out[0] = s.seen[0].load(); out[1] = s.seen[1].load(); out[2] = s.injected.load(); out[3] = s.lastOwner.load();
   out[4] = s.lastBytes.load(); out[5] = s.lastRuntimeCode.load(); out[6] = (uint64_t)s.live.load(); out[7] = s.kinds.load();
+  return TALC_OK;
+}
+// ---- Test hook: which retry stages the last correction of a context ran (search_retry_passes)
+int talc_test_retry_report(const talc_ctx* c, uint32_t out[4]) {
+  if (!c || !out) return fail(TALC_ERR_INVALID, "null argument");
+  for (int i = 0; i < 4; ++i) out[i] = c->retryReport[i];
   return TALC_OK;
 }
 // the checks of a scope go to a tally of its own

@@ -28,7 +28,11 @@ static void ensure_edge_boxes(talc_ctx* c, Stage& st) {
 }
 
 static int ensure_stage(talc_ctx* c, Stage& st, uint32_t maxLen, uint32_t scale, uint32_t n_work) {
-  const SearchCaps caps = make_caps(maxLen, c->p.k, scale, scale == 1 ? c->sw.seqArena : 0, scale == 1 && c->sw.tinyCaps);
+  // (test hook TALC_TEST_TINY_CAPS: level 1 shrinks the first pass, 2 the x 8 stage as well, 3 every stage)
+  const bool tiny = c->sw.tinyCaps >= (scale == 1 ? 1u : scale <= 8 ? 2u : 3u);
+  const SearchCaps caps = make_caps(maxLen, c->p.k, scale, scale == 1 ? c->sw.seqArena : 0, tiny);
+  if (!caps_hold_read(caps, maxLen))
+    return fail(TALC_ERR_NOMEM, "a read of %u bases is beyond the 32-bit capacities of the search scratch", maxLen);
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, c->device));
   // (a retry stage's slots are 8 / 64 times a first-pass slot: one wave per SIMD at x 8 — 28 GB for 2 kb reads, halved below
@@ -242,6 +246,8 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
   std::vector<uint32_t> retry;
   for (uint32_t r = 0; r < b->n_reads; ++r) if (b->h_state[r].overflow) retry.push_back(r);
   c->timing.n_retried = (uint32_t)retry.size();
+  uint32_t* const report = c->retryReport;   // reads sent to x 8, to x 64, still flagged at the end, stages refused
+  report[2] = (uint32_t)retry.size();
   HIPCHK(hipEventRecord(c->ev[kEvRetry0], s));
   for (uint32_t scale = 8; scale <= 64 && !retry.empty(); scale *= 8) {
     // The first pass has left a complete, valid batch: a retry stage that does not fit the device is not an error of the
@@ -249,11 +255,12 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
     // and the call returns TALC_WARN_READ_ERRORS; negative codes are kept for real HIP errors.
     Stage big;
     if ((rc = ensure_stage(c, big, b->max_len, scale, (uint32_t)retry.size()))) {
-      if (rc == TALC_ERR_NOMEM) break;
+      if (rc == TALC_ERR_NOMEM) { ++report[3]; break; }
       return rc;
     }
     DevBuf<uint32_t> d_retry;
-    if (d_retry.alloc(retry.size()) != hipSuccess) break;
+    if (d_retry.alloc(retry.size()) != hipSuccess) { ++report[3]; break; }
+    report[scale == 8 ? 0 : 1] = (uint32_t)retry.size();
     HIPCHK(hipMemcpyAsync(d_retry.get(), retry.data(), retry.size() * 4, hipMemcpyHostToDevice, s));
     for (uint32_t r : retry) {
       b->h_state[r].overflow = 0;
@@ -265,6 +272,7 @@ static int search_retry_passes(talc_ctx* c, talc_batch* b, const TraceBuf& tb, u
     std::vector<uint32_t> again;
     for (uint32_t r : retry) if (b->h_state[r].overflow) again.push_back(r);
     retry.swap(again);
+    report[2] = (uint32_t)retry.size();
   }
   HIPCHK(hipEventRecord(c->ev[kEvRetry1], s));
   return TALC_OK;
@@ -325,6 +333,7 @@ static int run_pipeline(talc_ctx* c, talc_batch* b, TraceHost* th, uint32_t trac
   HIPCHK(hipSetDevice(c->device));
   int rc;
   b->holds.drop_results();
+  memset(c->retryReport, 0, sizeof c->retryReport);
   const bool map = c->map;
   if (map) HIPCHK(b->d_mapedge.ensure(c->cache, 2ull * std::max<uint32_t>(b->n_reads, 1)));
   const TraceBuf tb = trace_buf(c, th);

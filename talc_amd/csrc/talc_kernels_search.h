@@ -18,9 +18,11 @@
 // in growth order in per-wave HBM scratch, in two ping-pong sets of TCAP slots.
 #pragma once
 #include "talc_common.h"
-#include "talc_kernels_probe.h"
 #include "talc_pure.h"
+#if defined(__HIPCC__)   // (the host build of the pure library takes the scratch layout below and nothing of the kernels)
+#include "talc_kernels_probe.h"
 #include "talc_wave.h"
+#endif
 
 namespace talc {
 
@@ -68,7 +70,7 @@ struct ReadState {
 #endif
 };
 
-__host__ __device__ inline uint64_t out_capacity_for(uint64_t L) { return 4 * L + 1024; }
+TALC_HD uint64_t out_capacity_for(uint64_t L) { return 4 * L + 1024; }
 
 struct FullMeta { uint32_t off, len; int32_t lanc, ranc; double dist; };
 
@@ -176,21 +178,26 @@ static inline SearchCaps make_caps(uint32_t maxLen, uint32_t K, uint32_t scale, 
     arena = std::min<uint64_t>(fullArena, std::max<uint64_t>(1ull << 20, 8ull * c.seqCap));
     if (arenaLimit) arena = std::min<uint64_t>(arena, arenaLimit);
   }
-  c.seqArena = (uint32_t)align_up(std::min<uint64_t>(arena, 0xFFFFFF00ull), 16);
-  c.refCap = (uint32_t)align_up(Lm + 2ull * K + 64, 16);
-  c.edgeCap = (uint32_t)align_up((uint64_t)c.seqCap + c.refCap, 16);
+  // (every 32-bit field saturates at 0xFFFFFF00, a multiple of 16: a sum that wrapped would leave a larger stage with
+  //  less room than the one before it — fullPool from reads of 14 Mb at x 64, weakPool from 1.07 Gb, edgeCap from 1.95 Gb;
+  //  batch_build takes reads up to 0x7fffff00.  The bridge pool is a counted capacity, the search flags what does not fit;
+  //  the buffers the search sizes by the read alone are not: caps_hold_read below, which ensure_stage asks)
+  auto sat = [](uint64_t x, uint64_t a) { return (uint32_t)align_up(std::min<uint64_t>(x, 0xFFFFFF00ull), a); };
+  c.seqArena = sat(arena, 16);
+  c.refCap = sat(Lm + 2ull * K + 64, 16);
+  c.edgeCap = sat((uint64_t)c.seqCap + c.refCap, 16);
   // (a region of n k-mers records at most n positions: beyond that the anchor lists cannot overflow.  2048 in the first
   //  pass already — 100 KB of a 3.4 MB slot: a nearly error-free read is ONE region of a kilobase and more, its lists hold
   //  every forking k-mer of it, and with 256 every such read went to the retry stage's few slots)
   c.anchCap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(256ull * scale, 2048ull), Lm + 8);
   if (c.anchCap < 8) c.anchCap = 8;
   c.fullCap = 128 * scale;
-  c.fullPool = (uint32_t)align_up(std::max<uint64_t>(65536, 4ull * c.seqCap) * scale, 16);
-  c.dpCap = (uint32_t)align_up(std::max<uint64_t>(c.edgeCap, c.seqCap) + 8, 4);
+  c.fullPool = sat(std::max<uint64_t>(65536, 4ull * c.seqCap) * scale, 16);
+  c.dpCap = sat(std::max<uint64_t>(c.edgeCap, c.seqCap) + 8, 4);
   if (c.dpCap < 2048) c.dpCap = 2048;   // (the phased x-drop keeps its hand-over state in these arrays)
   if (tiny) { c.anchCap = 3; c.fullCap = 1; c.fullPool = (uint32_t)align_up((uint64_t)c.seqCap, 16); }  // test hook: force the retry pass
   c.regCap = (uint32_t)(Lm / 2 + 4);
-  c.weakPool = (uint32_t)align_up(out_capacity_for(Lm), 16);
+  c.weakPool = sat(out_capacity_for(Lm), 16);
   uint64_t o = 0;
   auto take = [&](uint64_t bytes) { uint64_t r = o; o = align_up(o + bytes, 16); return r; };
   c.o_setA = take(TrailSetLayout::bytes);
@@ -218,6 +225,14 @@ static inline SearchCaps make_caps(uint32_t maxLen, uint32_t K, uint32_t scale, 
   c.o_trace = take(64);
   c.slotBytes = align_up(o, 256);
   return c;
+}
+
+// The buffers a search fills by the read's length without counting — an edge candidate (edgeCap), the DP arrays (dpCap: 8
+// ints beyond the longer of an edge candidate and a Trail), the corrected weak sequences (weakPool) — have the room their
+// formulas ask for; false only where a field saturated (reads beyond a gigabase): such a stage is refused, never launched.
+static inline bool caps_hold_read(const SearchCaps& c, uint32_t maxLen) {
+  return (uint64_t)c.edgeCap >= (uint64_t)c.seqCap + c.refCap && (uint64_t)c.dpCap >= std::max<uint64_t>(c.edgeCap, c.seqCap) + 8 &&
+         (uint64_t)c.weakPool >= out_capacity_for(maxLen);
 }
 
 #if defined(__HIPCC__)

@@ -19,7 +19,8 @@ struct Switches {
   // contexts
   uint32_t searchSlots = 0;     // TALC_SEARCH_SLOTS: wave slots of a search launch (0: by the device)
   uint32_t seqArena = 0;        // TALC_SEQ_ARENA (test hook): bytes of a first-pass search's Trail arena (0: make_caps's own)
-  bool tinyCaps = false;        // TALC_TEST_TINY_CAPS: first-pass scratch so small that reads go to the retry pass
+  uint32_t tinyCaps = 0;        // TALC_TEST_TINY_CAPS: a level.  1: first-pass scratch so small that reads go to the retry pass; 2: the
+                                // x 8 stage's as well (flagged reads reach a real x 64 stage); 3: every stage's (reads exhaust all three)
   bool failRetryAlloc = false;  // TALC_TEST_FAIL_RETRY_ALLOC: the retry stage is refused
   int edgeTasks = -1;           // TALC_EDGE_TASKS: -1 (unset) the batch's fork share decides, 0 off, 1 on
   uint32_t edgeTaskMin = 150, edgeTaskHeavy = 200, edgeTaskRounds = 0xFFFF, edgeLingerMod = 16;   // TALC_EDGE_TASK_*, TALC_EDGE_LINGER_MOD
@@ -45,7 +46,7 @@ inline Switches read_switches() {
   if (const char* e = std::getenv("TALC_TABLE_SLOTS_X10")) { const uint64_t v = std::strtoull(e, nullptr, 10); if (v >= 20 && v <= 80) s.tableSlotsX10 = (uint32_t)v; }
   s.searchSlots = clamped("TALC_SEARCH_SLOTS", 0, 0, 1L << 30);
   s.seqArena = clamped("TALC_SEQ_ARENA", 0, 0, 1L << 30);
-  s.tinyCaps = num("TALC_TEST_TINY_CAPS", 0) > 0;
+  s.tinyCaps = clamped("TALC_TEST_TINY_CAPS", 0, 0, 3);
   s.failRetryAlloc = given("TALC_TEST_FAIL_RETRY_ALLOC");
   if (given("TALC_EDGE_TASKS")) { const long v = num("TALC_EDGE_TASKS", 0); s.edgeTasks = v == 0 ? 0 : v > 0 ? 1 : -1; }
   s.edgeTaskMin = clamped("TALC_EDGE_TASK_MIN", 150, 0, 1L << 30);

@@ -278,6 +278,7 @@ def _abi():
         "talc_test_guard_selftest": (i32, [vp]),
         "talc_test_fail_alloc": (i32, [u32, C.c_int64, u32, i32]),
         "talc_test_alloc_report": (i32, [vp]),
+        "talc_test_retry_report": (i32, [vp, vp]),
         "talc_counter_histo": (i32, [vp, u32, vp, stats]),
         "talc_counter_get_histo_timing": (i32, [vp, vp]),
         "talc_table_histo": (i32, [vp, i32, u32, vp, stats]),
@@ -756,6 +757,13 @@ class Context(_Owner):
         t = Timing()
         _chk(lib().talc_ctx_get_timing(self._h, C.byref(t)))
         return t
+
+    def retry_report(self):
+        """Test hook: the retry passes of the context's last correction: dict of x8 and x64 (reads each stage searched), left
+        (reads still flagged behind the last stage that ran: timing().n_failed) and refused (stages that did not fit)."""
+        r = np.zeros(4, dtype=np.uint32)
+        _chk(lib().talc_test_retry_report(self._h, r.ctypes.data))
+        return dict(x8=int(r[0]), x64=int(r[1]), left=int(r[2]), refused=int(r[3]))
 
     def record_map(self, on=True):
         """Later corrections of this context keep the correction map (Batch.fetch_map, fetch_corrected(soft_mask=True))."""

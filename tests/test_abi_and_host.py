@@ -111,6 +111,13 @@ def test_alloc_failure_hooks_are_exported_refuse_unknown_kinds_and_report_withou
     assert e.value.code == -1 and T.alloc_report()["kinds"] == 0
 
 
+def test_retry_report_hook_is_exported_and_refuses_null_arguments():
+    L = T.lib()
+    assert hasattr(L, "talc_test_retry_report") and "talc_test_retry_report" in T.ABI_SYMBOLS
+    out = np.zeros(4, dtype=np.uint32)
+    assert L.talc_test_retry_report(None, out.ctypes.data) == -1 and L.talc_last_error()      # TALC_ERR_INVALID
+
+
 def test_every_owner_must_have_its_result_looked_at(tmp_path):
     """The five allocating calls of talc_devmem.h are [[nodiscard]], and the library's build makes a dropped result an error:
     -Wno-unused-value, which the build passes, silences -Wunused-result too, so -Werror=unused-result stands behind it.  A

@@ -303,11 +303,9 @@ def test_retry_passes_with_every_request_failing(monkeypatch):
     retry stage or d_retry leaves the reads still flagged as the first pass left them: their tuples are those of a run whose
     retry stage TALC_TEST_FAIL_RETRY_ALLOC refuses (test_gpu_solidity.py), everybody else's the baseline's.
 
-    NOT covered: the x 64 stage.  The hook shrinks the capacities of the first pass only (make_caps: `tiny` goes with scale 1);
-    the x 8 stage has eight times the ordinary capacities, which hold every read this suite has (the bush of
-    param_limit_cases.py fills the ordinary ones to three Trails below their end), so no read is still flagged behind it and
-    the second stage is never sized.  A x 64 stage refused behind a x 8 pass that ran — the states rewritten once more — is
-    checked by reading only (search_retry_passes: a read flagged again is passed through as the first pass passed it)."""
+    The x 64 stage: the hook at level 1 shrinks the capacities of the first pass only; the x 8 stage has eight times the
+    ordinary capacities, which hold every read this suite has, so no read is still flagged behind it and exactly one stage
+    is sized here.  A x 64 stage refused behind a x 8 pass that ran is the test below (level 2)."""
     s = pipe()
     reads, n = s["reads"], len(s["reads"])
     monkeypatch.setenv("TALC_TEST_TINY_CAPS", "1")
@@ -358,6 +356,79 @@ def test_retry_passes_with_every_request_failing(monkeypatch):
     warned.clear()
     tally = sweep(sc, DEVICE, 2, same)
     assert len([w for w in warned if w[-1] == "under the hook"]) >= stages, warned     # both attempts of a retry stage refused
+
+
+def test_a_refused_x64_stage_behind_an_x8_pass_that_ran(monkeypatch):
+    """TALC_TEST_TINY_CAPS=2: the x 8 stage is as small as the first pass, every read it searched is flagged again and the
+    x 64 stage and its d_retry are asked for.  The sweep finds two stages; a refused d_retry of either — for the x 64 stage:
+    behind a x 8 pass that ran and rewrote the states — leaves exactly the reads flagged before it, passed through as the
+    first pass passed them (the tuples of a run whose retry stage TALC_TEST_FAIL_RETRY_ALLOC refuses), and the call returns
+    the warning; a refused scratch is asked for once more and changes nothing."""
+    s = pipe()
+    reads, n = s["reads"], len(s["reads"])
+    monkeypatch.setenv("TALC_SEARCH_SLOTS", "8")
+    want = s["fresh"][False][0]
+
+    def make_ctx():
+        ctx = T.Context(s["pair"].ttab, s["pair"].p, 0)
+        ctx.record_map(True)
+        return ctx
+
+    monkeypatch.setenv("TALC_TEST_TINY_CAPS", "1")
+    monkeypatch.setenv("TALC_TEST_FAIL_RETRY_ALLOC", "1")
+    ctx = make_ctx()
+    try:
+        refused, refused_work, _ = everything(ctx, reads)
+    finally:
+        ctx.close()
+    monkeypatch.delenv("TALC_TEST_FAIL_RETRY_ALLOC")
+    monkeypatch.setenv("TALC_TEST_TINY_CAPS", "2")
+    ctx = make_ctx()
+    try:
+        got, got_work, _ = everything(ctx, reads)
+        rep = ctx.retry_report()
+    finally:
+        ctx.close()
+    first_flagged = [i for i in range(n) if refused[i][1] == T.READ_ERROR]
+    assert first_difference(got, want) is None and got_work[0] == 0 and got_work[6] == 0
+    assert rep == dict(x8=len(first_flagged), x64=len(first_flagged), left=0, refused=0) and first_flagged, (rep, first_flagged)
+    warned = []
+
+    def same(got, what):
+        per, work, _ = got
+        flagged = [i for i in range(n) if per[i][1] == T.READ_ERROR]
+        if work[0] == T.WARN_READ_ERRORS:
+            assert flagged == first_flagged and work[4] == len(flagged), (what, work, flagged)
+            warned.append(what)
+        else:
+            assert work[0] == 0 and not flagged and work[4] == 0, (what, work)
+        mixed = [refused[i] if i in flagged else want[i] for i in range(n)]
+        assert first_difference(per, mixed) is None, (what, first_difference(per, mixed))
+        assert work[3] == len(first_flagged), (what, work)
+        assert work[1:3] == (got_work[3], got_work[4]), (what, work)
+        if what[2] == T.OWNER_DEVBUF and what[-1] == "under the hook":
+            requested.append(what[3])
+
+    def result(e):
+        per, work, rep = per_read(e["f"], n), e["work"], e["ctx"].retry_report()
+        # the report of the correction whose outputs these are: a warning is one stage refused, the reads before it left
+        if work[0] == T.WARN_READ_ERRORS:
+            assert rep["refused"] == 1 and rep["left"] == work[4] == len(first_flagged) and rep["x64"] == 0 and rep["x8"] in (0, rep["left"]), (rep, work)
+        else:
+            assert rep == dict(x8=len(first_flagged), x64=len(first_flagged), left=0, refused=0), (rep, work)
+        return per, work, None
+
+    requested = []
+    sc = Scenario(batch_steps(make_ctx, s["packed"], False), 1, result, close_batch)
+    with guards_checked():
+        tally = sweep(sc, DEVICE, 1, same, poison=POISON)
+    under_hook = [w for w in warned if w[-1] == "under the hook"]
+    stages = len(under_hook)
+    assert stages == 2, warned                        # the d_retry of the x 8 stage and that of the x 64 stage
+    # the largest request a run got over is the x 64 stage's scratch (its first attempt)
+    print("x 64 stage of %d flagged reads, longest read %d bases, TALC_SEARCH_SLOTS=8: scratch of %d bytes" % (len(first_flagged), max(map(len, reads)), max(requested)))
+    assert all(w[2] == T.OWNER_DEVBUF and w[1] == 1 for w in under_hook)
+    assert tally["survived"].get(T.OWNER_DEVBUF, 0) == SURVIVABLE_CORRECTION + 2 * stages, (tally, stages)
 
 
 # ---------------------------------------------------------------- 3. preparation
