@@ -675,12 +675,12 @@ int talc_batch_ends(talc_ctx* c, talc_batch* b);
 /* rows: n_reads rows.  TALC_ERR_STATE when no scan has run on b. */
 int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows);
 /* talc_batch_create of the kept intervals: the raw bytes go to the device once, the scan runs on them, and the kept
- * intervals are gathered on the device into the batch's text (k_clip_gather).  From then on every call on the batch returns,
+ * intervals are gathered on the device into the batch's text (k_gather).  From then on every call on the batch returns,
  * byte for byte, what it returns on talc_batch_create of the reads clipped on the host — under -rev and auto strand too.
  * TALC_ERR_STATE when the clean-up is off. */
 int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads,
                               talc_batch** out);
-/* Measurement: device time (ms) of the context's last k_read_ends and k_clip_gather.  Either pointer may be NULL. */
+/* Measurement: device time (ms) of the context's last k_read_ends and the k_gather of its last clipped batch.  Either pointer may be NULL. */
 int talc_ctx_get_ends_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
 
 /* Chimeric long reads (docs/chimeras.md): the adapters of the end clean-up searched over the whole of every read, on both
@@ -719,7 +719,7 @@ uint64_t talc_batch_num_chimera_hits(const talc_batch* b);
  * TALC_ERR_CAPACITY names the size needed; TALC_ERR_STATE when no scan has run on b. */
 int talc_batch_fetch_chimera(talc_ctx* c, talc_batch* b, talc_chimera_hit* hits, uint64_t capacity, uint64_t* read_hit_offsets);
 /* talc_batch_create of the kept pieces: the bytes go to the device once, the scan runs on them, the host computes the
- * pieces from the hits and k_split_gather fills the batch's text.  The batch has one read per piece.  clip != 0 (needs the
+ * pieces from the hits and k_gather fills the batch's text.  The batch has one read per piece.  clip != 0 (needs the
  * end clean-up, else TALC_ERR_STATE): the pieces are gathered into a staging text and the batch is made from it as
  * talc_batch_create_clipped makes one, so the end rule applies to every piece.  From then on every call on the batch
  * returns, byte for byte, what it returns on talc_batch_create of the pieces cut (and clipped) on the host. */
@@ -729,7 +729,7 @@ uint64_t talc_batch_num_split_pieces(const talc_batch* b);
 /* pieces: talc_batch_num_split_pieces rows; read_piece_offsets: n_reads + 1 of the source reads.  Either may be NULL.
  * TALC_ERR_STATE on a batch that talc_batch_create_split did not make. */
 int talc_batch_fetch_split(talc_ctx* c, talc_batch* b, talc_split_piece* pieces, uint64_t* read_piece_offsets);
-/* Measurement: device time (ms) of the context's last k_read_chimera and k_split_gather.  Either pointer may be NULL. */
+/* Measurement: device time (ms) of the context's last k_read_chimera and the k_gather of its last split batch's pieces.  Either pointer may be NULL. */
 int talc_ctx_get_chimera_timing(const talc_ctx* c, float* scan_ms, float* gather_ms);
 
 /* Barcode demultiplexing (docs/demux.md): the sample barcode of every read, called on the device from the batch's raw bytes.

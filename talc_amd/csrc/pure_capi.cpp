@@ -169,15 +169,9 @@ int64_t pure_chimera_scan(const char* adapters, uint32_t max_error_pct, const ui
                           ChimeraHit* out, uint64_t capacity) {
   ChimeraParams P;
   P.nPatterns = 0; P.pad_ = 0;
-  for (const char* p = adapters && *adapters ? adapters : nullptr; p;) {
-    const char* e = p;
-    while (*e && *e != ',') ++e;
-    const size_t m = (size_t)(e - p);
-    if (m < 12 || m > 64 || P.nPatterns + 2 > kChimeraMaxPatterns) return -1;
-    uint8_t codes[64];
-    for (size_t i = 0; i < m; ++i) { codes[i] = ascii_to_code((uint8_t)p[i]); if (codes[i] >= 4) return -1; }
-    chimera_params_add(P, codes, (uint32_t)m, max_error_pct);
-    p = *e ? e + 1 : nullptr;
+  for (PatternList it(adapters); it.next(acgt_set);) {
+    if (it.fault || P.nPatterns + 2 > kChimeraMaxPatterns) return -1;
+    chimera_params_add(P, it.p, (uint32_t)it.m, acgt_set, max_error_pct);
   }
   std::vector<ChimeraHit> hits;
   for (uint32_t r = 0; r < n_reads; ++r) chimera_scan_host(bases + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), r, P, hits);
@@ -210,7 +204,7 @@ void pure_demux_geometry(uint32_t n_barcodes, uint32_t* out3) {
 void pure_demux_place(uint32_t n_barcodes, uint32_t end, uint32_t b, uint32_t q, uint32_t n, uint32_t* out3) {
   const DemuxGeometry g = demux_geometry(n_barcodes);
   out3[0] = demux_pattern_slot(g, end, b) + q;
-  demux_chunk(g, n, q, &out3[1], &out3[2]);
+  sellers_chunk(n, g.chunks, q, &out3[1], &out3[2]);
 }
 // The setting as talc_ctx_set_demux takes it, validated the same way: -1 and the message in `why` when it is refused or off.
 // One row per read.

@@ -172,8 +172,8 @@ enum CtxSpan {
   // the edit scripts (run_edits): the first k_edit_align rounds, k_edit_count, the second rounds, k_edit_pack
   kSpanEditAlignA, kSpanEditCount, kSpanEditAlignB, kSpanEditPack,
   kSpanSupport,                          // k_base_support
-  kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_clip_gather
-  kSpanChimeraScan, kSpanChimeraGather,  // the chimera split: k_read_chimera, k_split_gather
+  kSpanEndsScan, kSpanEndsGather,        // the end clean-up: k_read_ends, k_gather of a clipped batch
+  kSpanChimeraScan, kSpanChimeraGather,  // the chimera split: k_read_chimera, k_gather of the pieces
   kSpanDemuxScan,                        // barcode demultiplexing: k_read_demux
   kSpanUmiScan,                          // the UMI read-out: k_read_umi
   kSpanCount
@@ -350,7 +350,7 @@ static_assert(sizeof(EndRow) == sizeof(talc_end_row) && sizeof(talc_end_row) == 
 static_assert(sizeof(DemuxRow) == sizeof(talc_demux_row) && sizeof(talc_demux_row) == 16 && TALC_DEMUX_CONFLICT == DEMUX_CONFLICT, "k_read_demux writes talc_demux_row records");
 static_assert(sizeof(UmiRow) == sizeof(talc_umi_row) && sizeof(talc_umi_row) == 56 && sizeof(UmiRow) == kUmiRowWords * 4, "k_read_umi writes talc_umi_row records");
 static_assert(sizeof(ChimeraHit) == sizeof(talc_chimera_hit) && sizeof(talc_chimera_hit) == 16 && sizeof(SplitPiece) == sizeof(talc_split_piece) &&
-              sizeof(talc_split_piece) == 16, "k_read_chimera writes talc_chimera_hit records, k_split_gather reads talc_split_piece records");
+              sizeof(talc_split_piece) == 16, "k_read_chimera writes talc_chimera_hit records, k_gather reads talc_split_piece records");
 
 // What an entry point that takes a context and a batch checks first: they belong together and the `rest` of its arguments is there
 // (`msg`: the call's own wording).  enter() makes the context's device current as well; belong() where a state check comes before that.

@@ -16,7 +16,8 @@ int talc_ctx_set_chimera(talc_ctx* c, int on, uint32_t max_error_pct, uint32_t m
 static ChimeraParams chimera_params_of(const talc_ctx* c) {
   ChimeraParams P;
   memset(&P, 0, sizeof P);
-  for (uint32_t a = 0; a < c->ends.nAdapters && a < ENDS_MAX_ADAPTERS; ++a) chimera_params_add(P, c->endsCodes[a], c->ends.m[a], c->chimeraPct);
+  for (uint32_t a = 0; a < c->ends.nAdapters && a < ENDS_MAX_ADAPTERS; ++a)
+    chimera_params_add(P, c->endsCodes[a], c->ends.m[a], code_set, c->chimeraPct);
   return P;
 }
 
@@ -89,33 +90,20 @@ int talc_batch_fetch_chimera(talc_ctx* c, talc_batch* b, talc_chimera_hit* hits,
   return TALC_OK;
 }
 
-// The bytes go up once into a staging buffer; the scan runs on them; the host computes the pieces (split_pieces);
-// k_split_gather copies every piece to its place: into the new batch's text (batch_build), or, with clip, into a second
-// staging text from which the batch is made as a clipped one (clipped_from_staged).
+static const char* split_refusal(const talc_ctx* c) {   // (clip needs the end clean-up on; a setting with an adapter is on)
+  if (!c->chimeraOn) return "the chimera scan is off (talc_ctx_set_chimera)";
+  return c->ends.nAdapters ? nullptr : "the chimera scan has no adapter to look for (talc_ctx_set_ends)";
+}
+// The bytes go up once into a staging buffer (stage_reads); the scan runs on them; the host computes the pieces
+// (split_pieces); k_gather copies every piece to its place: into the new batch's text (batch_build), or, with clip, into a
+// second staging text from which the batch is made as a clipped one (clipped_from_staged).
 int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, int clip, talc_batch** out) {
-  if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
-  if (!c->chimeraOn) return fail(TALC_ERR_STATE, "the chimera scan is off (talc_ctx_set_chimera)");
-  if (!c->ends.nAdapters) return fail(TALC_ERR_STATE, "the chimera scan has no adapter to look for (talc_ctx_set_ends)");
-  // (clip needs the end clean-up on; a setting with an adapter is on)
-  if (offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
-  for (uint32_t r = 0; r < n_reads; ++r) {
-    if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must be non-decreasing");
-    if (offsets[r + 1] - offsets[r] > 0x7fffff00ull) return fail(TALC_ERR_INVALID, "read %u too long", r);
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const uint64_t nb = offsets[n_reads];
-  auto b = std::make_unique<talc_batch>();
-  talc_batch* const bp = b.get();
-  bp->ctx = c;
-  CachedBuf<uint8_t> stage;
-  CachedBuf<uint64_t> stageOff;
-  HIPCHK(stage.alloc(c->cache, std::max<uint64_t>(nb, 1)));
-  HIPCHK(stageOff.alloc(c->cache, (uint64_t)n_reads + 1));
-  if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  StagedReads st;
   int rc;
-  if (c->demuxOn && (rc = demux_scan(c, bp, stage.get(), stageOff.get(), n_reads))) return rc;   // (docs/demux.md: the rows of the source reads)
-  if ((rc = run_chimera_scan(c, stage.get(), stageOff.get(), offsets, n_reads, bp->h_hits, bp->h_read_hit_off))) return rc;
+  if ((rc = stage_reads(c, bases, offsets, n_reads, split_refusal, st))) return rc;
+  talc_batch* const bp = st.b.get();
+  if ((rc = run_chimera_scan(c, st.text.get(), st.off.get(), offsets, n_reads, bp->h_hits, bp->h_read_hit_off))) return rc;
   split_pieces(bp->h_hits.data(), bp->h_read_hit_off.data(), offsets, n_reads, c->chimeraMinPiece, bp->h_split, bp->h_read_split_off, nullptr, nullptr);
   if (bp->h_split.size() > 0xffffff00ull) return fail(TALC_ERR_INVALID, "%llu pieces: more than a batch holds", (unsigned long long)bp->h_split.size());
   const uint32_t n_pieces = (uint32_t)bp->h_split.size();
@@ -126,7 +114,7 @@ int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offs
   auto gather = [&](hipStream_t s, uint8_t* dst, const uint64_t* dstOff) {
     return c->span[kSpanChimeraGather].around(s, [&] {
       if (n_pieces)
-        hipLaunchKernelGGL(k_split_gather, dim3(n_pieces), dim3(256), 0, s, stage.get(), stageOff.get(), n_reads, d_split.get(), n_pieces, dst, dstOff);
+        hipLaunchKernelGGL(k_gather<SplitPiece>, dim3(n_pieces), dim3(256), 0, s, st.text.get(), st.off.get(), n_reads, d_split.get(), n_pieces, dst, dstOff);
     });
   };
   if (!clip) {
@@ -147,7 +135,7 @@ int talc_batch_create_split(talc_ctx* c, const char* bases, const uint64_t* offs
   bp->chimeraGen = c->chimeraGen;
   bp->chimeraEndsGen = c->endsGen;
   bp->holds.chimera = bp->holds.split = true;
-  *out = b.release();
+  *out = st.b.release();
   return TALC_OK;
 }
 

@@ -12,21 +12,15 @@ int talc_ctx_set_ends(talc_ctx* c, const char* adapters, uint32_t max_error_pct,
   memset(&P, 0, sizeof P);
   memset(codes, 0, sizeof codes);
   P.polyMin = poly_min; P.window = window;
-  for (const char* p = adapters && *adapters ? adapters : nullptr; p;) {
-    const char* e = strchr(p, ',');
-    const size_t m = e ? (size_t)(e - p) : strlen(p);
+  for (PatternList it(adapters); it.next(acgt_set);) {
     if (P.nAdapters == ENDS_MAX_ADAPTERS) return fail(TALC_ERR_INVALID, "adapters: more than %u", (uint32_t)ENDS_MAX_ADAPTERS);
-    if (m < 12 || m > 64) return fail(TALC_ERR_INVALID, "adapters: adapter %u has %llu letters: 12 .. 64", P.nAdapters + 1, (unsigned long long)m);
-    for (size_t i = 0; i < m; ++i) {
-      const uint8_t code = ascii_to_code((uint8_t)p[i]);
-      if (code >= 4) return fail(TALC_ERR_INVALID, "adapters: adapter %u has a letter that is not one of ACGTacgt", P.nAdapters + 1);
-      P.peq[P.nAdapters][code] |= 1ull << i;
-      codes[P.nAdapters][i] = code;
-    }
-    P.m[P.nAdapters] = (uint32_t)m;
-    P.k[P.nAdapters] = (uint32_t)(max_error_pct * m / 100);
+    if (it.fault == PATTERN_LENGTH) return fail(TALC_ERR_INVALID, "adapters: adapter %u has %llu letters: 12 .. 64", P.nAdapters + 1, (unsigned long long)it.m);
+    if (it.fault) return fail(TALC_ERR_INVALID, "adapters: adapter %u has a letter that is not one of ACGTacgt", P.nAdapters + 1);
+    pattern_masks(it.p, it.m, acgt_set, false, false, P.peq[P.nAdapters]);
+    for (size_t i = 0; i < it.m; ++i) codes[P.nAdapters][i] = ascii_to_code((uint8_t)it.p[i]);   // (the chimera scan's patterns are made from them)
+    P.m[P.nAdapters] = (uint32_t)it.m;
+    P.k[P.nAdapters] = (uint32_t)(max_error_pct * it.m / 100);
     ++P.nAdapters;
-    p = e ? e + 1 : nullptr;
   }
   c->ends = P;
   memcpy(c->endsCodes, codes, sizeof codes);
@@ -70,17 +64,18 @@ int talc_batch_fetch_ends(talc_ctx* c, talc_batch* b, talc_end_row* rows) {
   return read_spans(c);
 }
 
-static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
-                               uint32_t n_reads);
-static int clipped_from_staged_umi(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
-                                   uint32_t n_reads);
-
-// The raw bytes go up once, into a staging buffer of the context's cache; the scan's rows come to the host, which lays the
-// batch out from the kept lengths (batch_build, as talc_batch_create); k_clip_gather then fills the batch's text from the
-// staging buffer, device to device.  The staging buffers go back to the cache when the batch stands.
-int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
-  if (!c || !offsets || !out || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
-  if (!c->endsOn && !c->umiOn) return fail(TALC_ERR_STATE, "the end clean-up is off (talc_ctx_set_ends)");   // (docs/umi.md: the UMI alone clips too)
+// What talc_batch_create_clipped and talc_batch_create_split open with: the argument checks (`refusal`: why the context's
+// setting cannot make such a batch, or null), an empty batch, the raw bytes and the offsets up once into staging buffers of
+// the context's cache (they go back to it when the batch stands), and the barcode scan on them when it is on
+// (docs/demux.md: the batch will not hold the reads as they came, its rows are those of the source reads).
+struct StagedReads {
+  std::unique_ptr<talc_batch> b;
+  CachedBuf<uint8_t> text;
+  CachedBuf<uint64_t> off;
+};
+static int stage_reads(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, const char* (*refusal)(const talc_ctx*), StagedReads& st) {
+  if (!c || !offsets || (!bases && n_reads && offsets[n_reads] > 0)) return fail(TALC_ERR_INVALID, "null argument");
+  if (const char* const why = refusal(c)) return fail(TALC_ERR_STATE, "%s", why);
   if (offsets[0] != 0) return fail(TALC_ERR_INVALID, "offsets[0] must be 0");
   for (uint32_t r = 0; r < n_reads; ++r) {
     if (offsets[r + 1] < offsets[r]) return fail(TALC_ERR_INVALID, "offsets must be non-decreasing");
@@ -88,87 +83,73 @@ int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* of
   }
   HIPCHK(hipSetDevice(c->device));
   const uint64_t nb = offsets[n_reads];
-  auto b = std::make_unique<talc_batch>();
-  talc_batch* const bp = b.get();
-  bp->ctx = c;
-  CachedBuf<uint8_t> stage;
-  CachedBuf<uint64_t> stageOff;
-  HIPCHK(stage.alloc(c->cache, std::max<uint64_t>(nb, 1)));
-  HIPCHK(stageOff.alloc(c->cache, (uint64_t)n_reads + 1));
-  if (nb) HIPCHK(hipMemcpyAsync(stage.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(stageOff.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (c->demuxOn)   // (docs/demux.md: the batch will not hold the reads as they came)
-    if (int rc = demux_scan(c, bp, stage.get(), stageOff.get(), n_reads)) return rc;
-  if (int rc = clipped_from_staged(c, bp, stage, stageOff, offsets, n_reads)) return rc;
-  *out = b.release();
-  return TALC_OK;
+  st.b = std::make_unique<talc_batch>();
+  st.b->ctx = c;
+  HIPCHK(st.text.alloc(c->cache, std::max<uint64_t>(nb, 1)));
+  HIPCHK(st.off.alloc(c->cache, (uint64_t)n_reads + 1));
+  if (nb) HIPCHK(hipMemcpyAsync(st.text.get(), bases, nb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(st.off.get(), offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  return c->demuxOn ? demux_scan(c, st.b.get(), st.text.get(), st.off.get(), n_reads) : TALC_OK;
+}
+
+// The rows `d_rows` of the `scan` scan over the staged reads come to the host, which lays the batch out from their kept
+// lengths (batch_build, as talc_batch_create); k_gather then fills the batch's text from the staging buffer, device to device.
+extern "C++" template <class Row>   // (this file is included inside extern "C")
+static int clipped_build(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
+                         uint32_t n_reads, const Row* d_rows, const char* scan) {
+  std::vector<Row> rows(n_reads);
+  if (n_reads) HIPCHK(hipMemcpyAsync(rows.data(), d_rows, (size_t)n_reads * sizeof(Row), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::vector<uint64_t> kept((size_t)n_reads + 1, 0);
+  for (uint32_t r = 0; r < n_reads; ++r) {
+    const uint64_t L = offsets[r + 1] - offsets[r];
+    const GatherInterval iv = gather_interval(rows[r], r);
+    if ((uint64_t)iv.start + iv.len > L)
+      return fail(TALC_ERR_DEVICE, "the %s scan left read %u an interval beyond its %llu bytes", scan, r, (unsigned long long)L);
+    kept[r + 1] = kept[r] + iv.len;
+  }
+  return batch_build(c, bp, kept.data(), n_reads, [&](hipStream_t s) {
+    return c->span[kSpanEndsGather].around(s, [&] {
+      if (n_reads)
+        hipLaunchKernelGGL(k_gather<Row>, dim3(n_reads), dim3(256), 0, s, stage.get(), stageOff.get(), n_reads, d_rows, n_reads, bp->d_raw.get(),
+                           bp->d_offsets.get());
+    });
+  });
 }
 
 // The clipped batch `bp` from n_reads reads that stand on the device already (`stage` at `stageOff`, ordered on the
-// context's stream; `offsets` are the same offsets on the host): the scan, the rows to the host, the layout from the kept
-// lengths, k_clip_gather.  What talc_batch_create_clipped does behind its upload, and talc_batch_create_split behind its gather.
+// context's stream; `offsets` are the same offsets on the host): the scans, then clipped_build.  What
+// talc_batch_create_clipped does behind its upload, and talc_batch_create_split behind its gather.
+// Without the UMI read-out the rows are k_read_ends'.  With it (docs/umi.md) k_read_ends runs when the end clean-up is on,
+// and its rows stay what it wrote; k_read_umi runs on the same text, and its rows hold the combined intervals.
 static int clipped_from_staged(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
                                uint32_t n_reads) {
-  if (c->umiOn) return clipped_from_staged_umi(c, bp, stage, stageOff, offsets, n_reads);
-  HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
+  const bool umi = c->umiOn, ends = c->endsOn || !umi;
   int rc;
-  if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
-  std::vector<EndRow> rows(n_reads);
-  if (n_reads) HIPCHK(hipMemcpyAsync(rows.data(), bp->d_ends.get(), (size_t)n_reads * sizeof(EndRow), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  std::vector<uint64_t> kept((size_t)n_reads + 1, 0);
-  for (uint32_t r = 0; r < n_reads; ++r) {
-    const uint64_t L = offsets[r + 1] - offsets[r];
-    if ((uint64_t)rows[r].keptStart + rows[r].keptLen > L)
-      return fail(TALC_ERR_DEVICE, "the end scan left read %u an interval beyond its %llu bytes", r, (unsigned long long)L);
-    kept[r + 1] = kept[r] + rows[r].keptLen;
-  }
-  rc = batch_build(c, bp, kept.data(), n_reads, [&](hipStream_t s) {
-    return c->span[kSpanEndsGather].around(s, [&] {
-      if (n_reads)
-        hipLaunchKernelGGL(k_clip_gather, dim3(n_reads), dim3(256), 0, s, stage.get(), stageOff.get(), bp->d_ends.get(), n_reads, bp->d_raw.get(),
-                           bp->d_offsets.get());
-    });
-  });
-  if (rc) return rc;
-  if ((rc = read_spans(c))) return rc;
-  bp->endsGen = c->endsGen;
-  bp->holds.ended = bp->holds.clipped = true;
-  return TALC_OK;
-}
-
-// ... with the UMI read-out on (docs/umi.md): k_read_ends when the end clean-up is on, whose rows stay what it wrote;
-// k_read_umi on the same text, whose rows hold the combined intervals; the layout from those; k_clip_gather_umi.
-static int clipped_from_staged_umi(talc_ctx* c, talc_batch* bp, const CachedBuf<uint8_t>& stage, const CachedBuf<uint64_t>& stageOff, const uint64_t* offsets,
-                                   uint32_t n_reads) {
-  int rc;
-  if (c->endsOn) {
+  if (ends) {
     HIPCHK(bp->d_ends.alloc(c->cache, std::max<uint32_t>(n_reads, 1)));
     if ((rc = launch_ends(c, stage.get(), stageOff.get(), n_reads, bp->d_ends.get()))) return rc;
   }
-  if ((rc = umi_scan(c, bp, stage.get(), stageOff.get(), n_reads, c->endsOn ? bp->d_ends.get() : nullptr))) return rc;
-  std::vector<UmiRow> rows(n_reads);
-  if (n_reads) HIPCHK(hipMemcpyAsync(rows.data(), bp->d_umi.get(), (size_t)n_reads * sizeof(UmiRow), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  std::vector<uint64_t> kept((size_t)n_reads + 1, 0);
-  for (uint32_t r = 0; r < n_reads; ++r) {
-    const uint64_t L = offsets[r + 1] - offsets[r];
-    if ((uint64_t)rows[r].keptStart + rows[r].keptLen > L)
-      return fail(TALC_ERR_DEVICE, "the UMI scan left read %u an interval beyond its %llu bytes", r, (unsigned long long)L);
-    kept[r + 1] = kept[r] + rows[r].keptLen;
-  }
-  rc = batch_build(c, bp, kept.data(), n_reads, [&](hipStream_t s) {
-    return c->span[kSpanEndsGather].around(s, [&] {
-      if (n_reads)
-        hipLaunchKernelGGL(k_clip_gather_umi, dim3(n_reads), dim3(256), 0, s, stage.get(), stageOff.get(), bp->d_umi.get(), n_reads, bp->d_raw.get(),
-                           bp->d_offsets.get());
-    });
-  });
+  if (umi && (rc = umi_scan(c, bp, stage.get(), stageOff.get(), n_reads, ends ? bp->d_ends.get() : nullptr))) return rc;
+  rc = umi ? clipped_build(c, bp, stage, stageOff, offsets, n_reads, bp->d_umi.get(), "UMI")
+           : clipped_build(c, bp, stage, stageOff, offsets, n_reads, bp->d_ends.get(), "end");
   if (rc) return rc;
   if ((rc = read_spans(c))) return rc;
   bp->endsGen = c->endsGen;
-  bp->holds.ended = c->endsOn;
+  bp->holds.ended = ends;
   bp->holds.clipped = true;
+  return TALC_OK;
+}
+
+static const char* clipped_refusal(const talc_ctx* c) {   // (docs/umi.md: the UMI alone clips too)
+  return c->endsOn || c->umiOn ? nullptr : "the end clean-up is off (talc_ctx_set_ends)";
+}
+int talc_batch_create_clipped(talc_ctx* c, const char* bases, const uint64_t* offsets, uint32_t n_reads, talc_batch** out) {
+  if (!out) return fail(TALC_ERR_INVALID, "null argument");
+  StagedReads st;
+  if (int rc = stage_reads(c, bases, offsets, n_reads, clipped_refusal, st)) return rc;
+  if (int rc = clipped_from_staged(c, st.b.get(), st.text, st.off, offsets, n_reads)) return rc;
+  *out = st.b.release();
   return TALC_OK;
 }
 

@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "talc_common.h"
+#include "talc_sellers.h"
 
 namespace talc {
 
@@ -18,6 +18,7 @@ struct ChimeraHit {   // talc_chimera_hit
 struct SplitPiece {   // talc_split_piece
   uint32_t read, start, len, ordinal;
 };
+TALC_HD GatherInterval gather_interval(const SplitPiece& pc, uint32_t) { return GatherInterval{pc.read, pc.start, pc.len}; }
 
 // ------------------------------------------------------------------ how a wave is dealt over a read
 // A wave has 64 lanes and the setting 2 .. 8 patterns (two per adapter): every pattern gets 64 / patterns lanes, each
@@ -49,16 +50,14 @@ struct ChimeraParams {
   uint32_t m[kChimeraMaxPatterns], k[kChimeraMaxPatterns];
   uint32_t nPatterns, pad_;
 };
-// both patterns of an adapter of m codes (all below 4), k_a = floor(pct m / 100)
-inline void chimera_params_add(ChimeraParams& P, const uint8_t* codes, uint32_t m, uint32_t pct) {
+// both patterns of an adapter of m letters that pattern_fault has passed under set_of, k_a = floor(pct m / 100)
+template <class Letter, class SetOf>
+inline void chimera_params_add(ChimeraParams& P, const Letter* adapter, uint32_t m, SetOf set_of, uint32_t pct) {
   for (uint32_t s = 0; s < 2; ++s) {
     const uint32_t p = P.nPatterns++;
     for (uint32_t c = 0; c < 4; ++c) P.peq[p][c] = P.peqRev[p][c] = 0;
-    for (uint32_t i = 0; i < m; ++i) {
-      const uint32_t c = s ? 3u - codes[m - 1u - i] : codes[i];
-      P.peq[p][c] |= 1ull << i;
-      P.peqRev[p][c] |= 1ull << (m - 1u - i);
-    }
+    pattern_masks(adapter, m, set_of, s == 1u, false, P.peq[p]);
+    pattern_masks(adapter, m, set_of, s == 1u, true, P.peqRev[p]);
     P.m[p] = m;
     P.k[p] = pct * m / 100u;
   }

@@ -8,24 +8,22 @@
 // chimera_scan_host (pure_capi.cpp, the CPU test-suite) runs the same lanes one after another over the same tiles.
 #pragma once
 #include "talc_chimera_plan.h"
+#include "talc_sellers.h"
 #if defined(__HIPCC__)
-#include "talc_kernels_pieces.h"   // block_copy_bytes
+#include "talc_wave.h"
 #endif
 
 namespace talc {
 
-TALC_HD uint64_t chimera_eq(const uint64_t (&peq)[4], uint32_t c) {
-  return c == 0u ? peq[0] : c == 1u ? peq[1] : c == 2u ? peq[2] : c == 3u ? peq[3] : 0ull;
-}
-
 // One lane: pattern `peq` (m letters, bound k) over the columns (js, jend] of a read, of which it owns (c0, c1].  It starts
-// w + m + k columns before its chunk from the free-start state (adapter_match's proof: from m + k columns on its clamped
+// w + m + k columns before its chunk from the free-start state (sellers_lane's proof: from m + k columns on its clamped
 // scores are exact) and runs w columns beyond it, so that it knows C exactly on [c0 + 1 - w, c1 + w]: all the hit rule reads
 // for the columns it owns.  C moves by at most 1 per column, so the last 64 columns are two bit masks (up, dn: bit i is the
 // step into column t - i); `delayed` is C[tick - w], the column whose window has just been completed.
 struct ChimeraLane {
-  uint64_t Pv, Mv, up, dn;
-  uint32_t m, k, w, score, clamped, delayed;
+  SellersColumn col;   // column tick - 1
+  uint64_t up, dn;
+  uint32_t m, k, w, clamped, delayed;
   uint32_t js, jend, c0, c1;
   uint32_t tick;       // the next tick: column `tick` is computed (while tick <= jend), column tick - w is tested
   uint32_t ticks;      // how many this lane runs
@@ -37,8 +35,8 @@ TALC_HD void chimera_lane_init(ChimeraLane& s, uint32_t m, uint32_t k, uint32_t 
   s.c0 = c0; s.c1 = c1;
   s.js = c0 > pre ? c0 - pre : 0u;
   s.jend = c1 + s.w < L ? c1 + s.w : L;
-  s.Pv = ~0ull; s.Mv = 0ull; s.up = s.dn = 0ull;
-  s.score = m;
+  s.col.start(m);
+  s.up = s.dn = 0ull;
   s.clamped = s.delayed = k + 1u;     // column js (and everything outside the read) counts as k + 1: it forbids nothing
   s.tick = s.js + 1u;
   s.ticks = c0 < c1 ? c1 + s.w - s.js : 0u;
@@ -68,18 +66,8 @@ TALC_HD bool chimera_hit_test(uint64_t up, uint64_t dn, uint32_t t, uint32_t e, 
 TALC_HD bool chimera_lane_tick(ChimeraLane& s, const uint64_t (&peq)[4], uint32_t code, uint32_t* end, uint32_t* err) {
   const uint32_t tau = s.tick++;
   if (tau <= s.jend) {
-    const uint64_t top = 1ull << (s.m - 1u);
-    const uint64_t Eq = chimera_eq(peq, code);
-    const uint64_t Xv = Eq | s.Mv;
-    const uint64_t Xh = (((Eq & s.Pv) + s.Pv) ^ s.Pv) | Eq;
-    uint64_t Ph = s.Mv | ~(Xh | s.Pv);
-    uint64_t Mh = s.Pv & Xh;
-    s.score += (Ph & top) ? 1u : 0u;
-    s.score -= (Mh & top) ? 1u : 0u;
-    Ph <<= 1; Mh <<= 1;
-    s.Pv = Mh | ~(Xv | Ph);
-    s.Mv = Ph & Xv;
-    const uint32_t nc = s.score < s.k + 1u ? s.score : s.k + 1u;
+    s.col.step(sellers_eq(peq, code), s.m);
+    const uint32_t nc = s.col.score < s.k + 1u ? s.col.score : s.k + 1u;
     s.up = s.up << 1 | (nc > s.clamped ? 1ull : 0ull);
     s.dn = s.dn << 1 | (nc < s.clamped ? 1ull : 0ull);
     s.clamped = nc;
@@ -93,27 +81,17 @@ TALC_HD bool chimera_lane_tick(ChimeraLane& s, const uint64_t (&peq)[4], uint32_
   return true;
 }
 
-// The start of the hit that ends at column e with distance d: the same recurrence anchored at e (the top row is j: Ph's
-// carry is set), the pattern back to front over the read's bytes e - 1, e - 2, ...; the first column whose score is d.
+// The start of the hit that ends at column e with distance d: the same recurrence anchored at e (the top row is j), the
+// pattern back to front over the read's bytes e - 1, e - 2, ...; the first column whose score is d.
 // code_at(i) is the code of byte i of the read; at most m + k bytes are read, none below 0.
 template <class CodeAt>
 TALC_HD uint32_t chimera_start(CodeAt code_at, uint32_t e, const uint64_t (&peqRev)[4], uint32_t m, uint32_t k, uint32_t d) {
-  const uint64_t top = 1ull << (m - 1u);
-  uint64_t Pv = ~0ull, Mv = 0ull;
-  uint32_t score = m;
+  SellersColumn col;
+  col.start(m);
   const uint32_t far = e < m + k ? e : m + k;
   for (uint32_t j = 1; j <= far; ++j) {
-    const uint64_t Eq = chimera_eq(peqRev, code_at(e - j));
-    const uint64_t Xv = Eq | Mv;
-    const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    uint64_t Ph = Mv | ~(Xh | Pv);
-    uint64_t Mh = Pv & Xh;
-    score += (Ph & top) ? 1u : 0u;
-    score -= (Mh & top) ? 1u : 0u;
-    Ph = Ph << 1 | 1ull; Mh <<= 1;
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-    if (score == d) return e - j;
+    col.step<false>(sellers_eq(peqRev, code_at(e - j)), m);
+    if (col.score == d) return e - j;
   }
   return e - far;   // (never: some j <= m + d has that distance, by the definition of D)
 }
@@ -209,9 +187,7 @@ k_read_chimera(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ off
     if (pat >= P.nPatterns) c1 = c0;
     ChimeraLane s;
     chimera_lane_init(s, m, k, L, c0, c1);
-    uint32_t most = s.ticks;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) most = max(most, (uint32_t)__shfl_xor((int)most, off, 64));
+    const uint32_t most = wave_max_u32(s.ticks);
     for (uint32_t n = 0; n < most; ++n) {
       bool hit = false;
       uint32_t e = 0, d = 0;
@@ -234,22 +210,6 @@ k_read_chimera(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ off
     }
     __syncthreads();                                     // (the next tile is staged into the same bytes)
   }
-}
-
-// one block per piece: bytes [start, start + len) of read `read` in `src` to the piece's place in the dense text `dst`
-// (block_copy_bytes); never beyond the read, never beyond the piece's place
-__global__ void __launch_bounds__(256)
-k_split_gather(const uint8_t* __restrict__ src, const uint64_t* __restrict__ srcOff, uint32_t n_src_reads, const SplitPiece* __restrict__ pieces,
-               uint32_t n_pieces, uint8_t* __restrict__ dst, const uint64_t* __restrict__ dstOff) {
-  const uint32_t p = blockIdx.x;
-  if (p >= n_pieces) return;
-  const SplitPiece pc = pieces[p];
-  if (pc.read >= n_src_reads) return;
-  const uint32_t L = (uint32_t)(srcOff[pc.read + 1] - srcOff[pc.read]);
-  const uint32_t room = (uint32_t)(dstOff[p + 1] - dstOff[p]);
-  const uint32_t start = min(pc.start, L);
-  const uint32_t n = min(min(pc.len, L - start), room);
-  block_copy_bytes(dst + dstOff[p], src + srcOff[pc.read] + start, n);
 }
 #endif
 

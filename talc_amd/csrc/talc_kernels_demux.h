@@ -14,9 +14,9 @@
 #include <cstdio>
 #include <cstring>
 
-#include "talc_common.h"
+#include "talc_sellers.h"
 #if defined(__HIPCC__)
-#include "talc_kernels_ends.h"   // stage_end
+#include "talc_wave.h"
 #endif
 
 namespace talc {
@@ -38,7 +38,7 @@ struct DemuxParams { uint32_t nBarcodes, m, k, minMargin, window, bothEnds; };
 // ------------------------------------------------------------------ how a wave is dealt over the patterns
 // There are 2 B patterns (end, barcode) and 64 lanes.  A slot is a lane of a pass: slot = 64 pass + lane.
 //   B <= 16 (2 B <= 32): one pass; every pattern gets chunks = floor(64 / 2 B) lanes, each one chunk of the window behind a
-//     warm-up of m + k columns (adapter_match's argument); slot = (end B + b) chunks + q.
+//     warm-up of m + k columns (sellers_lane's argument); slot = (end B + b) chunks + q.
 //   B >= 17: a lane takes a whole window, no warm-up.  The heads' patterns are slots 0 .. B - 1, the tails' start at
 //     tailSlot = B rounded up to 32, so no 32-lane half of a pass holds patterns of both ends: the LDS serves byte reads by
 //     halves of the wave and broadcasts equal addresses, and every half reads one byte per column.  The rounding never costs
@@ -61,12 +61,6 @@ TALC_HD void demux_slot_place(const DemuxGeometry& g, uint32_t B, uint32_t slot,
 }
 // the first slot of pattern (end, b): its chunks are the g.chunks slots from there
 TALC_HD uint32_t demux_pattern_slot(const DemuxGeometry& g, uint32_t end, uint32_t b) { return (end ? g.tailSlot : 0u) + b * g.chunks; }
-// the columns [*c0, *c1) of chunk q of a text of n columns
-TALC_HD void demux_chunk(const DemuxGeometry& g, uint32_t n, uint32_t q, uint32_t* c0, uint32_t* c1) {
-  const uint32_t chunk = (n + g.chunks - 1u) / g.chunks;
-  *c0 = q * chunk < n ? q * chunk : n;
-  *c1 = *c0 + chunk < n ? *c0 + chunk : n;
-}
 
 // The kernel's LDS: one 8-byte key per slot, then the codes of the two end windows, each window rounded up to 16 bytes
 // (at most 4096).  2048 bytes at the default window with 96 barcodes, 9728 at the largest window.
@@ -76,49 +70,16 @@ TALC_HD uint32_t demux_code_stride(const DemuxParams& P) {
 }
 TALC_HD uint32_t demux_lds_bytes(const DemuxParams& P) { return demux_geometry(P.nBarcodes).passes * 64u * 8u + 2u * demux_code_stride(P); }
 
-// a pattern's key: c << 32 | (0xFFFFFFFF - e), the smallest over its columns: the smallest c, the largest e among ties;
-// without a column of D <= k it is demux_no_key: c = k + 1, no end
-TALC_HD uint64_t demux_no_key(uint32_t k) { return (uint64_t)(k + 1u) << 32 | 0xFFFFFFFFull; }
-
-// a pattern's key from its slots' keys (`key`: one per slot, in LDS or on the host): the smallest over its chunks
+// a pattern's key (sellers_lane) from its slots' keys (`key`: one per slot, in LDS or on the host): the smallest over its
+// chunks, sellers_no_key(k) without a column of D <= k
 TALC_HD uint64_t demux_pattern_key(const uint64_t* key, const DemuxGeometry& g, uint32_t end, uint32_t b, uint32_t k) {
-  uint64_t pk = demux_no_key(k);
+  uint64_t pk = sellers_no_key(k);
   const uint32_t first = demux_pattern_slot(g, end, b);
   for (uint32_t q = 0; q < g.chunks; ++q) { const uint64_t x = key[first + q]; pk = x < pk ? x : pk; }
   return pk;
 }
 // ... as the candidate the barcodes of an end are reduced by: c << 40 | b << 32 | (0xFFFFFFFF - e)
 TALC_HD uint64_t demux_candidate(uint64_t pk, uint32_t b) { return (pk >> 32) << 40 | (uint64_t)b << 32 | (uint32_t)pk; }
-
-// One lane: barcode `peq` (m letters, bound k) over the staged codes s[0, n), of which it owns the columns [c0, c1).  A lane
-// whose chunk does not start the text starts m + k columns before it from the free-start state (Pv all ones, score m): by
-// adapter_match's argument its score is exact wherever D <= k and >= D elsewhere, which is all the rule reads.  A lane that
-// owns the whole text starts at column 0, where that state is the true one: its scores are exact.
-TALC_HD uint64_t demux_lane(const uint8_t* s, const uint64_t (&peq)[4], uint32_t m, uint32_t k, uint32_t c0, uint32_t c1) {
-  uint64_t best = demux_no_key(k);
-  const uint32_t warm = m + k;
-  const uint64_t top = 1ull << (m - 1u);
-  uint64_t Pv = ~0ull, Mv = 0ull;
-  uint32_t score = m;
-  for (uint32_t j = c0 > warm ? c0 - warm : 0u; j < c1; ++j) {
-    const uint32_t c = s[j];
-    const uint64_t Eq = c == 0u ? peq[0] : c == 1u ? peq[1] : c == 2u ? peq[2] : c == 3u ? peq[3] : 0ull;
-    const uint64_t Xv = Eq | Mv;
-    const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    uint64_t Ph = Mv | ~(Xh | Pv);
-    uint64_t Mh = Pv & Xh;
-    score += (Ph & top) ? 1u : 0u;
-    score -= (Mh & top) ? 1u : 0u;
-    Ph <<= 1; Mh <<= 1;                                // (the top row is 0 in every column: a match may start anywhere)
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-    if (j >= c0 && score <= k) {
-      const uint64_t key = (uint64_t)score << 32 | (0xFFFFFFFFu - (j + 1u));
-      best = key < best ? key : best;
-    }
-  }
-  return best;
-}
 
 // What the barcodes of one end reduce to, and the end rule on it
 struct DemuxEnd { uint32_t best, err, margin, end, call; };
@@ -161,23 +122,18 @@ inline bool demux_make_setting(const char* barcodes, uint32_t max_error_pct, uin
   if (both_ends != 0 && both_ends != 1) { snprintf(why, whyLen, "both_ends=%d: 0 or 1", both_ends); return false; }
   uint64_t masks[kDemuxMaxBarcodes * 4];
   memset(masks, 0, sizeof masks);
-  for (const char* p = barcodes; p;) {
-    const char* e = strchr(p, ',');
-    const size_t m = e ? (size_t)(e - p) : strlen(p);
+  for (PatternList it(barcodes); it.next(acgt_set);) {
+    const unsigned long long m = it.m;
     if (Q.nBarcodes == kDemuxMaxBarcodes) { snprintf(why, whyLen, "barcodes: more than %u", kDemuxMaxBarcodes); return false; }
-    if (m < 12 || m > 64) { snprintf(why, whyLen, "barcodes: barcode %u has %llu letters: 12 .. 64", Q.nBarcodes + 1, (unsigned long long)m); return false; }
+    if (it.fault == PATTERN_LENGTH) { snprintf(why, whyLen, "barcodes: barcode %u has %llu letters: 12 .. 64", Q.nBarcodes + 1, m); return false; }
     if (Q.nBarcodes && m != Q.m) {
-      snprintf(why, whyLen, "barcodes: barcode %u has %llu letters, barcode 1 has %u: one length for all", Q.nBarcodes + 1, (unsigned long long)m, Q.m);
+      snprintf(why, whyLen, "barcodes: barcode %u has %llu letters, barcode 1 has %u: one length for all", Q.nBarcodes + 1, m, Q.m);
       return false;
     }
-    for (size_t i = 0; i < m; ++i) {
-      const uint8_t code = ascii_to_code((uint8_t)p[i]);
-      if (code >= 4) { snprintf(why, whyLen, "barcodes: barcode %u has a letter that is not one of ACGTacgt", Q.nBarcodes + 1); return false; }
-      masks[4u * Q.nBarcodes + code] |= 1ull << i;
-    }
+    if (it.fault) { snprintf(why, whyLen, "barcodes: barcode %u has a letter that is not one of ACGTacgt", Q.nBarcodes + 1); return false; }
+    pattern_masks(it.p, it.m, acgt_set, false, false, masks + 4u * Q.nBarcodes);
     Q.m = (uint32_t)m;
     ++Q.nBarcodes;
-    p = e ? e + 1 : nullptr;
   }
   Q.k = max_error_pct * Q.m / 100u;
   if (min_margin > Q.k + 1u) { snprintf(why, whyLen, "min_margin=%u: 0 .. k + 1 (%u)", min_margin, Q.k + 1u); return false; }
@@ -193,20 +149,16 @@ inline DemuxRow demux_scan_host(const uint8_t* rd, uint32_t L, const DemuxParams
   const uint32_t n = L < window ? L : window;
   const DemuxGeometry g = demux_geometry(B);
   static thread_local uint8_t code[2][kDemuxMaxWindow];
-  for (uint32_t i = 0; i < n; ++i) {                   // (stage_end's form)
-    code[0][i] = (uint8_t)ascii_to_code_select(rd[i]);
-    const uint32_t c = ascii_to_code_select(rd[L - 1u - i]);
-    code[1][i] = (uint8_t)(c < 4u ? 3u - c : c);
-  }
+  for (uint32_t end = 0; end < 2u; ++end) stage_end(code[end], rd, L, 0u, n, end == 1u, 0u, 1u);
   uint64_t key[kDemuxMaxSlots];
   for (uint32_t slot = 0; slot < g.passes * 64u; ++slot) {
     uint32_t end, b, q, c0, c1;
     demux_slot_place(g, B, slot, &end, &b, &q);
     key[slot] = ~0ull;
     if (b >= B) continue;
-    demux_chunk(g, n, q, &c0, &c1);
+    sellers_chunk(n, g.chunks, q, &c0, &c1);
     const uint64_t peq[4] = {peqTable[4u * b], peqTable[4u * b + 1u], peqTable[4u * b + 2u], peqTable[4u * b + 3u]};
-    key[slot] = demux_lane(code[end], peq, P.m, P.k, c0, c1);
+    key[slot] = sellers_lane(code[end], peq, P.m, P.k, c0, c1, sellers_no_key(P.k));
   }
   DemuxEnd ends[2];
   for (uint32_t end = 0; end < 2u; ++end) {
@@ -227,15 +179,6 @@ inline DemuxRow demux_scan_host(const uint8_t* rd, uint32_t L, const DemuxParams
 }
 
 #if defined(__HIPCC__)
-TALC_D uint64_t demux_wave_min(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-    v = min(v, (uint64_t)hi << 32 | lo);
-  }
-  return v;
-}
-
 // One wave per read.  Both end windows are staged once as codes; every pass gives each lane one pattern (and chunk), whose
 // key goes to LDS; then, per end, the lanes reduce the chunks of their barcodes and the wave the barcodes; lane 0 applies the
 // call rule and writes the row.  peqTable: P.nBarcodes x 4 words.
@@ -255,8 +198,8 @@ k_read_demux(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offse
   uint8_t* const s_head = (uint8_t*)(s_demux + g.passes * 64u);
   uint8_t* const s_tail = s_head + stride;
   const uint32_t n = min(L, min(P.window, stride));
-  stage_end(s_head, rd, L, 0u, n, false, lane);
-  stage_end(s_tail, rd, L, 0u, n, true, lane);
+  stage_end(s_head, rd, L, 0u, n, false, lane, 64u);
+  stage_end(s_tail, rd, L, 0u, n, true, lane, 64u);
   __syncthreads();
   for (uint32_t pass = 0; pass < g.passes; ++pass) {
     const uint32_t slot = pass * 64u + lane;           // < kDemuxMaxSlots: passes <= 3
@@ -264,9 +207,9 @@ k_read_demux(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offse
     demux_slot_place(g, B, slot, &end, &b, &q);
     uint64_t key = ~0ull;
     if (b < B) {
-      demux_chunk(g, n, q, &c0, &c1);
+      sellers_chunk(n, g.chunks, q, &c0, &c1);
       const uint64_t peq[4] = {peqTable[4u * b], peqTable[4u * b + 1u], peqTable[4u * b + 2u], peqTable[4u * b + 3u]};
-      key = demux_lane(end ? s_tail : s_head, peq, P.m, P.k, c0, c1);
+      key = sellers_lane(end ? s_tail : s_head, peq, P.m, P.k, c0, c1, sellers_no_key(P.k));
     }
     s_key[slot] = key;
   }
@@ -284,13 +227,13 @@ k_read_demux(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offse
       cOf[i] = (uint32_t)(pk >> 32);
       best = min(best, demux_candidate(pk, b));
     }
-    best = demux_wave_min(best);
+    best = wave_min_u64(best);
     const uint32_t bestB = (uint32_t)(best >> 32) & 0xFFu;
     uint64_t second = P.k + 1u;
 #pragma unroll
     for (uint32_t i = 0; i < 2u; ++i)
       if (lane + 64u * i < B && lane + 64u * i != bestB) second = min(second, (uint64_t)cOf[i]);
-    second = demux_wave_min(second);
+    second = wave_min_u64(second);
     ends[end] = demux_end_rule((uint32_t)(best >> 40), bestB, 0xFFFFFFFFu - (uint32_t)best, (uint32_t)second, P);
   }
   if (lane == 0) rows[r] = demux_row(ends[0], ends[1], P);

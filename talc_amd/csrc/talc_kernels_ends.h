@@ -8,9 +8,11 @@
 //            smallest j that maximises score; poly_len = p when poly_min > 0 and p >= poly_min, else 0;
 // and the tail rule is H(revcomp(S)): the codes are read back to front and complemented, the reverse complement is never
 // written anywhere.  A byte outside ACGTacgt is its own letter: it matches no adapter letter and is neither A nor T.
-// k_read_ends leaves one 32-byte talc_end_row per read; k_clip_gather copies the kept intervals into a dense text.
+// k_read_ends leaves one 32-byte talc_end_row per read; k_gather copies the kept intervals into a dense text.
 #pragma once
 #include "talc_kernels_pieces.h"   // block_copy_bytes
+#include "talc_sellers.h"
+#include "talc_wave.h"
 
 namespace talc {
 
@@ -31,63 +33,20 @@ struct EndsParams {
   uint32_t nAdapters, polyMin, window, pad_;
 };
 
-// code i of the end's text: the read's bytes as they lie (head), or back to front and complemented (tail)
-TALC_D uint32_t end_code(const uint8_t* __restrict__ rd, uint32_t L, uint32_t i, bool tail) {
-  const uint32_t c = ascii_to_code_select(rd[tail ? L - 1u - i : i]);
-  return tail && c < 4u ? 3u - c : c;
-}
-
-// codes [from, from + n) of the end's text into s[0, n), by the whole wave (from + n <= L, n <= ENDS_MAX_WINDOW)
-TALC_D void stage_end(uint8_t* s, const uint8_t* __restrict__ rd, uint32_t L, uint32_t from, uint32_t n, bool tail, uint32_t lane) {
-  for (uint32_t i = lane; i < n; i += 64u) s[i] = (uint8_t)end_code(rd, L, from + i, tail);
-}
-
-// One adapter over the staged text s[0, n): the accepted end with the smallest D, the largest among ties, as
-// D << 32 | (0xFFFFFFFF - e); all ones without one.  The text is split into 64 chunks, one per lane.  A lane starts m + k
-// columns before its chunk from the free-start state (Pv all ones, score m: what column 0 holds, and an upper bound of any
-// later column): an alignment of cost d <= k spans at most m + d letters, so for every column of the chunk whose true D is
-// <= k the lane's score is exact, and everywhere else it is >= D, which stays rejected.
-TALC_D uint64_t adapter_match(const uint8_t* s, uint32_t n, const uint64_t (&peq)[4], uint32_t m, uint32_t k, uint32_t lane) {
-  const uint32_t chunk = (n + 63u) / 64u;
-  const uint32_t c0 = min(n, lane * chunk), c1 = min(n, c0 + chunk);
-  const uint32_t warm = m + k;
-  uint64_t best = ~0ull;
-  if (c0 < c1) {
-    const uint64_t top = 1ull << (m - 1u);
-    uint64_t Pv = ~0ull, Mv = 0ull;
-    uint32_t score = m;
-    for (uint32_t j = c0 > warm ? c0 - warm : 0u; j < c1; ++j) {
-      const uint32_t c = s[j];
-      const uint64_t Eq = c == 0u ? peq[0] : c == 1u ? peq[1] : c == 2u ? peq[2] : c == 3u ? peq[3] : 0ull;
-      const uint64_t Xv = Eq | Mv;
-      const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-      uint64_t Ph = Mv | ~(Xh | Pv);
-      uint64_t Mh = Pv & Xh;
-      score += (Ph & top) ? 1u : 0u;
-      score -= (Mh & top) ? 1u : 0u;
-      Ph <<= 1; Mh <<= 1;                              // (the top row is 0 in every column: a match may start anywhere)
-      Pv = Mh | ~(Xv | Ph);
-      Mv = Ph & Xv;
-      if (j >= c0 && score <= k) {
-        const uint64_t key = (uint64_t)score << 32 | (0xFFFFFFFFu - (j + 1u));
-        best = min(best, key);
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)best, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), off, 64);
-    best = min(best, (uint64_t)hi << 32 | lo);
-  }
-  return best;
+// One adapter over the staged text s[0, n), dealt over the wave's 64 lanes (sellers_lane, talc_sellers.h): the accepted end
+// with the smallest D, the largest among ties, as D << 32 | (0xFFFFFFFF - e); all ones without one.
+TALC_D uint64_t adapter_key(const uint8_t* s, uint32_t n, const uint64_t (&peq)[4], uint32_t m, uint32_t k, uint32_t lane) {
+  uint32_t c0, c1;
+  sellers_chunk(n, 64u, lane, &c0, &c1);
+  return wave_min_u64(sellers_lane(s, peq, m, k, c0, c1, ~0ull));
 }
 
 // The poly run over the staged text s[0, n): the smallest j that maximises score(j), 0 <= j <= n.  Every lane sums its chunk
 // and keeps the chunk's best prefix; an exclusive wave scan of the sums places the chunks, a wave maximum of
 // (score, -j) picks the run's end.  score(0) = 0 wins every tie, so only a positive maximum moves the end.
 TALC_D uint32_t poly_run(const uint8_t* s, uint32_t n, uint32_t lane) {
-  const uint32_t chunk = (n + 63u) / 64u;
-  const uint32_t c0 = min(n, lane * chunk), c1 = min(n, c0 + chunk);
+  uint32_t c0, c1;
+  sellers_chunk(n, 64u, lane, &c0, &c1);
   int32_t sum = 0, bestV = INT32_MIN / 2;
   uint32_t bestJ = 0;
   for (uint32_t j = c0; j < c1; ++j) {
@@ -98,12 +57,7 @@ TALC_D uint32_t poly_run(const uint8_t* s, uint32_t n, uint32_t lane) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) { const int32_t t = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += t; }
   // (|score| <= 2 * ENDS_MAX_WINDOW: the bias keeps the key's upper half non-negative; an empty chunk has the lowest key)
-  uint64_t key = c0 < c1 ? (uint64_t)(uint32_t)(incl - sum + bestV + (1 << 20)) << 32 | (0xFFFFFFFFu - bestJ) : 0ull;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)key, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), off, 64);
-    key = max(key, (uint64_t)hi << 32 | lo);
-  }
+  const uint64_t key = wave_max_u64(c0 < c1 ? (uint64_t)(uint32_t)(incl - sum + bestV + (1 << 20)) << 32 | (0xFFFFFFFFu - bestJ) : 0ull);
   return (key >> 32) > (1u << 20) ? 0xFFFFFFFFu - (uint32_t)key : 0u;
 }
 
@@ -124,10 +78,10 @@ k_read_ends(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offset
     const bool tail = end == 1;
     if (P.nAdapters) {                                 // (wave-uniform)
       const uint32_t n = min(L, window);
-      stage_end(s_code, rd, L, 0u, n, tail, lane);
+      stage_end(s_code, rd, L, 0u, n, tail, lane, 64u);
       __syncthreads();
       for (uint32_t a = 0; a < P.nAdapters; ++a) {
-        const uint64_t best = adapter_match(s_code, n, P.peq[a], P.m[a], P.k[a], lane);
+        const uint64_t best = adapter_key(s_code, n, P.peq[a], P.m[a], P.k[a], lane);
         const uint32_t e = 0xFFFFFFFFu - (uint32_t)best;
         if (best != ~0ull && e > adLen[end]) { adLen[end] = e; adIdx[end] = a + 1u; adErr[end] = (uint32_t)(best >> 32); }
       }
@@ -136,7 +90,7 @@ k_read_ends(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offset
     if (P.polyMin) {
       const uint32_t from = adLen[end];                // <= L
       const uint32_t n = min(L - from, window);
-      stage_end(s_code, rd, L, from, n, tail, lane);
+      stage_end(s_code, rd, L, from, n, tail, lane, 64u);
       __syncthreads();
       const uint32_t p = poly_run(s_code, n, lane);
       poly[end] = p >= P.polyMin ? p : 0u;
@@ -156,20 +110,27 @@ k_read_ends(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offset
   }
 }
 
-// one block per read: bytes [keptStart, keptStart + keptLen) of the read in `src` to its place in the dense text `dst`
+// the kept interval of read i (GatherInterval, talc_sellers.h)
+TALC_HD GatherInterval gather_interval(const EndRow& row, uint32_t i) { return GatherInterval{i, row.keptStart, row.keptLen}; }
+
+// one block per record: its interval to the record's place in the dense text `dst`; never beyond the read, never beyond the
+// place, and an interval of a read that `src` does not hold is skipped.  The rows are read as they lie on the device: nothing
+// is built or uploaded for the gather.
 // (block_copy_bytes: aligned words of dst, each from the two aligned words of src that hold its bytes; the leading and
 // trailing bytes one by one; no word of src is read that does not hold a byte of the interval)
+template <class Row>
 __global__ void __launch_bounds__(256)
-k_clip_gather(const uint8_t* __restrict__ src, const uint64_t* __restrict__ srcOff, const EndRow* __restrict__ rows, uint32_t n_reads,
-              uint8_t* __restrict__ dst, const uint64_t* __restrict__ dstOff) {
-  const uint32_t r = blockIdx.x;
-  if (r >= n_reads) return;
-  const EndRow row = rows[r];
-  const uint32_t L = (uint32_t)(srcOff[r + 1] - srcOff[r]);
-  const uint32_t room = (uint32_t)(dstOff[r + 1] - dstOff[r]);
-  const uint32_t start = min(row.keptStart, L);
-  const uint32_t n = min(min(row.keptLen, L - start), room);   // (never beyond the read, never beyond its place)
-  block_copy_bytes(dst + dstOff[r], src + srcOff[r] + start, n);
+k_gather(const uint8_t* __restrict__ src, const uint64_t* __restrict__ srcOff, uint32_t n_src_reads, const Row* __restrict__ rows, uint32_t n,
+         uint8_t* __restrict__ dst, const uint64_t* __restrict__ dstOff) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const GatherInterval iv = gather_interval(rows[i], i);
+  if (iv.read >= n_src_reads) return;
+  const uint32_t L = (uint32_t)(srcOff[iv.read + 1] - srcOff[iv.read]);
+  const uint32_t room = (uint32_t)(dstOff[i + 1] - dstOff[i]);
+  const uint32_t start = min(iv.start, L);
+  const uint32_t len = min(min(iv.len, L - start), room);
+  block_copy_bytes(dst + dstOff[i], src + srcOff[iv.read] + start, len);
 }
 
 }  // namespace talc

@@ -18,10 +18,10 @@
 #include <cstdio>
 #include <cstring>
 
-#include "talc_common.h"
-#include "talc_kernels_demux.h"   // demux_lane: the Myers/Hyyrö column step over one chunk behind its warm-up
+#include "talc_sellers.h"
 #if defined(__HIPCC__)
-#include "talc_kernels_ends.h"    // stage_end, EndRow
+#include "talc_kernels_ends.h"    // EndRow
+#include "talc_wave.h"
 #endif
 
 namespace talc {
@@ -37,6 +37,7 @@ struct UmiRow {   // talc_umi_row
   char umi[32];
   uint32_t pad_;
 };
+TALC_HD GatherInterval gather_interval(const UmiRow& row, uint32_t i) { return GatherInterval{i, row.keptStart, row.keptLen}; }
 
 // The setting as the kernel takes it, by value: everything in it is wave-uniform.  peq[c]: bit i set when the set of
 // pattern letter i holds code c (a degenerate letter sets its bit in several of the four); degen: bit i set when letter i
@@ -68,11 +69,13 @@ inline bool umi_make_setting(const char* pattern, uint32_t max_error_pct, uint32
   if (!window) window = kUmiDefaultWindow;
   if (window < 32 || window > kUmiMaxWindow) { snprintf(why, whyLen, "window=%u: 32 .. %u (0: %u)", window, kUmiMaxWindow, kUmiDefaultWindow); return false; }
   const size_t m = strlen(pattern);
-  if (m < 12 || m > 64) { snprintf(why, whyLen, "pattern: %llu letters: 12 .. 64", (unsigned long long)m); return false; }
+  size_t bad = 0;
+  const PatternFault fault = pattern_fault(pattern, m, iupac_set, &bad);
+  if (fault == PATTERN_LENGTH) { snprintf(why, whyLen, "pattern: %llu letters: 12 .. 64", (unsigned long long)m); return false; }
+  if (fault) { snprintf(why, whyLen, "pattern: letter %llu is not one of ACGTRYSWKMBDHVN", (unsigned long long)(bad + 1)); return false; }
+  pattern_masks(pattern, m, iupac_set, false, false, Q.peq);
   for (size_t i = 0; i < m; ++i) {
     const uint32_t set = iupac_set((uint8_t)pattern[i]);
-    if (!set) { snprintf(why, whyLen, "pattern: letter %llu is not one of ACGTRYSWKMBDHVN", (unsigned long long)(i + 1)); return false; }
-    for (uint32_t c = 0; c < 4u; ++c) if (set >> c & 1u) Q.peq[c] |= 1ull << i;
     if (set & (set - 1u)) { Q.degen |= 1ull << i; ++Q.u; }
   }
   if (Q.u < 1 || Q.u > kUmiMaxDegenerate) { snprintf(why, whyLen, "pattern: %u degenerate letters: 1 .. %u", Q.u, kUmiMaxDegenerate); return false; }
@@ -90,13 +93,12 @@ TALC_HD uint32_t umi_code_stride(const UmiParams& P) {
 TALC_HD uint32_t umi_lds_bytes(const UmiParams& P) { return kUmiMaxColumns * 16u + kUmiRowWords * 4u + 2u * umi_code_stride(P); }
 
 // ------------------------------------------------------------------ 1. the search
-// lane `lane` of 64 over the staged codes s[0, n): its chunk of the columns behind a warm-up of m + k; the key is
-// score << 32 | (0xFFFFFFFF - j), demux_no_key(k) without a column of D <= k
+// lane `lane` of 64 over the staged codes s[0, n): its chunk of the columns behind a warm-up of m + k (sellers_lane); the
+// key is score << 32 | (0xFFFFFFFF - j), sellers_no_key(k) without a column of D <= k
 TALC_HD uint64_t umi_search_lane(const uint8_t* s, uint32_t n, const UmiParams& P, uint32_t lane) {
-  const uint32_t chunk = (n + 63u) / 64u;
-  const uint32_t c0 = lane * chunk < n ? lane * chunk : n, c1 = c0 + chunk < n ? c0 + chunk : n;
-  if (c0 >= c1) return demux_no_key(P.k);
-  return demux_lane(s, P.peq, P.m, P.k, c0, c1);
+  uint32_t c0, c1;
+  sellers_chunk(n, 64u, lane, &c0, &c1);
+  return sellers_lane(s, P.peq, P.m, P.k, c0, c1, sellers_no_key(P.k));
 }
 
 // the read's end from the two ends' keys: end 1 head, 2 tail, 0 none
@@ -122,19 +124,12 @@ TALC_HD UmiPick umi_pick(uint64_t keyHead, uint64_t keyTail, uint32_t k) {
 TALC_HD uint32_t umi_recompute(const uint8_t* s, const UmiParams& P, uint32_t stop, uint64_t* cols) {
   const uint32_t span = P.m + P.k;
   const uint32_t j0 = stop > span ? stop - span : 0u;
-  uint64_t Pv = ~0ull, Mv = 0ull;
-  cols[0] = Pv; cols[1] = Mv;
+  SellersColumn col;                                   // (its score is not read: the traceback sums the deltas)
+  col.start(P.m);
+  cols[0] = col.Pv; cols[1] = col.Mv;
   for (uint32_t j = j0; j < stop; ++j) {
-    const uint32_t c = s[j];
-    const uint64_t Eq = c == 0u ? P.peq[0] : c == 1u ? P.peq[1] : c == 2u ? P.peq[2] : c == 3u ? P.peq[3] : 0ull;
-    const uint64_t Xv = Eq | Mv;
-    const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    uint64_t Ph = Mv | ~(Xh | Pv);
-    uint64_t Mh = Pv & Xh;
-    Ph <<= 1; Mh <<= 1;
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-    cols[2u * (j + 1u - j0)] = Pv; cols[2u * (j + 1u - j0) + 1u] = Mv;
+    col.step(sellers_eq(P.peq, s[j]), P.m);
+    cols[2u * (j + 1u - j0)] = col.Pv; cols[2u * (j + 1u - j0) + 1u] = col.Mv;
   }
   return j0;
 }
@@ -157,8 +152,7 @@ TALC_HD uint32_t umi_traceback(const uint8_t* s, const UmiParams& P, uint32_t st
     const uint64_t bit = 1ull << (i - 1u);
     if (j > j0) {
       const uint32_t c = s[j - 1u];
-      const uint64_t Eq = c == 0u ? P.peq[0] : c == 1u ? P.peq[1] : c == 2u ? P.peq[2] : c == 3u ? P.peq[3] : 0ull;
-      if (umi_cell(cols, j - 1u - j0, i - 1u) + ((Eq & bit) ? 0 : 1) == here) {
+      if (umi_cell(cols, j - 1u - j0, i - 1u) + ((sellers_eq(P.peq, c) & bit) ? 0 : 1) == here) {
         if (P.degen & bit) umi[__builtin_popcountll(P.degen & (bit - 1ull))] = c == 0u ? 'A' : c == 1u ? 'C' : c == 2u ? 'G' : c == 3u ? 'T' : 'N';
         --i; --j;
         continue;
@@ -186,14 +180,10 @@ inline UmiRow umi_scan_host(const uint8_t* rd, uint32_t L, const UmiParams& P) {
   const uint32_t window = P.window < kUmiMaxWindow ? P.window : kUmiMaxWindow;
   const uint32_t n = L < window ? L : window;
   static thread_local uint8_t code[2][kUmiMaxWindow];
-  for (uint32_t i = 0; i < n; ++i) {                   // (stage_end's form)
-    code[0][i] = (uint8_t)ascii_to_code_select(rd[i]);
-    const uint32_t c = ascii_to_code_select(rd[L - 1u - i]);
-    code[1][i] = (uint8_t)(c < 4u ? 3u - c : c);
-  }
+  for (uint32_t end = 0; end < 2u; ++end) stage_end(code[end], rd, L, 0u, n, end == 1u, 0u, 1u);
   uint64_t key[2];
   for (uint32_t end = 0; end < 2u; ++end) {
-    key[end] = demux_no_key(P.k);
+    key[end] = sellers_no_key(P.k);
     for (uint32_t lane = 0; lane < 64u; ++lane) { const uint64_t x = umi_search_lane(code[end], n, P, lane); key[end] = x < key[end] ? x : key[end]; }
   }
   const UmiPick pk = umi_pick(key[0], key[1], P.k);
@@ -231,11 +221,11 @@ k_read_umi(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offsets
   uint8_t* const s_head = (uint8_t*)(s_umi + 2u * kUmiMaxColumns) + kUmiRowWords * 4u;
   uint8_t* const s_tail = s_head + stride;
   const uint32_t n = min(L, min(P.window, stride));
-  stage_end(s_head, rd, L, 0u, n, false, lane);
-  stage_end(s_tail, rd, L, 0u, n, true, lane);
+  stage_end(s_head, rd, L, 0u, n, false, lane, 64u);
+  stage_end(s_tail, rd, L, 0u, n, true, lane, 64u);
   __syncthreads();
-  const uint64_t keyHead = demux_wave_min(umi_search_lane(s_head, n, P, lane));
-  const uint64_t keyTail = demux_wave_min(umi_search_lane(s_tail, n, P, lane));
+  const uint64_t keyHead = wave_min_u64(umi_search_lane(s_head, n, P, lane));
+  const uint64_t keyTail = wave_min_u64(umi_search_lane(s_tail, n, P, lane));
   const UmiPick pk = umi_pick(keyHead, keyTail, P.k);
   if (lane == 0) {
     uint32_t start = 0u;
@@ -255,20 +245,6 @@ k_read_umi(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ offsets
   }
   __syncthreads();
   if (lane < kUmiRowWords) ((uint32_t*)(rows + r))[lane] = ((const uint32_t*)s_row)[lane];
-}
-
-// k_clip_gather by the UMI rows' intervals: one block per read
-__global__ void __launch_bounds__(256)
-k_clip_gather_umi(const uint8_t* __restrict__ src, const uint64_t* __restrict__ srcOff, const UmiRow* __restrict__ rows, uint32_t n_reads,
-                  uint8_t* __restrict__ dst, const uint64_t* __restrict__ dstOff) {
-  const uint32_t r = blockIdx.x;
-  if (r >= n_reads) return;
-  const uint32_t keptStart = rows[r].keptStart, keptLen = rows[r].keptLen;
-  const uint32_t L = (uint32_t)(srcOff[r + 1] - srcOff[r]);
-  const uint32_t room = (uint32_t)(dstOff[r + 1] - dstOff[r]);
-  const uint32_t start = min(keptStart, L);
-  const uint32_t n = min(min(keptLen, L - start), room);   // (never beyond the read, never beyond its place)
-  block_copy_bytes(dst + dstOff[r], src + srcOff[r] + start, n);
 }
 #endif
 

@@ -54,6 +54,21 @@ TALC_D unsigned long long wave_sum_u64(unsigned long long v) {
   for (int off = 32; off > 0; off >>= 1) v += (unsigned long long)__shfl_xor((long long)v, off, 64);
   return v;
 }
+// a 64-bit key's minimum / maximum over the wave, in every lane: a butterfly of its two halves
+TALC_D unsigned long long lane_xor_u64(unsigned long long v, int off) {
+  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, off, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, 64);
+  return (unsigned long long)hi << 32 | lo;
+}
+TALC_D unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min(v, lane_xor_u64(v, off));
+  return v;
+}
+TALC_D unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, lane_xor_u64(v, off));
+  return v;
+}
 TALC_D int bcast_i32(int v, int src) { return __shfl(v, src, 64); }
 // whole-wave lane moves as one DPP VALU op (gfx9 wave_shr:1 / wave_ror:1) instead of ds_bpermute:
 // lane L receives lane L-1's value; lane 0 keeps `self` (shr) or receives lane 63's (ror).

@@ -809,7 +809,7 @@ class Context(_Owner):
         _chk(lib().talc_ctx_set_ends(self._h, text.encode(), int(max_error_pct), int(poly_min), int(window)))
 
     def ends_timing(self):
-        """(k_read_ends ms, k_clip_gather ms) of the context's last end scan and last clipped batch."""
+        """(k_read_ends ms, k_gather ms) of the context's last end scan and last clipped batch."""
         a, b = C.c_float(), C.c_float()
         _chk(lib().talc_ctx_get_ends_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
@@ -821,7 +821,7 @@ class Context(_Owner):
         _chk(lib().talc_ctx_set_chimera(self._h, 1 if on else 0, int(max_error_pct), int(min_piece)))
 
     def chimera_timing(self):
-        """(k_read_chimera ms, k_split_gather ms) of the context's last chimera scan and last split batch."""
+        """(k_read_chimera ms, k_gather ms) of the context's last chimera scan and last split batch."""
         a, b = C.c_float(), C.c_float()
         _chk(lib().talc_ctx_get_chimera_timing(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

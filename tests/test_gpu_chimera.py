@@ -1,4 +1,4 @@
-"""The chimera scan and the split batch on the device (docs/chimeras.md; k_read_chimera, k_split_gather,
+"""The chimera scan and the split batch on the device (docs/chimeras.md; k_read_chimera, k_gather,
 talc_batch_create_split) against the contract in numpy (tests/chimera_ref.py: never from a device result), and a split batch
 against a plain batch of the pieces cut on the host.  Integers and bytes, tolerance 0.  Every case first asserts, from the
 reference alone, that its input reaches what it is there for."""

@@ -1,4 +1,4 @@
-"""The long-read end clean-up on the device (docs/read_ends.md; k_read_ends, k_clip_gather, talc_batch_create_clipped) against
+"""The long-read end clean-up on the device (docs/read_ends.md; k_read_ends, k_gather, talc_batch_create_clipped) against
 the contract in numpy (tests/ends_ref.py: never from a device result), and a clipped batch against a plain batch of the reads
 clipped on the host.  Integers and bytes, tolerance 0.  Every case first asserts, from the reference alone, that its input
 reaches what it is there for."""

@@ -3,7 +3,7 @@
 k = 21 dump) on one GPU, the reads dressed on the host: every `--every`-th read is joined to the next through
 A x 30 . revcomp(VN primer) . strand-switch primer, each primer with 0 to 2 edits.  `--reps` fresh batches after a warm-up
 are made plain (the scan alone, then the correction) and split; prints one JSON line with the device time of k_read_chimera
-and k_split_gather, the scan's bases x patterns per second, the hits and the pieces, and search_ms of the split batch
+and k_gather, the scan's bases x patterns per second, the hits and the pieces, and search_ms of the split batch
 against the unsplit one.
     python tools/chimera_bench.py [--reps R] [--reads N] [--kmers N] [--k K] [--every E] [--pct P] [--min-piece M]"""
 import argparse

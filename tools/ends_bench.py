@@ -3,7 +3,7 @@
 k = 21 dump) on one GPU, the reads dressed on the host: a fraction `--frac` of them (each class drawn on its own) gets a head
 primer (the strand-switch primer with 0 to 4 edits behind 0 to 30 bases of junk), a poly-T head of 12 to 120 bases, a tail
 primer (the reverse complement of the VN primer with 0 to 3 edits, junk behind it), a poly-A tail.  `--reps` fresh batches
-after a warm-up are made plain and clipped; prints one JSON line with the device time of k_read_ends and k_clip_gather
+after a warm-up are made plain and clipped; prints one JSON line with the device time of k_read_ends and k_gather
 beside coverage_ms, vote_ms and search_ms of the same batch, the scan's window positions per second, and the reads corrected
 and RAW bases with and without clipping.
     python tools/ends_bench.py [--reps R] [--reads N] [--kmers N] [--k K] [--frac F] [--window W]"""
